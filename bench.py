@@ -11,11 +11,15 @@ HBM before the timed region. Multi-GPU: ciphertexts (images) are independent, so
 on GPU r with no data-path collective (weak scaling); torch.distributed only provides the barriers and the
 max-over-ranks reduction of the elapsed time.
 
-Prints ONE JSON line (rank 0). `roofline.achieved` = algorithmic bytes per conv ((5B-1+2.5*log2B+0.5)
+Prints ONE JSON line (rank 0). A plain run sets up, warms up, times --steps steps and prints the headline (`value`, `ms_per_step`, the
+configuration); with --dump-outputs DIR it also writes what the last timed step computed (dump_outputs). Everything else the line can carry
+is measured only under --full:
+
+`roofline.achieved` = algorithmic bytes per conv ((5B-1+2.5*log2B+0.5)
 MiB) / average conv duration measured with HIP events on the library's own stream; `cpu_baseline` = the CPU
 oracle (a port of the reference's Go/Lattigo path, one thread) timed on this host on one full `conv 3 3`.
 
-The line validates itself (`parity_check`): the oracle runs on the SAME planted inputs as ciphertext 0 of context 0, and its output is compared word for word with what
+The --full line validates itself (`parity_check`): the oracle runs on the SAME planted inputs as ciphertext 0 of context 0, and its output is compared word for word with what
 the last timed step left on the GPU (outputs are cleared before the timed region); the convReLU 5 1 workload's launch set runs once more on the input and keys that were
 planted into the reference binary and its SHA-256 digests are compared with the binary's (tests/golden/ref_trace_chain_5_1.json); under N > 1 the sharded convolution
 is compared with the oracle too. Any mismatch: the line is still printed, then the process exits with status 1.
@@ -72,6 +76,24 @@ def synth_rows(rng, q, shape):
     return (rng.integers(0, 1 << 62, size=shape, dtype=np.uint64) % np.uint64(q)).astype(np.uint64)
 
 
+def timed_inputs(i_batch, rank):
+    """the planted data of ciphertext 0 of context 0 on rank `rank` (the other resident ciphertexts are rolled copies): the input ciphertext (2, 2, N),
+    the kernel plaintexts (B, 2, N), the switching keys as handed to hc_evk_load and the bias; the same for the same arguments in every run"""
+    B = BATCHS[i_batch]
+    rng = np.random.default_rng(0xC0FFEE + i_batch + 1000 * rank)
+    ct_in = np.stack([np.stack([synth_rows(rng, Q0, N), synth_rows(rng, Q1, N)]) for _ in range(2)])
+    pl_ker = np.empty((B, 2, N), dtype=np.uint64)
+    pl_ker[:, 0] = synth_rows(rng, Q0, (B, N)); pl_ker[:, 1] = synth_rows(rng, Q1, (B, N))
+    keys = []
+    step = B // 2
+    j = 16 - (step.bit_length() - 1)
+    while step >= 1:
+        keys.append(((1 << j) + 1, [synth_rows(rng, Q0, N), synth_rows(rng, Q0, N), synth_rows(rng, P0, N), synth_rows(rng, P0, N)]))
+        step //= 2; j += 1
+    bias = synth_rows(rng, Q0, N)
+    return ct_in, pl_ker, keys, bias
+
+
 def oracle_conv(B, ct_in, pl_ker, keys, bias):
     """One conv_then_pack + bias on the CPU oracle (test infrastructure: the checker and the reported baseline, never the product) on the given planted
     data; returns (output residues (2, N), seconds). `keys` = [(galEl = 2^j + 1, [b_Q0, a_Q0, b_P, a_P])] as handed to hc_evk_load."""
@@ -90,6 +112,30 @@ def oracle_conv(B, ct_in, pl_ker, keys, bias):
 def cpu_baseline(B, dt):
     return {"value": 1.0 / dt, "unit": "conv/s", "cores": 1, "kind": "port",
             "sample": f"1 full conv_then_pack+bias at B={B} (N=2^16) on the C oracle, {dt:.2f} s, host has {os.cpu_count()} cores; the SAME planted inputs as ciphertext 0 of context 0 of the timed region (parity_check compares the two outputs word for word)"}
+
+
+DUMP_BUDGET = 64 * 10 ** 6           # bytes of .npy files --dump-outputs may write
+DUMP_SEED = 0xD0                     # the sample of ciphertexts kept when the outputs exceed the budget
+
+
+def dump_outputs(d, lanes):
+    """--dump-outputs: the level-0 ciphertext (2, N) that the last timed step left in each resident ciphertext's output - what a caller of
+    conv_then_pack_batch receives - as d/out_c<context>_n<ciphertext>.npy. Residues mod Q0 reach 2^55, beyond float64's 53-bit mantissa, so each
+    is stored exactly as two float64 halves: array (2, N, 2), [..., 0] = residue >> 32, [..., 1] = residue & 0xFFFFFFFF. When all outputs exceed
+    DUMP_BUDGET, a fixed seeded sample of whole ciphertexts is written. Returns the names written."""
+    items = [(c, k, o) for c, L in enumerate(lanes) for k, o in enumerate(L["out"])]
+    per_file = 2 * N * 2 * 8 + 128
+    keep = len(items) if len(items) * per_file <= DUMP_BUDGET else DUMP_BUDGET // per_file
+    sel = sorted(np.random.default_rng(DUMP_SEED).choice(len(items), size=keep, replace=False)) if keep < len(items) else range(len(items))
+    os.makedirs(d, exist_ok=True)
+    names = []
+    for i in sel:
+        c, k, o = items[i]
+        w = o.download((2, N))
+        name = f"out_c{c}_n{k}"
+        np.save(os.path.join(d, name + ".npy"), np.stack([w >> np.uint64(32), w & np.uint64(0xFFFFFFFF)], axis=-1).astype(np.float64))
+        names.append(name)
+    return names
 
 
 def first_difference(got, want):
@@ -356,16 +402,21 @@ def main():
     ap.add_argument("--i-batch", type=int, default=3, help="reference batch index (main.go:578): 3 => B=256, W=16 = `conv 3 3`")
     ap.add_argument("--ker-wid", type=int, default=3)
     ap.add_argument("--chunk", type=int, default=512, help="jobs (channels / tree nodes, summed over the batch) per kernel launch")
-    ap.add_argument("--batch", type=int, default=4, help="ciphertexts per hc_conv_then_pack_batch call (one launch set covers them all); 4 x 4 contexts measured best (8 x 2: -4.5 %, 8 x 3: -1 %)")
+    ap.add_argument("--batch", type=int, default=4, help="ciphertexts per hc_conv_then_pack_batch call (one launch set covers them all); 4 x 4 contexts measured best (8 x 2: -4.5 %%, 8 x 3: -1 %%)")
     ap.add_argument("--streams", type=int, default=4, help="contexts (HIP streams) per GPU, each with its own batch of resident ciphertexts")
     ap.add_argument("--batch-alt", type=int, default=0, help="experiment: odd-numbered contexts use this batch size instead (desynchronises the streams)")
     ap.add_argument("--opt", action="append", default=[], help="extra context option name=value (hc_set_option), e.g. small_levels=0")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-workloads", action="store_true", help="skip the convReLU 5 1 / resnet-20 figures (BASELINE configs 4, 5: the C++ host CLI, ~40 s)")
+    ap.add_argument("--full", action="store_true", help="after the headline, also measure and check everything else: the per-kernel profile and roofline, one convolution alone, "
+                    "the CPU oracle's baseline and parity check, the convReLU 5 1 / resnet-20 workloads and the sharded conv 7 3 under N > 1")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed to DIR/<name>.npy (rank 0; see dump_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU oracle (cpu_baseline and the conv parity check)")
+    ap.add_argument("--no-workloads", action="store_true", help="--full: skip the convReLU 5 1 / resnet-20 figures (BASELINE configs 4, 5: the C++ host CLI, ~40 s)")
     ap.add_argument("--relu-batch", type=int, default=4, help="HCONV_IMAGE_BATCH of the convReLU 5 1 workload")
     ap.add_argument("--resnet-batch", type=int, default=8, help="HCONV_IMAGE_BATCH of the resnet-20 workload")
     ap.add_argument("--resnet-images", type=int, default=24)
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     import torch
     rank = int(os.environ.get("RANK", "0"))
@@ -389,17 +440,7 @@ def main():
     B, W = BATCHS[args.i_batch], WIDTHS[args.i_batch]
     S = max(1, args.streams)
     NB = max(1, min(16, args.batch))
-    rng = np.random.default_rng(0xC0FFEE + args.i_batch + 1000 * rank)
-    ct_in = np.stack([np.stack([synth_rows(rng, Q0, N), synth_rows(rng, Q1, N)]) for _ in range(2)])
-    pl_ker = np.empty((B, 2, N), dtype=np.uint64)
-    pl_ker[:, 0] = synth_rows(rng, Q0, (B, N)); pl_ker[:, 1] = synth_rows(rng, Q1, (B, N))
-    keys = []
-    step = B // 2
-    j = 16 - (step.bit_length() - 1)
-    while step >= 1:
-        keys.append(((1 << j) + 1, [synth_rows(rng, Q0, N), synth_rows(rng, Q0, N), synth_rows(rng, P0, N), synth_rows(rng, P0, N)]))
-        step //= 2; j += 1
-    bias = synth_rows(rng, Q0, N)
+    ct_in, pl_ker, keys, bias = timed_inputs(args.i_batch, rank)
     lanes = []                      # one lane = one context/stream with its own resident ciphertext, keys and kernel plaintexts
     for s_ in range(S):
         ctx = Context([Q0, Q1], [P0], device=device)            # raises if no GPU / no libhconv.so
@@ -418,7 +459,6 @@ def main():
             L["out"].append(ctx.buf(nwords=2 * N))
         lanes.append(L)
     ctx = lanes[0]["ctx"]
-    counter = [0]
 
     def one_step():
         """one pass of the hot path over one batch of input = one convolution on each of the S resident ciphertexts"""
@@ -459,12 +499,36 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=f"cuda:{device}" if backend == "nccl" else "cpu")
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, lanes)
+    per_step = sum(len(L["in"]) for L in lanes)
+    if rank == 0:
+        out = {
+            "metric": "homomorphic convs/sec (conv_then_pack + BN bias, k x k, batch B, N=2^16)",
+            "value": world * args.steps * per_step / elapsed, "unit": "conv/s",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": elapsed / args.steps * 1e3,
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "dtype": "u64", "data": "synthetic",
+            "config": {"workload": f"conv {args.ker_wid} {args.i_batch}", "ker_wid": args.ker_wid, "batch": B, "in_wid": W,
+                       "logN": 16, "moduli": "ckks.DefaultBootstrapParams[6] Q0,Q1 + P=0x1fffffffffe00001",
+                       "convs_per_step_per_gpu": per_step, "ciphertexts_per_launch_set": NB, "contexts_per_gpu": S, "chunk_nodes": args.chunk},
+        }
+    if not args.full:
+        for L in lanes:
+            for k in L["ker"]:
+                L["ctx"].ker_free(k)
+            L["ctx"].close()
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        if world > 1:
+            torch.distributed.destroy_process_group()
+        return
 
     timed_out0 = lanes[0]["out"][0].download((2, N))         # ciphertext 0 of context 0 after the LAST timed step (the region above is closed)
     timed_out_last = lanes[-1]["out"][-1].download((2, N))    # ... and the last ciphertext of the last context (a rolled copy of the same data: must differ from it, and is non-zero)
 
     # per-kernel HIP-event profile (separate untimed pass: event records between launches perturb the stream)
-    counter[0] = 0
     ctx.set_option("profile", 1)
     ctx.profile_reset()
     nprof = max(1, min(3, args.steps))
@@ -486,7 +550,6 @@ def main():
     single_ms = float(np.median(lone))
 
     if rank == 0:
-        per_step = sum(len(L["in"]) for L in lanes)
         conv_ms_events = ev_ms / (args.steps * per_step)
         alg_bytes = algorithmic_mib(B) * 2 ** 20
         achieved = alg_bytes / (conv_ms_events * 1e-3) / 1e9
@@ -505,25 +568,14 @@ def main():
             for name, ms, alg in (("loop_A", la, (2 * B + 2) * mib), ("loop_B", lb, (3 * (B - 1) + 2.5 * np.log2(B) + 0.5) * mib)):
                 if ms > 0:
                     loops[name] = {"ms_per_conv_one_stream": ms, "algorithmic_bytes": alg, "frac": alg / (ms * 1e-3) / 1e9 / 8000.0}
-        out = {
-            "metric": "homomorphic convs/sec (conv_then_pack + BN bias, k x k, batch B, N=2^16)",
-            "value": world * args.steps * per_step / elapsed, "unit": "conv/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": elapsed / args.steps * 1e3,
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "u64", "data": "synthetic",
-            "config": {"workload": f"conv {args.ker_wid} {args.i_batch}", "ker_wid": args.ker_wid, "batch": B, "in_wid": W,
-                       "logN": 16, "moduli": "ckks.DefaultBootstrapParams[6] Q0,Q1 + P=0x1fffffffffe00001",
-                       "convs_per_step_per_gpu": per_step, "ciphertexts_per_launch_set": NB, "contexts_per_gpu": S, "chunk_nodes": args.chunk},
-            "roofline": {"bound": bound, "achieved": achieved, "peak": 8000.0, "unit": "GB/s", "frac": achieved / 8000.0, "valu_frac": valu_frac,
-                         "state": "neither roof binds alone: VALU issue floor / achieved = valu_frac, fabric traffic / time well below the ~6.3 TB/s achievable - the kernels are latency / overlap bound (DESIGN.md 5)",
-                         "traffic": traffic, "traffic_measured_with": traffic_how,
-                         "unit_of_launch": "one conv_then_pack (its share of the batched launch set: all kernels of loop A and of the pack tree)",
-                         "algorithmic_bytes_per_conv": alg_bytes, "conv_ms_hip_events": conv_ms_events,
-                         "dominant_kernel": dom, "kernels": kern,
-                         "kernels_measured_with": {"contexts": 1, "ciphertexts_per_launch_set": NB, "note": "HIP events around every launch of one context, separate untimed pass"},
-                         "loops": loops, "single_conv_ms": single_ms, "valu": valu},
-        }
+        out["roofline"] = {"bound": bound, "achieved": achieved, "peak": 8000.0, "unit": "GB/s", "frac": achieved / 8000.0, "valu_frac": valu_frac,
+                           "state": "neither roof binds alone: VALU issue floor / achieved = valu_frac, fabric traffic / time well below the ~6.3 TB/s achievable - the kernels are latency / overlap bound (DESIGN.md 5)",
+                           "traffic": traffic, "traffic_measured_with": traffic_how,
+                           "unit_of_launch": "one conv_then_pack (its share of the batched launch set: all kernels of loop A and of the pack tree)",
+                           "algorithmic_bytes_per_conv": alg_bytes, "conv_ms_hip_events": conv_ms_events,
+                           "dominant_kernel": dom, "kernels": kern,
+                           "kernels_measured_with": {"contexts": 1, "ciphertexts_per_launch_set": NB, "note": "HIP events around every launch of one context, separate untimed pass"},
+                           "loops": loops, "single_conv_ms": single_ms, "valu": valu}
         # The record proves its own work: the oracle (2 s, one core) runs on the SAME planted inputs as ciphertext 0 of context 0 and its output is compared word for word with
         # what the timed region left there (conv.go:522-546 + eval.go:258). A mismatch fails the process after the line is printed.
         if not args.no_cpu_baseline:

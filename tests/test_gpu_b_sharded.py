@@ -124,7 +124,7 @@ def test_bench_two_gloo_ranks_on_one_gpu_carries_configs_3_and_5(tmp_path):
     slowest rank (`workloads.resnet20.images_per_hour`, n_gpus = 2) - so that the first SCALE record the driver can take holds them."""
     import json
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0", HC_BENCH_BACKEND="gloo")
-    args = ["--steps", "2", "--warmup", "1", "--batch", "2", "--streams", "1", "--no-cpu-baseline", "--relu-batch", "2", "--resnet-batch", "2", "--resnet-images", "4"]
+    args = ["--full", "--steps", "2", "--warmup", "1", "--batch", "2", "--streams", "1", "--no-cpu-baseline", "--relu-batch", "2", "--resnet-batch", "2", "--resnet-images", "4"]
     two = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1", "--master-port", str(29700 + os.getpid() % 90),
                           os.path.join(ROOT, "bench.py"), "--gpus", "2"] + args, env=env, capture_output=True, text=True, timeout=1200)
     assert two.returncode == 0, two.stdout[-2000:] + two.stderr[-3000:]
@@ -149,7 +149,7 @@ def test_bench_line_validates_itself_on_gpu():
     inputs the oracle gets, clears every output before the timed region, and compares all 131 072 words of what the LAST timed step left with the oracle's; the convReLU 5 1
     launch set (4 images) runs once more on the input and keys planted into the reference binary and must print the binary's three SHA-256 digests. rc = 0 only if both hold."""
     import json
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--resnet-images", "16"], capture_output=True, text=True, timeout=900)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "3", "--warmup", "1", "--resnet-images", "16"], capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-2000:]
     j = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
     pk = j["parity_check"]
@@ -160,3 +160,26 @@ def test_bench_line_validates_itself_on_gpu():
     assert j["cpu_baseline"]["kind"] == "port" and "SAME planted inputs" in j["cpu_baseline"]["sample"]
     cr = j["workloads"]["convReLU_5_1"]
     assert 0 < cr["valu_frac"] < 1 and cr["issue_floor_ms"] > 0 and cr["lane_instr_per_ct_layer"] > 0, {k: cr.get(k) for k in ("valu_frac", "issue_floor_ms")}
+
+
+def test_bench_plain_run_is_lean_and_dumps_what_the_timed_steps_computed(tmp_path):
+    """The plain line (no --full) carries the headline alone, and --dump-outputs writes what the last timed step left in every resident ciphertext's output,
+    exactly: ciphertext 0 of context 0, put back together from its two float64 halves, is the CPU oracle's conv_then_pack on the planted inputs, all 131 072 words."""
+    import json
+    import numpy as np
+    import bench
+    d = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--dump-outputs", str(d)],
+                       capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, lines
+    j = json.loads(lines[0])
+    assert j["steps"] == 2 and j["unit"] == "conv/s" and j["higher_is_better"] is True and j["dtype"] == "u64" and j["value"] > 0
+    assert abs(j["ms_per_step"] - 1e3 * j["config"]["convs_per_step_per_gpu"] / j["value"]) < 1e-6 * j["ms_per_step"]
+    assert not {"roofline", "parity_check", "cpu_baseline", "workloads"} & set(j), sorted(j)
+    assert sorted(os.listdir(d)) == sorted(f"out_c{c}_n{k}.npy" for c in range(4) for k in range(4))
+    a = np.load(d / "out_c0_n0.npy")
+    got = (a[..., 0].astype(np.uint64) << np.uint64(32)) | a[..., 1].astype(np.uint64)
+    want, _ = bench.oracle_conv(256, *bench.timed_inputs(3, 0))
+    assert bench.first_difference(got, want) == "ok"

@@ -3,7 +3,7 @@
 set -u
 O=gpurun_out/icache; mkdir -p $O; export TMPDIR=/tmp; R=$GRAFT_REPO_ROOT
 for st in 1 2; do
-  (cd /tmp && timeout 600 rocprofv3 --kernel-trace --pmc SQC_ICACHE_REQ SQC_ICACHE_HITS SQC_ICACHE_MISSES SQC_ICACHE_MISSES_DUPLICATE SQ_IFETCH SQ_WAVE_CYCLES SQ_WAIT_INST_ANY SQ_INSTS_VALU --output-format csv -d $R/$O/s$st -o run -- python $R/bench.py --steps 3 --warmup 1 --batch 8 --streams $st --no-cpu-baseline > $R/$O/s$st.log 2>&1)
+  (cd /tmp && timeout 600 rocprofv3 --kernel-trace --pmc SQC_ICACHE_REQ SQC_ICACHE_HITS SQC_ICACHE_MISSES SQC_ICACHE_MISSES_DUPLICATE SQ_IFETCH SQ_WAVE_CYCLES SQ_WAIT_INST_ANY SQ_INSTS_VALU --output-format csv -d $R/$O/s$st -o run -- python $R/bench.py --full --steps 3 --warmup 1 --batch 8 --streams $st --no-cpu-baseline > $R/$O/s$st.log 2>&1)
 done
 python - $O <<'PY'
 import csv,collections,glob,os,sys

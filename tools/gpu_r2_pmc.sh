@@ -5,7 +5,7 @@ set -u
 O=gpurun_out/${OUT:-pmc}; mkdir -p $O
 export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
-BENCH="python $R/bench.py --steps 2 --warmup 1 --batch ${BATCH:-8} --no-cpu-baseline ${BENCH_ARGS:-}"
+BENCH="python $R/bench.py --full --steps 2 --warmup 1 --batch ${BATCH:-8} --no-cpu-baseline ${BENCH_ARGS:-}"
 run_pmc() { name=$1; shift
   (cd /tmp && timeout 600 rocprofv3 --kernel-trace --pmc "$@" --output-format csv -d $R/$O/$name -o run -- $BENCH > $R/$O/$name.log 2>&1); }
 run_pmc fetch FETCH_SIZE

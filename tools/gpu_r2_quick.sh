@@ -13,7 +13,7 @@ tail -6 $O/pytest_gpu.log
 timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1; tail -1 $O/smoke.log
 IFS='|' read -ra CFGS <<< "${BENCH_CFGS:---steps 20 --warmup 5|--steps 100 --warmup 10}"
 for args in "${CFGS[@]}"; do
-  timeout 600 python bench.py $args --no-cpu-baseline > $O/bench_tmp.json 2>> $O/bench.err
+  timeout 600 python bench.py --full $args --no-cpu-baseline > $O/bench_tmp.json 2>> $O/bench.err
   python - "$args" $O/bench_tmp.json <<'PY'
 import json,sys
 try:

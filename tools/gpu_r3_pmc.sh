@@ -7,7 +7,7 @@ O=gpurun_out/${OUT:-r3pmc}; mkdir -p $O
 export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 S=${STREAMS:-1}; NB=${BATCH:-4}; K=2; W=1      # ONE stream: with several, rocprofv3 attributes the device-wide counters of overlapping kernels to each of them (r3pmc: 4 x 4 gave 4.82 GB "per conv", a1 writing 285 MiB instead of its 256)
-BENCH="python $R/bench.py --steps $K --warmup $W --batch $NB --streams $S --no-cpu-baseline ${BENCH_ARGS:-}"
+BENCH="python $R/bench.py --full --steps $K --warmup $W --batch $NB --streams $S --no-cpu-baseline ${BENCH_ARGS:-}"
 CONVS=$(( (1 + W + K) * S * NB + (K < 3 ? K : 3) * NB + 10 ))      # set-up + warm-up + steps, the 3 profiled launch sets of context 0, the 10 single convolutions bench.py times at the end
 echo "$BENCH ; convolutions in the run: $CONVS" > $O/command.txt
 run_pmc() { name=$1; shift

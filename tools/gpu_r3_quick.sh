@@ -13,7 +13,7 @@ tail -4 $O/pytest_gpu.log 2>/dev/null
 IFS='|' read -ra CFGS <<< "${BENCH_CFGS:---steps 20 --warmup 5}"
 for args in "${CFGS[@]}"; do
   lib=""; case "$args" in LIB=*) lib="${args%% *}"; args="${args#* }"; export HCONV_LIB="$PWD/optimal_conv_amd/variants/libhconv_${lib#LIB=}.so";; *) unset HCONV_LIB;; esac
-  timeout 600 python bench.py $args --no-cpu-baseline > $O/bench_tmp.json 2>> $O/bench.err
+  timeout 600 python bench.py --full $args --no-cpu-baseline > $O/bench_tmp.json 2>> $O/bench.err
   python - "$lib $args" $O/bench_tmp.json <<'PY'
 import json,sys
 try:

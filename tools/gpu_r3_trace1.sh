@@ -1,10 +1,11 @@
 #!/bin/bash
 # kernel timeline of single convolutions (bench.py's single_conv loop): per-level durations
 set -u
+R=$(cd "$(dirname "$0")/.." && pwd)
 O=$GRAFT_REPO_ROOT/gpurun_out/${OUT:-r3t1}; mkdir -p $O
 export TMPDIR=/tmp
 cd /tmp
-timeout 600 rocprofv3 --kernel-trace --output-format csv -d $O/tr -o run -- python $GRAFT_REPO_ROOT/bench.py --steps 1 --warmup 0 --streams 1 --batch 1 --no-cpu-baseline ${BENCH_ARGS:-} > $O/log.txt 2>&1
+timeout 600 rocprofv3 --kernel-trace --output-format csv -d $O/tr -o run -- python $R/bench.py --full --steps 1 --warmup 0 --streams 1 --batch 1 --no-cpu-baseline ${BENCH_ARGS:-} > $O/log.txt 2>&1
 python - $O <<'PY'
 import csv, re, collections, sys
 O=sys.argv[1]

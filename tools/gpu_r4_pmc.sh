@@ -8,7 +8,7 @@ python -c "import __graft_entry__ as g; g.build()" > $O/build.log 2>&1 || echo "
 (cd /tmp && rocprofv3 -L 2>/dev/null | grep -i -E "VALU|SQ_BUSY|SQ_INST_CYCLES" | head -60 > $O/counters_available.txt)
 if [ "${SKIP_CONV:-0}" != "1" ]; then
 S=1; NB=${BATCH:-4}; K=2; W=1
-BENCH="python $R/bench.py --steps $K --warmup $W --batch $NB --streams $S --no-cpu-baseline --no-workloads"
+BENCH="python $R/bench.py --full --steps $K --warmup $W --batch $NB --streams $S --no-cpu-baseline --no-workloads"
 CONVS=$(( (1 + W + K) * S * NB + (K < 3 ? K : 3) * NB + 10 ))
 echo "$BENCH ; convolutions in the run: $CONVS" > $O/command.txt
 run_pmc() { name=$1; shift

@@ -4,7 +4,7 @@
 set -u
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/${OUT:-r6b5mem}; mkdir -p $O; export TMPDIR=/tmp
 python -c "import __graft_entry__ as g; g.build()" > $O/build.log 2>&1 || echo "BUILD FAILED"
-BENCH="python $R/bench.py --steps 2 --warmup 1 --batch 4 --streams 1 --no-cpu-baseline --no-workloads"
+BENCH="python $R/bench.py --full --steps 2 --warmup 1 --batch 4 --streams 1 --no-cpu-baseline --no-workloads"
 for v in ${VARIANTS:-base ld4r1}; do
   export HCONV_LIB=$R/tools/_variants/libhconv_$v.so
   pass_() { name=$1; shift; (cd /tmp && timeout 600 rocprofv3 --kernel-trace --pmc "$@" --output-format csv -d $O/${v}_$name -o run -- $BENCH > $O/${v}_$name.log 2>&1); echo "$v $name exit $?"; }

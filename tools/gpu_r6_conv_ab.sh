@@ -6,7 +6,7 @@ R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/${OUT:-r6ab}; mkdir -p $O; export TMPDIR=/tm
 python -c "import __graft_entry__ as g; g.build()" > $O/build.log 2>&1 || echo "BUILD FAILED"
 for rep in $(seq 1 ${REPS:-3}); do
   for v in ${VARIANTS:-base}; do
-    HCONV_LIB=$R/tools/_variants/libhconv_$v.so timeout 600 python $R/bench.py --steps 20 --warmup 5 --no-workloads ${BENCH_ARGS:-} > $O/bench_tmp.json 2>> $O/bench.err
+    HCONV_LIB=$R/tools/_variants/libhconv_$v.so timeout 600 python $R/bench.py --full --steps 20 --warmup 5 --no-workloads ${BENCH_ARGS:-} > $O/bench_tmp.json 2>> $O/bench.err
     echo "rc=$?" >> $O/bench.err
     python - "$v rep $rep" $O/bench_tmp.json <<'PY'
 import json,sys

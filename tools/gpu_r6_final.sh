@@ -10,7 +10,7 @@ python -c "import __graft_entry__ as g; g.build()" > $O/build.log 2>&1 || echo "
 if [ "${SKIP_TESTS:-0}" != "1" ]; then
 ( time timeout 1500 python -m pytest tests -m gpu -x -q ) > $O/pytest_gpu.log 2>&1; tail -24 $O/pytest_gpu.log
 fi
-if [ "${SKIP_BENCH:-0}" != "1" ]; then python bench.py --steps 20 --warmup 5 > $O/bench_20_5.json 2> $O/bench_20_5.err; echo "bench rc=$?"; tail -c 900 $O/bench_20_5.json; echo; fi
+if [ "${SKIP_BENCH:-0}" != "1" ]; then python bench.py --full --steps 20 --warmup 5 > $O/bench_20_5.json 2> $O/bench_20_5.err; echo "bench rc=$?"; tail -c 900 $O/bench_20_5.json; echo; fi
 [ "${ONLY_BENCH:-0}" = "1" ] && exit 0
 OUT=${OUT:-r6final}/pmc SKIP_CHAIN=1 bash tools/gpu_r4_pmc.sh > $O/pmc.log 2>&1; tail -4 $O/pmc.log
 OUT=${OUT:-r6final}/chain NBCHAIN=4 bash tools/gpu_r6_chain_counters.sh > $O/chain.log 2>&1; tail -3 $O/chain.log

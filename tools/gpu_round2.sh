@@ -9,18 +9,18 @@ R=$GRAFT_REPO_ROOT
 python -c "import __graft_entry__ as g; g.build()" > $O/build.log 2>&1 || echo "BUILD FAILED"
 timeout 1800 python -m pytest tests -m gpu -x -q --durations=10 > $O/pytest_gpu.log 2>&1; echo "pytest exit $?" >> $O/pytest_gpu.log; grep -E "passed|failed|exit" $O/pytest_gpu.log | tail -3
 timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1; tail -1 $O/smoke.log
-timeout 900 python bench.py --steps 20 --warmup 5 > $O/bench_20_5.json 2> $O/bench.err; cut -c1-330 $O/bench_20_5.json
-timeout 900 python bench.py --no-cpu-baseline > $O/bench_100_10.json 2>> $O/bench.err
-timeout 300 python bench.py --steps 20 --warmup 5 --streams 1 --no-cpu-baseline > $O/bench_streams1.json 2>> $O/bench.err
-timeout 300 python bench.py --steps 20 --warmup 5 --streams 1 --batch 1 --no-cpu-baseline > $O/bench_single_conv.json 2>> $O/bench.err
-for ib in 0 1 2; do timeout 300 python bench.py --i-batch $ib --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_ib$ib.json 2>> $O/bench.err; done
+timeout 900 python bench.py --full --steps 20 --warmup 5 > $O/bench_20_5.json 2> $O/bench.err; cut -c1-330 $O/bench_20_5.json
+timeout 900 python bench.py --full --no-cpu-baseline > $O/bench_100_10.json 2>> $O/bench.err
+timeout 300 python bench.py --full --steps 20 --warmup 5 --streams 1 --no-cpu-baseline > $O/bench_streams1.json 2>> $O/bench.err
+timeout 300 python bench.py --full --steps 20 --warmup 5 --streams 1 --batch 1 --no-cpu-baseline > $O/bench_single_conv.json 2>> $O/bench.err
+for ib in 0 1 2; do timeout 300 python bench.py --full --i-batch $ib --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_ib$ib.json 2>> $O/bench.err; done
 python - $O <<'PY'
 import json,sys,glob,os
 for f in sorted(glob.glob(os.path.join(sys.argv[1],"bench_*.json"))):
     try: d=json.load(open(f)); print(os.path.basename(f), "%.1f conv/s  %.3f ms/conv  frac %.3f" % (d["value"], d["roofline"]["conv_ms_hip_events"], d["roofline"]["frac"]))
     except Exception as e: print(f, "FAILED", e)
 PY
-(cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$O/prof -o conv33 -- python $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline > $R/$O/prof_run.log 2>&1)
+(cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$O/prof -o conv33 -- python $R/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $R/$O/prof_run.log 2>&1)
 OUT=round2/pmc BATCH=8 BENCH_ARGS="--streams 1" PMC_CONVS=48 bash tools/gpu_r2_pmc.sh > $O/pmc_table.txt 2>&1; tail -14 $O/pmc_table.txt
 # the other CLI configurations
 mkdir -p /tmp/cli && cd /tmp/cli
