@@ -227,6 +227,12 @@ int hc_ker_load_device(hc_ctx *ctx, const uint64_t *pl_ker_dptr, int max_ob, hc_
  * scaling, max_bat embedding with stride norm, encode_ker_final, EncodeCoeffs at `scale` (level 1), ToNTT. */
 int hc_prep_ker(hc_ctx *ctx, const double *ker_in, int ker_len, const double *bn_a, int in_wid, int ker_wid,
                 int real_ib, int real_ob, int norm, double scale, hc_ker **out);
+/* prep_Ker(pos = 0, trans) (conv.go:487-518, hc_version() >= 3): trans = 0 is hc_prep_ker, bit for bit. trans = 1 is the transposed
+ * convolution's kernel (reshape_ker's trans form, conv.go:192): ker_in HWOI flat, ker_out[o][c*k^2 + (k^2-1-t)] = ker_in[c + o*real_ib + t*real_ob*real_ib],
+ * then the same BN scaling, embedding, encode_ker_final, EncodeCoeffs and ToNTT. The input goes on the odd grid points (prep_Input's trans form,
+ * main.go:1011-1021); conv_then_pack and its batch and sharded forms take the handle unchanged. Any other trans is HC_ERR_ARG. */
+int hc_prep_ker_ex(hc_ctx *ctx, const double *ker_in, int ker_len, const double *bn_a, int in_wid, int ker_wid,
+                   int real_ib, int real_ob, int norm, double scale, int trans, hc_ker **out);
 /* the plaintexts of a handle as Lattigo would hold them: HOST out [max_ob][2][N], canonical NTT residues */
 int hc_ker_download(hc_ctx *ctx, const hc_ker *ker, uint64_t *host_out);
 void hc_ker_free(hc_ctx *ctx, hc_ker *ker);

@@ -732,36 +732,47 @@ __global__ __launch_bounds__(HC_TPB) void hc_k_ctc_pairs(HcPtrs ct_in, HcTw *out
 // x = uint64(|v|*scale + 0.5) in plain f64, q - (x mod q) for negative v) and scatters the two residues into a
 // zero-filled limb-major staging buffer stage[limb][i][N] (coefficient domain). IEEE f64 ops, so the integers are
 // the ones the reference's Go code produces.
+// TRANS = reshape_ker(trans = true) (conv.go:192): HWOI source ker_in[c + o*real_ib + t*real_ob*real_ib] at the flipped tap
+// ker_rs[o][c*k_sz + (k_sz-1-t)]; its threads run c fastest so that they read the kernel file in order. The rest is the same.
 struct HcPrepKer {
-    const double *ker_in;   // HWIO flat: ker_in[o + c*real_ob + t*real_ob*real_ib]
+    const double *ker_in;   // HWIO flat: ker_in[o + c*real_ob + t*real_ob*real_ib] (TRANS: HWOI, ker_in[c + o*real_ib + t*real_ob*real_ib])
     const double *bn_a;     // [real_ob]
     u64 *stage;             // [2][max_bat][N]
     int in_wid, ker_wid, real_ib, real_ob, norm, max_bat;
     double scale;
     u64 q0, q1;
 };
+// max_ker_rs[i][col] = v through encode_ker_final (row i read at col = (in_batch-1-j)*k_sz + (k_sz-1-k)), EncodeCoeffs' rounding, both residues
+__device__ __forceinline__ void hc_prep_ker_put(const HcPrepKer &P, int k_sz, int vec_size, int adj, int i, int col, double v) {
+    const int jj = P.max_bat - 1 - col / k_sz, kk = k_sz - 1 - col % k_sz;
+    const int p0 = (P.in_wid * (kk / P.ker_wid) + kk % P.ker_wid) * P.max_bat + jj;
+    const bool wrap = p0 < adj;                          // moved to the top block with a sign flip (conv.go:224-234)
+    const int p = wrap ? vec_size - adj + p0 : p0 - adj;
+    const double val = wrap ? -v : v;
+    const bool neg = val < 0;
+    const double x = neg ? -P.scale * val : P.scale * val;
+    const u64 xi = (u64)(x + 0.5);
+    const u64 r0 = xi % P.q0, r1 = xi % P.q1;
+    P.stage[((size_t)0 * P.max_bat + i) * 65536 + p] = neg ? P.q0 - r0 : r0;
+    P.stage[((size_t)1 * P.max_bat + i) * 65536 + p] = neg ? P.q1 - r1 : r1;
+}
+template <bool TRANS>
 __global__ __launch_bounds__(HC_TPB) void hc_k_prep_ker(HcPrepKer P) {
     const int k_sz = P.ker_wid * P.ker_wid;
     const long total = (long)P.real_ob * P.real_ib * k_sz;
     const int vec_size = P.in_wid * P.in_wid * P.max_bat;
     const int adj = (P.max_bat - 1) + P.max_bat * (P.in_wid + 1) * (P.ker_wid - 1) / 2;
     for (long id = (long)blockIdx.x * HC_TPB + threadIdx.x; id < total; id += (long)gridDim.x * HC_TPB) {
-        const int o = (int)(id % P.real_ob), c = (int)((id / P.real_ob) % P.real_ib), t = (int)(id / ((long)P.real_ob * P.real_ib));
-        const double v = P.ker_in[o + c * P.real_ob + (long)t * P.real_ob * P.real_ib] * P.bn_a[o];   // ker_rs[o][c*k_sz+t] * BN_a[o]
-        // max_ker_rs[norm*o][norm*c*k_sz + t]; encode_ker_final reads row i at (in_batch-1-j)*k_sz + (k_sz-1-k)
-        const int i = P.norm * o;
-        const int col = P.norm * c * k_sz + t;              // = (in_batch-1-j)*k_sz + (k_sz-1-k)
-        const int jj = P.max_bat - 1 - col / k_sz, kk = k_sz - 1 - col % k_sz;
-        const int p0 = (P.in_wid * (kk / P.ker_wid) + kk % P.ker_wid) * P.max_bat + jj;
-        const bool wrap = p0 < adj;                          // moved to the top block with a sign flip (conv.go:224-234)
-        const int p = wrap ? vec_size - adj + p0 : p0 - adj;
-        const double val = wrap ? -v : v;
-        const bool neg = val < 0;
-        const double x = neg ? -P.scale * val : P.scale * val;
-        const u64 xi = (u64)(x + 0.5);
-        const u64 r0 = xi % P.q0, r1 = xi % P.q1;
-        P.stage[((size_t)0 * P.max_bat + i) * 65536 + p] = neg ? P.q0 - r0 : r0;
-        P.stage[((size_t)1 * P.max_bat + i) * 65536 + p] = neg ? P.q1 - r1 : r1;
+        if constexpr (!TRANS) {
+            const int o = (int)(id % P.real_ob), c = (int)((id / P.real_ob) % P.real_ib), t = (int)(id / ((long)P.real_ob * P.real_ib));
+            const double v = P.ker_in[o + c * P.real_ob + (long)t * P.real_ob * P.real_ib] * P.bn_a[o];   // ker_rs[o][c*k_sz+t] * BN_a[o]
+            // max_ker_rs[norm*o][norm*c*k_sz + t]
+            hc_prep_ker_put(P, k_sz, vec_size, adj, P.norm * o, P.norm * c * k_sz + t, v);
+        } else {
+            const int c = (int)(id % P.real_ib), o = (int)((id / P.real_ib) % P.real_ob), t = (int)(id / ((long)P.real_ob * P.real_ib));
+            const double v = P.ker_in[id] * P.bn_a[o];        // id = c + o*real_ib + t*real_ob*real_ib: ker_rs[o][c*k_sz + (k_sz-1-t)] * BN_a[o]
+            hc_prep_ker_put(P, k_sz, vec_size, adj, P.norm * o, P.norm * c * k_sz + (k_sz - 1 - t), v);
+        }
     }
 }
 // limb-major NTT'd stage[limb][i][N] -> hc_ker layout dst[i][limb][N]; to_mont != 0: Montgomery form (x * 2^64 mod q)

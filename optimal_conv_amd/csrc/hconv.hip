@@ -323,7 +323,7 @@ static int hc_build_tables(hc_ctx *c, HcModHost *mh, bool inverse) {
     return HC_OK;
 }
 
-extern "C" int hc_version(void) { return 2; }      // 2: a plaintext shared by the images of a batch is said by the operation (HC_LV_MUL_PLAIN), never inferred from b0 == b1
+extern "C" int hc_version(void) { return 3; }      // 2: a plaintext shared by the images of a batch is said by the operation (HC_LV_MUL_PLAIN), never inferred from b0 == b1; 3: hc_prep_ker_ex (transposed kernels)
 extern "C" const char *hc_last_error(const hc_ctx *c) { return c ? c->err.c_str() : g_create_err.c_str(); }
 
 // the per-modulus table of the batched transforms (HcRowMod); again after option small32 changes
@@ -979,18 +979,20 @@ extern "C" int hc_ker_load_device(hc_ctx *c, const uint64_t *dptr, int max_ob, h
     if (!dptr || !out || max_ob < 1 || c->nq < 2) return hc_fail(c, HC_ERR_ARG, "hc_ker_load_device: bad arguments");
     return hc_ker_from_device(c, (u64 *)dptr, max_ob, false, out);
 }
-// prep_Ker (conv.go:487-518) entirely on the device: scatter/round the k^2*B^2 non-zeros, 2 batched NTTs, Montgomery form
-extern "C" int hc_prep_ker(hc_ctx *c, const double *ker_in, int ker_len, const double *bn_a, int in_wid, int ker_wid,
-                           int real_ib, int real_ob, int norm, double scale, hc_ker **out) {
+// prep_Ker (conv.go:487-518) entirely on the device: scatter/round the k^2*B^2 non-zeros, 2 batched NTTs, Montgomery form.
+// trans = 1: reshape_ker's transposed form (conv.go:192); the scatter is hc_k_prep_ker<true>, everything after it is shared.
+extern "C" int hc_prep_ker_ex(hc_ctx *c, const double *ker_in, int ker_len, const double *bn_a, int in_wid, int ker_wid,
+                              int real_ib, int real_ob, int norm, double scale, int trans, hc_ker **out) {
     HC_ENTER(c);
-    if (!ker_in || !bn_a || !out || c->nq < 2 || in_wid < 1 || ker_wid < 1 || real_ib < 1 || real_ob < 1 || norm < 1)
-        return hc_fail(c, HC_ERR_ARG, "hc_prep_ker: bad arguments");
-    if (HC_N % (in_wid * in_wid)) return hc_fail(c, HC_ERR_ARG, "hc_prep_ker: in_wid^2 must divide N");
+    const char *fn = trans ? "hc_prep_ker_ex" : "hc_prep_ker";
+    if (!ker_in || !bn_a || !out || c->nq < 2 || in_wid < 1 || ker_wid < 1 || real_ib < 1 || real_ob < 1 || norm < 1 || (trans != 0 && trans != 1))
+        return hc_fail(c, HC_ERR_ARG, "%s: bad arguments", fn);
+    if (HC_N % (in_wid * in_wid)) return hc_fail(c, HC_ERR_ARG, "%s: in_wid^2 must divide N", fn);
     const int max_bat = HC_N / (in_wid * in_wid), k_sz = ker_wid * ker_wid;
     if (ker_len != k_sz * real_ib * real_ob) return hc_fail(c, HC_ERR_ARG, "input size inconsistent!");   // readTxt's panic text (main.go:986)
-    if (norm * real_ib > max_bat || norm * real_ob > max_bat) return hc_fail(c, HC_ERR_ARG, "hc_prep_ker: norm*batch exceeds max_bat=%d", max_bat);
+    if (norm * real_ib > max_bat || norm * real_ob > max_bat) return hc_fail(c, HC_ERR_ARG, "%s: norm*batch exceeds max_bat=%d", fn, max_bat);
     const int adj = (max_bat - 1) + max_bat * (in_wid + 1) * (ker_wid - 1) / 2;
-    if (2 * adj > HC_N) return hc_fail(c, HC_ERR_ARG, "hc_prep_ker: kernel too wide for this input width");
+    if (2 * adj > HC_N) return hc_fail(c, HC_ERR_ARG, "%s: kernel too wide for this input width", fn);
     HcScratch S(c);
     double *dk = nullptr, *da = nullptr; u64 *stage = nullptr, *dst = nullptr;
     HC_HIP(c, S.alloc(&dk, (size_t)ker_len * sizeof(double)));
@@ -1002,15 +1004,20 @@ extern "C" int hc_prep_ker(hc_ctx *c, const double *ker_in, int ker_len, const d
     HC_HIP(c, hipMemsetAsync(stage, 0, (size_t)max_bat * 2 * HC_N * sizeof(u64), c->stream));
     HcPrepKer P; P.ker_in = dk; P.bn_a = da; P.stage = stage; P.in_wid = in_wid; P.ker_wid = ker_wid; P.real_ib = real_ib; P.real_ob = real_ob;
     P.norm = norm; P.max_bat = max_bat; P.scale = scale; P.q0 = c->mods[0].m.q; P.q1 = c->mods[1].m.q;
-    int rc = hc_launch(c, "prep_ker_scatter", hc_k_prep_ker, hc_pw_grid((size_t)ker_len), P);
+    int rc = trans ? hc_launch(c, "prep_ker_scatter_trans", hc_k_prep_ker<true>, hc_pw_grid((size_t)ker_len), P)
+                   : hc_launch(c, "prep_ker_scatter", hc_k_prep_ker<false>, hc_pw_grid((size_t)ker_len), P);
     HC_HIP(c, hipStreamSynchronize(c->stream));      // host buffers may go away after return; hc_ntt below may regrow ws_tmp
     for (int l = 0; l < 2 && !rc; l++) rc = hc_ntt(c, l, stage + (size_t)l * max_bat * HC_N, stage + (size_t)l * max_bat * HC_N, max_bat);
     if (!rc) rc = hc_launch(c, "ker_interleave", hc_k_ker_interleave, hc_pw_grid((size_t)max_bat * 2 * HC_N), (const u64 *)stage, dst, max_bat, c->mods[0].m, c->mods[1].m, 0);
-    if (!rc && hipStreamSynchronize(c->stream) != hipSuccess) rc = hc_fail(c, HC_ERR_HIP, "hc_prep_ker: stream synchronize failed");
+    if (!rc && hipStreamSynchronize(c->stream) != hipSuccess) rc = hc_fail(c, HC_ERR_HIP, "%s: stream synchronize failed", fn);
     if (rc) return rc;
     S.keep(dst);
     hc_ker *k = new hc_ker(); k->d = dst; k->max_ob = max_bat; *out = k;
     return HC_OK;
+}
+extern "C" int hc_prep_ker(hc_ctx *c, const double *ker_in, int ker_len, const double *bn_a, int in_wid, int ker_wid,
+                           int real_ib, int real_ob, int norm, double scale, hc_ker **out) {
+    return hc_prep_ker_ex(c, ker_in, ker_len, bn_a, in_wid, ker_wid, real_ib, real_ob, norm, scale, 0, out);
 }
 // plain (non-Montgomery) NTT rows of a kernel handle, [max_ob][2][N] to the HOST: what prep_Ker's pl_ker[i].Value.Coeffs hold
 extern "C" int hc_ker_download(hc_ctx *c, const hc_ker *k, uint64_t *host_out) {

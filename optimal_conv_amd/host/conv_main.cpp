@@ -4,6 +4,9 @@
 // It runs the slot-packed "Base Line" (hconv_bl.cpp, scope row 8f-2) and then "Ours" (hconv_host.cpp), as main.go:639-643 does.
 // `convReLU k i n` runs both with their bootstrapping chains (hconv_relu.cpp, scope row 8f-1: the baseline's stock Bootstrapp over
 // parameter set [7] and Ours' CtoS / StoC over set [6]); `resnet ker depth 1 n false` runs the encrypted ResNet inference (hconv_resnet.cpp, scope row 8f-3).
+// `transconv <ker_wid 3|5|7> <i_batch 0..3> <num_tests <= 10>` (not a reference command; the reference builds TransConv's operators but runs
+// none of them): stride-2 transposed convolution, Ours only (the reference's baseline side of it is unfinished), on
+// test_conv_data/test_transconv{k}_batch_{B}_{in,ker,bna,bnb,out}_{t}.csv with raw width widths[i]/2 - k/2, B in and B/4 out channels.
 // HCONV_SKIP_BL=1 skips the baseline half (not a reference feature; for timing "Ours" alone).
 // `conv --test-mode <args>` honours the test-only overrides HCONV_SEED / HCONV_CHAIN_REPLAY; without the flag they are fatal when set.
 #include <stdio.h>
@@ -18,7 +21,7 @@ int main(int argc, char **argv) {
         fprintf(stderr, "hconv: --test-mode: test-only overrides from the environment are honoured\n");
     }
     const int batchs[5] = {4, 16, 64, 256, 1024}, widths[5] = {128, 64, 32, 16, 8};   // main.go:578-579
-    if (argc < 5) hconv::panic("runtime error: index out of range (usage: conv|convReLU <ker_wid> <i_batch> <num_tests>)");
+    if (argc < 5) hconv::panic("runtime error: index out of range (usage: conv|convReLU|transconv <ker_wid> <i_batch> <num_tests>)");
     const std::string test_name = argv[1];
     // The bootstrapping chains allocate and free a few buffers per evaluator operation, and hipFree drains the device every time: the chain commands run on cached
     // allocations (hconv.hip hcx_malloc) unless HCONV_ASYNC_ALLOC=0 says otherwise - ResNet-20 at 8 images per launch set 2.12 -> 2.02 s per set (profiles/round4_cached_alloc_ab.txt)
@@ -39,6 +42,14 @@ int main(int argc, char **argv) {
         // BASELINE config 5 is `resnet 3 20 1 n false`; the wide networks and the CIFAR-100 head are outside the scope table and not built
         if (wide_case != 1 || cf100) hconv::panic("resnet: wide_case 2 / 3 and cf100 = true are out of scope in this build (SURVEY.md section 2, row 14)");
         hconv::testResNet_crop_sparse(0, test_num, ker_wid, depth, false);
+        return 0;
+    } else if (test_name == "transconv") {                              // not a reference command (see the top of this file)
+        if (num_tests > 10 || i_batch > 3) hconv::panic("Too many tests (>10) or too many batch index (>3)");
+        if (i_batch < 0) hconv::panic("runtime error: index out of range");
+        printf("Transposed convolution test start! (No Bootstrapping)\n");
+        printf("Ker:  %d batches:  %d widths:  %d\n", ker_wid, batchs[i_batch], widths[i_batch]);
+        printf("Ours start.\n");
+        hconv::testTransConv_in(batchs[i_batch], widths[i_batch], ker_wid, num_tests);
         return 0;
     } else hconv::panic("wrong test type");
     if (i_batch < 0) hconv::panic("runtime error: index out of range");

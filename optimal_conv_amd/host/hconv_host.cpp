@@ -172,7 +172,7 @@ void applyEnvOptions(hc_ctx *hc, int pack32_default) {
 
 Context *newContext(int logN, int ker_wid, const std::vector<int> &in_wids, const std::vector<int> &kp_wids, bool boot, const std::string &kind) {
     (void)ker_wid;
-    if (kind != "Conv" && kind != "Resnet_crop_sparse") panic("Wrong kinds!");       // main.go:404 (the kinds the built command lines use)
+    if (kind != "Conv" && kind != "Resnet_crop_sparse" && !(kind == "TransConv" && !boot)) panic("Wrong kinds!");       // main.go:404 (the kinds the built command lines use; TransConv without the bootstrapping chain)
     Context *c = new Context();
     double logqp = 0; for (uint64_t q : PARAMS6_Q) logqp += log2((double)q); for (uint64_t p : PARAMS6_P) logqp += log2((double)p);
     printf("CKKS parameters: logN = %d, logSlots = %d, h = %d, logQP = %d, levels = %d, scale= 2^%f, sigma = %f \n",
@@ -222,18 +222,22 @@ std::vector<double> readTxt(const std::string &name_file, int size) {      // ma
     return input;
 }
 std::vector<double> prep_Input(const std::vector<double> &input, int raw_in_wid, int in_wid, int Nn, int norm, bool trans, bool) {   // main.go:1007-1042
-    if (trans) panic("transposed convolution is outside the conv CLI path");
     std::vector<double> out((size_t)Nn, 0.0); int batch = Nn / (in_wid * in_wid), k = 0;
+    if (trans) {            // main.go:1011-1021: the raw image on the odd grid points (2i+1, 2j+1) of the in_wid x in_wid frame
+        for (int i = 0; i < in_wid / 2; i++) for (int j = 0; j < in_wid / 2; j++) for (int b = 0; b < batch / norm; b++)
+            if (i < raw_in_wid && j < raw_in_wid) out[(size_t)((2 * i + 1) * in_wid * batch + (2 * j + 1) * batch + b * norm)] = input[(size_t)k++];
+        return out;
+    }
     for (int i = 0; i < in_wid; i++) for (int j = 0; j < in_wid; j++) for (int b = 0; b < batch / norm; b++)
         if (i < raw_in_wid && j < raw_in_wid) out[(size_t)(i * in_wid * batch + j * batch + b * norm)] = input[(size_t)k++];
     return out;
 }
 std::vector<std::vector<double>> reshape_ker(const std::vector<double> &ker_in, int k_sz, int out_batch, bool trans) {   // conv.go:184-202
-    if (trans) panic("transposed convolution is outside the conv CLI path");
     int in_batch = (int)ker_in.size() / (k_sz * out_batch);
     std::vector<std::vector<double>> ker_out((size_t)out_batch, std::vector<double>((size_t)(k_sz * in_batch)));
     for (int i = 0; i < out_batch; i++) for (int j = 0; j < in_batch; j++) for (int k = 0; k < k_sz; k++)
-        ker_out[(size_t)i][(size_t)(j * k_sz + k)] = ker_in[(size_t)(i + j * out_batch + k * out_batch * in_batch)];
+        if (trans) ker_out[(size_t)i][(size_t)(j * k_sz + (k_sz - k - 1))] = ker_in[(size_t)(j + i * in_batch + k * out_batch * in_batch)];   // conv.go:192
+        else ker_out[(size_t)i][(size_t)(j * k_sz + k)] = ker_in[(size_t)(i + j * out_batch + k * out_batch * in_batch)];
     return ker_out;
 }
 std::vector<double> encode_ker_final(const std::vector<std::vector<double>> &ker_in, int pos, int i, int in_wid, int in_batch, int ker_wid) {   // conv.go:206-237
@@ -258,9 +262,13 @@ std::vector<double> post_process(const std::vector<double> &in_cfs, int raw_in_w
 void set_Variables(int batch, int raw_in_wid, int in_wid, int ker_wid, const std::string &kind, int *kp_wid, int *out_batch, int *logN, bool *trans) {   // eval.go:13-54
     int Nn = batch * in_wid * in_wid; *logN = 0; while ((1 << *logN) < Nn) (*logN)++;
     int max_kp_wid = in_wid - ((ker_wid - 1) / 2);
-    if (kind != "Conv") panic("Wrong kinds!");
-    *trans = false; *kp_wid = raw_in_wid; *out_batch = batch;
-    if (*kp_wid > max_kp_wid) { printf("max raw_in_wid:  %d\n", max_kp_wid); panic("too large raw_in_wid."); }
+    if (kind == "Conv") {
+        *trans = false; *kp_wid = raw_in_wid; *out_batch = batch;
+        if (*kp_wid > max_kp_wid) { printf("max raw_in_wid:  %d\n", max_kp_wid); panic("too large raw_in_wid."); }
+    } else if (kind == "TransConv") {                                                              // eval.go:41-48
+        *trans = true; *kp_wid = 2 * raw_in_wid; *out_batch = batch / 4;
+        if (*kp_wid > max_kp_wid) { printf("max raw_in_wid:  %d\n", max_kp_wid / 2); panic("too large raw_in_wid."); }
+    } else panic("Wrong kinds!");
 }
 void printDebugCfsPlain(const std::vector<double> &valuesTest, const std::vector<double> &valuesWant) {   // main.go:694-717
     printf("ValuesTest:"); for (int i = 0; i < 10; i++) printf("%6.10f, ", valuesTest[(size_t)i]); printf("... \n");
@@ -321,14 +329,18 @@ void freeCt(Context *c, Ciphertext &ct) { if (ct.d) HC(c->hc, hc_free(c->hc, ct.
 // ---------------------------------------------------------------- prep_Ker (conv.go:487-518)
 KerPlain prep_Ker(Context *c, const std::vector<double> &ker_in, const std::vector<double> &BN_a, int in_wid, int ker_wid,
                   int real_ib, int real_ob, int norm, int ECD_LV, int pos, bool trans) {
-    // The whole of conv.go:487-518 runs on the device (hc_prep_ker: reshape_ker, BN scale, max_bat embedding,
+    // The whole of conv.go:487-518 runs on the device (hc_prep_ker / hc_prep_ker_ex: reshape_ker, BN scale, max_bat embedding,
     // encode_ker_final, EncodeCoeffs rounding, ToNTT); reshape_ker/encode_ker_final above remain as the host-side
     // statement of the layout (used by tests and by anyone who wants to inspect a kernel plaintext).
-    if (trans || pos != 0 || ECD_LV != 1) panic("prep_Ker: only the conv path's (pos=0, trans=false, ECD_LV=1) form is built");
+    if (pos != 0 || ECD_LV != 1) panic("prep_Ker: only the conv path's (pos=0, ECD_LV=1) form is built");
     KerPlain k; k.max_bat = N / (in_wid * in_wid); k.Scale = c->scale;
-    HC(c->hc, hc_prep_ker(c->hc, ker_in.data(), (int)ker_in.size(), BN_a.data(), in_wid, ker_wid, real_ib, real_ob, norm, c->scale, &k.h));
+    auto prep = [&](hc_ctx *h, hc_ker **out) {
+        if (trans) HC(h, hc_prep_ker_ex(h, ker_in.data(), (int)ker_in.size(), BN_a.data(), in_wid, ker_wid, real_ib, real_ob, norm, c->scale, 1, out));
+        else HC(h, hc_prep_ker(h, ker_in.data(), (int)ker_in.size(), BN_a.data(), in_wid, ker_wid, real_ib, real_ob, norm, c->scale, out));
+    };
+    prep(c->hc, &k.h);
     k.shard_h.push_back(k.h);
-    for (size_t g = 1; g < c->shards.size(); g++) { hc_ker *h = nullptr; HC(c->shards[g], hc_prep_ker(c->shards[g], ker_in.data(), (int)ker_in.size(), BN_a.data(), in_wid, ker_wid, real_ib, real_ob, norm, c->scale, &h)); k.shard_h.push_back(h); }
+    for (size_t g = 1; g < c->shards.size(); g++) { hc_ker *h = nullptr; prep(c->shards[g], &h); k.shard_h.push_back(h); }
     return k;
 }
 
@@ -637,6 +649,65 @@ void testConv_in(int in_batch, int in_wid, int ker_wid, int total_test_num, bool
         std::vector<double> real_out = readTxt(pre + "out" + suf, raw_in_wid * raw_in_wid * raw_in_batch);
         printDebugCfsPlain(test_out, real_out);
         freeCt(cont, ctxt_input); freeCt(cont, ct_result);
+    }
+    freeContext(cont);
+}
+
+// ---------------------------------------------------------------- testTransConv_in (not a reference routine: testConv_in's shape for kind "TransConv")
+// The reference builds the transposed convolution's operators (set_Variables "TransConv", prep_Input / reshape_ker / prep_Ker with trans) but no
+// command runs them. Here: raw_in_wid = in_wid/2 - ker_wid/2, real_ib = in_batch, real_ob = in_batch/4, norm = 1; the result is TF's
+// conv2d_transpose(strides = 2, padding = 'SAME') on the 2*raw_in_wid grid in the first real_ob channels. Ours only, without bootstrapping.
+void testTransConv_in(int in_batch, int in_wid, int ker_wid, int total_test_num) {
+    const std::string kind = "TransConv";
+    const int raw_in_batch = in_batch, raw_in_wid = in_wid / 2 - ker_wid / 2, norm = 1;
+    const std::string test_dir = "test_conv_data/";
+    int kp_wid, out_batch, logN; bool trans;
+    set_Variables(in_batch, raw_in_wid, in_wid, ker_wid, kind, &kp_wid, &out_batch, &logN, &trans);
+    const int raw_out_batch = out_batch / norm, out_wid = kp_wid;
+    Context *cont = newContext(logN, ker_wid, {in_wid}, {kp_wid}, false, kind);
+    printf("vec size: log2 =  %d\n", cont->logN);
+    printf("raw input width:  %d\n", raw_in_wid);
+    printf("kernel width:  %d\n", ker_wid);
+    printf("num raw batches in & out:  %d ,  %d\n", raw_in_batch, raw_out_batch);
+    const int nimg = imageBatch();
+    // the result's first raw_out_batch channels on the out_wid x out_wid grid, [(i*out_wid + j)*raw_out_batch + o]
+    auto out_channels = [&](const std::vector<double> &cfs) {
+        std::vector<double> all = post_process(cfs, out_wid, in_wid), out((size_t)out_wid * out_wid * raw_out_batch);
+        for (int p = 0; p < out_wid * out_wid; p++) for (int o = 0; o < raw_out_batch; o++) out[(size_t)p * raw_out_batch + o] = all[(size_t)p * in_batch + o];
+        return out;
+    };
+    for (int test_iter = 0; test_iter < total_test_num; test_iter++) {
+        printf("%d -th iter...start\n", test_iter + 1);
+        const std::string pre = test_dir + "test_transconv" + std::to_string(ker_wid) + "_batch_" + std::to_string(in_batch) + "_";
+        const std::string suf = "_" + std::to_string(test_iter) + ".csv";
+        std::vector<double> raw_input = readTxt(pre + "in" + suf, raw_in_wid * raw_in_wid * raw_in_batch);
+        std::vector<double> ker_in = readTxt(pre + "ker" + suf, raw_in_batch * raw_out_batch * ker_wid * ker_wid);
+        std::vector<double> bn_a = readTxt(pre + "bna" + suf, raw_out_batch);
+        std::vector<double> bn_b = readTxt(pre + "bnb" + suf, raw_out_batch);
+        std::vector<double> input = prep_Input(raw_input, raw_in_wid, in_wid, cont->Nn, norm, trans, false);
+        auto start = now();
+        std::vector<Ciphertext> ins{EncryptNew(cont, EncodeCoeffs(input, cont->ECD_LV, cont->scale), cont->ECD_LV, cont->scale)};
+        printf("Encryption done in %s \n", dur(start).c_str());
+        // HCONV_IMAGE_BATCH = n > 1: n independent encryptions of the input through ONE set of launches (evalConv_BN_batch)
+        for (int z = 1; z < nimg; z++) ins.push_back(EncryptNew(cont, EncodeCoeffs(input, cont->ECD_LV, cont->scale), cont->ECD_LV, cont->scale));
+        std::vector<Ciphertext> ct_result = evalConv_BN_batch(cont, ins, ker_in, bn_a, bn_b, in_wid, ker_wid, raw_in_batch, raw_out_batch, norm, (double)(1 << 30), trans);
+        if (getenv("HCONV_PRINT_DIGEST")) {      // FNV-1a over the result ciphertext: lets tests compare code paths bit for bit
+            std::vector<uint64_t> h = dev_download(cont, ct_result[0].d, 2); uint64_t f = 1469598103934665603ull;
+            for (uint64_t w : h) for (int b = 0; b < 8; b++) { f ^= (w >> (8 * b)) & 0xff; f *= 1099511628211ull; }
+            printf("ciphertext digest: %016llx\n", (unsigned long long)f);
+        }
+        start = now();
+        std::vector<double> test_out = out_channels(DecryptDecodeCoeffs(cont, ct_result[0]));
+        printf("Decryption Done in %s \n", dur(start).c_str());
+        std::vector<double> real_out = readTxt(pre + "out" + suf, out_wid * out_wid * raw_out_batch);
+        printDebugCfsPlain(test_out, real_out);
+        for (int z = 1; z < nimg; z++) {                                                               // the other encryptions decrypt to the same values up to the scheme's noise
+            std::vector<double> cz = out_channels(DecryptDecodeCoeffs(cont, ct_result[(size_t)z]));
+            double mx = 0, mr = 0; for (size_t i = 0; i < cz.size(); i++) { mx = std::max(mx, fabs(cz[i] - test_out[i])); mr = std::max(mr, fabs(cz[i] - real_out[i])); }
+            printf("image %d of the batch: max |difference| to image 0 = %.3g, to the expected output = %.3g\n", z, mx, mr);
+        }
+        for (Ciphertext &ct : ins) freeCt(cont, ct);
+        for (Ciphertext &ct : ct_result) freeCt(cont, ct);
     }
     freeContext(cont);
 }

@@ -121,6 +121,8 @@ Ciphertext conv_then_pack(Context *cont, const Ciphertext &ctxt_in, const KerPla
 Ciphertext evalConv_BN(Context *cont, const Ciphertext &ct_input, const std::vector<double> &ker_in, const std::vector<double> &bn_a,
                        const std::vector<double> &bn_b, int in_wid, int ker_wid, int real_ib, int real_ob, int norm, double out_scale, bool trans);
 void testConv_in(int in_batch, int in_wid, int ker_wid, int total_test_num, bool boot);
+// `transconv` (not a reference command): kind "TransConv" through prep_Input / prep_Ker with trans = true and the same conv_then_pack, Ours only
+void testTransConv_in(int in_batch, int in_wid, int ker_wid, int total_test_num);
 // ---- convReLU chain (hconv_relu.cpp; eval.go:272-607 for kind "Conv") ----
 Boot *newBoot(const std::vector<int64_t> &sk, const Seed256 &seed, int device, const std::vector<int> &log_sparse_sets, int image_batch = 1);   // one "bootstrapper" per log_sparse; image_batch: images per launch set of the tail (HCONV_IMAGE_BATCH)
 void freeBoot(Boot *);
