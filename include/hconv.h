@@ -47,7 +47,7 @@ typedef struct hc_ker hc_ker; /* device-resident kernel plaintexts pl_ker[0..max
 int hc_ctx_create(hc_ctx **out, int logN, const uint64_t *q, int nq, const uint64_t *p, int np, int device);
 void hc_ctx_destroy(hc_ctx *ctx);
 const char *hc_last_error(const hc_ctx *ctx); /* ctx may be NULL: error of the last failed hc_ctx_create */
-int hc_version(void);
+int hc_version(void);   /* 3: hc_prep_ker_ex (transposed kernels); 4: hc_prep_ker_ex2 (dilated, channel-strided kernels) */
 
 /* ---- device memory ---- */
 int hc_malloc(hc_ctx *ctx, size_t bytes, void **dptr);
@@ -233,6 +233,14 @@ int hc_prep_ker(hc_ctx *ctx, const double *ker_in, int ker_len, const double *bn
  * main.go:1011-1021); conv_then_pack and its batch and sharded forms take the handle unchanged. Any other trans is HC_ERR_ARG. */
 int hc_prep_ker_ex(hc_ctx *ctx, const double *ker_in, int ker_len, const double *bn_a, int in_wid, int ker_wid,
                    int real_ib, int real_ob, int norm, double scale, int trans, hc_ker **out);
+/* prep_Ker of a dilated, channel-strided kernel (hc_version() >= 4; the "inside" layers Conv_inside / StrConv_inside, eval.go:418-431,
+ * test.go:484-492). ker_in is the UNDILATED HWIO kernel (ker_len = ker_wid^2 * real_ib * real_ob). The plaintexts are those of the kernel of
+ * width dilation*(ker_wid-1)+1 whose tap (dilation*ty, dilation*tx) and input channel ib_stride*c hold ker_in's tap (ty, tx), channel c
+ * (every other entry zero; real_ib*ib_stride input channels): bit for bit what hc_prep_ker_ex returns on that host-expanded kernel.
+ * dilation = ib_stride = 1 is hc_prep_ker_ex. HC_ERR_ARG: dilation or ib_stride < 1, trans = 1 with either != 1, and every expanded shape
+ * hc_prep_ker_ex refuses (norm*real_ib*ib_stride > max_bat, a dilated width whose encode_ker_final shift 2*adj exceeds N). */
+int hc_prep_ker_ex2(hc_ctx *ctx, const double *ker_in, int ker_len, const double *bn_a, int in_wid, int ker_wid,
+                    int real_ib, int real_ob, int norm, double scale, int trans, int dilation, int ib_stride, hc_ker **out);
 /* the plaintexts of a handle as Lattigo would hold them: HOST out [max_ob][2][N], canonical NTT residues */
 int hc_ker_download(hc_ctx *ctx, const hc_ker *ker, uint64_t *host_out);
 void hc_ker_free(hc_ctx *ctx, hc_ker *ker);

@@ -81,6 +81,8 @@ SYMBOLS = {
                             C.c_double, C.POINTER(C.c_void_p)]),
     "hc_prep_ker_ex": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_double), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                C.c_double, C.c_int, C.POINTER(C.c_void_p)]),
+    "hc_prep_ker_ex2": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_double), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                C.c_double, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "hc_ker_download": (C.c_int, [C.c_void_p, C.c_void_p, u64p]),
     "hc_ker_free": (None, [C.c_void_p, C.c_void_p]),
     "hc_idx_load": (C.c_int, [C.c_void_p, u64p]),
@@ -504,12 +506,17 @@ class Context:
         self._ck(self.L.hc_ker_load(self.h, _hp(pl_ker.reshape(-1)), max_ob, C.byref(k)))
         return k
 
-    def prep_ker(self, ker_in, bn_a, in_wid, ker_wid, real_ib, real_ob, norm=1, scale=2.0 ** 30, trans=False):
-        """trans=True: the transposed convolution's kernel (hc_prep_ker_ex), ker_in laid out HWOI"""
+    def prep_ker(self, ker_in, bn_a, in_wid, ker_wid, real_ib, real_ob, norm=1, scale=2.0 ** 30, trans=False, dilation=1, ib_stride=1):
+        """trans=True: the transposed convolution's kernel (hc_prep_ker_ex), ker_in laid out HWOI. dilation / ib_stride != 1: the plaintexts
+        of the undilated HWIO ker_in dilated to width dilation*(ker_wid-1)+1, input channel c at ib_stride*c (hc_prep_ker_ex2)"""
         ker_in = np.ascontiguousarray(ker_in, dtype=np.float64).reshape(-1)
         bn_a = np.ascontiguousarray(bn_a, dtype=np.float64)
         k = C.c_void_p()
         f64p = C.POINTER(C.c_double)
+        if dilation != 1 or ib_stride != 1:
+            self._ck(self.L.hc_prep_ker_ex2(self.h, ker_in.ctypes.data_as(f64p), ker_in.size, bn_a.ctypes.data_as(f64p), in_wid, ker_wid, real_ib,
+                                            real_ob, norm, scale, 1 if trans else 0, dilation, ib_stride, C.byref(k)))
+            return k
         if trans:
             self._ck(self.L.hc_prep_ker_ex(self.h, ker_in.ctypes.data_as(f64p), ker_in.size, bn_a.ctypes.data_as(f64p), in_wid, ker_wid, real_ib,
                                            real_ob, norm, scale, 1, C.byref(k)))

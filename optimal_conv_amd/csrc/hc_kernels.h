@@ -741,6 +741,7 @@ struct HcPrepKer {
     int in_wid, ker_wid, real_ib, real_ob, norm, max_bat;
     double scale;
     u64 q0, q1;
+    int src_wid, dil, ib_stride;   // EXP only: ker_in is src_wid x src_wid; ker_wid = dil*(src_wid-1)+1 is the dilated width the plaintexts encode
 };
 // max_ker_rs[i][col] = v through encode_ker_final (row i read at col = (in_batch-1-j)*k_sz + (k_sz-1-k)), EncodeCoeffs' rounding, both residues
 __device__ __forceinline__ void hc_prep_ker_put(const HcPrepKer &P, int k_sz, int vec_size, int adj, int i, int col, double v) {
@@ -756,14 +757,23 @@ __device__ __forceinline__ void hc_prep_ker_put(const HcPrepKer &P, int k_sz, in
     P.stage[((size_t)0 * P.max_bat + i) * 65536 + p] = neg ? P.q0 - r0 : r0;
     P.stage[((size_t)1 * P.max_bat + i) * 65536 + p] = neg ? P.q1 - r1 : r1;
 }
-template <bool TRANS>
+// EXP (hc_prep_ker_ex2, never with TRANS): ker_in is the undilated src_wid x src_wid HWIO kernel; source tap (ty, tx) goes to (dil*ty, dil*tx)
+// of the dilated ker_wid x ker_wid kernel and input channel c to ib_stride*c, exactly where the host-expanded kernel's non-zero would go. The
+// expanded kernel's zeros are the stage's clear. k_sz, adj and hc_prep_ker_put's row / column split are those of the dilated width.
+template <bool TRANS, bool EXP = false>
 __global__ __launch_bounds__(HC_TPB) void hc_k_prep_ker(HcPrepKer P) {
+    static_assert(!(TRANS && EXP), "dilated / channel-strided kernels have no transposed form");
     const int k_sz = P.ker_wid * P.ker_wid;
-    const long total = (long)P.real_ob * P.real_ib * k_sz;
+    const long total = (long)P.real_ob * P.real_ib * (EXP ? P.src_wid * P.src_wid : k_sz);
     const int vec_size = P.in_wid * P.in_wid * P.max_bat;
     const int adj = (P.max_bat - 1) + P.max_bat * (P.in_wid + 1) * (P.ker_wid - 1) / 2;
     for (long id = (long)blockIdx.x * HC_TPB + threadIdx.x; id < total; id += (long)gridDim.x * HC_TPB) {
-        if constexpr (!TRANS) {
+        if constexpr (EXP) {
+            const int o = (int)(id % P.real_ob), c = (int)((id / P.real_ob) % P.real_ib), t = (int)(id / ((long)P.real_ob * P.real_ib));
+            const double v = P.ker_in[id] * P.bn_a[o];                                                   // id = o + c*real_ob + t*real_ob*real_ib
+            const int td = P.dil * (t / P.src_wid) * P.ker_wid + P.dil * (t % P.src_wid);               // dilated tap
+            hc_prep_ker_put(P, k_sz, vec_size, adj, P.norm * o, P.norm * P.ib_stride * c * k_sz + td, v);
+        } else if constexpr (!TRANS) {
             const int o = (int)(id % P.real_ob), c = (int)((id / P.real_ob) % P.real_ib), t = (int)(id / ((long)P.real_ob * P.real_ib));
             const double v = P.ker_in[o + c * P.real_ob + (long)t * P.real_ob * P.real_ib] * P.bn_a[o];   // ker_rs[o][c*k_sz+t] * BN_a[o]
             // max_ker_rs[norm*o][norm*c*k_sz + t]

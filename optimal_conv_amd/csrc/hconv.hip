@@ -323,7 +323,7 @@ static int hc_build_tables(hc_ctx *c, HcModHost *mh, bool inverse) {
     return HC_OK;
 }
 
-extern "C" int hc_version(void) { return 3; }      // 2: a plaintext shared by the images of a batch is said by the operation (HC_LV_MUL_PLAIN), never inferred from b0 == b1; 3: hc_prep_ker_ex (transposed kernels)
+extern "C" int hc_version(void) { return 4; }      // 2: a plaintext shared by the images of a batch is said by the operation (HC_LV_MUL_PLAIN), never inferred from b0 == b1; 3: hc_prep_ker_ex (transposed kernels); 4: hc_prep_ker_ex2 (dilated, channel-strided kernels)
 extern "C" const char *hc_last_error(const hc_ctx *c) { return c ? c->err.c_str() : g_create_err.c_str(); }
 
 // the per-modulus table of the batched transforms (HcRowMod); again after option small32 changes
@@ -981,17 +981,20 @@ extern "C" int hc_ker_load_device(hc_ctx *c, const uint64_t *dptr, int max_ob, h
 }
 // prep_Ker (conv.go:487-518) entirely on the device: scatter/round the k^2*B^2 non-zeros, 2 batched NTTs, Montgomery form.
 // trans = 1: reshape_ker's transposed form (conv.go:192); the scatter is hc_k_prep_ker<true>, everything after it is shared.
-extern "C" int hc_prep_ker_ex(hc_ctx *c, const double *ker_in, int ker_len, const double *bn_a, int in_wid, int ker_wid,
-                              int real_ib, int real_ob, int norm, double scale, int trans, hc_ker **out) {
-    HC_ENTER(c);
-    const char *fn = trans ? "hc_prep_ker_ex" : "hc_prep_ker";
-    if (!ker_in || !bn_a || !out || c->nq < 2 || in_wid < 1 || ker_wid < 1 || real_ib < 1 || real_ob < 1 || norm < 1 || (trans != 0 && trans != 1))
+// dil / ib_stride (hc_prep_ker_ex2) != 1: the plaintexts of the dilated, channel-spread kernel; the scatter is hc_k_prep_ker<false, true>.
+static int hc_prep_ker_impl(hc_ctx *c, const char *fn, const double *ker_in, int ker_len, const double *bn_a, int in_wid, int ker_wid,
+                            int real_ib, int real_ob, int norm, double scale, int trans, int dil, int ib_stride, hc_ker **out) {
+    if (!ker_in || !bn_a || !out || c->nq < 2 || in_wid < 1 || ker_wid < 1 || real_ib < 1 || real_ob < 1 || norm < 1 || (trans != 0 && trans != 1) ||
+        dil < 1 || ib_stride < 1 || (trans && (dil != 1 || ib_stride != 1)))
         return hc_fail(c, HC_ERR_ARG, "%s: bad arguments", fn);
     if (HC_N % (in_wid * in_wid)) return hc_fail(c, HC_ERR_ARG, "%s: in_wid^2 must divide N", fn);
+    const bool exp = dil != 1 || ib_stride != 1;
     const int max_bat = HC_N / (in_wid * in_wid), k_sz = ker_wid * ker_wid;
     if (ker_len != k_sz * real_ib * real_ob) return hc_fail(c, HC_ERR_ARG, "input size inconsistent!");   // readTxt's panic text (main.go:986)
-    if (norm * real_ib > max_bat || norm * real_ob > max_bat) return hc_fail(c, HC_ERR_ARG, "%s: norm*batch exceeds max_bat=%d", fn, max_bat);
-    const int adj = (max_bat - 1) + max_bat * (in_wid + 1) * (ker_wid - 1) / 2;
+    const long kd = (long)dil * (ker_wid - 1) + 1;                                                           // the width the plaintexts encode
+    if ((long)norm * real_ib * ib_stride > max_bat || norm * real_ob > max_bat) return hc_fail(c, HC_ERR_ARG, "%s: norm*batch exceeds max_bat=%d", fn, max_bat);
+    if (kd > in_wid) return hc_fail(c, HC_ERR_ARG, "%s: kernel too wide for this input width", fn);
+    const int adj = (max_bat - 1) + max_bat * (in_wid + 1) * ((int)kd - 1) / 2;
     if (2 * adj > HC_N) return hc_fail(c, HC_ERR_ARG, "%s: kernel too wide for this input width", fn);
     HcScratch S(c);
     double *dk = nullptr, *da = nullptr; u64 *stage = nullptr, *dst = nullptr;
@@ -1002,9 +1005,11 @@ extern "C" int hc_prep_ker_ex(hc_ctx *c, const double *ker_in, int ker_len, cons
     HC_HIP(c, hcx_h2d_async(c, dk, ker_in, (size_t)ker_len * sizeof(double)));
     HC_HIP(c, hcx_h2d_async(c, da, bn_a, (size_t)real_ob * sizeof(double)));
     HC_HIP(c, hipMemsetAsync(stage, 0, (size_t)max_bat * 2 * HC_N * sizeof(u64), c->stream));
-    HcPrepKer P; P.ker_in = dk; P.bn_a = da; P.stage = stage; P.in_wid = in_wid; P.ker_wid = ker_wid; P.real_ib = real_ib; P.real_ob = real_ob;
+    HcPrepKer P; P.ker_in = dk; P.bn_a = da; P.stage = stage; P.in_wid = in_wid; P.ker_wid = (int)kd; P.real_ib = real_ib; P.real_ob = real_ob;
     P.norm = norm; P.max_bat = max_bat; P.scale = scale; P.q0 = c->mods[0].m.q; P.q1 = c->mods[1].m.q;
-    int rc = trans ? hc_launch(c, "prep_ker_scatter_trans", hc_k_prep_ker<true>, hc_pw_grid((size_t)ker_len), P)
+    P.src_wid = ker_wid; P.dil = dil; P.ib_stride = ib_stride;
+    int rc = exp ? hc_launch(c, "prep_ker_scatter_dilated", hc_k_prep_ker<false, true>, hc_pw_grid((size_t)ker_len), P)
+           : trans ? hc_launch(c, "prep_ker_scatter_trans", hc_k_prep_ker<true>, hc_pw_grid((size_t)ker_len), P)
                    : hc_launch(c, "prep_ker_scatter", hc_k_prep_ker<false>, hc_pw_grid((size_t)ker_len), P);
     HC_HIP(c, hipStreamSynchronize(c->stream));      // host buffers may go away after return; hc_ntt below may regrow ws_tmp
     for (int l = 0; l < 2 && !rc; l++) rc = hc_ntt(c, l, stage + (size_t)l * max_bat * HC_N, stage + (size_t)l * max_bat * HC_N, max_bat);
@@ -1014,6 +1019,16 @@ extern "C" int hc_prep_ker_ex(hc_ctx *c, const double *ker_in, int ker_len, cons
     S.keep(dst);
     hc_ker *k = new hc_ker(); k->d = dst; k->max_ob = max_bat; *out = k;
     return HC_OK;
+}
+extern "C" int hc_prep_ker_ex2(hc_ctx *c, const double *ker_in, int ker_len, const double *bn_a, int in_wid, int ker_wid,
+                               int real_ib, int real_ob, int norm, double scale, int trans, int dilation, int ib_stride, hc_ker **out) {
+    HC_ENTER(c);
+    return hc_prep_ker_impl(c, "hc_prep_ker_ex2", ker_in, ker_len, bn_a, in_wid, ker_wid, real_ib, real_ob, norm, scale, trans, dilation, ib_stride, out);
+}
+extern "C" int hc_prep_ker_ex(hc_ctx *c, const double *ker_in, int ker_len, const double *bn_a, int in_wid, int ker_wid,
+                              int real_ib, int real_ob, int norm, double scale, int trans, hc_ker **out) {
+    HC_ENTER(c);
+    return hc_prep_ker_impl(c, trans ? "hc_prep_ker_ex" : "hc_prep_ker", ker_in, ker_len, bn_a, in_wid, ker_wid, real_ib, real_ob, norm, scale, trans, 1, 1, out);
 }
 extern "C" int hc_prep_ker(hc_ctx *c, const double *ker_in, int ker_len, const double *bn_a, int in_wid, int ker_wid,
                            int real_ib, int real_ob, int norm, double scale, hc_ker **out) {

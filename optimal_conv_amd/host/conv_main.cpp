@@ -7,6 +7,8 @@
 // `transconv <ker_wid 3|5|7> <i_batch 0..3> <num_tests <= 10>` (not a reference command; the reference builds TransConv's operators but runs
 // none of them): stride-2 transposed convolution, Ours only (the reference's baseline side of it is unfinished), on
 // test_conv_data/test_transconv{k}_batch_{B}_{in,ker,bna,bnb,out}_{t}.csv with raw width widths[i]/2 - k/2, B in and B/4 out channels.
+// `resnet_fast <ker_wid> <depth> 1 <test_num> false` (not a reference command: the reference reaches testResNet_crop_fast_in, test.go:372-636, only by swapping
+// main.go:620-622): the same network as `resnet` on full slots, one bootstrapper (hconv_resnet.cpp). Same arguments; wide_case != 1 and cf100 are refused like `resnet`'s.
 // HCONV_SKIP_BL=1 skips the baseline half (not a reference feature; for timing "Ours" alone).
 // `conv --test-mode <args>` honours the test-only overrides HCONV_SEED / HCONV_CHAIN_REPLAY; without the flag they are fatal when set.
 #include <stdio.h>
@@ -25,9 +27,19 @@ int main(int argc, char **argv) {
     const std::string test_name = argv[1];
     // The bootstrapping chains allocate and free a few buffers per evaluator operation, and hipFree drains the device every time: the chain commands run on cached
     // allocations (hconv.hip hcx_malloc) unless HCONV_ASYNC_ALLOC=0 says otherwise - ResNet-20 at 8 images per launch set 2.12 -> 2.02 s per set (profiles/round4_cached_alloc_ab.txt)
-    if (test_name == "convReLU" || test_name == "resnet") setenv("HCONV_ASYNC_ALLOC", "1", 0);
+    if (test_name == "convReLU" || test_name == "resnet" || test_name == "resnet_fast") setenv("HCONV_ASYNC_ALLOC", "1", 0);
     const int ker_wid = atoi(argv[2]), i_batch = atoi(argv[3]), num_tests = atoi(argv[4]);
     if (!(ker_wid == 3 || ker_wid == 5 || ker_wid == 7)) hconv::panic("Wrong kernel wid (not in 3,5,7)");
+    if (test_name == "resnet_fast") {                                    // not a reference command (see the top of this file); main.go:609-621's argument handling
+        if (argc < 7) hconv::panic("runtime error: index out of range (usage: resnet_fast <ker_wid> <depth> <wide_case> <test_num> <cf100>)");
+        const int depth = atoi(argv[3]), wide_case = atoi(argv[4]), test_num = atoi(argv[5]);
+        const bool cf100 = std::string(argv[6]) == "true" || std::string(argv[6]) == "1";
+        if (wide_case < 1 || wide_case > 3) hconv::panic("Wrong wide case!");                              // main.go:628
+        if (wide_case != 1 || cf100) hconv::panic("resnet_fast: wide_case 2 / 3 and cf100 = true are out of scope in this build (SURVEY.md section 2, row 14)");
+        if (!(depth == 8 || depth == 14 || depth == 20)) hconv::panic("wrong depth (not in 8, 14, 20)!");  // test.go:397-405, before any device work
+        hconv::testResNet_crop_fast_in(0, test_num, ker_wid, depth, false);
+        return 0;
+    }
     bool boot = false;
     if (test_name == "conv") {
         if (num_tests > 10 || i_batch > 3) hconv::panic("Too many tests (>10) or too many batch index (>3)");

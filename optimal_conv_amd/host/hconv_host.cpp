@@ -172,7 +172,7 @@ void applyEnvOptions(hc_ctx *hc, int pack32_default) {
 
 Context *newContext(int logN, int ker_wid, const std::vector<int> &in_wids, const std::vector<int> &kp_wids, bool boot, const std::string &kind) {
     (void)ker_wid;
-    if (kind != "Conv" && kind != "Resnet_crop_sparse" && !(kind == "TransConv" && !boot)) panic("Wrong kinds!");       // main.go:404 (the kinds the built command lines use; TransConv without the bootstrapping chain)
+    if (kind != "Conv" && kind != "Resnet_crop_sparse" && kind != "Resnet_crop_fast" && !(kind == "TransConv" && !boot)) panic("Wrong kinds!");       // main.go:404 (the kinds the built command lines use; TransConv without the bootstrapping chain)
     Context *c = new Context();
     double logqp = 0; for (uint64_t q : PARAMS6_Q) logqp += log2((double)q); for (uint64_t p : PARAMS6_P) logqp += log2((double)p);
     printf("CKKS parameters: logN = %d, logSlots = %d, h = %d, logQP = %d, levels = %d, scale= 2^%f, sigma = %f \n",
@@ -202,11 +202,19 @@ Context *newContext(int logN, int ker_wid, const std::vector<int> &in_wids, cons
     if (boot) {                                                                                        // main.go:464-507
         printf("Generating bootstrapping keys...\n");
         auto start = now();
-        // DFT matrices and every switching key, same secret key. "Conv": one full-slot bootstrapper; the resnet kind: the
+        // DFT matrices and every switching key, same secret key. "Conv" and "Resnet_crop_fast": one full-slot bootstrapper; the sparse resnet kind: the
         // four sparse ones its layers use (btp2..btp5 of main.go:480-500; log_sparse 1..4)
-        c->btp = kind == "Conv" ? newBoot(c->sk, c->seed, dev, {0}, imageBatch()) : newBoot(c->sk, c->seed, dev, std::vector<int>{2, 1, 3, 4}, imageBatch());
-        if (kind != "Conv") { bootPrepareCompress(c->btp, in_wids[0], kp_wids[1], 1); bootPrepareCompress(c->btp, in_wids[1], kp_wids[2], 2); }   // main.go:163-215
+        const bool full = kind == "Conv" || kind == "Resnet_crop_fast";
+        c->btp = full ? newBoot(c->sk, c->seed, dev, {0}, imageBatch()) : newBoot(c->sk, c->seed, dev, std::vector<int>{2, 1, 3, 4}, imageBatch());
+        if (!full) { bootPrepareCompress(c->btp, in_wids[0], kp_wids[1], 1); bootPrepareCompress(c->btp, in_wids[1], kp_wids[2], 2); }   // main.go:163-215
         printf("Done in %s \n", dur(start).c_str());
+    }
+    if (kind == "Resnet_crop_fast") {                                                                  // main.go:123-136: masks only, no rotation keys
+        for (size_t i = 0; i < in_wids.size(); i++) {
+            const int step = 1 << i;
+            c->ext_idx[step].resize(2);
+            for (int ul = 0; ul < 2; ul++) c->ext_idx[step][(size_t)ul] = gen_keep_vec_stride(N / 2, in_wids[0], kp_wids[i], step, ul, kp_wids[i] % 2 != 0);
+        }
     }
     return c;
 }
@@ -328,14 +336,16 @@ void freeCt(Context *c, Ciphertext &ct) { if (ct.d) HC(c->hc, hc_free(c->hc, ct.
 
 // ---------------------------------------------------------------- prep_Ker (conv.go:487-518)
 KerPlain prep_Ker(Context *c, const std::vector<double> &ker_in, const std::vector<double> &BN_a, int in_wid, int ker_wid,
-                  int real_ib, int real_ob, int norm, int ECD_LV, int pos, bool trans) {
+                  int real_ib, int real_ob, int norm, int ECD_LV, int pos, bool trans, int dilation, int ib_stride) {
     // The whole of conv.go:487-518 runs on the device (hc_prep_ker / hc_prep_ker_ex: reshape_ker, BN scale, max_bat embedding,
     // encode_ker_final, EncodeCoeffs rounding, ToNTT); reshape_ker/encode_ker_final above remain as the host-side
     // statement of the layout (used by tests and by anyone who wants to inspect a kernel plaintext).
     if (pos != 0 || ECD_LV != 1) panic("prep_Ker: only the conv path's (pos=0, ECD_LV=1) form is built");
     KerPlain k; k.max_bat = N / (in_wid * in_wid); k.Scale = c->scale;
     auto prep = [&](hc_ctx *h, hc_ker **out) {
-        if (trans) HC(h, hc_prep_ker_ex(h, ker_in.data(), (int)ker_in.size(), BN_a.data(), in_wid, ker_wid, real_ib, real_ob, norm, c->scale, 1, out));
+        // the "inside" layers' dilated / channel-spread kernels (eval.go:418-431, test.go:484-492) from the undilated weights
+        if (dilation != 1 || ib_stride != 1) HC(h, hc_prep_ker_ex2(h, ker_in.data(), (int)ker_in.size(), BN_a.data(), in_wid, ker_wid, real_ib, real_ob, norm, c->scale, trans ? 1 : 0, dilation, ib_stride, out));
+        else if (trans) HC(h, hc_prep_ker_ex(h, ker_in.data(), (int)ker_in.size(), BN_a.data(), in_wid, ker_wid, real_ib, real_ob, norm, c->scale, 1, out));
         else HC(h, hc_prep_ker(h, ker_in.data(), (int)ker_in.size(), BN_a.data(), in_wid, ker_wid, real_ib, real_ob, norm, c->scale, out));
     };
     prep(c->hc, &k.h);
@@ -511,10 +521,10 @@ Ciphertext conv_then_pack(Context *c, const Ciphertext &ctxt_in, const KerPlain 
     return r;
 }
 Ciphertext evalConv_BN(Context *c, const Ciphertext &ct_input, const std::vector<double> &ker_in, const std::vector<double> &bn_a,
-                       const std::vector<double> &bn_b, int in_wid, int ker_wid, int real_ib, int real_ob, int norm, double out_scale, bool trans) {
+                       const std::vector<double> &bn_b, int in_wid, int ker_wid, int real_ib, int real_ob, int norm, double out_scale, bool trans, int dilation, int ib_stride) {
     const int max_batch = N / (in_wid * in_wid);
     auto start = now();
-    KerPlain pl_ker = prep_Ker(c, ker_in, bn_a, in_wid, ker_wid, real_ib, real_ob, norm, c->ECD_LV, 0, trans);      // eval.go:231
+    KerPlain pl_ker = prep_Ker(c, ker_in, bn_a, in_wid, ker_wid, real_ib, real_ob, norm, c->ECD_LV, 0, trans, dilation, ib_stride);      // eval.go:231
     std::vector<double> b_coeffs((size_t)N, 0.0);
     for (size_t i = 0; i < bn_b.size(); i++) for (int j = 0; j < in_wid * in_wid; j++) b_coeffs[(size_t)(norm * (int)i + j * max_batch)] = bn_b[i];   // eval.go:233-238
     Plaintext pl_bn_b; pl_bn_b.level = 0; pl_bn_b.Scale = out_scale;
@@ -547,16 +557,17 @@ int imageBatch() {
 }
 // eval.go:224-263 for the images of a batch: prep_Ker and the bias plaintext once (they depend on the layer only), conv_then_pack + the bias add of all images as ONE launch set
 std::vector<Ciphertext> evalConv_BN_batch(Context *c, const std::vector<Ciphertext> &ct_inputs, const std::vector<double> &ker_in, const std::vector<double> &bn_a,
-                                          const std::vector<double> &bn_b, int in_wid, int ker_wid, int real_ib, int real_ob, int norm, double out_scale, bool trans) {
+                                          const std::vector<double> &bn_b, int in_wid, int ker_wid, int real_ib, int real_ob, int norm, double out_scale, bool trans,
+                                          int dilation, int ib_stride) {
     const int n = (int)ct_inputs.size();
     if (n == 1 || getenv("HCONV_OPWISE") || c->shards.size() > 1) {      // one image (the reference's own flow, with its two timers), or modes that exist per image only
-        std::vector<Ciphertext> r; for (const Ciphertext &ct : ct_inputs) r.push_back(evalConv_BN(c, ct, ker_in, bn_a, bn_b, in_wid, ker_wid, real_ib, real_ob, norm, out_scale, trans));
+        std::vector<Ciphertext> r; for (const Ciphertext &ct : ct_inputs) r.push_back(evalConv_BN(c, ct, ker_in, bn_a, bn_b, in_wid, ker_wid, real_ib, real_ob, norm, out_scale, trans, dilation, ib_stride));
         return r;
     }
     if (n < 1 || n > 16) panic("evalConv_BN_batch: 1..16 images");
     const int max_batch = N / (in_wid * in_wid);
     auto start = now();
-    KerPlain pl_ker = prep_Ker(c, ker_in, bn_a, in_wid, ker_wid, real_ib, real_ob, norm, c->ECD_LV, 0, trans);      // eval.go:231
+    KerPlain pl_ker = prep_Ker(c, ker_in, bn_a, in_wid, ker_wid, real_ib, real_ob, norm, c->ECD_LV, 0, trans, dilation, ib_stride);      // eval.go:231
     std::vector<double> b_coeffs((size_t)N, 0.0);
     for (size_t i = 0; i < bn_b.size(); i++) for (int j = 0; j < in_wid * in_wid; j++) b_coeffs[(size_t)(norm * (int)i + j * max_batch)] = bn_b[i];   // eval.go:233-238
     Plaintext pl_bn_b; pl_bn_b.level = 0; pl_bn_b.Scale = out_scale;

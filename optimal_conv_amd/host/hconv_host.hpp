@@ -92,7 +92,27 @@ struct Context {
     Seed256 seed;                             // key of this context's generators (hconv_prng.hpp)
     ChaChaRng g;                              // this context's own generator: secret key, Galois keys, encryption randomness
     uint64_t replay_encryptions = 0;          // HCONV_RESNET_REPLAY: encryptions so far (the i-th takes the oracle harness' seed 5 + 1000 i)
+    std::map<int, std::vector<std::vector<int>>> ext_idx;   // kind "Resnet_crop_fast": ext_idx[step][ul], the keep masks of the "inside" layers (main.go:123-136)
 };
+
+// rot_util.go:226-267 gen_keep_vec_stride: gen_keep_vec (ul = 0 upper, 1 lower half of the full-slot bootstrapping) that keeps only the outputs at
+// stride `step` on the in_wid grid: kp_wid x kp_wid of them, from position init = 0 (raw_in_wid_odd) or step - 1, slot order bit-reversed over logN - 1 bits.
+// Header-only so that a test can build it without a device.
+inline std::vector<int> gen_keep_vec_stride(int vec_size, int in_wid, int kp_wid, int step, int ul, bool raw_in_wid_odd) {
+    int logN = 0; for (; (1 << logN) < 2 * vec_size; logN++) {}
+    std::vector<int> idx((size_t)vec_size, 0);
+    const int batch = 2 * vec_size / (in_wid * in_wid);
+    const int init = raw_in_wid_odd ? 0 : step - 1;
+    auto rev = [&](int x) { uint32_t v = (uint32_t)x, r = 0; for (int k = 0; k < logN - 1; k++) r |= ((v >> k) & 1u) << (logN - 2 - k); return (size_t)r; };
+    if (ul == 0) {
+        for (int i = 0; i < kp_wid; i++) if (init + i * step < in_wid / 2)
+            for (int j = 0; j < kp_wid; j++) for (int b = 0; b < batch; b++) idx[rev(in_wid * batch * (init + i * step) + batch * (j * step + init) + b)] = 1;
+    } else if (ul == 1) {
+        for (int i = 0; i < kp_wid; i++) if (init + i * step >= in_wid / 2)
+            for (int j = 0; j < kp_wid; j++) for (int b = 0; b < batch; b++) idx[rev(in_wid * batch * (init + i * step - in_wid / 2) + batch * (j * step + init) + b)] = 1;
+    } else panic("ul not 0 nor 1");
+    return idx;
+}
 
 // ---- harness / reference-shaped API ----
 Context *newContext(int logN, int ker_wid, const std::vector<int> &in_wids, const std::vector<int> &kp_wids, bool boot, const std::string &kind);
@@ -114,12 +134,13 @@ void freeCt(Context *cont, Ciphertext &ct);
 // kernel plaintexts: handle to the B device-resident plaintexts
 struct KerPlain { hc_ker *h = nullptr; int max_bat = 0; double Scale = 0; std::vector<hc_ker *> shard_h; };   // shard_h[g]: the same plaintexts on device g
 KerPlain prep_Ker(Context *cont, const std::vector<double> &ker_in, const std::vector<double> &BN_a, int in_wid, int ker_wid,
-                  int real_ib, int real_ob, int norm, int ECD_LV, int pos, bool trans);
+                  int real_ib, int real_ob, int norm, int ECD_LV, int pos, bool trans, int dilation = 1, int ib_stride = 1);   // dilation / ib_stride: hc_prep_ker_ex2
 
 Ciphertext conv_then_pack(Context *cont, const Ciphertext &ctxt_in, const KerPlain &pl_ker, int max_ob, int norm, int ECD_LV,
                           double out_scale, const Plaintext *pl_bn_b);
 Ciphertext evalConv_BN(Context *cont, const Ciphertext &ct_input, const std::vector<double> &ker_in, const std::vector<double> &bn_a,
-                       const std::vector<double> &bn_b, int in_wid, int ker_wid, int real_ib, int real_ob, int norm, double out_scale, bool trans);
+                       const std::vector<double> &bn_b, int in_wid, int ker_wid, int real_ib, int real_ob, int norm, double out_scale, bool trans,
+                       int dilation = 1, int ib_stride = 1);
 void testConv_in(int in_batch, int in_wid, int ker_wid, int total_test_num, bool boot);
 // `transconv` (not a reference command): kind "TransConv" through prep_Input / prep_Ker with trans = true and the same conv_then_pack, Ours only
 void testTransConv_in(int in_batch, int in_wid, int ker_wid, int total_test_num);
@@ -130,7 +151,9 @@ void bootPrepareCompress(Boot *B, int in_wid, int kp_wid, int log_sparse);   // 
 // everything after evalConv_BN: Scale *= 2^pow, BootstrappConv_CtoS, evalReLU + MulByPow2, keep_ctxt, BootstrappConv_StoC
 BootCiphertext evalConv_BNRelu_tail(Boot *B, const std::string &kind, int log_sparse, const uint64_t *ct_conv_dev, double ct_scale, double alpha, double pow, int in_wid, int kp_wid);
 // the same tail for the images of a batch (same layer, same weights) as ONE set of launches; at most the image_batch the bootstrapper was built with
-std::vector<BootCiphertext> evalConv_BNRelu_tail_batch(Boot *B, const std::string &kind, int log_sparse, const std::vector<const uint64_t *> &ct_conv_dev, double ct_scale, double alpha, double pow, int in_wid, int kp_wid);
+// kinds "Conv_inside" / "StrConv_inside" (the "Conv" tail on full slots) keep with keep_idx[ul] (Context::ext_idx[step]) instead of gen_keep_vec; mask_key names them in the mask cache
+std::vector<BootCiphertext> evalConv_BNRelu_tail_batch(Boot *B, const std::string &kind, int log_sparse, const std::vector<const uint64_t *> &ct_conv_dev, double ct_scale, double alpha, double pow, int in_wid, int kp_wid,
+                                                       const std::vector<std::vector<int>> *keep_idx = nullptr, const std::string &mask_key = "");
 std::vector<double> bootDecryptDecodeCoeffs(Boot *B, const BootCiphertext &ct);
 void freeBootCt(Boot *B, BootCiphertext &ct);
 void bootStats(Boot *B, long *keys, long *keyswitches);
@@ -142,16 +165,22 @@ void blBootReLU(Boot *B, const uint64_t *ct_res0, const uint64_t *ct_res1, doubl
 // eval.go:272-607 for kinds "Conv", "Conv_sparse", "StrConv_sparse" (hconv_resnet.cpp); returns a level-1, scale-2^30 ciphertext
 // evalConv_BN / evalConv_BNRelu_new for the images of a batch: kernel plaintexts prepared once, hc_conv_then_pack_batch, the tail as one launch set
 std::vector<Ciphertext> evalConv_BN_batch(Context *cont, const std::vector<Ciphertext> &ct_inputs, const std::vector<double> &ker_in, const std::vector<double> &bn_a,
-                                          const std::vector<double> &bn_b, int in_wid, int ker_wid, int real_ib, int real_ob, int norm, double out_scale, bool trans);
+                                          const std::vector<double> &bn_b, int in_wid, int ker_wid, int real_ib, int real_ob, int norm, double out_scale, bool trans,
+                                          int dilation = 1, int ib_stride = 1);
+// step (kinds "Conv_inside" / "StrConv_inside" of a "Resnet_crop_fast" context): the stride of the layer's OUTPUT on the in_wid grid; the kernel is dilated by step
+// (StrConv_inside: step / 2). ib_stride: input channel c of ker_in is channel ib_stride*c of the kernel (test.go:484-492), real_ib counts ker_in's channels.
 std::vector<Ciphertext> evalConv_BNRelu_new_batch(Context *cont, const std::vector<Ciphertext> &ct_inputs, const std::vector<double> &ker_in, const std::vector<double> &bn_a,
                                                   const std::vector<double> &bn_b, double alpha, double pow, int in_wid, int kp_wid, int ker_wid, int real_ib, int real_ob,
-                                                  int norm, int log_sparse, const std::string &kind);
+                                                  int norm, int log_sparse, const std::string &kind, int step = 1, int ib_stride = 1);
 int imageBatch();                                // HCONV_IMAGE_BATCH (1..8; default 1): images that go through a layer as one launch set
 Ciphertext evalConv_BNRelu_new(Context *cont, const Ciphertext &ct_input, const std::vector<double> &ker_in, const std::vector<double> &bn_a,
                                const std::vector<double> &bn_b, double alpha, double pow, int in_wid, int kp_wid, int ker_wid, int real_ib, int real_ob,
                                int norm, int log_sparse, const std::string &kind);
 // test.go:76-370 — `resnet ker depth 1 n false`
 void testResNet_crop_sparse(int st, int end, int ker_wid, int depth, bool debug);
+// test.go:372-636 — `resnet_fast ker depth 1 n false` (not a reference command; the reference's main.go:622 alternative to the line above): full slots on the 32-wide grid,
+// stride layers keep their outputs in place (gen_keep_vec_stride), later layers use dilated kernels; one full-slot bootstrapper
+void testResNet_crop_fast_in(int st, int end, int ker_wid, int depth, bool debug);
 // test_BL.go:16 — the slot-packed baseline the reference runs first (hconv_bl.cpp); boot = true adds Bootstrapp + ReLU (test_BL.go:113-168)
 void testConv_BL_in(int real_batch, int in_wid, int ker_wid, int total_test_num, bool boot);
 

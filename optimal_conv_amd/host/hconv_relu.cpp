@@ -1288,12 +1288,15 @@ static void replay_digest_line(Boot *B, const char *what, const DCt &c, int firs
 // eval.go:437-565: everything after the convolution(s). ct_conv = the level-0 convolution result at out_scale
 // 2^(round(log2 Q0) - (pow+8)). kind "Conv" (log_sparse 0, two ciphertexts through sine/ReLU, keep_ctxt masks of gen_keep_vec),
 // "Conv_sparse" (one packed ciphertext, gen_keep_vec_sparse), "StrConv_sparse" (one packed ciphertext, ext_double_ctxt with
-// gen_comprs_sparse: kp_wid is then the NEXT block's raw width).
+// gen_comprs_sparse: kp_wid is then the NEXT block's raw width), "Conv_inside" / "StrConv_inside" (the "Conv" tail, keep_ctxt with the
+// gen_keep_vec_stride masks keep_idx[ul] of the context's ext_idx[step]: eval.go:522-531).
 // The images of a batch (ct_conv_dev.size() <= the bootstrapper's HCONV_IMAGE_BATCH) go through the tail as ONE set of launches; results in the same order.
-std::vector<BootCiphertext> evalConv_BNRelu_tail_batch(Boot *B, const std::string &kind, int log_sparse, const std::vector<const uint64_t *> &ct_conv_dev, double ct_scale, double alpha, double pow_, int in_wid, int kp_wid) {
+std::vector<BootCiphertext> evalConv_BNRelu_tail_batch(Boot *B, const std::string &kind, int log_sparse, const std::vector<const uint64_t *> &ct_conv_dev, double ct_scale, double alpha, double pow_, int in_wid, int kp_wid,
+                                                       const std::vector<std::vector<int>> *keep_idx, const std::string &mask_key) {
     hc_ctx *hc = B->hc;
-    const bool stride = kind == "StrConv_sparse", sparse = kind == "Conv_sparse" || stride;
-    if (!sparse && kind != "Conv") panic("No kind!");
+    const bool stride = kind == "StrConv_sparse", sparse = kind == "Conv_sparse" || stride, inside = kind == "Conv_inside" || kind == "StrConv_inside";
+    if (!sparse && !inside && kind != "Conv") panic("No kind!");
+    if (inside && (!keep_idx || keep_idx->size() != 2)) panic("evalConv_BNRelu_tail: the inside kinds keep with the context's ext_idx[step] (kind Resnet_crop_fast)");
     if (!sparse && log_sparse != 0) panic("No cases for log_sparse");
     const int nimg = (int)ct_conv_dev.size();
     if (nimg < 1 || nimg > (B->merge_parts ? B->nb_max / 2 : B->nb_max)) panic("evalConv_BNRelu_tail: more images than the bootstrapper's image batch (HCONV_IMAGE_BATCH)");
@@ -1351,6 +1354,7 @@ std::vector<BootCiphertext> evalConv_BNRelu_tail_batch(Boot *B, const std::strin
     if (stride) for (int ul = 0; ul < iter; ul++) {                                                                                                                            // eval.go:500-506: m_idx / m_idx_l
         IdxMap m_idx, r_idx; gen_comprs_sparse(N / 2, in_wid, kp_wid, log_sparse, ul, m_idx, r_idx); keep[ul] = ext_double_ctxt(B, boots[ul], m_idx, r_idx, "comprs/" + mk + "/" + std::to_string(ul)); }
     else if (sparse && log_sparse) keep[0] = keep_ctxt(B, boots[0], gen_keep_vec_sparse(N / 2, in_wid, kp_wid, log_sparse), "keep/" + mk);                                         // eval.go:534
+    else if (inside) for (int ul = 0; ul < 2; ul++) keep[ul] = keep_ctxt(B, boots[ul], (*keep_idx)[(size_t)ul], "keep_stride/" + mask_key + "/" + std::to_string(ul));            // eval.go:526-528
     // "Conv_sparse" on full packing (wide_case 3, block 1) keeps with gen_keep_vec per half, like "Conv" (main.go:155-156)
     else for (int ul = 0; ul < 2; ul++) keep[ul] = keep_ctxt(B, boots[ul], gen_keep_vec(N / 2, in_wid, kp_wid, ul), "keep/" + mk + "/" + std::to_string(ul));
     DCt res = B->stoc(keep[0], iter == 2 ? &keep[1] : nullptr, log_sparse);                              // eval.go:550-561 ; Rescale (564) is a no-op here
@@ -1370,7 +1374,7 @@ std::vector<BootCiphertext> evalConv_BNRelu_tail_batch(Boot *B, const std::strin
     return outs;
 }
 BootCiphertext evalConv_BNRelu_tail(Boot *B, const std::string &kind, int log_sparse, const uint64_t *ct_conv_dev, double ct_scale, double alpha, double pow_, int in_wid, int kp_wid) {
-    return evalConv_BNRelu_tail_batch(B, kind, log_sparse, {ct_conv_dev}, ct_scale, alpha, pow_, in_wid, kp_wid)[0];
+    return evalConv_BNRelu_tail_batch(B, kind, log_sparse, {ct_conv_dev}, ct_scale, alpha, pow_, in_wid, kp_wid, nullptr, "")[0];
 }
 // ---------------------------------------------------------------- baseline: Bootstrapp + ReLU (test_BL.go:113-168)
 Boot *newBootBL(const std::vector<int64_t> &sk, const Seed256 &seed, int device) {

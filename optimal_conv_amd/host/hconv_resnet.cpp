@@ -11,6 +11,9 @@
 //                     shift, add, offset monomial                                                -> evalConv_BNRelu_new
 //   eval.go:437-565   bootstrapping (sparse slots), evalReLU, keep_ctxt / ext_double_ctxt, StoC   -> hconv_relu.cpp
 //   main.go:920-939   prt_mat_one_norm                                                            -> prt_mat_one_norm
+//   test.go:372-636   testResNet_crop_fast_in (`resnet_fast`, not a reference command: main.go:622's alternative driver): every layer on the 32-wide
+//                     grid at full slots; kinds "Conv_inside" / "StrConv_inside" (eval.go:295-302, 418-431: dilated kernels through hc_prep_ker_ex2,
+//                     the stride layers' input channels spread to ib_stride 2 on the device instead of test.go:484-492's host copy)  -> testResNet_crop
 // Weights and images are not shipped with the reference (README.md:23); tests/golden/gen_resnet_csv.py writes synthetic
 // ones in the same file layout together with the plain float model's class scores.
 #include <math.h>
@@ -53,8 +56,10 @@ static void mul_monomial_l0(Context *c, Ciphertext &ct, int idx, bool negative) 
 // sees the operations of the reference's per-image flow, but a launch covers all of them (hc_conv_then_pack_batch; hc_set_batch inside the tail)
 std::vector<Ciphertext> evalConv_BNRelu_new_batch(Context *cont, const std::vector<Ciphertext> &ct_inputs, const std::vector<double> &ker_in, const std::vector<double> &bn_a,
                                                   const std::vector<double> &bn_b, double alpha, double pow_, int in_wid, int kp_wid, int ker_wid, int real_ib, int real_ob,
-                                                  int norm, int log_sparse, const std::string &kind) {
+                                                  int norm, int log_sparse, const std::string &kind, int step, int ib_stride) {
     if (!cont->btp) panic("evalConv_BNRelu_new needs a context built with boot = true");
+    const bool inside = kind == "Conv_inside" || kind == "StrConv_inside";
+    if (ib_stride != 1 && !inside) panic("evalConv_BNRelu_new: ib_stride is for the inside kinds only");
     const int nimg = (int)ct_inputs.size();
     const double out_scale = exp2(round(log2((double)PARAMS6_Q[0]) - (pow_ + 8)));                       // eval.go:433
     std::vector<Ciphertext> ct_conv;
@@ -78,12 +83,22 @@ std::vector<Ciphertext> evalConv_BNRelu_new_batch(Context *cont, const std::vect
         ct_conv = r1;
     } else if (kind == "Conv_sparse" || kind == "Conv") {
         ct_conv = evalConv_BN_batch(cont, ct_inputs, ker_in, bn_a, bn_b, in_wid, ker_wid, real_ib, real_ob, norm, out_scale, false);             // eval.go:433
+    } else if (inside) {                                                                                  // eval.go:295-302, 418-431
+        if (kind == "StrConv_inside" && step % 2 != 0) panic("step can not be divided by 2 (for strided conv)");
+        const int in_step = kind == "StrConv_inside" ? step / 2 : step;
+        ct_conv = evalConv_BN_batch(cont, ct_inputs, ker_in, bn_a, bn_b, in_wid, ker_wid, real_ib, real_ob, norm, out_scale, false, in_step, ib_stride);
     } else panic("No kind!");
     // hand-over to the bootstrapper's context (its own stream): everything queued on the convolution context - the stride layers end on a product and an addition that
     // nothing has waited for - must be complete before the other stream reads ct_conv
     HCX(cont->hc, hc_sync(cont->hc));
     std::vector<const uint64_t *> conv_d; for (const Ciphertext &c : ct_conv) conv_d.push_back(c.d);
-    std::vector<BootCiphertext> r = evalConv_BNRelu_tail_batch(cont->btp, kind, log_sparse, conv_d, ct_conv[0].Scale, alpha, pow_, in_wid, kp_wid);
+    const std::vector<std::vector<int>> *keep_idx = nullptr;
+    if (inside) {                                                                                         // eval.go:526-528: keep_ctxt(ext_idx[step][ul])
+        auto it = cont->ext_idx.find(step);
+        if (it == cont->ext_idx.end()) panic("evalConv_BNRelu_new: no ext_idx for step " + std::to_string(step) + " (the inside kinds need a Resnet_crop_fast context)");
+        keep_idx = &it->second;
+    }
+    std::vector<BootCiphertext> r = evalConv_BNRelu_tail_batch(cont->btp, kind, log_sparse, conv_d, ct_conv[0].Scale, alpha, pow_, in_wid, kp_wid, keep_idx, "step" + std::to_string(step));
     for (Ciphertext &c : ct_conv) freeCt(cont, c);
     // [2][2][N] over (Q0, Q1): what the next convolution reads. The result blocks belong to the bootstrapper's context and go back to it; the layer's outputs are
     // blocks of the convolution context (a block released into a context that did not allocate it would leave the owner's block table pointing at memory it no longer
@@ -102,7 +117,7 @@ std::vector<Ciphertext> evalConv_BNRelu_new_batch(Context *cont, const std::vect
 Ciphertext evalConv_BNRelu_new(Context *cont, const Ciphertext &ct_input, const std::vector<double> &ker_in, const std::vector<double> &bn_a,
                                const std::vector<double> &bn_b, double alpha, double pow_, int in_wid, int kp_wid, int ker_wid, int real_ib, int real_ob,
                                int norm, int log_sparse, const std::string &kind) {
-    return evalConv_BNRelu_new_batch(cont, {ct_input}, ker_in, bn_a, bn_b, alpha, pow_, in_wid, kp_wid, ker_wid, real_ib, real_ob, norm, log_sparse, kind)[0];
+    return evalConv_BNRelu_new_batch(cont, {ct_input}, ker_in, bn_a, bn_b, alpha, pow_, in_wid, kp_wid, ker_wid, real_ib, real_ob, norm, log_sparse, kind, 1, 1)[0];
 }
 
 // main.go:920-939
@@ -131,23 +146,36 @@ static void writeTxt(const std::string &name, const std::vector<double> &v) {
 
 // test.go:76-370: `resnet ker depth 1 n false` (BASELINE config 5). The wide drivers (wide_case 2 / 3: testResNet_crop_sparse_wide, test.go:638-912) and the CIFAR-100 head
 // (cf100: two final convolutions, test.go:287-315) are SURVEY section 2 row 14 - out of scope - and were removed from this host in round 6 (they lived here in rounds 1-5).
-void testResNet_crop_sparse(int st, int end, int ker_wid, int depth, bool debug) {
+// fast = true: test.go:372-636 testResNet_crop_fast_in, the same network, files and console lines; every layer runs on the 32-wide grid at full slots (log_sparse 0),
+// norm 4 / 2 / 1, outputs at stride step 1 / 2 / 4 kept in place (ext_idx[step]), the stride layers' weights read with their input channels at ib_stride 2.
+static void testResNet_crop(int st, int end, int ker_wid, int depth, bool fast) {
     if (const char *fi = testOnlyEnv("HCONV_RESNET_FIRST_IMAGE")) st = atoi(fi);      // test mode: images st .. end - 1 (one image of a batch run alone, for the batch == single digest test)
-    (void)debug;
     const std::string ker_name = "ker" + std::to_string(ker_wid), tag = "crop_" + ker_name + "_d" + std::to_string(depth) + "_wid1/";
     const std::string weight_dir = "Resnet_weights/weights_" + tag, out_dir = "Resnet_enc_results/results_" + tag, img_dir = "Resnet_plain_data/" + tag;
     const int fc_out = 10; const double init_pow = 6.0, mid_pow = 6.0, final_pow = 6.0;                  // test.go:84-89 (cifar10)
     int num_blcs[3];
     if (depth == 20) { num_blcs[0] = 7; num_blcs[1] = 5; num_blcs[2] = 5; } else if (depth == 14) { num_blcs[0] = 5; num_blcs[1] = 3; num_blcs[2] = 3; }
     else if (depth == 8) { num_blcs[0] = 3; num_blcs[1] = 1; num_blcs[2] = 1; } else panic("wrong depth (not in 8, 14, 20)!");
-    const int real_batch[3] = {16, 32, 64}, norm[3] = {4, 8, 16}, log_sparse[3] = {2, 3, 4};           // test.go:107-112
+    const int real_batch[3] = {16, 32, 64}, norm_sparse[3] = {4, 8, 16}, log_sparse_sparse[3] = {2, 3, 4};   // test.go:107-112
+    const int norm_fast[3] = {4, 2, 1}, log_sparse_fast[3] = {0, 0, 0}, steps[3] = {1, 2, 4};                 // test.go:409-411
+    const int *norm = fast ? norm_fast : norm_sparse, *log_sparse = fast ? log_sparse_fast : log_sparse_sparse;
     const int logN = 16; const double alpha = 0.0;
     const std::vector<int> in_wids = {32, 16, 8}, raw_in_wids = {32 - ker_wid / 2, 16 - ker_wid / 2, 8 - ker_wid / 2};
     const int ker_size = ker_wid * ker_wid;
     int max_batch[3]; for (int i = 0; i < 3; i++) max_batch[i] = (1 << logN) / (in_wids[(size_t)i] * in_wids[(size_t)i]);
     mkdir("Resnet_enc_results", 0755); mkdir(out_dir.c_str(), 0755);
     auto W = [&](int i, const char *what, int size) { return readTxt(weight_dir + "w" + std::to_string(i) + "-" + what + ".csv", size); };
-    const char *kind_name = "Resnet_crop_sparse";
+    const char *kind_name = fast ? "Resnet_crop_fast" : "Resnet_crop_sparse";
+    // one conv-BN-ReLU layer whose output belongs to block blk (strided: the layer that enters it). Sparse: on block blk's grid (a stride layer on the previous one's, its
+    // sparse bootstrapper one slot set below: test.go:200, 225). Fast: on the 32-wide grid, the output at stride steps[blk], dilated kernels, a stride layer's input channels at 2c.
+    auto layer = [&](Context *cont, const std::vector<Ciphertext> &in, int w, int ib, int ob, int blk, bool strided, double pow_) {
+        const std::vector<double> ker = W(w, "conv", ib * ob * ker_size), a = W(w, "a", ob), b = W(w, "b", ob);
+        if (fast) return evalConv_BNRelu_new_batch(cont, in, ker, a, b, alpha, pow_, in_wids[0], raw_in_wids[(size_t)blk], ker_wid, ib, ob, norm[blk], 0,
+                                                   strided ? "StrConv_inside" : "Conv_inside", steps[blk], strided ? 2 : 1);
+        const int gb = strided ? blk - 1 : blk;
+        return evalConv_BNRelu_new_batch(cont, in, ker, a, b, alpha, pow_, in_wids[(size_t)gb], raw_in_wids[(size_t)blk], ker_wid, ib, ob, norm[blk],
+                                         strided ? log_sparse[gb] - 1 : log_sparse[blk], strided ? "StrConv_sparse" : "Conv_sparse");
+    };
 
     // HCONV_IMAGE_THREADS=K (not a reference feature): K host threads, each with its own context (keys, bootstrappers, stream),
     // classify disjoint shares of the images at the same time. A layer's launches are mostly far below one wave of workgroups, so the
@@ -196,37 +224,29 @@ void testResNet_crop_sparse(int st, int end, int ker_wid, int depth, bool debug)
 
         double pow_ = init_pow;                                                                          // ResNet Block 1
         for (int i = 1; i <= num_blcs[0]; i++) {
-            const int ib = i == 1 ? 3 : real_batch[0], ob = real_batch[0];
-            step(evalConv_BNRelu_new_batch(cont, ct_layer, W(i - 1, "conv", ib * ob * ker_size), W(i - 1, "a", ob), W(i - 1, "b", ob),
-                                           alpha, pow_, in_wids[0], raw_in_wids[0], ker_wid, ib, ob, norm[0], log_sparse[0], "Conv_sparse"));
+            step(layer(cont, ct_layer, i - 1, i == 1 ? 3 : real_batch[0], real_batch[0], 0, false, pow_));
             pow_ = mid_pow;
             printf("Block1, Layer  %d done!\n", i);
         }
         printf("Block1 done.\n"); timings[0] = secs(start); start = now();
-        step(evalConv_BNRelu_new_batch(cont, ct_layer, W(num_blcs[0], "conv", real_batch[0] * real_batch[1] * ker_size), W(num_blcs[0], "a", real_batch[1]), W(num_blcs[0], "b", real_batch[1]),
-                                       alpha, pow_, in_wids[0], raw_in_wids[1], ker_wid, real_batch[0], real_batch[1], norm[1], log_sparse[0] - 1, "StrConv_sparse"));           // test.go:200
+        step(layer(cont, ct_layer, num_blcs[0], real_batch[0], real_batch[1], 1, true, pow_));                                           // test.go:200 / 480-495
         printf("Block1 to 2 done!\n"); timings[1] = secs(start); start = now();
         for (int i = 1; i <= num_blcs[1]; i++) {                                                         // ResNet Block 2
-            const int w = num_blcs[0] + i;
-            step(evalConv_BNRelu_new_batch(cont, ct_layer, W(w, "conv", real_batch[1] * real_batch[1] * ker_size), W(w, "a", real_batch[1]), W(w, "b", real_batch[1]),
-                                           alpha, pow_, in_wids[1], raw_in_wids[1], ker_wid, real_batch[1], real_batch[1], norm[1], log_sparse[1], "Conv_sparse"));
+            step(layer(cont, ct_layer, num_blcs[0] + i, real_batch[1], real_batch[1], 1, false, pow_));
             printf("Block2, Layer  %d done!\n", i);
         }
         printf("Block2 done.\n"); timings[2] = secs(start); start = now();
-        { const int w = num_blcs[0] + num_blcs[1] + 1;
-          step(evalConv_BNRelu_new_batch(cont, ct_layer, W(w, "conv", real_batch[1] * real_batch[2] * ker_size), W(w, "a", real_batch[2]), W(w, "b", real_batch[2]),
-                                         alpha, pow_, in_wids[1], raw_in_wids[2], ker_wid, real_batch[1], real_batch[2], norm[2], log_sparse[1] - 1, "StrConv_sparse")); }               // test.go:225
+        step(layer(cont, ct_layer, num_blcs[0] + num_blcs[1] + 1, real_batch[1], real_batch[2], 2, true, pow_));                        // test.go:225 / 513-529
         printf("Block2 to 3 done!\n"); timings[3] = secs(start); start = now();
         for (int i = 1; i <= num_blcs[2]; i++) {                                                         // ResNet Block 3
-            const int w = num_blcs[0] + num_blcs[1] + i + 1;
             if (i == num_blcs[2]) pow_ = final_pow;
-            step(evalConv_BNRelu_new_batch(cont, ct_layer, W(w, "conv", real_batch[2] * real_batch[2] * ker_size), W(w, "a", real_batch[2]), W(w, "b", real_batch[2]),
-                                           alpha, pow_, in_wids[2], raw_in_wids[2], ker_wid, real_batch[2], real_batch[2], norm[2], log_sparse[2], "Conv_sparse"));
+            step(layer(cont, ct_layer, num_blcs[0] + num_blcs[1] + i + 1, real_batch[2], real_batch[2], 2, false, pow_));
             printf("Block3, Layer  %d done!\n", i);
         }
         printf("Block3 done.\n"); timings[4] = secs(start); start = now();
 
-        int ker_inf_wid = raw_in_wids[2]; if (ker_inf_wid % 2 == 0) ker_inf_wid++;                       // test.go:279-334: reduce_mean + FC
+        const int fb = fast ? 0 : 2;                                                                     // the grid the FC convolution runs on (fast: test.go:555-600)
+        int ker_inf_wid = raw_in_wids[(size_t)fb]; if (ker_inf_wid % 2 == 0) ker_inf_wid++;             // test.go:279-334: reduce_mean + FC
         std::vector<double> ker_inf = readTxt(weight_dir + "final-fckernel.csv", real_batch[2] * fc_out);
         std::vector<double> bn_bf = readTxt(weight_dir + "final-fcbias.csv", fc_out);
         std::vector<Ciphertext> ct_result;
@@ -234,14 +254,14 @@ void testResNet_crop_sparse(int st, int end, int ker_wid, int depth, bool debug)
             std::vector<double> ker_inf_((size_t)(ker_inf_wid * ker_inf_wid * real_batch[2] * fc_out));
             for (size_t i = 0; i < ker_inf.size(); i++) for (int b = 0; b < ker_inf_wid * ker_inf_wid; b++) ker_inf_[i + (size_t)b * real_batch[2] * fc_out] = ker_inf[i];
             std::vector<double> bn_af((size_t)fc_out, 1.0 / (double)(raw_in_wids[2] * raw_in_wids[2]));
-            ct_result = evalConv_BN_batch(cont, ct_layer, ker_inf_, bn_af, bn_bf, in_wids[2], ker_inf_wid, real_batch[2], fc_out, norm[2], (double)(1 << 30), false);
+            ct_result = evalConv_BN_batch(cont, ct_layer, ker_inf_, bn_af, bn_bf, in_wids[(size_t)fb], ker_inf_wid, real_batch[2], fc_out, norm[2], (double)(1 << 30), false);
         }
         printf("Final FC done.\n"); timings[5] = secs(start); start = now();
         printf("\n===============  DECRYPTION  ===============\n\n");
         for (int z = 0; z < nimg; z++) {
             std::vector<double> res_tmp = DecryptDecodeCoeffs(cont, ct_result[(size_t)z]);
             printf("Decryption Done in %s \n", dur(start).c_str());
-            std::vector<double> res_out = prt_mat_one_norm(res_tmp, max_batch[2], norm[2], ker_inf_wid / 2 + 1, ker_inf_wid / 2 + 1);
+            std::vector<double> res_out = prt_mat_one_norm(res_tmp, max_batch[fb], norm[2], ker_inf_wid / 2 + 1, ker_inf_wid / 2 + 1);
             res_out.resize((size_t)fc_out);
             printf("\n result:  ["); for (double v : res_out) printf("%.10f ", v);
             printf("]\n");
@@ -259,5 +279,7 @@ void testResNet_crop_sparse(int st, int end, int ker_wid, int depth, bool debug)
     // all contexts were ready at t_go; context release is included in the figure below (a few hipFree), image work dominates
     printf("All %d images done in %s  (%d image threads)\n", end - st, dur(t_go).c_str(), n_threads);
 }
+void testResNet_crop_sparse(int st, int end, int ker_wid, int depth, bool debug) { (void)debug; testResNet_crop(st, end, ker_wid, depth, false); }
+void testResNet_crop_fast_in(int st, int end, int ker_wid, int depth, bool debug) { (void)debug; testResNet_crop(st, end, ker_wid, depth, true); }
 
 }  // namespace hconv
