@@ -124,6 +124,15 @@ HC_HD u64 hc_mont(u64 a, u64 b, u64 q, u64 qinv) {
     u64 r = hi - h;
     return hi < h ? r + q : r;
 }
+// x*w mod q, lazy, for ANY 64-bit x and a FIXED operand kept as ONE 8-byte word wm = w * 2^64 mod q in [0, q) (Montgomery form) - half the bytes of a Shoup pair, for
+// the kernels that wait on their operand loads and not on the VALU (hc_k_b5m's epilogue). With m = x * wm = hi * 2^64 + lo and h = mulhi(lo * qinv, q):
+// (lo * qinv) * q = h * 2^64 + lo exactly, so x * wm - (lo * qinv) * q = (hi - h) * 2^64 and hi - h is congruent to x * w. hi <= (2^64 - 1)(q - 1) / 2^64 < q - 1 and
+// h <= q - 1, so hi - h lies in (-q, q) and the result hi + q - h in [1, 2q - 1]: inside hc_shoup4's [0, 4q), so it can stand wherever a hc_shoup4 product stood.
+// Needs only 2q < 2^64 (every accepted modulus). hc_mont without its final select. Both high halves are EXACT (the short hc_mulhi_lo2 would break the identity above).
+HC_HD u64 hc_mont_lazy(u64 x, u64 wm, u64 q, u64 qinv) {
+    const u128 m = (u128)x * wm;
+    return (u64)(m >> 64) + q - hc_mulhi((u64)m * qinv, q);
+}
 // Montgomery reduction of an ACCUMULATED 128-bit sum T = sum a_d * b_d (Montgomery operands as hc_mont takes them): T * 2^-64 mod q, canonical. Needs T < q * 2^64
 // (seven products of residues below 2^61 at most): then (T >> 64) - mulhi(lo * qinv, q) lies in (-q, q), as in hc_mont. Equal to the modular sum of the hc_mont results.
 HC_HD u64 hc_mont_redc(u128 T, u64 q, u64 qinv) {

@@ -218,6 +218,9 @@ template <bool KC = false> struct HcRowsTwA { const HcTw *p; __device__ __forcei
 #ifndef HC_DBG_TWB_FIXED
 #define HC_DBG_TWB_FIXED 0          // timing probe only (WRONG residues): every per-thread twiddle of a rows pass is the slot-0 one - what the 60 KiB of per-thread twiddles per tile cost
 #endif
+#if HC_DBG_TWB_FIXED
+#warning "HC_DBG_TWB_FIXED is set: a TIMING PROBE build - every residue that goes through a rows pass is WRONG"
+#endif
 template <bool KC = false> struct HcRowsTwB { const HcTw *p; __device__ __forceinline__ HcTw operator()(int slot) const { if (HC_DBG_TWB_FIXED) slot = 0; if (KC) return HC_TW_LOADK(p, slot * 16); else return HC_TW_LOAD(p, slot * 16); } };
 
 // forward rows pass on registers: in  e[hi] = element (row, hi*16+tid)  [lazy < 4q]
@@ -1008,6 +1011,9 @@ struct HcLoopB {
     const HcTw *idx;     // [N]             idx[s] plaintext, natural order
     const HcTw *evkQ;    // [2][N]          b_Q * P^-1, a_Q * P^-1 mod Q0, natural order
     const HcTw *evkP;    // [2][N]          b_P * N^-1, a_P * N^-1 mod P in lo-local-coalesced order (hc_k_b3)
+    // the same idx and evkQ residues as single 8-byte words in Montgomery form (w * 2^64 mod Q0, natural order) for hc_k_b5m, whose epilogue waits on its operand loads: hc_mont_lazy
+    const u64 *idxM;     // [N]
+    const u64 *evkQM;    // [2][N]
     int n0, step, norm;  // first node of this chunk
     int nodes;           // nodes of this launch per ciphertext (HC_JOB = z * nodes + node for a batch)
     size_t src_stride, dst_stride;   // distance between the ciphertext arrays of consecutive batch members (u64 words)
@@ -1205,300 +1211,126 @@ __global__ __launch_bounds__(HC_TPB, 3) void hc_k_b5(HcLoopB B, HcTwTab T0fwd, H
     }
 }
 
-// KB5M: one workgroup per (node, tile) does BOTH polynomials, k = 1 first: grid = (batch*nodes, 16). Row-local permutations only
-// (galEl = 2^j + 1, j >= 9). Against two hc_k_b5 jobs: t2.c1 = y1 - I*x1 is recomputed from x1, y1 and idx in the k = 1 epilogue (the very
-// expression b1 fed into the key switch) and kept in registers for k = 0 (168 VGPRs, 3 waves per SIMD). Round 4 measured the alternative the review asked for - t2.c1 re-derived in the k = 0
-// epilogue from x1 / y1: 127 VGPRs, 4 waves per SIMD, no scratch - at +0.3 % conv/s but +6 % fabric traffic (x1, y1 are not L2-hot a transform later: 563 MiB read per
-// launch against 428): not kept (profiles/round4_conv33_b5m_ab.txt, round4_conv33_counters_b5m_recompute.txt), so b1 does not write tmpT and nobody reads it (1.5 MiB less
-// per node: 0.5 written, 2 x 0.5 read, against 0.5 more for x1), and idx is read once per node. Per row batch of either polynomial:
-//   k = 1: m1 = I*x1 ; T = y1 - m1 ; t1 = y1 + m1 ; F = (a_Q/P)*T                      k = 0: m = I*x0 ; t1 = y0 + m ; F = y0 - m + (b_Q/P)*T
-//   d = F - n_k (n_k = rows-forward of the k-th extension, divided by P by b4) ; through the LDS row ; dst = reduce(t1 + perm(d)) (+ bias, k = 0)
+// KB5M: one workgroup per (node, tile) does BOTH polynomials AT ONCE: grid = (batch*nodes, 16). Row-local permutations only (galEl = 2^j + 1, j >= 9).
+// Against two hc_k_b5 jobs: t2.c1 = y1 - I*x1 is recomputed from x1, y1 and idx (the very expression b1 fed into the key switch), so b1 does not write tmpT and
+// nobody reads it (round 3; round 4 measured re-deriving it a second time instead of carrying it: +6 % fabric traffic, not kept - profiles/round4_conv33_b5m_ab.txt).
+// The kernel waits on its loads, not on the VALU (VALU pipe 41 %, SQ_WAIT_ANY 58 %, 14.3 M L1->L2 read requests per launch, 62 % of them L2 hits on fixed tables), so
+// its shape follows the bytes a workgroup sends through the CU's address unit (profiles/b5m_request_stream_*.txt: 576 -> 352 KiB per workgroup, -37 % requests, -15 % time):
+//  * both rows-forward transforms run together on two register tiles and two LDS tiles (hc_rows_fwd2_lin): same 16 rows, same modulus, so every twiddle is loaded ONCE
+//    for both (64 KiB of per-thread twiddles instead of 128); 64 KiB of LDS, two workgroups per CU (the kernel measured the same at 2, 3 and 4), 126-159 VGPRs, no scratch;
+//  * the two fixed multiplicands (idx, the key's Q rows) are read as ONE 8-byte Montgomery word each (B.idxM, B.evkQM; hc_mont_lazy) instead of 16-byte Shoup pairs,
+//    ~12 more VALU instructions per product, and idx is read once for both polynomials;
+//  * one epilogue over the row batches does both polynomials, so t2.c1 lives for one batch and not across a transform.
+// Per row batch:
+//   m_k = I*x_k ; T = y1 - m1 ; t1_k = y_k + m_k (+ bias, k = 0) ; F_1 = (a_Q/P)*T ; F_0 = y0 - m0 + (b_Q/P)*T
+//   d_k = F_k - n_k (n_k = rows-forward of the k-th extension, divided by P by b4) ; through the LDS row of tile k ; dst_k = reduce(t1_k + perm(d_k))
+// Both kinds of product lie in (0, 2q), inside the [0, 4q) of hc_shoup4 that the lazy accounting was made for: FREE mode (Q0 < 2^57) t1 < 4q, T < 4q, d < 79q,
+// t1 + d < 83q < 2^64, one hc_reduce64 at the end; ALT mode works on canonical terms.
 #ifndef HC_B5_ROWS
-#define HC_B5_ROWS 2                  // rows per epilogue batch of hc_k_b5m
-#endif
-#ifndef HC_B5M_UNROLL
-#define HC_B5M_UNROLL 2
+#define HC_B5_ROWS 4                  // rows per epilogue batch of hc_k_b5m, both polynomials: 4 x 7 operand loads in flight per thread and barrier (2 rows: 783 against 789 conv/s; 159 VGPRs at 4, 126 at 2)
 #endif
 #ifndef HC_B5M_WAVES
-#define HC_B5M_WAVES 3
+#define HC_B5M_WAVES 2                // 64 KiB of LDS per workgroup: two workgroups per CU (the one-tile form measured the same at 2, 3 and 4)
 #endif
-#ifndef HC_B5M_PIPE
-#define HC_B5M_PIPE 0
-#endif
-// `#pragma unroll MACRO` is not expanded in the second phase of `hipcc -save-temps` (the macro is gone from the preprocessed file): _Pragma is expanded by the preprocessor itself
-#define HC_PRAGMA_(x) _Pragma(#x)
-#define HC_UNROLL_N(n) HC_PRAGMA_(unroll n)
+// Both transforms of a workgroup run over the same 16 rows modulo Q0, i.e. with the same twiddles: hc_ct_round on TWO register tiles, every twiddle loaded once
+template <int FM, class TW>
+__device__ __forceinline__ void hc_ct_round2(u64 (&e0)[16], u64 (&e1)[16], const TW &tw, const HcQ &Q) {
+#pragma unroll
+    for (int s = 0; s < 4; s++) {
+        const int half = 8 >> s;
+#pragma unroll
+        for (int g = 0; g < (1 << s); g++) {
+            const HcTw w = tw((1 << s) - 1 + g);
+#pragma unroll
+            for (int k = 0; k < half; k++) {
+                const int a = g * 2 * half + k, b = a + half;
+                u64 X0 = e0[a], X1 = e1[a];
+                if (FM == HC_FM_ALT) { X0 = hc_fold(X0, Q.nq4); X1 = hc_fold(X1, Q.nq4); }
+                const u64 T0 = hc_shoup4(e0[b], w.w, w.ws, Q), T1 = hc_shoup4(e1[b], w.w, w.ws, Q);
+                e0[a] = X0 + T0; e0[b] = (X0 + Q.q4) - T0;
+                e1[a] = X1 + T1; e1[b] = (X1 + Q.q4) - T1;
+            }
+        }
+    }
+}
+// hc_rows_fwd on two polynomials (tiles l0, l1 of LDS), then hc_rows_lo_to_lin on both: out e_k[kk] = n_k at (row kk, column t)
+template <int FM>
+__device__ __forceinline__ void hc_rows_fwd2_lin(u64 (&e0)[16], u64 (&e1)[16], u64 *l0, u64 *l1, const HcTwTab &T, int row, int rloc, int tid, int t, const HcQ &Q) {
+    hc_ct_round2<FM>(e0, e1, HcRowsTwA<false>{T.rowsA + row * 16}, Q);
+#pragma unroll
+    for (int hi = 0; hi < 16; hi++) { const int a = hc_rows_lds(rloc, hi * 16 + tid); l0[a] = e0[hi]; l1[a] = e1[hi]; }
+    HC_ROW_SYNC();
+#pragma unroll
+    for (int lo = 0; lo < 16; lo++) { const int a = hc_rows_lds(rloc, tid * 16 + lo); e0[lo] = l0[a]; e1[lo] = l1[a]; }
+    hc_ct_round2<FM>(e0, e1, HcRowsTwB<false>{T.rowsB + row * 256 + tid}, Q);
+    HC_ROW_SYNC();        // row-local: the reads before and the writes after stay inside the 16 lanes of a row
+#pragma unroll
+    for (int lo = 0; lo < 16; lo++) { const int a = hc_rows_lds(rloc, tid * 16 + lo); l0[a] = e0[lo]; l1[a] = e1[lo]; }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < 16; k++) { const int a = hc_rows_lds(k, t); e0[k] = l0[a]; e1[k] = l1[a]; }
+}
 template <int FM>
 __global__ __launch_bounds__(HC_TPB, HC_B5M_WAVES) void hc_k_b5m(HcLoopB B, HcTwTab T0fwd, HcPtrs biases, HcPtrs outs) {
-    __shared__ u64 lds[HC_ROWS_LDS];
+    __shared__ u64 lds[2 * HC_ROWS_LDS];
+    u64 *l0 = lds, *l1 = lds + HC_ROWS_LDS;
     const int t = threadIdx.x, tid = t & 15, rloc = t >> 4, row = HC_TILE * 16 + rloc;
     const int zn = HC_JOB, z = zn / B.nodes, node = zn - z * B.nodes, i = (B.n0 + node) * B.norm;
     const HcQ Q = hc_q(B.m0.q);
-    const u64 q = Q.q;
+    const u64 q = Q.q, qinv = B.m0.qinv;
     const size_t tile = (size_t)HC_TILE * 4096 + t;
     const u64 *__restrict__ ys = B.src + (size_t)z * B.src_stride + (size_t)i * 2 * 65536 + tile;                  // y_k = ys[k * 65536 + ...]
     const u64 *__restrict__ xs = B.src + (size_t)z * B.src_stride + (size_t)(i + B.step) * 2 * 65536 + tile;
-    const HcTw *__restrict__ idx = B.idx + tile;
-    const HcTw *__restrict__ evk = B.evkQ + tile;                                                                  // b_Q/P, then a_Q/P 65536 pairs on
+    const u64 *__restrict__ idx = B.idxM + tile;                                                                   // the 8-byte Montgomery words of idx and of the key's Q rows
+    const u64 *__restrict__ evk = B.evkQM + tile;                                                                  // b_Q/P, then a_Q/P 65536 words on
     u64 *__restrict__ o = (outs.p[z] != nullptr ? const_cast<u64 *>(outs.p[z]) : B.dst + (size_t)z * B.dst_stride + (size_t)i * 2 * 65536) + tile;
     const u64 *__restrict__ bias = biases.p[z] != nullptr ? biases.p[z] + tile : nullptr;        // null except on the last node of the tree (eval.go:258)
-    u64 e[16], T[16];
-#if HC_B5M_PIPE
-    // software-pipelined epilogue: the operands of row batch 0 are requested BEFORE the transform of the polynomial (their round trip hides behind the
-    // butterflies instead of following them), and every later batch is requested before the batch in front of it is worked on
-    HC_UNROLL_N(HC_B5M_UNROLL)
-    for (int k = 1; k >= 0; k--) {
-        const u64 *__restrict__ in = B.tmpE + ((size_t)zn * 2 + k) * 65536 + (size_t)row * 256;
+    u64 e0[16], e1[16];
+    {
+        const u64 *__restrict__ in = B.tmpE + (size_t)zn * 2 * 65536 + (size_t)row * 256;
 #pragma unroll
-        for (int hi = 0; hi < 16; hi++) e[hi] = in[hi * 16 + tid];
-        u64 Yn[HC_B5_ROWS], Xn[HC_B5_ROWS], bn[HC_B5_ROWS]; HcTw Kn[HC_B5_ROWS], In[HC_B5_ROWS];
+        for (int hi = 0; hi < 16; hi++) { e0[hi] = in[hi * 16 + tid]; e1[hi] = in[65536 + hi * 16 + tid]; }
+    }
+    hc_rows_fwd2_lin<FM>(e0, e1, l0, l1, T0fwd, row, rloc, tid, t, Q);
+    __syncthreads();
+#pragma unroll
+    for (int b = 0; b < 16; b += HC_B5_ROWS) {
+        u64 Y0[HC_B5_ROWS], X0[HC_B5_ROWS], Y1[HC_B5_ROWS], X1[HC_B5_ROWS], K0[HC_B5_ROWS], K1[HC_B5_ROWS], I[HC_B5_ROWS], bs[HC_B5_ROWS], s0[HC_B5_ROWS], s1[HC_B5_ROWS];
 #pragma unroll
         for (int j = 0; j < HC_B5_ROWS; j++) {
-            const int off = j * 256;
-            Yn[j] = ys[(size_t)k * 65536 + off]; Xn[j] = xs[(size_t)k * 65536 + off]; In[j] = idx[off]; Kn[j] = evk[(size_t)k * 65536 + off];
-            bn[j] = (k == 0 && bias != nullptr) ? bias[off] : 0;
+            const int off = (b + j) * 256;
+            Y1[j] = ys[65536 + off]; X1[j] = xs[65536 + off]; Y0[j] = ys[off]; X0[j] = xs[off]; I[j] = idx[off]; K0[j] = evk[off]; K1[j] = evk[65536 + off];
+            bs[j] = bias != nullptr ? bias[off] : 0;
         }
-        if (k == 0) __syncthreads();                      // the last gather of k = 1 is done before the transform writes LDS again
-        hc_rows_fwd<FM>(e, lds, T0fwd, row, rloc, tid, Q);
-        HC_ROW_SYNC();
-        hc_rows_lo_to_lin(e, lds, t, rloc, tid);          // e[kk] = n_k at (row kk, column t)
+#pragma unroll
+        for (int j = 0; j < HC_B5_ROWS; j++) {
+            const int kk = b + j, a = hc_rows_lds(kk, t);
+            u64 m1 = hc_mont_lazy(X1[j], I[j], q, qinv), m0 = hc_mont_lazy(X0[j], I[j], q, qinv);            // I * x_k, in (0, 2q)
+            const u64 T = hc_fold(Y1[j] + Q.q4 - m1, Q.nq4);                                               // t2.c1 (conv.go:288-289) as b1 formed it, lazy < 4q
+            u64 g1 = hc_mont_lazy(T, K1[j], q, qinv), g0 = hc_mont_lazy(T, K0[j], q, qinv);                  // (key row / P) * t2.c1, in (0, 2q)
+            if (FM == HC_FM_FREE) {
+                s1[j] = Y1[j] + m1; s0[j] = Y0[j] + m0 + bs[j];                                            // conv.go:290 (+ bias), < 4q
+                l1[a] = g1 + HC_FREE_OFF * q - e1[kk];                                                     // (key switch)_1 - n_1: positive (n_k < 70q), < 74q
+                l0[a] = Y0[j] + Q.q4 - m0 + g0 + HC_FREE_OFF * q - e0[kk];                                 // t2.c0 + (key switch)_0 - n_0: positive, < 79q
+            } else {
+                m1 = hc_canon4(m1, Q); m0 = hc_canon4(m0, Q); g1 = hc_canon4(g1, Q); g0 = hc_canon4(g0, Q);
+                s1[j] = hc_addmod(Y1[j], m1, q); s0[j] = hc_addmod(hc_addmod(Y0[j], m0, q), bs[j], q);
+                l1[a] = hc_submod(g1, hc_canon8(e1[kk], Q), q);
+                l0[a] = hc_submod(hc_addmod(hc_submod(Y0[j], m0, q), g0, q), hc_canon8(e0[kk], Q), q);
+            }
+        }
         __syncthreads();
 #pragma unroll
-        for (int b = 0; b < 16; b += HC_B5_ROWS) {
-            u64 Y[HC_B5_ROWS], X[HC_B5_ROWS], t1[HC_B5_ROWS], bs[HC_B5_ROWS]; HcTw K[HC_B5_ROWS], I[HC_B5_ROWS];
-#pragma unroll
-            for (int j = 0; j < HC_B5_ROWS; j++) { Y[j] = Yn[j]; X[j] = Xn[j]; I[j] = In[j]; K[j] = Kn[j]; bs[j] = bn[j]; }
-            if (b + HC_B5_ROWS < 16) {
-#pragma unroll
-                for (int j = 0; j < HC_B5_ROWS; j++) {
-                    const int off = (b + HC_B5_ROWS + j) * 256;
-                    Yn[j] = ys[(size_t)k * 65536 + off]; Xn[j] = xs[(size_t)k * 65536 + off]; In[j] = idx[off]; Kn[j] = evk[(size_t)k * 65536 + off];
-                    bn[j] = (k == 0 && bias != nullptr) ? bias[off] : 0;
-                }
-            }
-#pragma unroll
-            for (int j = 0; j < HC_B5_ROWS; j++) {
-                const int kk = b + j;
-                u64 m = hc_shoup4(X[j], I[j].w, I[j].ws, Q), f;
-                if (k == 1) T[kk] = hc_fold(Y[j] + Q.q4 - m, Q.nq4);
-                u64 g = hc_shoup4(T[kk], K[j].w, K[j].ws, Q);
-                if (FM == HC_FM_FREE) {
-                    t1[j] = Y[j] + m + bs[j];
-                    f = (k == 0 ? Y[j] + Q.q4 - m + g : g) + HC_FREE_OFF * q - e[kk];
-                } else {
-                    m = hc_canon4(m, Q); g = hc_canon4(g, Q);
-                    t1[j] = hc_addmod(hc_addmod(Y[j], m, q), bs[j], q);
-                    f = hc_submod(k == 0 ? hc_addmod(hc_submod(Y[j], m, q), g, q) : g, hc_canon8(e[kk], Q), q);
-                }
-                lds[hc_rows_lds(kk, t)] = f;
-            }
-            __syncthreads();
-#pragma unroll
-            for (int j = 0; j < HC_B5_ROWS; j++) {
-                const int kk = b + j;
-                const u32 srcidx = hc_perm_src((u32)((HC_TILE * 16 + kk) * 256 + t), B.gal);
-                const u64 d = lds[hc_rows_lds(kk, (int)(srcidx & 255))];
-                o[(size_t)k * 65536 + kk * 256] = FM == HC_FM_FREE ? hc_reduce64(t1[j] + d, B.m0.mu, Q) : hc_addmod(t1[j], d, q);
-            }
+        for (int j = 0; j < HC_B5_ROWS; j++) {
+            const int kk = b + j;
+            const u32 srcidx = hc_perm_src((u32)((HC_TILE * 16 + kk) * 256 + t), B.gal);
+            const int a = hc_rows_lds(kk, (int)(srcidx & 255));                                            // the source is in the same row
+            const u64 d1 = l1[a], d0 = l0[a];
+            o[65536 + kk * 256] = FM == HC_FM_FREE ? hc_reduce64(s1[j] + d1, B.m0.mu, Q) : hc_addmod(s1[j], d1, q);
+            o[kk * 256] = FM == HC_FM_FREE ? hc_reduce64(s0[j] + d0, B.m0.mu, Q) : hc_addmod(s0[j], d0, q);
         }
     }
-#else
-    HC_UNROLL_N(HC_B5M_UNROLL)
-    for (int k = 1; k >= 0; k--) {
-        const u64 *__restrict__ in = B.tmpE + ((size_t)zn * 2 + k) * 65536 + (size_t)row * 256;
-#pragma unroll
-        for (int hi = 0; hi < 16; hi++) e[hi] = in[hi * 16 + tid];
-        if (k == 0) __syncthreads();                      // the last gather of k = 1 is done before the transform writes LDS again
-        hc_rows_fwd<FM>(e, lds, T0fwd, row, rloc, tid, Q);
-        HC_ROW_SYNC();        // row-local: the reads before and the writes after stay inside the 16 lanes of a row
-        hc_rows_lo_to_lin(e, lds, t, rloc, tid);          // e[kk] = n_k at (row kk, column t)
-        __syncthreads();
-#pragma unroll
-        for (int b = 0; b < 16; b += HC_B5_ROWS) {
-            u64 Y[HC_B5_ROWS], X[HC_B5_ROWS], t1[HC_B5_ROWS], bs[HC_B5_ROWS]; HcTw K[HC_B5_ROWS], I[HC_B5_ROWS];
-#pragma unroll
-            for (int j = 0; j < HC_B5_ROWS; j++) {
-                const int off = (b + j) * 256;
-                Y[j] = ys[(size_t)k * 65536 + off]; X[j] = xs[(size_t)k * 65536 + off]; I[j] = idx[off]; K[j] = evk[(size_t)k * 65536 + off];
-                bs[j] = (k == 0 && bias != nullptr) ? bias[off] : 0;
-            }
-#pragma unroll
-            for (int j = 0; j < HC_B5_ROWS; j++) {
-                const int kk = b + j;
-                u64 m = hc_shoup4(X[j], I[j].w, I[j].ws, Q), f;                                            // I * x_k, < 4q
-                if (k == 1) T[kk] = hc_fold(Y[j] + Q.q4 - m, Q.nq4);                                       // t2.c1 (conv.go:288-289) as b1 formed it, lazy < 4q
-                u64 g = hc_shoup4(T[kk], K[j].w, K[j].ws, Q);                                              // (key row / P) * t2.c1, < 4q
-                if (FM == HC_FM_FREE) {
-                    t1[j] = Y[j] + m + bs[j];                                                              // conv.go:290 (+ bias), < 6q
-                    f = (k == 0 ? Y[j] + Q.q4 - m + g : g) + HC_FREE_OFF * q - e[kk];                      // t2.c_k + (key switch)_k - n_k, < 81q
-                } else {
-                    m = hc_canon4(m, Q); g = hc_canon4(g, Q);
-                    t1[j] = hc_addmod(hc_addmod(Y[j], m, q), bs[j], q);
-                    f = hc_submod(k == 0 ? hc_addmod(hc_submod(Y[j], m, q), g, q) : g, hc_canon8(e[kk], Q), q);
-                }
-                lds[hc_rows_lds(kk, t)] = f;
-            }
-            __syncthreads();
-#pragma unroll
-            for (int j = 0; j < HC_B5_ROWS; j++) {
-                const int kk = b + j;
-                const u32 srcidx = hc_perm_src((u32)((HC_TILE * 16 + kk) * 256 + t), B.gal);
-                const u64 d = lds[hc_rows_lds(kk, (int)(srcidx & 255))];                                   // the source is in the same row
-                o[(size_t)k * 65536 + kk * 256] = FM == HC_FM_FREE ? hc_reduce64(t1[j] + d, B.m0.mu, Q) : hc_addmod(t1[j], d, q);
-            }
-        }
-    }
-#endif
 }
-
-// ---------------------------------------------------------------- KB5M with a LOADER wavefront (round 6 probe)
-// hc_k_b5m's epilogue is sixteen dependent round trips per workgroup (load two rows' operands -> wait -> multiply -> barrier -> store; the ISA shows exactly that order), and
-// what a CU keeps in flight - at best one 24 KiB row batch per resident workgroup - is what its fabric rate comes to (3.5 TB/s of the ~6 achievable). Register prefetch cannot
-// decouple it (round 5: HC_B5M_PIPE, +0.3 %): one batch of lookahead is 0.2 us of arithmetic against a 2-3 us round trip, and more batches do not fit the register file.
-// Here a FIFTH wavefront does nothing but `global_load_lds_dwordx4` (LDS-DMA: no VGPR destination, its own vmcnt) the epilogue operands of BOTH polynomials - y_k, x_k, the
-// idx pair and the key pair of a row: 48 bytes per coefficient, 12 KiB = twelve 1 KiB wave-instructions per row - into a ring of HC_LD_RING one-row slots behind the 32 KiB
-// tile; the four transform wavefronts read their operands from LDS and wait on global memory only for the transform's own tile and twiddles. The ring runs across the two
-// polynomials: while the transform wavefronts are in the second transform the loader already holds the first rows of its epilogue. Barrier protocol (every wavefront executes
-// the same 3 + 16 / R barriers per polynomial, + 1 in front of k = 0): a slot is refilled after the barrier that follows its last read; before the barrier that precedes the
-// first read of a row the loader waits until that row has landed (vmcnt is in order: rows issued - rows needed, x 12 instructions). LDS: 32 + HC_LD_RING x 12 KiB = 80 KiB:
-// two workgroups per CU (ten wavefronts).
-#ifndef HC_B5M_LOADER
-#define HC_B5M_LOADER 0
-#endif
-#if HC_B5M_LOADER && !defined(HC_EMU)
-#ifndef HC_LD_RING
-#define HC_LD_RING 4                  // one-row slots (each 1536 u64 words: y 256, x 256, idx pairs 512, key pairs 512)
-#endif
-#ifndef HC_LD_AUX
-#define HC_LD_AUX 0                   // cache policy bits of the LDS-DMA loads (2 = nt)
-#endif
-#define HC_LD_SLOT 1536
-#define HC_LD_TPB (HC_TPB + 64)
-typedef const void __attribute__((address_space(1))) *HcGlobalVoidPtr;
-typedef void __attribute__((address_space(3))) *HcLdsVoidPtr;
-// s_waitcnt vmcnt(n) needs an immediate: the callers' loops are fully unrolled, so n is a constant by the time this switch is compiled and one case survives
-__device__ __forceinline__ void hc_wait_vmcnt(int n) {
-#define HC_VMC(k) case k: asm volatile("s_waitcnt vmcnt(" #k ")" ::: "memory"); break;
-    switch (n) { HC_VMC(0) HC_VMC(12) HC_VMC(24) HC_VMC(36) HC_VMC(48) HC_VMC(60) default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break; }
-#undef HC_VMC
-}
-// one row (k = polynomial, kk = row of the tile) of epilogue operands into slot `slot`: 12 wave-instructions of 1 KiB
-__device__ __forceinline__ void hc_ld_row(u64 *ring, int slot, const u64 *ys, const u64 *xs, const HcTw *idx, const HcTw *evk, int k, int kk, int lane) {
-    u64 *s = ring + slot * HC_LD_SLOT;
-    const u64 *y = ys + (size_t)k * 65536 + kk * 256 + lane * 2, *x = xs + (size_t)k * 65536 + kk * 256 + lane * 2;
-    const HcTw *I = idx + kk * 256 + lane, *K = evk + (size_t)k * 65536 + kk * 256 + lane;
-#pragma unroll
-    for (int h = 0; h < 2; h++) {
-        __builtin_amdgcn_global_load_lds((HcGlobalVoidPtr)(y + h * 128), (HcLdsVoidPtr)(s + h * 128), 16, 0, HC_LD_AUX);
-        __builtin_amdgcn_global_load_lds((HcGlobalVoidPtr)(x + h * 128), (HcLdsVoidPtr)(s + 256 + h * 128), 16, 0, HC_LD_AUX);
-    }
-#pragma unroll
-    for (int h = 0; h < 4; h++) {
-        __builtin_amdgcn_global_load_lds((HcGlobalVoidPtr)(I + h * 64), (HcLdsVoidPtr)(s + 512 + h * 128), 16, 0, 0);
-        __builtin_amdgcn_global_load_lds((HcGlobalVoidPtr)(K + h * 64), (HcLdsVoidPtr)(s + 1024 + h * 128), 16, 0, 0);
-    }
-}
-// rows are numbered 0..31 through both polynomials (k = 1 first): row g is (k = g < 16, kk = g & 15) and lives in slot g % HC_LD_RING
-__device__ __forceinline__ void hc_ld_rows(int g0, int g1, u64 *ring, const u64 *ys, const u64 *xs, const HcTw *idx, const HcTw *evk, int lane) {
-#pragma unroll
-    for (int g = g0; g < g1; g++)
-        if (g < 32) hc_ld_row(ring, g % HC_LD_RING, ys, xs, idx, evk, g < 16 ? 1 : 0, g & 15, lane);
-}
-constexpr int hc_ld_min(int a, int b) { return a < b ? a : b; }
-template <int FM>
-__global__ __launch_bounds__(HC_LD_TPB, 3) void hc_k_b5m_ld(HcLoopB B, HcTwTab T0fwd, HcPtrs biases, HcPtrs outs) {
-    __shared__ u64 lds[HC_ROWS_LDS + HC_LD_RING * HC_LD_SLOT];
-    u64 *ring = lds + HC_ROWS_LDS;
-    constexpr int R = HC_B5_ROWS, S = HC_LD_RING, NBAT = 16 / R;
-    static_assert(S >= 2 * R && S % R == 0 && (S - R) * 12 <= 60, "ring: at least two row batches, a whole number of them, and a vmcnt that fits its 6-bit field");
-    const int zn = HC_JOB, z = zn / B.nodes, node = zn - z * B.nodes, i = (B.n0 + node) * B.norm;
-    const size_t tile0 = (size_t)HC_TILE * 4096;
-    const u64 *__restrict__ ys0 = B.src + (size_t)z * B.src_stride + (size_t)i * 2 * 65536 + tile0;
-    const u64 *__restrict__ xs0 = B.src + (size_t)z * B.src_stride + (size_t)(i + B.step) * 2 * 65536 + tile0;
-    if (threadIdx.x >= HC_TPB) {
-        // ---- the loader wavefront
-        const int lane = threadIdx.x - HC_TPB;
-        const HcTw *idx0 = B.idx + tile0, *evk0 = B.evkQ + tile0;
-        hc_ld_rows(0, S, ring, ys0, xs0, idx0, evk0, lane);
-#pragma unroll
-        for (int k = 1; k >= 0; k--) {
-            const int gb0 = (1 - k) * NBAT;                                   // first row batch of this polynomial
-            if (k == 0) __builtin_amdgcn_s_barrier();                         // in front of the second transform
-            __builtin_amdgcn_s_barrier();                                     // inside hc_rows_lo_to_lin
-            hc_wait_vmcnt((hc_ld_min(gb0 * R + S, 32) - (gb0 + 1) * R) * 12); // the first row batch of this polynomial has landed (rows issued - rows needed)
-            __builtin_amdgcn_s_barrier();                                     // behind hc_rows_lo_to_lin: the epilogue starts
-#pragma unroll
-            for (int b = 0; b < NBAT; b++) {
-                // batch gb (rows gb R .. gb R + R - 1) is being read; rows up to gb R + S - 1 are issued. The next batch of the SAME polynomial must have landed before the
-                // barrier (the next polynomial's first batch is waited for above); behind the barrier the slots of batch gb are free: rows gb R + S .. go into them
-                const int gb = gb0 + b, left = hc_ld_min(gb * R + S, 32) - (gb + 2) * R;
-                if (b + 1 < NBAT) hc_wait_vmcnt(left < 0 ? 0 : left * 12);
-                __builtin_amdgcn_s_barrier();
-                hc_ld_rows(gb * R + S, gb * R + S + R, ring, ys0, xs0, idx0, evk0, lane);
-            }
-        }
-        return;
-    }
-    // ---- the four transform wavefronts: hc_k_b5m with the epilogue operands read from the ring
-    const int t = threadIdx.x, tid = t & 15, rloc = t >> 4, row = HC_TILE * 16 + rloc;
-    const HcQ Q = hc_q(B.m0.q);
-    const u64 q = Q.q;
-    u64 *__restrict__ o = (outs.p[z] != nullptr ? const_cast<u64 *>(outs.p[z]) : B.dst + (size_t)z * B.dst_stride + (size_t)i * 2 * 65536) + tile0 + t;
-    const u64 *__restrict__ bias = biases.p[z] != nullptr ? biases.p[z] + tile0 + t : nullptr;
-    u64 e[16], T[16];
-    HC_UNROLL_N(HC_B5M_UNROLL)
-    for (int k = 1; k >= 0; k--) {
-        const u64 *__restrict__ in = B.tmpE + ((size_t)zn * 2 + k) * 65536 + (size_t)row * 256;
-#pragma unroll
-        for (int hi = 0; hi < 16; hi++) e[hi] = in[hi * 16 + tid];
-        if (k == 0) __syncthreads();
-        hc_rows_fwd<FM>(e, lds, T0fwd, row, rloc, tid, Q);
-        HC_ROW_SYNC();
-        hc_rows_lo_to_lin(e, lds, t, rloc, tid);
-        __syncthreads();
-        // the bias (root node of a tree only) is the one global load left in the epilogue: a copy of the loop for it, so that the common copy never waits on vmcnt
-        // (a conditional load inside the loop made every batch wait for vmcnt(0), i.e. for the previous batch's stores as well)
-        auto epilogue = [&](auto HB) {
-            constexpr bool HASB = decltype(HB)::value;
-#pragma unroll
-            for (int b = 0; b < 16; b += R) {
-                u64 Y[R], X[R], t1[R], bs[R]; HcTw K[R], I[R];
-#pragma unroll
-                for (int j = 0; j < R; j++) {
-                    const u64 *s = ring + (((1 - k) * 16 + b + j) % S) * HC_LD_SLOT;
-                    Y[j] = s[t]; X[j] = s[256 + t]; I[j] = *reinterpret_cast<const HcTw *>(s + 512 + 2 * t); K[j] = *reinterpret_cast<const HcTw *>(s + 1024 + 2 * t);
-                    bs[j] = HASB ? bias[(b + j) * 256] : 0;
-                }
-#pragma unroll
-                for (int j = 0; j < R; j++) {
-                    const int kk = b + j;
-                    u64 m = hc_shoup4(X[j], I[j].w, I[j].ws, Q), f;
-                    if (k == 1) T[kk] = hc_fold(Y[j] + Q.q4 - m, Q.nq4);
-                    u64 g = hc_shoup4(T[kk], K[j].w, K[j].ws, Q);
-                    if (FM == HC_FM_FREE) {
-                        t1[j] = Y[j] + m + bs[j];
-                        f = (k == 0 ? Y[j] + Q.q4 - m + g : g) + HC_FREE_OFF * q - e[kk];
-                    } else {
-                        m = hc_canon4(m, Q); g = hc_canon4(g, Q);
-                        t1[j] = hc_addmod(hc_addmod(Y[j], m, q), bs[j], q);
-                        f = hc_submod(k == 0 ? hc_addmod(hc_submod(Y[j], m, q), g, q) : g, hc_canon8(e[kk], Q), q);
-                    }
-                    lds[hc_rows_lds(kk, t)] = f;
-                }
-                __syncthreads();
-#pragma unroll
-                for (int j = 0; j < R; j++) {
-                    const int kk = b + j;
-                    const u32 srcidx = hc_perm_src((u32)((HC_TILE * 16 + kk) * 256 + t), B.gal);
-                    const u64 d = lds[hc_rows_lds(kk, (int)(srcidx & 255))];
-                    o[(size_t)k * 65536 + kk * 256] = FM == HC_FM_FREE ? hc_reduce64(t1[j] + d, B.m0.mu, Q) : hc_addmod(t1[j], d, q);
-                }
-            }
-        };
-        if (k == 0 && bias != nullptr) epilogue(HcBool<true>{}); else epilogue(HcBool<false>{});
-    }
-}
-#endif
 
 // ================================================================ loop B for SMALL tree levels (round 3)
 // The top levels of a pack tree have 1..16 nodes: 16..256 workgroups for 256 CUs, one wave per SIMD, and a level costs the LATENCY of five
@@ -1879,6 +1711,9 @@ struct HcBasisExt {
 #endif
 #ifndef HC_DBG_EXT_ONELOAD
 #define HC_DBG_EXT_ONELOAD 0          // timing probe only (WRONG residues): the extension reads ONE of a coefficient's n + 1 operand words - what its 6x re-read of the y rows costs
+#endif
+#if HC_DBG_EXT_ONELOAD
+#warning "HC_DBG_EXT_ONELOAD is set: a TIMING PROBE build - the basis extensions compute WRONG residues"
 #endif
 #define HC_MAX_NP 5                    // most special primes of a context (hc_ctx_create refuses more): the extension's operand registers are sized by it (NS = 2 or HC_MAX_NP)
 // target side of the extension for one coefficient: y[0..n-1] = the y_i, y[n] = v. NS = the most source limbs the caller can have (the context's number of special primes:

@@ -101,7 +101,7 @@ struct HcModHost {
     HcTwTab inv_f64;             // moduli below 2^49: the inverse tables as {w, w/q} doubles (fp64 inverse transform of loop A)
     std::vector<void *> allocs;
 };
-struct HcEvk { HcTw *q_rows; HcTw *p_rows; bool row_local; bool row256; };   // row_local: the permutation stays inside 4096-coefficient tiles; row256: even inside 256-coefficient rows   // [2][N] each, Shoup pairs: q_rows (key / P mod Q0) natural order; p_rows (key / N mod P) lo-local order
+struct HcEvk { HcTw *q_rows; HcTw *p_rows; u64 *q_mont; bool row_local; bool row256; };   // row_local: the permutation stays inside 4096-coefficient tiles; row256: even inside 256-coefficient rows   // [2][N] each, Shoup pairs: q_rows (key / P mod Q0) natural order; p_rows (key / N mod P) lo-local order; q_mont: the residues of q_rows as 8-byte Montgomery words (hc_k_b5m), [2][N] behind q_rows in ITS allocation
 struct HcSwk { u64 *rows = nullptr; int level = 0, beta = 0; };   // general switching key: [beta][2][level+1+np][N], stored form
 struct HcProfRec { std::string name; hipEvent_t a, b; };
 struct hc_ctx {
@@ -111,6 +111,7 @@ struct hc_ctx {
     std::map<u64, HcEvk> evk;
     std::map<u64, HcSwk> swk;
     HcTw *idx_pairs = nullptr;   // [logN][N] idx plaintexts as Shoup pairs
+    u64 *idx_mont = nullptr;     // [logN][N] the same residues as 8-byte Montgomery words (w * 2^64 mod Q0: hc_k_b5m), behind the pairs in idx_pairs' allocation
     // workspace
     u64 *ws_cts = nullptr; size_t ws_cts_rows = 0;     // loop A output / tree ping
     u64 *ws_cts2 = nullptr; size_t ws_cts2_rows = 0;   // tree pong
@@ -898,9 +899,10 @@ extern "C" int hc_evk_load(hc_ctx *c, uint64_t galEl, const uint64_t *b_q, const
     // the P rows are only re-ordered into the lo-local coalesced order hc_k_b3 reads.
     HcScratch S(c);
     u64 *stage = nullptr; HC_HIP(c, S.alloc(&stage, 2 * HC_N * sizeof(u64)));
-    HcEvk e; e.q_rows = nullptr; e.p_rows = nullptr; e.row_local = hc_perm_row_local(galEl); e.row256 = e.row_local && hc_perm_row_local(galEl, 8);
+    HcEvk e; e.q_rows = nullptr; e.p_rows = nullptr; e.q_mont = nullptr; e.row_local = hc_perm_row_local(galEl); e.row256 = e.row_local && hc_perm_row_local(galEl, 8);
     u64 *stageq = nullptr; HC_HIP(c, S.alloc(&stageq, 2 * HC_N * sizeof(u64)));
-    HC_HIP(c, S.alloc(&e.q_rows, 2 * HC_N * sizeof(HcTw)));
+    HC_HIP(c, S.alloc(&e.q_rows, 2 * HC_N * (sizeof(HcTw) + sizeof(u64))));      // the pairs, then the 8-byte Montgomery words of the same residues
+    e.q_mont = reinterpret_cast<u64 *>(e.q_rows + 2 * HC_N);
     HC_HIP(c, S.alloc(&e.p_rows, 2 * HC_N * sizeof(HcTw)));
     HC_HIP(c, hcx_h2d_async(c, stageq, b_q, HC_N * sizeof(u64)));
     HC_HIP(c, hcx_h2d_async(c, stageq + HC_N, a_q, HC_N * sizeof(u64)));
@@ -913,6 +915,8 @@ extern "C" int hc_evk_load(hc_ctx *c, uint64_t galEl, const uint64_t *b_q, const
     int rc = hc_launch(c, "evk_from_mont", hc_k_pointwise<HC_PW_FROM_MONT>, hc_pw_grid(2 * HC_N), (const u64 *)stageq, (const u64 *)stageq, stageq, (size_t)2 * HC_N, m0.m, z);
     if (!rc) rc = hc_launch(c, "evk_div_p", hc_k_pointwise<HC_PW_MULC>, hc_pw_grid(2 * HC_N), (const u64 *)stageq, (const u64 *)stageq, stageq, (size_t)2 * HC_N, m0.m, pinv);
     if (!rc) rc = hc_launch(c, "make_pairs", hc_k_make_pairs, hc_pw_grid(2 * HC_N), (const u64 *)stageq, e.q_rows, (size_t)2 * HC_N, m0.m.q, 0);
+    // ... and once more as ONE word each, w * 2^64 mod Q0: hc_k_b5m multiplies by these (hc_mont_lazy) and loads half the bytes
+    if (!rc) rc = hc_launch(c, "evk_to_mont", hc_k_pointwise<HC_PW_TO_MONT>, hc_pw_grid(2 * HC_N), (const u64 *)stageq, (const u64 *)stageq, e.q_mont, (size_t)2 * HC_N, m0.m, z);
     // P rows: stored Montgomery form -> plain residues -> (w, floor(w*2^64/P)) pairs in lo-local order
     if (!rc) rc = hc_launch(c, "evk_from_mont", hc_k_pointwise<HC_PW_FROM_MONT>, hc_pw_grid(2 * HC_N), (const u64 *)stage, (const u64 *)stage, stage, (size_t)2 * HC_N, mp.m, z);
     // ... times N^-1 mod P: the inverse transform of the P accumulators (hc_k_b4) then runs without its scaling products
@@ -943,12 +947,15 @@ extern "C" int hc_idx_load(hc_ctx *c, const uint64_t *idx_host) {
         HC_TRY(HC_LAUNCH_FM(m0.m.q, c, "cols_fwd", hc_k_cols_fwd, dim3(16, HC_LOGN), (const u64 *)stage, tmp, m0.fwd, m0.m.q));
         HC_TRY(HC_LAUNCH_FM(m0.m.q, c, "rows_fwd_canon", hc_k_rows_fwd_canon, dim3(16, HC_LOGN), (const u64 *)tmp, stage, m0.fwd, m0.m.q, m0.m.mu));
     }
-    HcTw *pairs = nullptr; HC_HIP(c, S.alloc(&pairs, (size_t)HC_LOGN * HC_N * sizeof(HcTw)));
+    HcTw *pairs = nullptr; HC_HIP(c, S.alloc(&pairs, (size_t)HC_LOGN * HC_N * (sizeof(HcTw) + sizeof(u64))));      // the pairs, then the 8-byte Montgomery words of the same residues
+    u64 *mont = reinterpret_cast<u64 *>(pairs + (size_t)HC_LOGN * HC_N);
+    HcTw z; z.w = z.ws = 0;
     HC_TRY(hc_launch(c, "idx_pairs", hc_k_make_pairs, hc_pw_grid((size_t)HC_LOGN * HC_N), (const u64 *)stage, pairs, (size_t)HC_LOGN * HC_N, m0.m.q, 0));
+    HC_TRY(hc_launch(c, "idx_to_mont", hc_k_pointwise<HC_PW_TO_MONT>, hc_pw_grid((size_t)HC_LOGN * HC_N), (const u64 *)stage, (const u64 *)stage, mont, (size_t)HC_LOGN * HC_N, m0.m, z));
     HC_HIP(c, hipStreamSynchronize(c->stream));
     S.keep(pairs);
     if (c->idx_pairs) HC_HIP(c, hcx_free(c, c->idx_pairs));
-    c->idx_pairs = pairs;
+    c->idx_pairs = pairs; c->idx_mont = mont;
     return HC_OK;
 }
 
@@ -1051,6 +1058,7 @@ static int hc_fill_loopB(hc_ctx *c, HcLoopB *B, const u64 *src, u64 *dst, const 
     B->tmpC = c->ws_tmp; B->tmpE = c->ws_tmp + (size_t)chunk * HC_N; B->tmpT = c->ws_tmp + (size_t)chunk * 3 * HC_N;
     B->idx = c->idx_pairs + (size_t)logStep * HC_N;
     B->evkQ = e.q_rows; B->evkP = e.p_rows;
+    B->idxM = c->idx_mont + (size_t)logStep * HC_N; B->evkQM = e.q_mont;
     B->n0 = 0; B->step = step; B->norm = norm; B->nodes = 1; B->src_stride = 0; B->dst_stride = 0;
     B->m0 = m0.m; B->mp = mp.m;
     B->pmodq = h_pair(mp.m.q % m0.m.q, m0.m.q);
@@ -1102,12 +1110,7 @@ static int hc_pack_level(hc_ctx *c, const u64 *src, u64 *dst, size_t sstride, si
         HC_TRY(HC_LAUNCH_FM(mp.m.q, c, "b3_rowsfwdP_mac_rowsinvP", hc_k_b3, g1, B, mp.fwd, mp.inv));
         HC_TRY(HC_LAUNCH_FM(m0.m.q, c, "b4_colsinvP_modup_colsfwd", hc_k_b4, g2, B, mp.inv, m0.fwd));
         const HcPtrs pb = bias_last ? *bias_last : nobias, po = outs_last ? *outs_last : nobias;
-#if HC_B5M_LOADER && !defined(HC_EMU)
-        if (it->second.row256) HC_TRY((hc_fm_free(m0.m.q) ? hc_launch<HC_LD_TPB>(c, "b5_rowsfwd_moddown_perm_add", hc_k_b5m_ld<HC_FM_FREE>, g1, B, m0.fwd, pb, po)
-                                                          : hc_launch<HC_LD_TPB>(c, "b5_rowsfwd_moddown_perm_add", hc_k_b5m_ld<HC_FM_ALT>, g1, B, m0.fwd, pb, po)));   // + a loader wavefront
-#else
         if (it->second.row256) HC_TRY(HC_LAUNCH_FM(m0.m.q, c, "b5_rowsfwd_moddown_perm_add", hc_k_b5m, g1, B, m0.fwd, pb, po));      // one workgroup per (node, tile), both polynomials
-#endif
         else HC_TRY(HC_LAUNCH_FM(m0.m.q, c, "b5_rowsfwd_moddown_perm_add", hc_k_b5, g2, B, m0.fwd, pb, po));                        // tile-local permutation (2^j + 1, j = 5..8)
     }
     return HC_OK;
