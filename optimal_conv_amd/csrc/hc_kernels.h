@@ -270,16 +270,7 @@ __device__ __forceinline__ void hc_cols_inv(u64 (&e)[16], u64 *lds, const HcTwTa
     hc_gs_round<SCALE>(e, HcRowsTwA<KC>{T.colsA}, Q, T.ninv, T.w_last_ninv);
 }
 
-// fp64 forms of the two inverse passes (same data movement; LDS carries the doubles' bit patterns)
-__device__ __forceinline__ void hc_rows_inv_f64(double (&e)[16], u64 *lds, const HcTwTab &T, int row, int rloc, int tid, HcF64Mod m) {
-    hc_gs_round_f64<false>(e, HcRowsTwB<false>{T.rowsB + row * 256 + tid}, m, T.ninv, T.ninv);
-#pragma unroll
-    for (int lo = 0; lo < 16; lo++) lds[hc_rows_lds(rloc, tid * 16 + lo)] = hc_d2u(e[lo]);
-    HC_ROW_SYNC();
-#pragma unroll
-    for (int hi = 0; hi < 16; hi++) e[hi] = hc_u2d(lds[hc_rows_lds(rloc, hi * 16 + tid)]);
-    hc_gs_round_f64<false>(e, HcRowsTwA<false>{T.rowsA + row * 16}, m, T.ninv, T.ninv);
-}
+// fp64 form of the inverse cols pass (same data movement; LDS carries the doubles' bit patterns; the rows pass is hc_rows_inv2_f64)
 __device__ __forceinline__ void hc_cols_inv_f64(double (&e)[16], u64 *lds, const HcTwTab &T, int c, int tid, HcF64Mod m) {
     hc_gs_round_f64<false>(e, HcRowsTwB<false>{T.colsB + tid}, m, T.ninv, T.ninv);
 #pragma unroll
@@ -837,6 +828,109 @@ __global__ __launch_bounds__(HC_TPB) void hc_k_rotate_finish(const u64 *d0, cons
     HC_ROW_DISPATCH(mods[l].row32, body);
 }
 
+// ---------------------------------------------------------------- two register tiles in lock step
+// Two transforms over the same 16 rows and the same modulus want the same twiddles - 15 rowsA pairs per row and 15 rowsB pairs per THREAD and pass, 480 of the 608 bytes a
+// thread loads in a rows pass. The forms below run the butterflies of both tiles behind ONE load per twiddle slot: the same lazy arithmetic on the same values as the one-tile
+// rounds, only the order of independent operations differs (bit-identical results). Used where one workgroup has both tiles anyway (hc_k_b3: the two key components of a
+// node; hc_k_b5m: the two polynomials) or can take them (hc_k_a1 / hc_k_a3: the two polynomials of a channel, which also share the kernel-plaintext tile).
+template <int FM, class TW>
+__device__ __forceinline__ void hc_ct_round2(u64 (&e0)[16], u64 (&e1)[16], const TW &tw, const HcQ &Q) {
+#pragma unroll
+    for (int s = 0; s < 4; s++) {
+        const int half = 8 >> s;
+#pragma unroll
+        for (int g = 0; g < (1 << s); g++) {
+            const HcTw w = tw((1 << s) - 1 + g);
+#pragma unroll
+            for (int k = 0; k < half; k++) {
+                const int a = g * 2 * half + k, b = a + half;
+                u64 X0 = e0[a], X1 = e1[a];
+                if (FM == HC_FM_ALT) { X0 = hc_fold(X0, Q.nq4); X1 = hc_fold(X1, Q.nq4); }
+                const u64 T0 = hc_shoup4(e0[b], w.w, w.ws, Q), T1 = hc_shoup4(e1[b], w.w, w.ws, Q);
+                e0[a] = X0 + T0; e0[b] = (X0 + Q.q4) - T0;
+                e1[a] = X1 + T1; e1[b] = (X1 + Q.q4) - T1;
+            }
+        }
+    }
+}
+// hc_gs_round<false> on two tiles
+template <class TW>
+__device__ __forceinline__ void hc_gs_round2(u64 (&e0)[16], u64 (&e1)[16], const TW &tw, const HcQ &Q) {
+#pragma unroll
+    for (int s = 0; s < 4; s++) {
+        const int dist = 1 << s;
+#pragma unroll
+        for (int g = 0; g < (8 >> s); g++) {
+            const HcTw w = tw((8 >> s) - 1 + g);
+#pragma unroll
+            for (int k = 0; k < dist; k++) {
+                const int a = g * 2 * dist + k, b = a + dist;
+                const u64 X0 = e0[a], Y0 = e0[b], X1 = e1[a], Y1 = e1[b];
+                e0[a] = hc_fold(X0 + Y0, Q.nq4); e0[b] = hc_shoup4((X0 + Q.q4) - Y0, w.w, w.ws, Q);
+                e1[a] = hc_fold(X1 + Y1, Q.nq4); e1[b] = hc_shoup4((X1 + Q.q4) - Y1, w.w, w.ws, Q);
+            }
+        }
+    }
+}
+// hc_gs_round_f64<false> on two tiles
+template <class TW>
+__device__ __forceinline__ void hc_gs_round2_f64(double (&e0)[16], double (&e1)[16], const TW &tw, HcF64Mod m) {
+#pragma unroll
+    for (int s = 0; s < 4; s++) {
+        const int dist = 1 << s;
+#pragma unroll
+        for (int g = 0; g < (8 >> s); g++) {
+            const HcTw w = tw((8 >> s) - 1 + g);
+            const double ww = hc_u2d(w.w), wq = hc_u2d(w.ws);
+#pragma unroll
+            for (int k = 0; k < dist; k++) {
+                const int a = g * 2 * dist + k, b = a + dist;
+                const double X0 = e0[a], Y0 = e0[b], X1 = e1[a], Y1 = e1[b], u0 = X0 + Y0, u1 = X1 + Y1;
+                e0[a] = (s & 1) ? hc_f64_reduce(u0, m.q, m.qinv) : u0; e0[b] = hc_f64_mulmod(X0 - Y0, ww, wq, m.q);
+                e1[a] = (s & 1) ? hc_f64_reduce(u1, m.q, m.qinv) : u1; e1[b] = hc_f64_mulmod(X1 - Y1, ww, wq, m.q);
+            }
+        }
+    }
+}
+// The exchanges of two tiles go through ONE 32 KiB LDS tile, one after the other (occupancy: two tiles side by side would halve the workgroups a CU holds).
+// SY: HC_ROW_SYNC for the row-local exchanges, __syncthreads for the ones to and from the linear order.
+template <class WA, class RA, class SY>
+__device__ __forceinline__ void hc_xchg2(u64 (&e0)[16], u64 (&e1)[16], u64 *lds, WA wa, RA ra, SY sync) {
+#pragma unroll
+    for (int i = 0; i < 16; i++) lds[wa(i)] = e0[i];
+    sync();
+#pragma unroll
+    for (int i = 0; i < 16; i++) e0[i] = lds[ra(i)];
+    sync();                                                                  // every word of the first tile has been read before the second lands on it
+#pragma unroll
+    for (int i = 0; i < 16; i++) lds[wa(i)] = e1[i];
+    sync();
+#pragma unroll
+    for (int i = 0; i < 16; i++) e1[i] = lds[ra(i)];
+}
+// hc_rows_fwd / hc_rows_inv / hc_rows_inv_f64 on two tiles: same element orders in and out
+template <int FM>
+__device__ __forceinline__ void hc_rows_fwd2(u64 (&e0)[16], u64 (&e1)[16], u64 *lds, const HcTwTab &T, int row, int rloc, int tid, const HcQ &Q) {
+    hc_ct_round2<FM>(e0, e1, HcRowsTwA<false>{T.rowsA + row * 16}, Q);
+    hc_xchg2(e0, e1, lds, [&](int hi) { return hc_rows_lds(rloc, hi * 16 + tid); }, [&](int lo) { return hc_rows_lds(rloc, tid * 16 + lo); }, [] { HC_ROW_SYNC(); });
+    hc_ct_round2<FM>(e0, e1, HcRowsTwB<false>{T.rowsB + row * 256 + tid}, Q);
+}
+__device__ __forceinline__ void hc_rows_inv2(u64 (&e0)[16], u64 (&e1)[16], u64 *lds, const HcTwTab &T, int row, int rloc, int tid, const HcQ &Q) {
+    hc_gs_round2(e0, e1, HcRowsTwB<false>{T.rowsB + row * 256 + tid}, Q);
+    hc_xchg2(e0, e1, lds, [&](int lo) { return hc_rows_lds(rloc, tid * 16 + lo); }, [&](int hi) { return hc_rows_lds(rloc, hi * 16 + tid); }, [] { HC_ROW_SYNC(); });
+    hc_gs_round2(e0, e1, HcRowsTwA<false>{T.rowsA + row * 16}, Q);
+}
+__device__ __forceinline__ void hc_rows_inv2_f64(double (&f0)[16], double (&f1)[16], u64 *lds, const HcTwTab &T, int row, int rloc, int tid, HcF64Mod m) {
+    hc_gs_round2_f64(f0, f1, HcRowsTwB<false>{T.rowsB + row * 256 + tid}, m);
+    u64 b0[16], b1[16];
+#pragma unroll
+    for (int i = 0; i < 16; i++) { b0[i] = hc_d2u(f0[i]); b1[i] = hc_d2u(f1[i]); }
+    hc_xchg2(b0, b1, lds, [&](int lo) { return hc_rows_lds(rloc, tid * 16 + lo); }, [&](int hi) { return hc_rows_lds(rloc, hi * 16 + tid); }, [] { HC_ROW_SYNC(); });
+#pragma unroll
+    for (int i = 0; i < 16; i++) { f0[i] = hc_u2d(b0[i]); f1[i] = hc_u2d(b1[i]); }
+    hc_gs_round2_f64(f0, f1, HcRowsTwA<false>{T.rowsA + row * 16}, m);
+}
+
 // ================================================================ loop A (conv.go:525-531), fused
 // Per output channel i and ciphertext polynomial p:
 //   a_l = c'_p[l] (*) k_i[l]  (l = 0,1; c' = ct_in * MultByConst constant, kept as Shoup pairs: it is the FIXED operand of 2B products)
@@ -861,13 +955,13 @@ __global__ __launch_bounds__(HC_TPB) void hc_k_rotate_finish(const u64 *d0, cons
 #define HC_FREE_OFF 72                // FREE-mode forward outputs are below 70q (hc_ct_round): X + 72q - (such a value) stays positive
 // wavefronts per SIMD each transform kernel of the convolution is compiled for (its VGPR budget)
 #ifndef HC_W_A1
-#define HC_W_A1 4
+#define HC_W_A1 3                     // a1 and a3 carry two polynomials per workgroup (145-152 VGPRs): three workgroups = six tiles per CU
 #endif
 #ifndef HC_W_A2
 #define HC_W_A2 4
 #endif
 #ifndef HC_W_A3
-#define HC_W_A3 4
+#define HC_W_A3 3
 #endif
 #ifndef HC_W_B1
 #define HC_W_B1 4
@@ -880,6 +974,9 @@ __global__ __launch_bounds__(HC_TPB) void hc_k_rotate_finish(const u64 *d0, cons
 #endif
 #ifndef HC_W_B4
 #define HC_W_B4 1
+#endif
+#ifndef HC_A3_ROWS
+#define HC_A3_ROWS 4                  // rows per epilogue batch of hc_k_a3p: 2 x 4 c' pairs in flight per thread
 #endif
 struct HcLoopA {
     const HcTw *ctc;  // [2 polys][2 limbs][N]   ct_in times the integer constant (canonical) with its Shoup companion
@@ -894,41 +991,40 @@ struct HcLoopA {
     HcTw q1inv;       // Q1^-1 mod Q0
     u64 h, negh0;     // (Q1-1)>>1 ; Q0 - (h mod Q0)
 };
-// KA1: rows-inverse of a_1 (mod Q1). grid = (jobs, 16, batch). F64 = 1: Q1 < 2^49, the transform runs in fp64 (T1inv = the fp64 table)
-// and tmp carries doubles (bit patterns) to KA2.
-#ifndef HC_A_WAVES
-#define HC_A_WAVES 4          // a1 / a2 sit at 98 / 99 VGPRs; forcing five waves per SIMD spills 8 / 28 bytes per lane (+19 % fabric writes on a2) and measured no faster
-#endif
+// KA1: a_1 = c'_p[1] (*) k_i[1] and its rows-inverse (mod Q1) for BOTH polynomials of a channel (jobs 2c and 2c + 1 of tmp): grid = (jobs / 2, 16, batch). F64 = 1: Q1 < 2^49, the transform
+// runs in fp64 (T1inv = the fp64 table) and tmp carries doubles (bit patterns) to KA2. The kernel-plaintext tile
+// k_i[1] is loaded once and every T1inv twiddle once for the two transforms (hc_rows_inv2 / hc_rows_inv2_f64); one LDS tile, used by the two polynomials in turn.
 template <int F64>
-__global__ __launch_bounds__(HC_TPB, HC_W_A1) void hc_k_a1(HcLoopA A, HcTwTab T1inv) {
+__global__ __launch_bounds__(HC_TPB, HC_W_A1) void hc_k_a1p(HcLoopA A, HcTwTab T1inv) {
     __shared__ hc_cvr_lds_t lds[HC_ROWS_LDS];
     const int t = threadIdx.x, tid = t & 15, rloc = t >> 4, row = HC_TILE * 16 + rloc;
-    const int job = HC_JOB, p = job & 1, i = A.i0 + (job >> 1) * A.norm, z = blockIdx.z;
-    const HcTw *__restrict__ c = A.ctc + ((size_t)z * 4 + (size_t)p * 2 + 1) * 65536;
-    const u64 *__restrict__ k = A.ker.p[z] + ((size_t)i * 2 + 1) * 65536;
+    const int ch = HC_JOB, i = A.i0 + ch * A.norm, z = blockIdx.z;
+    const HcTw *__restrict__ c0 = A.ctc + ((size_t)z * 4 + 1) * 65536 + (size_t)HC_TILE * 4096 + t;          // c'_0[1] ; c'_1[1] is 2 * 65536 pairs on
+    const u64 *__restrict__ k = A.ker.p[z] + ((size_t)i * 2 + 1) * 65536 + (size_t)HC_TILE * 4096 + t;
     const HcQ Q = hc_q(A.m1.q);
-    u64 e[16];
+    u64 e0[16], e1[16];
 #pragma unroll
     for (int kk = 0; kk < 16; kk++) {
-        const size_t off = (size_t)(HC_TILE * 16 + kk) * 256 + t;
-        const HcTw cw = c[off];
-        e[kk] = hc_shoup4(k[off], cw.w, cw.ws, Q);                              // [0, 4*Q1)
+        const u64 kv = k[kk * 256];
+        const HcTw w0 = c0[kk * 256], w1 = c0[2 * 65536 + kk * 256];
+        e0[kk] = hc_shoup4(kv, w0.w, w0.ws, Q);                                 // [0, 4*Q1)
+        e1[kk] = hc_shoup4(kv, w1.w, w1.ws, Q);
     }
-    u64 *o = A.tmp + ((size_t)z * A.njobs + job) * 65536 + (size_t)row * 256;
-    hc_rows_lin_to_lo(e, lds, t, rloc, tid);
+    u64 *o = A.tmp + ((size_t)z * A.njobs + 2 * ch) * 65536 + (size_t)row * 256;     // polynomial 1 is 65536 words on
+    hc_xchg2(e0, e1, lds, [&](int kk) { return hc_rows_lds(kk, t); }, [&](int lo) { return hc_rows_lds(rloc, tid * 16 + lo); }, [] { __syncthreads(); });
     HC_ROW_SYNC();        // row-local: the reads before and the writes after stay inside the 16 lanes of a row
     if (F64) {
         const HcF64Mod m{(double)A.m1.q, 1.0 / (double)A.m1.q};
-        double f[16];
+        double f0[16], f1[16];
 #pragma unroll
-        for (int kk = 0; kk < 16; kk++) f[kk] = hc_f64_reduce(hc_f64_from_u(e[kk]), m.q, m.qinv);   // 4*Q1 < 2^51: exact; |f| <= Q1/2
-        hc_rows_inv_f64(f, lds, T1inv, row, rloc, tid, m);
+        for (int kk = 0; kk < 16; kk++) { f0[kk] = hc_f64_reduce(hc_f64_from_u(e0[kk]), m.q, m.qinv); f1[kk] = hc_f64_reduce(hc_f64_from_u(e1[kk]), m.q, m.qinv); }   // 4*Q1 < 2^51: exact; |f| <= Q1/2
+        hc_rows_inv2_f64(f0, f1, lds, T1inv, row, rloc, tid, m);
 #pragma unroll
-        for (int hi = 0; hi < 16; hi++) o[hi * 16 + tid] = hc_d2u(f[hi]);
+        for (int hi = 0; hi < 16; hi++) { o[hi * 16 + tid] = hc_d2u(f0[hi]); o[65536 + hi * 16 + tid] = hc_d2u(f1[hi]); }
     } else {
-        hc_rows_inv(e, lds, T1inv, row, rloc, tid, Q);
+        hc_rows_inv2(e0, e1, lds, T1inv, row, rloc, tid, Q);
 #pragma unroll
-        for (int hi = 0; hi < 16; hi++) o[hi * 16 + tid] = e[hi];
+        for (int hi = 0; hi < 16; hi++) { o[hi * 16 + tid] = e0[hi]; o[65536 + hi * 16 + tid] = e1[hi]; }
     }
 }
 // KA2: cols-inverse mod Q1, centred lift to Q0, cols-forward mod Q0, in place on tmp. grid = (jobs * batch, 16)
@@ -968,34 +1064,42 @@ __global__ __launch_bounds__(HC_TPB, HC_W_A2) void hc_k_a2(HcLoopA A, HcTwTab T1
 #pragma unroll
     for (int lo = 0; lo < 16; lo++) base[(size_t)(tid * 16 + lo) * 256] = e[lo];
 }
-// KA3: rows-forward mod Q0, then out = (a_0 - u) * Q1^-1. grid = (jobs, 16, batch)
-// a_0 = c'_p[0] (*) k_i[0] is formed first, in the linear layout the epilogue uses, so that every global load of
-// the kernel is issued before the transform starts and nothing stalls behind the stores at the end.
+// KA3: rows-forward mod Q0, then out = (a_0 - u) * Q1^-1 with a_0 = c'_p[0] (*) k_i[0], for both polynomials of a channel per workgroup, grid = (jobs / 2, 16, batch): k_i[0] loaded once (held across the transform: 32 VGPRs), every T0fwd twiddle once
+// (hc_rows_fwd2). The two c'_p[0] tiles are loaded behind the transform in row batches, as hc_k_b5m's epilogue loads its operands: two a_0 tiles formed before the transform
+// (all loads up front, as the one-polynomial form of this kernel had them) would be 64 more registers across it.
 template <int FM>
-__global__ __launch_bounds__(HC_TPB, HC_W_A3) void hc_k_a3(HcLoopA A, HcTwTab T0fwd) {
+__global__ __launch_bounds__(HC_TPB, HC_W_A3) void hc_k_a3p(HcLoopA A, HcTwTab T0fwd) {
     __shared__ hc_cvr_lds_t lds[HC_ROWS_LDS];
     const int t = threadIdx.x, tid = t & 15, rloc = t >> 4, row = HC_TILE * 16 + rloc;
-    const int job = HC_JOB, p = job & 1, i = A.i0 + (job >> 1) * A.norm, z = blockIdx.z;
-    const u64 *__restrict__ in = A.tmp + ((size_t)z * A.njobs + job) * 65536 + (size_t)row * 256;
-    const HcTw *__restrict__ c = A.ctc + ((size_t)z * 4 + (size_t)p * 2) * 65536 + (size_t)HC_TILE * 4096 + t;
+    const int ch = HC_JOB, i = A.i0 + ch * A.norm, z = blockIdx.z;
+    const u64 *__restrict__ in = A.tmp + ((size_t)z * A.njobs + 2 * ch) * 65536 + (size_t)row * 256;
+    const HcTw *__restrict__ c0 = A.ctc + (size_t)z * 4 * 65536 + (size_t)HC_TILE * 4096 + t;                 // c'_0[0] ; c'_1[0] is 2 * 65536 pairs on
     const u64 *__restrict__ k = A.ker.p[z] + ((size_t)i * 2) * 65536 + (size_t)HC_TILE * 4096 + t;
-    u64 *__restrict__ o = A.cts + (size_t)z * A.cts_stride + ((size_t)(A.slot0 + (job >> 1) * A.slot_step) * 2 + p) * 65536 + (size_t)HC_TILE * 4096 + t;
+    u64 *__restrict__ o = A.cts + (size_t)z * A.cts_stride + (size_t)(A.slot0 + ch * A.slot_step) * 2 * 65536 + (size_t)HC_TILE * 4096 + t;
     const HcQ Q = hc_q(A.m0.q);
-    u64 e[16], a0[16];
+    u64 e0[16], e1[16], kv[16];
 #pragma unroll
-    for (int hi = 0; hi < 16; hi++) e[hi] = in[hi * 16 + tid];
+    for (int hi = 0; hi < 16; hi++) { e0[hi] = in[hi * 16 + tid]; e1[hi] = in[65536 + hi * 16 + tid]; }
 #pragma unroll
-    for (int kk = 0; kk < 16; kk++) a0[kk] = k[kk * 256];
-#pragma unroll
-    for (int kk = 0; kk < 16; kk++) { const HcTw cw = c[kk * 256]; a0[kk] = hc_shoup4(a0[kk], cw.w, cw.ws, Q); }      // [0, 4q)
-    hc_rows_fwd<FM>(e, lds, T0fwd, row, rloc, tid, Q);
+    for (int kk = 0; kk < 16; kk++) kv[kk] = k[kk * 256];
+    hc_rows_fwd2<FM>(e0, e1, lds, T0fwd, row, rloc, tid, Q);
     HC_ROW_SYNC();        // row-local: the reads before and the writes after stay inside the 16 lanes of a row
-    hc_rows_lo_to_lin(e, lds, t, rloc, tid);
+    hc_xchg2(e0, e1, lds, [&](int lo) { return hc_rows_lds(rloc, tid * 16 + lo); }, [&](int kk) { return hc_rows_lds(kk, t); }, [] { __syncthreads(); });
 #pragma unroll
-    for (int kk = 0; kk < 16; kk++) {
-        // FREE: u = e < 70q stays lazy, a_0 + 72q - u is positive and below 2^64; ALT (8q < 2^64 only): u canonical first
-        const u64 d = FM == HC_FM_FREE ? a0[kk] + HC_FREE_OFF * Q.q - e[kk] : a0[kk] + Q.q - hc_canon8(e[kk], Q);
-        o[kk * 256] = hc_canon4(hc_shoup4(d, A.q1inv.w, A.q1inv.ws, Q), Q);
+    for (int b = 0; b < 16; b += HC_A3_ROWS) {
+        HcTw w0[HC_A3_ROWS], w1[HC_A3_ROWS];
+#pragma unroll
+        for (int j = 0; j < HC_A3_ROWS; j++) { w0[j] = c0[(b + j) * 256]; w1[j] = c0[2 * 65536 + (b + j) * 256]; }
+#pragma unroll
+        for (int j = 0; j < HC_A3_ROWS; j++) {
+            const int kk = b + j;
+            const u64 a0 = hc_shoup4(kv[kk], w0[j].w, w0[j].ws, Q), a1 = hc_shoup4(kv[kk], w1[j].w, w1[j].ws, Q);      // [0, 4q)
+            // FREE: u = e < 70q stays lazy, a_0 + 72q - u is positive and below 2^64; ALT (8q < 2^64 only): u canonical first
+            const u64 d0 = FM == HC_FM_FREE ? a0 + HC_FREE_OFF * Q.q - e0[kk] : a0 + Q.q - hc_canon8(e0[kk], Q);
+            const u64 d1 = FM == HC_FM_FREE ? a1 + HC_FREE_OFF * Q.q - e1[kk] : a1 + Q.q - hc_canon8(e1[kk], Q);
+            o[kk * 256] = hc_canon4(hc_shoup4(d0, A.q1inv.w, A.q1inv.ws, Q), Q);
+            o[65536 + kk * 256] = hc_canon4(hc_shoup4(d1, A.q1inv.w, A.q1inv.ws, Q), Q);
+        }
     }
 }
 
@@ -1073,32 +1177,33 @@ __global__ __launch_bounds__(HC_TPB, HC_W_B2) void hc_k_b2(HcLoopB B, HcTwTab T0
 #pragma unroll
     for (int lo = 0; lo < 16; lo++) base[(size_t)(tid * 16 + lo) * 256] = e[lo];
 }
-// KB3: rows-forward mod P, multiply by b_P and a_P, rows-inverse mod P of both. grid = (batch*nodes, 16)
+// KB3: rows-forward mod P, multiply by b_P and a_P, rows-inverse mod P of both in lock step, every TPinv twiddle loaded once (hc_rows_inv2). grid = (batch*nodes, 16)
 template <int FMP>
-__global__ __launch_bounds__(HC_TPB, HC_W_B3) void hc_k_b3(HcLoopB B, HcTwTab TPfwd, HcTwTab TPinv) {
+__global__ __launch_bounds__(HC_TPB, HC_W_B3) void hc_k_b3p(HcLoopB B, HcTwTab TPfwd, HcTwTab TPinv) {
     __shared__ hc_cvr_lds_t lds[HC_ROWS_LDS];
     const int t = threadIdx.x, tid = t & 15, rloc = t >> 4, row = HC_TILE * 16 + rloc;
     const int node = HC_JOB;
     const u64 *in = B.tmpC + (size_t)node * 65536 + (size_t)row * 256;
     const HcQ Q = hc_q(B.mp.q);
-    u64 cp[16], e[16];
+    u64 e0[16], e1[16];
+    {
+        u64 cp[16];
 #pragma unroll
-    for (int hi = 0; hi < 16; hi++) cp[hi] = in[hi * 16 + tid];
-    hc_rows_fwd<FMP>(cp, lds, TPfwd, row, rloc, tid, Q);
-#pragma unroll
-    for (int k = 0; k < 2; k++) {
-        const HcTw *__restrict__ ev = B.evkP + (size_t)k * 65536 + (size_t)HC_TILE * 4096 + t;
+        for (int hi = 0; hi < 16; hi++) cp[hi] = in[hi * 16 + tid];
+        hc_rows_fwd<FMP>(cp, lds, TPfwd, row, rloc, tid, Q);
+        const HcTw *__restrict__ ev = B.evkP + (size_t)HC_TILE * 4096 + t;                 // b_P rows ; a_P is 65536 pairs on
 #pragma unroll
         for (int lo = 0; lo < 16; lo++) {
-            const HcTw w = ev[lo * 256];
-            e[lo] = hc_shoup4(cp[lo], w.w, w.ws, Q);
+            const HcTw w0 = ev[lo * 256], w1 = ev[65536 + lo * 256];
+            e0[lo] = hc_shoup4(cp[lo], w0.w, w0.ws, Q);
+            e1[lo] = hc_shoup4(cp[lo], w1.w, w1.ws, Q);
         }
-        HC_ROW_SYNC();             // row-local (the forward pass's / the previous k's reads of this row, then the inverse pass's writes): hc_k_b3 has no workgroup barrier left
-        hc_rows_inv(e, lds, TPinv, row, rloc, tid, Q);
-        u64 *o = B.tmpE + ((size_t)node * 2 + k) * 65536 + (size_t)row * 256;
-#pragma unroll
-        for (int hi = 0; hi < 16; hi++) o[hi * 16 + tid] = e[hi];
     }
+    HC_ROW_SYNC();             // row-local (the forward pass's reads of this row, then the inverse pass's writes): hc_k_b3 has no workgroup barrier
+    hc_rows_inv2(e0, e1, lds, TPinv, row, rloc, tid, Q);
+    u64 *o = B.tmpE + (size_t)node * 2 * 65536 + (size_t)row * 256;
+#pragma unroll
+    for (int hi = 0; hi < 16; hi++) { o[hi * 16 + tid] = e0[hi]; o[65536 + hi * 16 + tid] = e1[hi]; }
 }
 // KB4: cols-inverse mod P, exact basis extension P -> Q0 (ring.modUpExact, one P prime), cols-forward mod Q0.
 // grid = (2*batch*nodes, 16), in place on tmpE
@@ -1232,27 +1337,6 @@ __global__ __launch_bounds__(HC_TPB, 3) void hc_k_b5(HcLoopB B, HcTwTab T0fwd, H
 #ifndef HC_B5M_WAVES
 #define HC_B5M_WAVES 2                // 64 KiB of LDS per workgroup: two workgroups per CU (the one-tile form measured the same at 2, 3 and 4)
 #endif
-// Both transforms of a workgroup run over the same 16 rows modulo Q0, i.e. with the same twiddles: hc_ct_round on TWO register tiles, every twiddle loaded once
-template <int FM, class TW>
-__device__ __forceinline__ void hc_ct_round2(u64 (&e0)[16], u64 (&e1)[16], const TW &tw, const HcQ &Q) {
-#pragma unroll
-    for (int s = 0; s < 4; s++) {
-        const int half = 8 >> s;
-#pragma unroll
-        for (int g = 0; g < (1 << s); g++) {
-            const HcTw w = tw((1 << s) - 1 + g);
-#pragma unroll
-            for (int k = 0; k < half; k++) {
-                const int a = g * 2 * half + k, b = a + half;
-                u64 X0 = e0[a], X1 = e1[a];
-                if (FM == HC_FM_ALT) { X0 = hc_fold(X0, Q.nq4); X1 = hc_fold(X1, Q.nq4); }
-                const u64 T0 = hc_shoup4(e0[b], w.w, w.ws, Q), T1 = hc_shoup4(e1[b], w.w, w.ws, Q);
-                e0[a] = X0 + T0; e0[b] = (X0 + Q.q4) - T0;
-                e1[a] = X1 + T1; e1[b] = (X1 + Q.q4) - T1;
-            }
-        }
-    }
-}
 // hc_rows_fwd on two polynomials (tiles l0, l1 of LDS), then hc_rows_lo_to_lin on both: out e_k[kk] = n_k at (row kk, column t)
 template <int FM>
 __device__ __forceinline__ void hc_rows_fwd2_lin(u64 (&e0)[16], u64 (&e1)[16], u64 *l0, u64 *l1, const HcTwTab &T, int row, int rloc, int tid, int t, const HcQ &Q) {

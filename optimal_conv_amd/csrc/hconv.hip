@@ -793,17 +793,17 @@ static int hc_loopA_run_set(hc_ctx *c, const HcPtrs &kers, int n, int i_first, i
         A.i0 = i_first + j0 * i_stride;
         A.slot0 = compact ? j0 : A.i0; A.slot_step = compact ? 1 : i_stride;
         A.njobs = 2 * nj;
-        const dim3 grid = hc_grid(2 * nj, n), flat = hc_grid(2 * nj * n);
+        const dim3 pair = hc_grid(nj, n), flat = hc_grid(2 * nj * n);            // a1, a3: one workgroup per channel and tile does both polynomials
         if (hc_f64_ok(m1.m.q)) {
-            HC_TRY(hc_launch(c, "a1_mul_rowsinv", hc_k_a1<1>, grid, A, m1.inv_f64));
+            HC_TRY(hc_launch(c, "a1_mul_rowsinv", hc_k_a1p<1>, pair, A, m1.inv_f64));
             HC_TRY(hc_fm_free(m0.m.q) ? hc_launch(c, "a2_colsinv_lift_colsfwd", hc_k_a2<HC_FM_FREE, 1>, flat, A, m1.inv_f64, m0.fwd)
                                       : hc_launch(c, "a2_colsinv_lift_colsfwd", hc_k_a2<HC_FM_ALT, 1>, flat, A, m1.inv_f64, m0.fwd));
         } else {
-            HC_TRY(hc_launch(c, "a1_mul_rowsinv", hc_k_a1<0>, grid, A, m1.inv));
+            HC_TRY(hc_launch(c, "a1_mul_rowsinv", hc_k_a1p<0>, pair, A, m1.inv));
             HC_TRY(hc_fm_free(m0.m.q) ? hc_launch(c, "a2_colsinv_lift_colsfwd", hc_k_a2<HC_FM_FREE, 0>, flat, A, m1.inv, m0.fwd)
                                       : hc_launch(c, "a2_colsinv_lift_colsfwd", hc_k_a2<HC_FM_ALT, 0>, flat, A, m1.inv, m0.fwd));
         }
-        HC_TRY(HC_LAUNCH_FM(m0.m.q, c, "a3_rowsfwd_rescale", hc_k_a3, grid, A, m0.fwd));
+        HC_TRY(HC_LAUNCH_FM(m0.m.q, c, "a3_rowsfwd_rescale", hc_k_a3p, pair, A, m0.fwd));
     }
     return HC_OK;
 }
@@ -1107,7 +1107,7 @@ static int hc_pack_level(hc_ctx *c, const u64 *src, u64 *dst, size_t sstride, si
         }
         HC_TRY(hc_launch(c, "b1_node_rowsinv", hc_k_b1, g1, B, m0.inv));
         HC_TRY(HC_LAUNCH_FM(mp.m.q, c, "b2_colsinv_colsfwdP", hc_k_b2, g1, B, m0.inv, mp.fwd));
-        HC_TRY(HC_LAUNCH_FM(mp.m.q, c, "b3_rowsfwdP_mac_rowsinvP", hc_k_b3, g1, B, mp.fwd, mp.inv));
+        HC_TRY(HC_LAUNCH_FM(mp.m.q, c, "b3_rowsfwdP_mac_rowsinvP", hc_k_b3p, g1, B, mp.fwd, mp.inv));
         HC_TRY(HC_LAUNCH_FM(m0.m.q, c, "b4_colsinvP_modup_colsfwd", hc_k_b4, g2, B, mp.inv, m0.fwd));
         const HcPtrs pb = bias_last ? *bias_last : nobias, po = outs_last ? *outs_last : nobias;
         if (it->second.row256) HC_TRY(HC_LAUNCH_FM(m0.m.q, c, "b5_rowsfwd_moddown_perm_add", hc_k_b5m, g1, B, m0.fwd, pb, po));      // one workgroup per (node, tile), both polynomials
@@ -1193,7 +1193,7 @@ static int hc_ks_common(hc_ctx *c, uint64_t galEl, const uint64_t *c0, const uin
             const HcModHost &m0 = c->mods[0], &mp = c->mods[(size_t)c->nq];
             if (!rc) rc = hc_launch(c, "b1_node_rowsinv", hc_k_b1, hc_grid(1), B, m0.inv);
             if (!rc) rc = HC_LAUNCH_FM(mp.m.q, c, "b2_colsinv_colsfwdP", hc_k_b2, hc_grid(1), B, m0.inv, mp.fwd);
-            if (!rc) rc = HC_LAUNCH_FM(mp.m.q, c, "b3_rowsfwdP_mac_rowsinvP", hc_k_b3, hc_grid(1), B, mp.fwd, mp.inv);
+            if (!rc) rc = HC_LAUNCH_FM(mp.m.q, c, "b3_rowsfwdP_mac_rowsinvP", hc_k_b3p, hc_grid(1), B, mp.fwd, mp.inv);
             if (!rc) rc = HC_LAUNCH_FM(m0.m.q, c, "b4_colsinvP_modup_colsfwd", hc_k_b4, hc_grid(2), B, mp.inv, m0.fwd);
             HcPtrs nobias; memset(&nobias, 0, sizeof nobias);
             if (!rc) rc = HC_LAUNCH_FM(m0.m.q, c, "b5_rowsfwd_moddown_perm_add", hc_k_b5, hc_grid(2), B, m0.fwd, nobias, nobias);
