@@ -67,7 +67,7 @@ struct HcTwTab {
 };
 
 // The same tables for a modulus below 2^31 as 8-byte entries (low word of w, high word of w' = floor(w 2^32 / q)): what the 32-bit form of the batched transforms reads
-// (HC_S32). Half the table bytes: a rows pass reads 4 KB of 16-byte twiddles per 2 KB (1 KB as 4-byte words) row of data.
+// (HcRowMod::s32). Half the table bytes: a rows pass reads 4 KB of 16-byte twiddles per 2 KB (1 KB as 4-byte words) row of data.
 struct __attribute__((aligned(8))) HcTw32 { u32 w, ws; };
 struct HcTwTab32 { const HcTw32 *rowsA, *rowsB, *colsA, *colsB; };
 
@@ -164,12 +164,9 @@ __device__ __forceinline__ void hc_gs_round_f64(double (&e)[16], const TW &tw, H
 //   4 column bits with bits 5..7 of the column and flips bits 3 and 4 on odd rows: bijective per row, and each of
 //   the three patterns spreads its 32 lanes over all 32 slots (derivation in DESIGN.md).
 // A rows pass exchanges data only inside the 16 lanes that share a row (hc_rows_lds keeps row rloc in words [256 rloc, 256 rloc + 256)), i.e. inside ONE wavefront, whose LDS
-// instructions execute in program order: the exchange needs no workgroup barrier, only that the compiler keeps the order (round 3; HC_ROWS_WAVE_SYNC=0 restores __syncthreads).
+// instructions execute in program order: the exchange needs no workgroup barrier, only that the compiler keeps the order (round 3).
 // The CPU emulator runs the threads of a block as fibers one after the other, so there the wave-level synchronisation has to be a yield like any barrier.
-#ifndef HC_ROWS_WAVE_SYNC
-#define HC_ROWS_WAVE_SYNC 1
-#endif
-#if defined(HC_EMU) || !HC_ROWS_WAVE_SYNC
+#if defined(HC_EMU)
 #define HC_ROW_SYNC() __syncthreads()
 #else
 #define HC_ROW_SYNC() do { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); } while (0)
@@ -196,7 +193,7 @@ typedef const HcTw __attribute__((address_space(4))) *HcTwConstPtr;
 #endif
 // Tables the kernels only read - twiddles, the per-modulus rows of HcRowMod, the extension's constants - are read through the CONSTANT address space: a load whose address is
 // uniform then goes through the scalar cache into SGPRs whatever else the kernel does. As global-memory loads they depend on the compiler proving that no store of the kernel
-// can reach them, and with the 32-bit and 64-bit bodies side by side (HC_S32) it stopped proving that for the second body: hc_k_cols_fwd_mm<1, 5> went from 267 s_load / 196
+// can reach them, and with the 32-bit and 64-bit bodies side by side it stopped proving that for the second body: hc_k_cols_fwd_mm<1, 5> went from 267 s_load / 196
 // global_load to 30 / 596 - every constant fetched per lane into VGPRs - and lost 8 %. hc_const_copy: a table entry selected by blockIdx, copied into registers that way.
 template <class T>
 __device__ __forceinline__ T hc_const_copy(const T *p) {
@@ -215,13 +212,7 @@ __device__ __forceinline__ T hc_const_copy(const T *p) {
 // KC: through the CONSTANT address space (the batched multi-modulus kernels, whose 32-bit and 64-bit bodies sit side by side: hc_const_copy). The convolution's kernels keep
 // global loads: as constant-memory loads their twiddle fetches may be hoisted anywhere, and hc_k_b3 / hc_k_b5m - two transforms each - then spill 430-530 bytes (-19 % conv/s)
 template <bool KC = false> struct HcRowsTwA { const HcTw *p; __device__ __forceinline__ HcTw operator()(int slot) const { if (KC) return HC_TW_LOADK(p, slot); else return HC_TW_LOAD(p, slot); } };
-#ifndef HC_DBG_TWB_FIXED
-#define HC_DBG_TWB_FIXED 0          // timing probe only (WRONG residues): every per-thread twiddle of a rows pass is the slot-0 one - what the 60 KiB of per-thread twiddles per tile cost
-#endif
-#if HC_DBG_TWB_FIXED
-#warning "HC_DBG_TWB_FIXED is set: a TIMING PROBE build - every residue that goes through a rows pass is WRONG"
-#endif
-template <bool KC = false> struct HcRowsTwB { const HcTw *p; __device__ __forceinline__ HcTw operator()(int slot) const { if (HC_DBG_TWB_FIXED) slot = 0; if (KC) return HC_TW_LOADK(p, slot * 16); else return HC_TW_LOAD(p, slot * 16); } };
+template <bool KC = false> struct HcRowsTwB { const HcTw *p; __device__ __forceinline__ HcTw operator()(int slot) const { if (KC) return HC_TW_LOADK(p, slot * 16); else return HC_TW_LOAD(p, slot * 16); } };
 
 // forward rows pass on registers: in  e[hi] = element (row, hi*16+tid)  [lazy < 4q]
 //                                 out e[lo] = element (row, tid*16+lo)  [lazy, bound per forward mode]
@@ -270,17 +261,6 @@ __device__ __forceinline__ void hc_cols_inv(u64 (&e)[16], u64 *lds, const HcTwTa
     hc_gs_round<SCALE>(e, HcRowsTwA<KC>{T.colsA}, Q, T.ninv, T.w_last_ninv);
 }
 
-// fp64 form of the inverse cols pass (same data movement; LDS carries the doubles' bit patterns; the rows pass is hc_rows_inv2_f64)
-__device__ __forceinline__ void hc_cols_inv_f64(double (&e)[16], u64 *lds, const HcTwTab &T, int c, int tid, HcF64Mod m) {
-    hc_gs_round_f64<false>(e, HcRowsTwB<false>{T.colsB + tid}, m, T.ninv, T.ninv);
-#pragma unroll
-    for (int lo = 0; lo < 16; lo++) lds[hc_cols_lds(tid * 16 + lo, c)] = hc_d2u(e[lo]);
-    __syncthreads();
-#pragma unroll
-    for (int hi = 0; hi < 16; hi++) e[hi] = hc_u2d(lds[hc_cols_lds(hi * 16 + tid, c)]);
-    hc_gs_round_f64<true>(e, HcRowsTwA<false>{T.colsA}, m, T.ninv, T.w_last_ninv);
-}
-
 // rows tile <-> "linear" order (thread t holds column t of the 16 rows; k = local row) through LDS
 __device__ __forceinline__ void hc_rows_lin_to_lo(u64 (&e)[16], u64 *lds, int t, int rloc, int tid) {
 #pragma unroll
@@ -301,9 +281,6 @@ __device__ __forceinline__ void hc_rows_lo_to_lin(u64 (&e)[16], u64 *lds, int t,
 // 256-thread workgroup caps a CU at 5 workgroups = 5 wavefronts per SIMD; these kernels wait on memory two thirds of the time at VALU busy 0.4-0.5 (rocprofv3 SQ counters,
 // profiles/round4_chain_valu_table.txt), their 44-56 VGPRs would admit 8. The swizzles below are the 8-byte ones with one more row bit folded in: a ds_*_b32 is serviced
 // over 64 banks for all 64 lanes, and the four rows (rows passes) / four tids (cols passes) of a wavefront must land in four different 16-word groups.
-#ifndef HC_MM_LDS32
-#define HC_MM_LDS32 1
-#endif
 #ifndef HC_MM_WAVES
 #define HC_MM_WAVES 7                  // wavefronts per SIMD the multi-modulus transform kernels are compiled for (VGPR budget 512 / HC_MM_WAVES)
 #endif
@@ -315,20 +292,7 @@ __device__ __forceinline__ void hc_rows_lo_to_lin(u64 (&e)[16], u64 *lds, int t,
 // 7 / 4 180.8, 8 / 6 193.0 (spills), 7 / 7 with two-element extension groups 169.6
 // The convolution's transform kernels (61-bit P, 82-126 VGPRs: occupancy is set by registers, not LDS): measured per kernel (profiles/round4_conv33_lds32_ab.txt), the
 // 4-byte exchange pays in the cols kernels a2, b2, b4 (-2..4 % each) and costs in the rows kernels a3, b3 (two exchanges each, +14 %), which keep the 8-byte one.
-#ifndef HC_CV_LDS32
-#define HC_CV_LDS32 1
-#endif
-#if HC_CV_LDS32
-typedef u32 hc_cvc_lds_t;
-#else
-typedef u64 hc_cvc_lds_t;
-#endif
-typedef u64 hc_cvr_lds_t;
-#if HC_MM_LDS32
-typedef u32 hc_mm_lds_t;
-#else
-typedef u64 hc_mm_lds_t;
-#endif
+// So: u32 tiles in every multi-modulus kernel and in the convolution's cols kernels, u64 tiles in its rows kernels and in the standalone transforms.
 __device__ __forceinline__ int hc_rows_lds32(int rloc, int col) {
     return rloc * 256 + ((col & 0xF0) ^ ((rloc & 1) << 4) ^ ((rloc & 2) << 4)) + ((col & 15) ^ ((col >> 5) & 7) ^ ((rloc & 1) << 3));
 }
@@ -372,7 +336,7 @@ __device__ __forceinline__ void hc_cols_inv(u64 (&e)[16], u32 *lds, const HcTwTa
     hc_xchg32(e, lds, [&](int lo) { return hc_cols_lds32(tid * 16 + lo, c); }, [&](int hi) { return hc_cols_lds32(hi * 16 + tid, c); }, [] { __syncthreads(); });
     hc_gs_round<SCALE>(e, HcRowsTwA<KC>{T.colsA}, Q, T.ninv, T.w_last_ninv);
 }
-// fp64 forms: the doubles travel as their bit patterns
+// the same exchange for doubles: they travel as their bit patterns
 template <class WA, class RA, class SY>
 __device__ __forceinline__ void hc_xchg32_f64(double (&f)[16], u32 *lds, WA wa, RA ra, SY sync) {
     u64 b[16];
@@ -382,11 +346,7 @@ __device__ __forceinline__ void hc_xchg32_f64(double (&f)[16], u32 *lds, WA wa, 
 #pragma unroll
     for (int i = 0; i < 16; i++) f[i] = hc_u2d(b[i]);
 }
-__device__ __forceinline__ void hc_rows_inv_f64(double (&e)[16], u32 *lds, const HcTwTab &T, int row, int rloc, int tid, HcF64Mod m) {
-    hc_gs_round_f64<false>(e, HcRowsTwB<false>{T.rowsB + row * 256 + tid}, m, T.ninv, T.ninv);
-    hc_xchg32_f64(e, lds, [&](int lo) { return hc_rows_lds32(rloc, tid * 16 + lo); }, [&](int hi) { return hc_rows_lds32(rloc, hi * 16 + tid); }, [] { HC_ROW_SYNC(); });
-    hc_gs_round_f64<false>(e, HcRowsTwA<false>{T.rowsA + row * 16}, m, T.ninv, T.ninv);
-}
+// fp64 form of the inverse cols pass (the rows pass is hc_rows_inv2_f64, through 8-byte words)
 __device__ __forceinline__ void hc_cols_inv_f64(double (&e)[16], u32 *lds, const HcTwTab &T, int c, int tid, HcF64Mod m) {
     hc_gs_round_f64<false>(e, HcRowsTwB<false>{T.colsB + tid}, m, T.ninv, T.ninv);
     hc_xchg32_f64(e, lds, [&](int lo) { return hc_cols_lds32(tid * 16 + lo, c); }, [&](int hi) { return hc_cols_lds32(hi * 16 + tid, c); }, [] { __syncthreads(); });
@@ -412,10 +372,7 @@ __device__ __forceinline__ u64 hc_barrett64(u64 x, u64 q, u64 mu) {
 // each (ONE exchange and barrier per pass instead of the two halves' three). The 32-bit companion of a table entry (w, w' = floor(w 2^64 / q)) is (low word of w, high word of
 // w'): floor(floor(w 2^64 / q) / 2^32) = floor(w 2^32 / q), so the 64-bit tables serve both forms. Everything is canonical, in and out: the same residues as the 64-bit
 // kernels, bit for bit. A workgroup takes this form as a WHOLE (its modulus is block-uniform): the 64-bit and 32-bit bodies share no live registers (round 4 switched per
-// butterfly inside one body and paid 108-132 VGPRs for 65-86: profiles/round4_chain_class_paths_ab.txt).
-#ifndef HC_S32
-#define HC_S32 1
-#endif
+// butterfly inside one body and paid 108-132 VGPRs for 65-86: profiles/round4_chain_class_paths_ab.txt). Chosen at run time per modulus: HcRowMod::s32 (option small32).
 __device__ __forceinline__ HcTw32 hc_tw32(const HcTw &t) { return HcTw32{(u32)t.w, (u32)(t.ws >> 32)}; }
 __device__ __forceinline__ u32 hc_umulhi32(u32 a, u32 b) { return (u32)(((u64)a * b) >> 32); }
 __device__ __forceinline__ u32 hc_min32(u32 a, u32 b) { return a < b ? a : b; }
@@ -476,7 +433,7 @@ __device__ __forceinline__ void hc_xchg1(u32 (&e)[16], u32 *lds, WA wa, RA ra, S
 #define HC_TW32_LOADK(p, i) ((p)[i])
 #endif
 struct HcRowsTw32A { const HcTw32 *p; __device__ __forceinline__ HcTw32 operator()(int slot) const { return HC_TW32_LOADK(p, slot); } };
-struct HcRowsTw32B { const HcTw32 *p; __device__ __forceinline__ HcTw32 operator()(int slot) const { if (HC_DBG_TWB_FIXED) slot = 0; return HC_TW32_LOADK(p, slot * 16); } };
+struct HcRowsTw32B { const HcTw32 *p; __device__ __forceinline__ HcTw32 operator()(int slot) const { return HC_TW32_LOADK(p, slot * 16); } };
 __device__ __forceinline__ void hc_rows_fwd32(u32 (&e)[16], u32 *lds, const HcTwTab32 &T, int row, int rloc, int tid, u32 q) {
     hc_ct_round32(e, HcRowsTw32A{T.rowsA + row * 16}, q);
     hc_xchg1(e, lds, [&](int hi) { return hc_rows_lds32(rloc, hi * 16 + tid); }, [&](int lo) { return hc_rows_lds32(rloc, tid * 16 + lo); }, [] { HC_ROW_SYNC(); });
@@ -940,18 +897,10 @@ __device__ __forceinline__ void hc_rows_inv2_f64(double (&f0)[16], double (&f1)[
 // any time work on the same tile of different jobs and share that tile's fixed operands -- 64 KiB of per-row twiddles, 64 KiB of c'
 // pairs, 64-128 KiB of key / idx pairs per tile, as much as or more than the 32-96 KiB of data a workgroup moves -- out of L2. With
 // the tile index fast (round 1) every resident workgroup wanted a different tile of every table and those bytes came over the fabric.
-#ifndef HC_JOB_FAST
-#define HC_JOB_FAST 0       // 16 tiles over 8 XCDs: with the tile index fast, XCD r serves tiles r and r + 8 of EVERY job, so each L2 keeps just
-#endif                      // two tiles of every twiddle / key / c' table (measured 2-4 % faster than job-fast, which cycles all 16 through every L2)
-#if HC_JOB_FAST
-#define HC_JOB blockIdx.x
-#define HC_TILE blockIdx.y
-#define HC_NJOBS gridDim.x
-#else
+// 16 tiles over 8 XCDs: with the tile index fast, XCD r serves tiles r and r + 8 of EVERY job, so each L2 keeps just two tiles of every twiddle / key / c' table (measured 2-4 %
+// faster than the job index fast, which cycles all 16 through every L2)
 #define HC_JOB blockIdx.y
 #define HC_TILE blockIdx.x
-#define HC_NJOBS gridDim.y
-#endif
 #define HC_FREE_OFF 72                // FREE-mode forward outputs are below 70q (hc_ct_round): X + 72q - (such a value) stays positive
 // wavefronts per SIMD each transform kernel of the convolution is compiled for (its VGPR budget)
 #ifndef HC_W_A1
@@ -996,7 +945,7 @@ struct HcLoopA {
 // k_i[1] is loaded once and every T1inv twiddle once for the two transforms (hc_rows_inv2 / hc_rows_inv2_f64); one LDS tile, used by the two polynomials in turn.
 template <int F64>
 __global__ __launch_bounds__(HC_TPB, HC_W_A1) void hc_k_a1p(HcLoopA A, HcTwTab T1inv) {
-    __shared__ hc_cvr_lds_t lds[HC_ROWS_LDS];
+    __shared__ u64 lds[HC_ROWS_LDS];
     const int t = threadIdx.x, tid = t & 15, rloc = t >> 4, row = HC_TILE * 16 + rloc;
     const int ch = HC_JOB, i = A.i0 + ch * A.norm, z = blockIdx.z;
     const HcTw *__restrict__ c0 = A.ctc + ((size_t)z * 4 + 1) * 65536 + (size_t)HC_TILE * 4096 + t;          // c'_0[1] ; c'_1[1] is 2 * 65536 pairs on
@@ -1030,7 +979,7 @@ __global__ __launch_bounds__(HC_TPB, HC_W_A1) void hc_k_a1p(HcLoopA A, HcTwTab T
 // KA2: cols-inverse mod Q1, centred lift to Q0, cols-forward mod Q0, in place on tmp. grid = (jobs * batch, 16)
 template <int FM, int F64>
 __global__ __launch_bounds__(HC_TPB, HC_W_A2) void hc_k_a2(HcLoopA A, HcTwTab T1inv, HcTwTab T0fwd) {
-    __shared__ hc_cvc_lds_t lds[HC_COLS_LDS];
+    __shared__ u32 lds[HC_COLS_LDS];
     const int t = threadIdx.x, c = t & 15, tid = t >> 4;
     u64 *base = A.tmp + (size_t)HC_JOB * 65536 + HC_TILE * 16 + c;
     const HcQ Q0 = hc_q(A.m0.q);
@@ -1069,7 +1018,7 @@ __global__ __launch_bounds__(HC_TPB, HC_W_A2) void hc_k_a2(HcLoopA A, HcTwTab T1
 // (all loads up front, as the one-polynomial form of this kernel had them) would be 64 more registers across it.
 template <int FM>
 __global__ __launch_bounds__(HC_TPB, HC_W_A3) void hc_k_a3p(HcLoopA A, HcTwTab T0fwd) {
-    __shared__ hc_cvr_lds_t lds[HC_ROWS_LDS];
+    __shared__ u64 lds[HC_ROWS_LDS];
     const int t = threadIdx.x, tid = t & 15, rloc = t >> 4, row = HC_TILE * 16 + rloc;
     const int ch = HC_JOB, i = A.i0 + ch * A.norm, z = blockIdx.z;
     const u64 *__restrict__ in = A.tmp + ((size_t)z * A.njobs + 2 * ch) * 65536 + (size_t)row * 256;
@@ -1131,7 +1080,7 @@ struct HcLoopB {
 // KB1: t2.c1 = y1 - I*x1 (kept in tmpT for KB5) and its rows-inverse (mod Q0). grid = (batch*nodes, 16). Everything else a node needs
 // from x and y (t1, t2.c0, the Q-part of the key switch) is formed in KB5 from src and tmpT.
 __global__ __launch_bounds__(HC_TPB, HC_W_B1) void hc_k_b1(HcLoopB B, HcTwTab T0inv) {
-    __shared__ hc_cvr_lds_t lds[HC_ROWS_LDS];
+    __shared__ u64 lds[HC_ROWS_LDS];
     const int t = threadIdx.x, tid = t & 15, rloc = t >> 4, row = HC_TILE * 16 + rloc;
     const int job = HC_JOB, z = job / B.nodes, node = job - z * B.nodes, i = (B.n0 + node) * B.norm;
     const size_t tile = (size_t)HC_TILE * 4096 + t;
@@ -1162,7 +1111,7 @@ __global__ __launch_bounds__(HC_TPB, HC_W_B1) void hc_k_b1(HcLoopB B, HcTwTab T0
 // KB2: cols-inverse mod Q0 (-> canonical c < Q0 < P), cols-forward mod P, in place on tmpC. grid = (batch*nodes, 16)
 template <int FMP>
 __global__ __launch_bounds__(HC_TPB, HC_W_B2) void hc_k_b2(HcLoopB B, HcTwTab T0inv, HcTwTab TPfwd) {
-    __shared__ hc_cvc_lds_t lds[HC_COLS_LDS];
+    __shared__ u32 lds[HC_COLS_LDS];
     const int t = threadIdx.x, c = t & 15, tid = t >> 4;
     u64 *base = B.tmpC + (size_t)HC_JOB * 65536 + HC_TILE * 16 + c;
     const HcQ Q0 = hc_q(B.m0.q), QP = hc_q(B.mp.q);
@@ -1180,7 +1129,7 @@ __global__ __launch_bounds__(HC_TPB, HC_W_B2) void hc_k_b2(HcLoopB B, HcTwTab T0
 // KB3: rows-forward mod P, multiply by b_P and a_P, rows-inverse mod P of both in lock step, every TPinv twiddle loaded once (hc_rows_inv2). grid = (batch*nodes, 16)
 template <int FMP>
 __global__ __launch_bounds__(HC_TPB, HC_W_B3) void hc_k_b3p(HcLoopB B, HcTwTab TPfwd, HcTwTab TPinv) {
-    __shared__ hc_cvr_lds_t lds[HC_ROWS_LDS];
+    __shared__ u64 lds[HC_ROWS_LDS];
     const int t = threadIdx.x, tid = t & 15, rloc = t >> 4, row = HC_TILE * 16 + rloc;
     const int node = HC_JOB;
     const u64 *in = B.tmpC + (size_t)node * 65536 + (size_t)row * 256;
@@ -1209,7 +1158,7 @@ __global__ __launch_bounds__(HC_TPB, HC_W_B3) void hc_k_b3p(HcLoopB B, HcTwTab T
 // grid = (2*batch*nodes, 16), in place on tmpE
 template <int FM>
 __global__ __launch_bounds__(HC_TPB, HC_W_B4) void hc_k_b4(HcLoopB B, HcTwTab TPinv, HcTwTab T0fwd) {
-    __shared__ hc_cvc_lds_t lds[HC_COLS_LDS];
+    __shared__ u32 lds[HC_COLS_LDS];
     const int t = threadIdx.x, c = t & 15, tid = t >> 4;
     u64 *base = B.tmpE + (size_t)HC_JOB * 65536 + HC_TILE * 16 + c;
     const HcQ QP = hc_q(B.mp.q), Q = hc_q(B.m0.q);
@@ -1428,7 +1377,7 @@ __global__ __launch_bounds__(HC_TPB, HC_B5M_WAVES) void hc_k_b5m(HcLoopB B, HcTw
 #define HC_STPB 256
 #define HC_STILES 64               // quarter tiles per row
 #define HC_S_LDS 1024
-template <bool ROWS> __device__ __forceinline__ int hc_s_addr(int line, int x) { return ROWS ? line * 256 + x : x * 4 + line; }
+__device__ __forceinline__ int hc_s_addr(int line, int x) { return x * 4 + line; }       // cols tile in LDS: 256 rows x 4 columns (the rows passes run in registers: hc_s_pass_fwd_reg)
 __device__ __forceinline__ int hc_s_pos(int u, int lo) { return (u & ((1 << lo) - 1)) | ((u >> lo) << (lo + 2)); }     // u (6 bits) with two zero bits inserted at lo, lo + 1
 // twiddle of the forward butterfly at distance D whose lower element sits at position x of its 256-point line (gline: global row, rows passes)
 template <bool ROWS, int D> __device__ __forceinline__ HcTw hc_s_tw_fwd(const HcTwTab &T, int x, int gline) {
@@ -1457,43 +1406,41 @@ template <bool ROWS> __device__ __forceinline__ void hc_s_tw_load_inv(HcTw (&w)[
     { const int x0 = hc_s_pos(u, 4); w[6] = hc_s_tw_inv<ROWS, 16>(T, x0, gline); w[7] = hc_s_tw_inv<ROWS, 16>(T, x0 + 32, gline); w[8] = hc_s_tw_inv<ROWS, 32>(T, x0, gline); }
     { const int x0 = hc_s_pos(u, 6); w[9] = hc_s_tw_inv<ROWS, 64>(T, x0, gline); w[10] = hc_s_tw_inv<ROWS, 64>(T, x0 + 128, gline); w[11] = hc_s_tw_inv<ROWS, 128>(T, x0, gline); }
 }
-// one radix-4 round of a forward pass: distances D and D/2 (wa: stage D; wb, wc: stage D/2 of the lower / upper pair)
-template <bool ROWS, int D> __device__ __forceinline__ void hc_s_round_fwd(u64 *lds, HcTw wa, HcTw wb, HcTw wc, int line, int u, const HcQ &Q) {
+// one radix-4 round of a forward cols pass over the tile in LDS: distances D and D/2 (wa: stage D; wb, wc: stage D/2 of the lower / upper pair)
+template <int D> __device__ __forceinline__ void hc_s_round_fwd(u64 *lds, HcTw wa, HcTw wb, HcTw wc, int line, int u, const HcQ &Q) {
     constexpr int lo = D == 128 ? 6 : D == 32 ? 4 : D == 8 ? 2 : 0, H = D / 2;
     const int x0 = hc_s_pos(u, lo);
-    u64 e0 = lds[hc_s_addr<ROWS>(line, x0)], e1 = lds[hc_s_addr<ROWS>(line, x0 + H)], e2 = lds[hc_s_addr<ROWS>(line, x0 + D)], e3 = lds[hc_s_addr<ROWS>(line, x0 + D + H)];
+    u64 e0 = lds[hc_s_addr(line, x0)], e1 = lds[hc_s_addr(line, x0 + H)], e2 = lds[hc_s_addr(line, x0 + D)], e3 = lds[hc_s_addr(line, x0 + D + H)];
     hc_s_bf_fwd(e0, e2, wa, Q); hc_s_bf_fwd(e1, e3, wa, Q);
     hc_s_bf_fwd(e0, e1, wb, Q); hc_s_bf_fwd(e2, e3, wc, Q);
-    lds[hc_s_addr<ROWS>(line, x0)] = e0; lds[hc_s_addr<ROWS>(line, x0 + H)] = e1; lds[hc_s_addr<ROWS>(line, x0 + D)] = e2; lds[hc_s_addr<ROWS>(line, x0 + D + H)] = e3;
+    lds[hc_s_addr(line, x0)] = e0; lds[hc_s_addr(line, x0 + H)] = e1; lds[hc_s_addr(line, x0 + D)] = e2; lds[hc_s_addr(line, x0 + D + H)] = e3;
 }
-// one radix-4 round of an inverse pass: distances D and 2D (wa, wb: stage D of the lower / upper pair; wc: stage 2D). SCALE_LAST (D == 64 of a cols pass that carries
+// one radix-4 round of an inverse cols pass: distances D and 2D (wa, wb: stage D of the lower / upper pair; wc: stage 2D). SCALE_LAST (D == 64 of a pass that carries
 // N^-1): the final stage multiplies its sums by N^-1 and uses the twiddle that has N^-1 folded in (hc_gs_round<LAST>)
-template <bool ROWS, int D, bool SCALE_LAST> __device__ __forceinline__ void hc_s_round_inv(u64 *lds, const HcTwTab &T, HcTw wa, HcTw wb, HcTw wc, int line, int u, const HcQ &Q) {
+template <int D, bool SCALE_LAST> __device__ __forceinline__ void hc_s_round_inv(u64 *lds, const HcTwTab &T, HcTw wa, HcTw wb, HcTw wc, int line, int u, const HcQ &Q) {
     constexpr int lo = D == 1 ? 0 : D == 4 ? 2 : D == 16 ? 4 : 6, G = 2 * D;
     const int x0 = hc_s_pos(u, lo);
-    u64 e0 = lds[hc_s_addr<ROWS>(line, x0)], e1 = lds[hc_s_addr<ROWS>(line, x0 + D)], e2 = lds[hc_s_addr<ROWS>(line, x0 + G)], e3 = lds[hc_s_addr<ROWS>(line, x0 + G + D)];
+    u64 e0 = lds[hc_s_addr(line, x0)], e1 = lds[hc_s_addr(line, x0 + D)], e2 = lds[hc_s_addr(line, x0 + G)], e3 = lds[hc_s_addr(line, x0 + G + D)];
     hc_s_bf_inv(e0, e1, wa, Q); hc_s_bf_inv(e2, e3, wb, Q);
     if (SCALE_LAST) {
         const u64 ua = e0 + e2, da = (e0 + Q.q4) - e2, ub = e1 + e3, db = (e1 + Q.q4) - e3;
         e0 = hc_shoup4(ua, T.ninv.w, T.ninv.ws, Q); e2 = hc_shoup4(da, T.w_last_ninv.w, T.w_last_ninv.ws, Q);
         e1 = hc_shoup4(ub, T.ninv.w, T.ninv.ws, Q); e3 = hc_shoup4(db, T.w_last_ninv.w, T.w_last_ninv.ws, Q);
     } else { hc_s_bf_inv(e0, e2, wc, Q); hc_s_bf_inv(e1, e3, wc, Q); }
-    lds[hc_s_addr<ROWS>(line, x0)] = e0; lds[hc_s_addr<ROWS>(line, x0 + D)] = e1; lds[hc_s_addr<ROWS>(line, x0 + G)] = e2; lds[hc_s_addr<ROWS>(line, x0 + G + D)] = e3;
+    lds[hc_s_addr(line, x0)] = e0; lds[hc_s_addr(line, x0 + D)] = e1; lds[hc_s_addr(line, x0 + G)] = e2; lds[hc_s_addr(line, x0 + G + D)] = e3;
 }
-// between the rounds of a ROWS pass a line belongs to ONE wavefront (line = t >> 6): wave-level order is enough (HC_ROW_SYNC); a cols line is spread over the four waves
-template <bool ROWS> __device__ __forceinline__ void hc_s_sync() { if (ROWS) { HC_ROW_SYNC(); } else __syncthreads(); }
-// whole passes over the tile in LDS with preloaded twiddles; every thread must call them; they end with a barrier (the tile is complete and visible)
-template <bool ROWS> __device__ __forceinline__ void hc_s_pass_fwd(u64 *lds, const HcTw (&w)[12], int line, int u, const HcQ &Q) {
-    hc_s_round_fwd<ROWS, 128>(lds, w[0], w[1], w[2], line, u, Q); hc_s_sync<ROWS>();
-    hc_s_round_fwd<ROWS, 32>(lds, w[3], w[4], w[5], line, u, Q); hc_s_sync<ROWS>();
-    hc_s_round_fwd<ROWS, 8>(lds, w[6], w[7], w[8], line, u, Q); hc_s_sync<ROWS>();
-    hc_s_round_fwd<ROWS, 2>(lds, w[9], w[10], w[11], line, u, Q); __syncthreads();
+// whole cols passes over the tile in LDS with preloaded twiddles (a cols line is spread over the four waves: a barrier between the rounds); every thread must call them; they end with a barrier (the tile is complete and visible)
+__device__ __forceinline__ void hc_s_pass_fwd(u64 *lds, const HcTw (&w)[12], int line, int u, const HcQ &Q) {
+    hc_s_round_fwd<128>(lds, w[0], w[1], w[2], line, u, Q); __syncthreads();
+    hc_s_round_fwd<32>(lds, w[3], w[4], w[5], line, u, Q); __syncthreads();
+    hc_s_round_fwd<8>(lds, w[6], w[7], w[8], line, u, Q); __syncthreads();
+    hc_s_round_fwd<2>(lds, w[9], w[10], w[11], line, u, Q); __syncthreads();
 }
-template <bool ROWS, bool SCALE> __device__ __forceinline__ void hc_s_pass_inv(u64 *lds, const HcTwTab &T, const HcTw (&w)[12], int line, int u, const HcQ &Q) {
-    hc_s_round_inv<ROWS, 1, false>(lds, T, w[0], w[1], w[2], line, u, Q); hc_s_sync<ROWS>();
-    hc_s_round_inv<ROWS, 4, false>(lds, T, w[3], w[4], w[5], line, u, Q); hc_s_sync<ROWS>();
-    hc_s_round_inv<ROWS, 16, false>(lds, T, w[6], w[7], w[8], line, u, Q); hc_s_sync<ROWS>();
-    hc_s_round_inv<ROWS, 64, SCALE>(lds, T, w[9], w[10], w[11], line, u, Q); __syncthreads();
+template <bool SCALE> __device__ __forceinline__ void hc_s_pass_inv(u64 *lds, const HcTwTab &T, const HcTw (&w)[12], int line, int u, const HcQ &Q) {
+    hc_s_round_inv<1, false>(lds, T, w[0], w[1], w[2], line, u, Q); __syncthreads();
+    hc_s_round_inv<4, false>(lds, T, w[3], w[4], w[5], line, u, Q); __syncthreads();
+    hc_s_round_inv<16, false>(lds, T, w[6], w[7], w[8], line, u, Q); __syncthreads();
+    hc_s_round_inv<64, SCALE>(lds, T, w[9], w[10], w[11], line, u, Q); __syncthreads();
 }
 // ---- rows passes in REGISTERS with cross-lane exchanges (round 3): a 256-point line is the work of ONE wavefront (64 lanes x 4 residues), so the three regroupings between
 // the four radix-4 rounds are 4 x 4 transposes between the register index and a pair of lane bits - lane distances 32 / 16 (v_permlane32_swap, v_permlane16_swap: gfx950),
@@ -1501,9 +1448,6 @@ template <bool ROWS, bool SCALE> __device__ __forceinline__ void hc_s_pass_inv(u
 // the lanes whose bit LB is 0 hand r1 to their partner (lane ^ 2^LB) and receive its r0 into r1's place... precisely: lane(bit = 0).r1 <-> lane(bit = 1).r0.
 // (lane semantics of the five instructions probed on MI355X: tools/dpp_probe.hip). Under the CPU emulator the threads of a block are fibers: the exchange goes through a
 // static array with two yields.
-#ifndef HC_S_REG_PASSES
-#define HC_S_REG_PASSES 1
-#endif
 #if defined(HC_EMU)
 template <int LB> __device__ __forceinline__ void hc_xswap(u64 &r0, u64 &r1) {
     __shared__ u64 xch[HC_STPB];
@@ -1564,7 +1508,6 @@ __device__ __forceinline__ void hc_s_pass_inv_reg(u64 (&e)[4], const HcTw (&w)[1
 
 // SB1: t2.c1 = y1 - I*x1, rows-inverse mod Q0 -> tmpC. grid = (64, batch*nodes)
 __global__ __launch_bounds__(HC_STPB) void hc_k_sb1(HcLoopB B, HcTwTab T0inv) {
-    __shared__ u64 lds[HC_S_LDS];
     HC_S_ROWS_MAP;
     const int job = HC_JOB, z = job / B.nodes, node = job - z * B.nodes, i = (B.n0 + node) * B.norm;
     const size_t tile = (size_t)HC_TILE * 1024;
@@ -1574,8 +1517,6 @@ __global__ __launch_bounds__(HC_STPB) void hc_k_sb1(HcLoopB B, HcTwTab T0inv) {
     const HcQ Q = hc_q(B.m0.q);
     HcTw w[12]; hc_s_tw_load_inv<true>(w, T0inv, grow, u);
     u64 *__restrict__ o = B.tmpC + (size_t)job * 65536 + tile;
-#if HC_S_REG_PASSES
-    (void)lds;
     u64 e[4];
 #pragma unroll
     for (int j = 0; j < 4; j++) {
@@ -1585,17 +1526,6 @@ __global__ __launch_bounds__(HC_STPB) void hc_k_sb1(HcLoopB B, HcTwTab T0inv) {
     hc_s_pass_inv_reg(e, w, Q);
 #pragma unroll
     for (int j = 0; j < 4; j++) o[line * 256 + j * 64 + u] = e[j];
-#else
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        const int p = k * 256 + t; const HcTw I = idx[p];
-        lds[p] = hc_fold(y1[p] + Q.q4 - hc_shoup4(x1[p], I.w, I.ws, Q), Q.nq4);          // t2.c1 (conv.go:288-289), lazy < 4q
-    }
-    __syncthreads();
-    hc_s_pass_inv<true, false>(lds, T0inv, w, line, u, Q);
-#pragma unroll
-    for (int k = 0; k < 4; k++) o[k * 256 + t] = lds[k * 256 + t];
-#endif
 }
 // SB2: cols-inverse mod Q0 (with N^-1) -> canonical -> cols-forward mod P, in place on tmpC. grid = (64, batch*nodes); the tile is 256 rows x 4 columns
 __global__ __launch_bounds__(HC_STPB) void hc_k_sb2(HcLoopB B, HcTwTab T0inv, HcTwTab TPfwd) {
@@ -1607,19 +1537,18 @@ __global__ __launch_bounds__(HC_STPB) void hc_k_sb2(HcLoopB B, HcTwTab T0inv, Hc
 #pragma unroll
     for (int k = 0; k < 4; k++) { const int r = k * 64 + u; lds[r * 4 + line] = base[(size_t)r * 256 + line]; }
     __syncthreads();
-    hc_s_pass_inv<false, true>(lds, T0inv, w, line, u, Q0);
+    hc_s_pass_inv<true>(lds, T0inv, w, line, u, Q0);
     hc_s_tw_load_fwd<false>(w, TPfwd, 0, u);
 #pragma unroll
     for (int k = 0; k < 4; k++) { const int a = (k * 64 + u) * 4 + line; lds[a] = hc_canon4(lds[a], Q0); }       // each thread its own four words: no barrier needed before, one after
     __syncthreads();
-    hc_s_pass_fwd<false>(lds, w, line, u, QP);
+    hc_s_pass_fwd(lds, w, line, u, QP);
 #pragma unroll
     for (int k = 0; k < 4; k++) { const int r = k * 64 + u; base[(size_t)r * 256 + line] = lds[r * 4 + line]; }
 }
 // SB3: rows-forward mod P, times the k-th P row of the key, rows-inverse mod P -> tmpE[k]. grid = (64, batch*nodes, 2): blockIdx.z = k (both polynomials in parallel;
 // the forward pass is done twice, a level's latency is what counts here)
 __global__ __launch_bounds__(HC_STPB) void hc_k_sb3(HcLoopB B, HcTwTab TPfwd, HcTwTab TPinv) {
-    __shared__ u64 lds[HC_S_LDS];
     HC_S_ROWS_MAP;
     const int node = HC_JOB, k = blockIdx.z;
     const size_t tile = (size_t)HC_TILE * 1024;
@@ -1627,43 +1556,21 @@ __global__ __launch_bounds__(HC_STPB) void hc_k_sb3(HcLoopB B, HcTwTab TPfwd, Hc
     const HcQ Q = hc_q(B.mp.q);
     HcTw w[12]; hc_s_tw_load_fwd<true>(w, TPfwd, grow, u);
     const HcTw *__restrict__ ev = B.evkP + (size_t)k * 65536;                    // lo-local coalesced order: natural (R, C = tid*16 + lo) -> ((R>>4)*16 + lo)*256 + (R&15)*16 + tid
-#if HC_S_REG_PASSES
-    {
-        (void)lds;
-        u64 e[4];
+    u64 e[4];
 #pragma unroll
-        for (int j = 0; j < 4; j++) e[j] = in[line * 256 + j * 64 + u];
-        hc_s_pass_fwd_reg(e, w, Q);
-        hc_s_tw_load_inv<true>(w, TPinv, grow, u);
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            const int R = grow, C = u * 4 + j;
-            const HcTw kw = ev[((R >> 4) * 16 + (C & 15)) * 256 + (R & 15) * 16 + (C >> 4)];
-            e[j] = hc_shoup4(e[j], kw.w, kw.ws, Q);                                // < 4q for any 64-bit input: what the inverse pass takes
-        }
-        hc_s_pass_inv_reg(e, w, Q);
-        u64 *o = B.tmpE + ((size_t)node * 2 + k) * 65536 + tile;
-#pragma unroll
-        for (int j = 0; j < 4; j++) o[line * 256 + j * 64 + u] = e[j];
-        return;
-    }
-#endif
-#pragma unroll
-    for (int j = 0; j < 4; j++) lds[j * 256 + t] = in[j * 256 + t];
-    __syncthreads();
-    hc_s_pass_fwd<true>(lds, w, line, u, Q);
+    for (int j = 0; j < 4; j++) e[j] = in[line * 256 + j * 64 + u];
+    hc_s_pass_fwd_reg(e, w, Q);
     hc_s_tw_load_inv<true>(w, TPinv, grow, u);
 #pragma unroll
     for (int j = 0; j < 4; j++) {
-        const int p = j * 256 + t, R = HC_TILE * 4 + (p >> 8), C = p & 255;
-        const HcTw w = ev[((R >> 4) * 16 + (C & 15)) * 256 + (R & 15) * 16 + (C >> 4)];
-        lds[p] = hc_shoup4(lds[p], w.w, w.ws, Q);                                  // < 4q for any 64-bit input: what the inverse pass takes
+        const int R = grow, C = u * 4 + j;
+        const HcTw kw = ev[((R >> 4) * 16 + (C & 15)) * 256 + (R & 15) * 16 + (C >> 4)];
+        e[j] = hc_shoup4(e[j], kw.w, kw.ws, Q);                                // < 4q for any 64-bit input: what the inverse pass takes
     }
-    __syncthreads();
-    hc_s_pass_inv<true, false>(lds, TPinv, w, line, u, Q);
+    hc_s_pass_inv_reg(e, w, Q);
     u64 *o = B.tmpE + ((size_t)node * 2 + k) * 65536 + tile;
 #pragma unroll
-    for (int j = 0; j < 4; j++) o[j * 256 + t] = lds[j * 256 + t];
+    for (int j = 0; j < 4; j++) o[line * 256 + j * 64 + u] = e[j];
 }
 // SB4: cols-inverse mod P (N^-1 is inside the key rows), exact extension P -> Q0 divided by P, cols-forward mod Q0, in place on tmpE. grid = (64, 2*batch*nodes)
 __global__ __launch_bounds__(HC_STPB) void hc_k_sb4(HcLoopB B, HcTwTab TPinv, HcTwTab T0fwd) {
@@ -1675,7 +1582,7 @@ __global__ __launch_bounds__(HC_STPB) void hc_k_sb4(HcLoopB B, HcTwTab TPinv, Hc
 #pragma unroll
     for (int k = 0; k < 4; k++) { const int r = k * 64 + u; lds[r * 4 + line] = base[(size_t)r * 256 + line]; }
     __syncthreads();
-    hc_s_pass_inv<false, false>(lds, TPinv, w, line, u, QP);
+    hc_s_pass_inv<false>(lds, TPinv, w, line, u, QP);
     hc_s_tw_load_fwd<false>(w, T0fwd, 0, u);
 #pragma unroll
     for (int k = 0; k < 4; k++) {
@@ -1686,7 +1593,7 @@ __global__ __launch_bounds__(HC_STPB) void hc_k_sb4(HcLoopB B, HcTwTab TPinv, Hc
         lds[a] = r;
     }
     __syncthreads();
-    hc_s_pass_fwd<false>(lds, w, line, u, Q);
+    hc_s_pass_fwd(lds, w, line, u, Q);
 #pragma unroll
     for (int k = 0; k < 4; k++) { const int r = k * 64 + u; base[(size_t)r * 256 + line] = lds[r * 4 + line]; }
 }
@@ -1706,27 +1613,15 @@ __global__ __launch_bounds__(HC_STPB) void hc_k_sb5(HcLoopB B, HcTwTab T0fwd, Hc
     u64 *__restrict__ o = (outs.p[z] != nullptr ? const_cast<u64 *>(outs.p[z]) + (size_t)k * 65536 : B.dst + (size_t)z * B.dst_stride + ((size_t)i * 2 + k) * 65536) + tile;
     const u64 *__restrict__ bias = (k == 0 && biases.p[z] != nullptr) ? biases.p[z] + tile : nullptr;
     HcTw w[12]; hc_s_tw_load_fwd<true>(w, T0fwd, grow, u);
-#if HC_S_REG_PASSES
     u64 e[4];
 #pragma unroll
     for (int j = 0; j < 4; j++) e[j] = hc_reduce64(in[line * 256 + j * 64 + u], B.m0.mu, Q);       // canonical whatever produced it: the full-tile b4 hands over in its free-running lazy range (option "s_mask")
     hc_s_pass_fwd_reg(e, w, Q);                                                                    // e[j] = n_k at (line, 4 u + j): the epilogue below is elementwise, any thread may hold any position
-#else
-#pragma unroll
-    for (int j = 0; j < 4; j++) lds[j * 256 + t] = in[j * 256 + t];
-    __syncthreads();
-    hc_s_pass_fwd<true>(lds, w, line, u, Q);
-#endif
     u64 t1[4];
 #pragma unroll
     for (int j = 0; j < 4; j++) {
-#if HC_S_REG_PASSES
         const int p = line * 256 + u * 4 + j;
         const u64 nraw = e[j];
-#else
-        const int p = j * 256 + t;
-        const u64 nraw = lds[p];
-#endif
         const HcTw I = idx[p], K = evk[p];
         const u64 y1 = ys[65536 + p], x1 = xs[65536 + p];
         const u64 T = hc_fold(y1 + Q.q4 - hc_shoup4(x1, I.w, I.ws, Q), Q.nq4);                    // t2.c1, the expression of hc_k_sb1 / hc_k_b1
@@ -1747,11 +1642,7 @@ __global__ __launch_bounds__(HC_STPB) void hc_k_sb5(HcLoopB B, HcTwTab T0fwd, Hc
     __syncthreads();
 #pragma unroll
     for (int j = 0; j < 4; j++) {
-#if HC_S_REG_PASSES
         const int p = line * 256 + u * 4 + j;
-#else
-        const int p = j * 256 + t;
-#endif
         const u32 srcidx = hc_perm_src((u32)(HC_TILE * 1024 + p), B.gal);
         o[p] = hc_addmod(t1[j], lds[srcidx & 1023], Q.q);                                          // row-local permutation: the source is in this 4-row tile
     }
@@ -1789,15 +1680,6 @@ struct HcBasisExt {
 // kernel waited one L2 round trip per element: 626 us per launch against 548 for the separate extension and cols pass it replaces)
 #ifndef HC_EXT_GROUP
 #define HC_EXT_GROUP 4
-#endif
-#ifndef HC_EXT_FULL
-#define HC_EXT_FULL 1                  // a straight-line form of the extension for operands with exactly NS source limbs (hc_basis_ext_tile)
-#endif
-#ifndef HC_DBG_EXT_ONELOAD
-#define HC_DBG_EXT_ONELOAD 0          // timing probe only (WRONG residues): the extension reads ONE of a coefficient's n + 1 operand words - what its 6x re-read of the y rows costs
-#endif
-#if HC_DBG_EXT_ONELOAD
-#warning "HC_DBG_EXT_ONELOAD is set: a TIMING PROBE build - the basis extensions compute WRONG residues"
 #endif
 #define HC_MAX_NP 5                    // most special primes of a context (hc_ctx_create refuses more): the extension's operand registers are sized by it (NS = 2 or HC_MAX_NP)
 // target side of the extension for one coefficient: y[0..n-1] = the y_i, y[n] = v. NS = the most source limbs the caller can have (the context's number of special primes:
@@ -1845,7 +1727,7 @@ __device__ __forceinline__ u64 hc_basis_ext_sum_full(const u64 (&y)[NS + 1], con
 template <int NS>
 __device__ __forceinline__ void hc_basis_ext_tile(u64 (&e)[16], const u64 *yv, const HcBasisExt &B, int tid) {
     const int n = B.n; const HcQ Q = hc_q(B.t);
-    if (HC_EXT_FULL && NS > 1 && n == NS) {                                  // block-uniform
+    if (NS > 1 && n == NS) {                                                 // block-uniform: the straight-line form for operands with exactly NS source limbs
 #pragma unroll
         for (int g0 = 0; g0 < 16; g0 += HC_EXT_GROUP) {
             u64 y[HC_EXT_GROUP][NS + 1];
@@ -1853,7 +1735,7 @@ __device__ __forceinline__ void hc_basis_ext_tile(u64 (&e)[16], const u64 *yv, c
             for (int g = 0; g < HC_EXT_GROUP; g++) {
                 const u64 *p = yv + (size_t)((g0 + g) * 16 + tid) * 256;
 #pragma unroll
-                for (int i = 0; i <= NS; i++) y[g][i] = p[(size_t)(HC_DBG_EXT_ONELOAD ? 0 : i) * 65536];
+                for (int i = 0; i <= NS; i++) y[g][i] = p[(size_t)i * 65536];
             }
 #pragma unroll
             for (int g = 0; g < HC_EXT_GROUP; g++) e[g0 + g] = hc_basis_ext_sum_full<NS>(y[g], B, Q);
@@ -1873,7 +1755,7 @@ __device__ __forceinline__ void hc_basis_ext_tile(u64 (&e)[16], const u64 *yv, c
         for (int g = 0; g < HC_EXT_GROUP; g++) e[g0 + g] = hc_basis_ext_sum<NS>(y[g], B, Q);
     }
 }
-// The target side for a target limb below 2^31 (HC_S32): the constants h_i = S/s_i mod t are 31-bit words, so y_i h_i is formed from the two 32 x 32 -> 64-bit products of
+// The target side for a target limb below 2^31 (the 32-bit body): the constants h_i = S/s_i mod t are 31-bit words, so y_i h_i is formed from the two 32 x 32 -> 64-bit products of
 // y_i's halves (two v_mad_u64_u32 per term instead of a 64-bit lazy Shoup product's 12-14 instructions) and summed WITHOUT carry chains: the high halves' products (y_i < 2^61:
 // below 2^60 each) share one 64-bit accumulator, the low halves' (below 2^63 each) one per PAIR of terms; sum = H 2^32 + L with H = hi-sum + the pairs' upper words, L = the
 // pairs' lower words (34 bits). v (S mod t) comes off as 8t - v (S mod t) >= 0 (v <= n <= 8). Two 64-bit Barrett steps reduce H, then (H mod t) 2^32 + L. Canonical, hence the
@@ -1918,7 +1800,7 @@ __device__ __forceinline__ void hc_basis_ext_tile32(u32 (&e)[16], const u64 *yv,
         for (int g = 0; g < HC_EXT_GROUP; g++) {
             const u64 *p = yv + (size_t)((g0 + g) * 16 + tid) * 256;
 #pragma unroll
-            for (int i = 0; i <= NS; i++) y[g][i] = p[HC_DBG_EXT_ONELOAD ? 0 : roff[i]];
+            for (int i = 0; i <= NS; i++) y[g][i] = p[roff[i]];
         }
 #pragma unroll
         for (int g = 0; g < HC_EXT_GROUP; g++) e[g0 + g] = hc_basis_ext_sum32<NS>(y[g], hat, off, smodt, t, mu_t);
@@ -1926,7 +1808,7 @@ __device__ __forceinline__ void hc_basis_ext_tile32(u32 (&e)[16], const u64 *yv,
 }
 struct HcRowMod { HcTwTab fwd, inv; u64 q, mu;
                   HcTwTab32 fwd32, inv32;   // moduli below 2^31 (null otherwise)
-                  u64 s32; };            // nonzero: the batched transforms take their 32-bit form (HC_S32) for rows of this modulus: q < 2^31 and option small32 (in the table the
+                  u64 s32; };            // nonzero: the batched transforms take their 32-bit form for rows of this modulus: q < 2^31 and option small32 (in the table the
                                          // kernels read their moduli from, so that the option costs no launch argument; the kernels test HC_SMALL_Q(q) && s32)
 // blockIdx.z = operand + nz * image: `nz` operands zs_* words apart (the two polynomials of a ciphertext, the digits of a key switch), and the
 // images of a batch (hc_set_batch) is_* words apart
@@ -2016,7 +1898,7 @@ __device__ __forceinline__ void hc_cols_fwd_mm_small(const u64 *in, u64 *out, u3
     for (int lo = 0; lo < 16; lo++) out[(size_t)y * 65536 + (size_t)(blockIdx.x * 16 + c) + (size_t)(tid * 16 + lo) * 256] = e[lo];
 }
 template <int EXT, int NS>
-__device__ __forceinline__ void hc_cols_fwd_mm_big(const u64 *in, u64 *out, hc_mm_lds_t *lds, const HcMm &A, const HcRowMod &R, int y, int zi, int img) {
+__device__ __forceinline__ void hc_cols_fwd_mm_big(const u64 *in, u64 *out, u32 *lds, const HcMm &A, const HcRowMod &R, int y, int zi, int img) {
     const int t = threadIdx.x, c = t & 15, tid = t >> 4;
     const size_t base = (size_t)y * 65536 + blockIdx.x * 16 + c;
     u64 e[16];
@@ -2054,9 +1936,9 @@ __device__ __forceinline__ void hc_cols_fwd_mm_big(const u64 *in, u64 *out, hc_m
 }
 template <int EXT, int NS = 8>      // EXT 1: the input is the fused basis extension; 2: the extension plus P times Rescale's lift (ModDown and Rescale in one transform); NS: most source limbs of the extension
 __global__ __launch_bounds__(HC_TPB, EXT ? HC_MM_WAVES_EXT : HC_MM_WAVES) void hc_k_cols_fwd_mm(const u64 *in, u64 *out, HcMm A) {
-    __shared__ hc_mm_lds_t lds[HC_COLS_LDS];
+    __shared__ u32 lds[HC_COLS_LDS];
     HC_MM_PROLOGUE
-    if (HC_S32 && HC_SMALL_Q(R.q) && R.s32) hc_cols_fwd_mm_small<EXT, NS>(in, out, reinterpret_cast<u32 *>(lds), A, R, y, zi, img);       // block-uniform
+    if (HC_SMALL_Q(R.q) && R.s32) hc_cols_fwd_mm_small<EXT, NS>(in, out, lds, A, R, y, zi, img);       // block-uniform
     else hc_cols_fwd_mm_big<EXT, NS>(in, out, lds, A, R, y, zi, img);
 }
 #ifndef HC_EPI_ROWS
@@ -2065,7 +1947,7 @@ __global__ __launch_bounds__(HC_TPB, EXT ? HC_MM_WAVES_EXT : HC_MM_WAVES) void h
 #ifndef HC_MM_WAVES_RF
 #define HC_MM_WAVES_RF 6                  // the rows-forward pass with its clustered epilogue loads: 80 VGPRs, no scratch (7 wavefronts: 72 VGPRs and 44 bytes of scratch; measured 18.38 vs 18.51 ms per ciphertext-layer)
 #endif
-// hc_k_rows_fwd_canon_mm for a row whose modulus is below 2^31 (HC_S32): 32-bit residues through the pass and the epilogue
+// hc_k_rows_fwd_canon_mm for a row whose modulus is below 2^31: 32-bit residues through the pass and the epilogue
 __device__ __forceinline__ void hc_rows_fwd_canon_mm_small(const u64 *in, u64 *out, u32 *lds, const HcMm &A, const HcRowMod &R, int y, int zi, int img, int bx) {
     const int t = threadIdx.x, tid = t & 15, rloc = t >> 4, row = bx * 16 + rloc;
     const size_t pbase = (size_t)y * 65536;
@@ -2127,9 +2009,9 @@ __device__ __forceinline__ void hc_rows_fwd_canon_mm_small(const u64 *in, u64 *o
     for (int k = 0; k < 16; k++) out[pbase + lj + (size_t)k * 256] = e[k];
 }
 __global__ __launch_bounds__(HC_TPB, HC_MM_WAVES_RF) void hc_k_rows_fwd_canon_mm(const u64 *in, u64 *out, HcMm A) {
-    __shared__ hc_mm_lds_t lds[HC_ROWS_LDS];
+    __shared__ u32 lds[HC_ROWS_LDS];
     HC_MM_PROLOGUE_ROWS
-    if (HC_S32 && HC_SMALL_Q(R.q) && R.s32) { hc_rows_fwd_canon_mm_small(in, out, reinterpret_cast<u32 *>(lds), A, R, y, zi, img, bx); return; }       // block-uniform
+    if (HC_SMALL_Q(R.q) && R.s32) { hc_rows_fwd_canon_mm_small(in, out, lds, A, R, y, zi, img, bx); return; }       // block-uniform
     const int t = threadIdx.x, tid = t & 15, rloc = t >> 4, row = bx * 16 + rloc;
     const size_t pbase = (size_t)y * 65536;
     u64 e[16];
@@ -2197,7 +2079,7 @@ __global__ __launch_bounds__(HC_TPB, HC_MM_WAVES_RF) void hc_k_rows_fwd_canon_mm
 #ifndef HC_MM_WAVES_INV
 #define HC_MM_WAVES_INV 6              // the inverse passes: 78-80 VGPRs without scratch (at 7 the typed / pitch row loads of round 5 spill 16-24 bytes)
 #endif
-// hc_k_rows_inv_mm / hc_k_cols_inv_canon_mm for a row whose modulus is below 2^31 (HC_S32)
+// hc_k_rows_inv_mm / hc_k_cols_inv_canon_mm for a row whose modulus is below 2^31
 __device__ __forceinline__ void hc_rows_inv_mm_small(const u64 *in, u64 *out, u32 *lds, const HcMm &A, const HcRowMod &R, int y, int bx) {
     const int t = threadIdx.x, tid = t & 15, rloc = t >> 4, row = bx * 16 + rloc;
     const size_t pbase = (size_t)y * 65536;
@@ -2249,9 +2131,9 @@ __device__ __forceinline__ void hc_cols_inv_canon_mm_small(const u64 *in, u64 *o
     for (int hi = 0; hi < 16; hi++) out[obase + col + (size_t)(hi * 16 + tid) * 256] = e[hi];
 }
 __global__ __launch_bounds__(HC_TPB, HC_MM_WAVES_INV) void hc_k_rows_inv_mm(const u64 *in, u64 *out, HcMm A) {
-    __shared__ hc_mm_lds_t lds[HC_ROWS_LDS];
+    __shared__ u32 lds[HC_ROWS_LDS];
     HC_MM_PROLOGUE_ROWS
-    if (HC_S32 && HC_SMALL_Q(R.q) && R.s32) { hc_rows_inv_mm_small(in, out, reinterpret_cast<u32 *>(lds), A, R, y, bx); return; }       // block-uniform
+    if (HC_SMALL_Q(R.q) && R.s32) { hc_rows_inv_mm_small(in, out, lds, A, R, y, bx); return; }       // block-uniform
     const int t = threadIdx.x, tid = t & 15, rloc = t >> 4, row = bx * 16 + rloc;
     const size_t pbase = (size_t)y * 65536;
     u64 e[16];
@@ -2273,7 +2155,7 @@ __global__ __launch_bounds__(HC_TPB, HC_MM_WAVES_INV) void hc_k_rows_inv_mm(cons
 // scale != null: the coefficients leave multiplied by that constant of the row's modulus - the source side of the basis extension, y_i = x_i (S/s_i)^-1 mod s_i, taken here
 // where x_i is in registers instead of in a pass of its own over memory (hc_k_basis_v then only adds the v row); yo: the row of `out` the result goes to
 template <bool IN32>
-__device__ __forceinline__ void hc_cols_inv_canon_mm_body(const u64 *in, u64 *out, hc_mm_lds_t *lds, const HcRowMod &R, int y, int yo, bool out32, const HcTw *scale) {
+__device__ __forceinline__ void hc_cols_inv_canon_mm_body(const u64 *in, u64 *out, u32 *lds, const HcRowMod &R, int y, int yo, bool out32, const HcTw *scale) {
     const int t = threadIdx.x, c = t & 15, tid = t >> 4;
     const size_t base = (size_t)y * 65536 + blockIdx.x * 16 + c;
     u64 e[16];
@@ -2299,12 +2181,12 @@ __device__ __forceinline__ void hc_cols_inv_canon_mm_body(const u64 *in, u64 *ou
     for (int hi = 0; hi < 16; hi++) out[obase + (size_t)(hi * 16 + tid) * 256] = e[hi];
 }
 __global__ __launch_bounds__(HC_TPB, HC_MM_WAVES_INV) void hc_k_cols_inv_canon_mm(const u64 *in, u64 *out, HcMm A) {
-    __shared__ hc_mm_lds_t lds[HC_COLS_LDS];
+    __shared__ u32 lds[HC_COLS_LDS];
     HC_MM_PROLOGUE
     const bool small = HC_SMALL_Q(R.q);
     const int yo = A.out_gap > 0 ? y + y / A.out_gap : y;
     const HcTw *scale = A.epi_mul != nullptr ? A.epi_mul + y : nullptr;
-    if (HC_S32 && small && R.s32) hc_cols_inv_canon_mm_small(in, out, reinterpret_cast<u32 *>(lds), A, R, y, yo, scale);      // block-uniform
+    if (small && R.s32) hc_cols_inv_canon_mm_small(in, out, lds, A, R, y, yo, scale);      // block-uniform
     else if (A.pk_in && small) hc_cols_inv_canon_mm_body<true>(in, out, lds, R, y, yo, A.pk_out && small, scale);
     else hc_cols_inv_canon_mm_body<false>(in, out, lds, R, y, yo, A.pk_out && small, scale);
 }
@@ -2345,7 +2227,7 @@ __global__ __launch_bounds__(HC_STPB) void hc_k_cols_inv_canon_mm_s(const u64 *i
 #pragma unroll
     for (int k = 0; k < 4; k++) { const int r = k * 64 + u; lds[r * 4 + line] = hc_ldp(in + pbase, (size_t)r * 256 + col, in32); }
     __syncthreads();
-    hc_s_pass_inv<false, true>(lds, R.inv, w, line, u, Q);                   // incl. N^-1; lazy < 4q, natural order
+    hc_s_pass_inv<true>(lds, R.inv, w, line, u, Q);                   // incl. N^-1; lazy < 4q, natural order
     const size_t obase = (size_t)yo * 65536;
     HcTw sc{0, 0};
     const bool scaled = A.epi_mul != nullptr;                                // y_i = x_i (S/s_i)^-1 (hc_cols_inv_canon_mm_body)

@@ -97,7 +97,7 @@ struct HcModHost {
     HcMod m;
     u64 psi, psi_inv;
     HcTwTab fwd, inv;            // device tables
-    HcTwTab32 fwd32 = {nullptr, nullptr, nullptr, nullptr}, inv32 = {nullptr, nullptr, nullptr, nullptr};     // moduli below 2^31: the same tables as 8-byte entries (HC_S32)
+    HcTwTab32 fwd32 = {nullptr, nullptr, nullptr, nullptr}, inv32 = {nullptr, nullptr, nullptr, nullptr};     // moduli below 2^31: the same tables as 8-byte entries (the 32-bit bodies)
     HcTwTab inv_f64;             // moduli below 2^49: the inverse tables as {w, w/q} doubles (fp64 inverse transform of loop A)
     std::vector<void *> allocs;
 };
@@ -147,7 +147,7 @@ struct hc_ctx {
     int pack32 = 1;                       // 1: library-internal rows of moduli below 2^31 as 4-byte words (hc_kernels.h hc_ld32): transform seams, extended digits, switching keys. 2: the rows of the caller's leveled
                                           // operands as well (include/hconv.h "4-byte rows"; option pack32). 0: off (A/B)
     int rot_fuse = 1;                     // hc_keyswitch_qp_rotate_many: the rotations' tails (+ P c0, permutation) in the inner product's stores (HcRotFin) instead of one hc_k_qp_rotate_finish per rotation (option rot_fuse / HCONV_ROT_FUSE=0 for A/B)
-    int small32 = 1;                      // the batched transform kernels take their 32-bit form for rows of a modulus below 2^31 (hc_kernels.h HC_S32; option small32 / HCONV_SMALL32=0 for A/B)
+    int small32 = 1;                      // the batched transform kernels take their 32-bit form for rows of a modulus below 2^31 (hc_kernels.h HcRowMod::s32; option small32 / HCONV_SMALL32=0 for A/B)
     unsigned peer_warned = 0;             // bit d: enabling peer access to device d failed and was reported once
     unsigned peer_enabled = 0;            // bit d: peer access from this context's device to device d was enabled by (or found enabled for) this context
     long profile = 0;
@@ -749,8 +749,8 @@ extern "C" uint64_t hc_const_for(double constant, double q_level_f, uint64_t q, 
 }
 
 // ------------------------------------------------------------------ loop A plumbing
-// grid of the fused conv kernels: `jobs` x 16 tiles (x batch); which of the two is blockIdx.x follows HC_JOB_FAST (hc_kernels.h)
-static dim3 hc_grid(int jobs, int z = 1) { return HC_JOB_FAST ? dim3((unsigned)jobs, 16, (unsigned)z) : dim3(16, (unsigned)jobs, (unsigned)z); }
+// grid of the fused conv kernels: 16 tiles (blockIdx.x = HC_TILE) x `jobs` (blockIdx.y = HC_JOB) (x batch): hc_kernels.h
+static dim3 hc_grid(int jobs, int z = 1) { return dim3(16, (unsigned)jobs, (unsigned)z); }
 static HcPtrs hc_ptrs1(const u64 *p) { HcPtrs P; memset(&P, 0, sizeof P); P.p[0] = p; return P; }
 static int hc_fill_loopA(hc_ctx *c, HcLoopA *A, const HcPtrs &kers, u64 *cts, size_t cts_stride, int norm) {
     const HcModHost &m0 = c->mods[0], &m1 = c->mods[1];
@@ -1092,7 +1092,7 @@ static int hc_pack_level(hc_ctx *c, const u64 *src, u64 *dst, size_t sstride, si
         const int nn = (nodes - n0) < chunk ? (nodes - n0) : chunk;
         B.n0 = n0; B.nodes = nn;
         const dim3 g1 = hc_grid(n * nn), g2 = hc_grid(2 * n * nn);
-        if (c->small_levels > 0 && (long)n * nn <= c->small_levels && it->second.row256 && !HC_JOB_FAST) {
+        if (c->small_levels > 0 && (long)n * nn <= c->small_levels && it->second.row256) {
             // a level of a few nodes is one partial wave of workgroups and costs the latency of its five kernels: quarter tiles (1024 residues per workgroup, four per
             // thread: hc_kernels.h, "loop B for SMALL tree levels") spread a row over 64 CUs instead of 16. Same tables, same tmp layouts, same bits.
             const HcPtrs pb = bias_last ? *bias_last : nobias, po = outs_last ? *outs_last : nobias;

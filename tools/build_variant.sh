@@ -1,5 +1,5 @@
 #!/bin/bash
-# build a variant of libhconv.so with extra compile flags: tools/build_variant.sh NAME "-DHC_JOB_FAST=0 ..."  -> tools/_variants/libhconv_NAME.so
+# build a variant of libhconv.so with extra compile flags: tools/build_variant.sh NAME "-DHC_W_B3=3 ..."  -> tools/_variants/libhconv_NAME.so
 # (select it with HCONV_LIB=<path>; experiments only — the product is optimal_conv_amd/libhconv.so built by __graft_entry__.build())
 set -eu
 cd "$(dirname "$0")/.."
