@@ -74,43 +74,98 @@ struct HcTwTab32 { const HcTw32 *rowsA, *rowsB, *colsA, *colsB; };
 // ---------------------------------------------------------------- radix-16 rounds
 // Slot numbering: a 4-stage round has 1+2+4+8 twiddles; the stage with 2^s twiddles uses slots (2^s - 1 + g).
 // Forward rounds walk s = 0..3 (distance 8,4,2,1); inverse rounds walk distance 1,2,4,8 (s = 3..0).
-// Every butterfly product is hc_shoup4 (hc_arith.h): T = w*Y in [0,4q) for ANY 64-bit Y, so only X needs care.
-// Forward lazy-reduction modes:
+// A forward round is ONE skeleton (hc_ct_round below: the stage, group and butterfly loops and the twiddle slot of each group) over a butterfly POLICY: the modulus data, the element
+// type `elem`, the twiddle type `tw` and the Cooley-Tukey butterfly fwd(X, Y, w): (X, Y) <- (X + wY, X - wY) in place. A policy that is used on two tiles in lock step also has
+// the butterflies of a PAIR, fwd / inv(s, X0, Y0, X1, Y1, w), with the operations of the two interleaved by hand (hc_ct_round / hc_gs_round on two tiles below).
+// The lazy-reduction bounds that bit-exactness rests on are stated on the policies. The one-tile inverse rounds are written out per arithmetic (hc_gs_round, hc_gs_round_f64).
+
+// 64-bit lazy. Every butterfly product is hc_shoup4 (hc_arith.h): T = w*Y in [0,4q) for ANY 64-bit Y, so only X needs care.
+// Forward lazy-reduction modes (FM; 0 = for inverse rounds only):
 //   HC_FM_FREE  no fold at all: every stage adds at most 4q to the bound, 16 stages of a full transform turn inputs < 6q into
 //               outputs < 70q. Needs 74q < 2^64, i.e. moduli below 2^57 (Q0, Q1 and the 30..55-bit primes of the chains).
 //   HC_FM_ALT   X is folded by 4q before every stage: inputs < 8q stay < 8q. Needs 8q < 2^64, which holds for every modulus
 //               this library accepts (q < 2^61 incl. the 61-bit P: 8P = 2^64 - 2^24 + 8).
-// Inverse rounds keep every value in [0,4q): sums are folded by 4q, differences X - Y + 4q go straight into the product.
+// Inverse butterflies keep every value in [0,4q): sums are folded by 4q, differences X - Y + 4q go straight into the product.
 enum { HC_FM_FREE = 1, HC_FM_ALT = 2 };
-template <int FM, class TW>
-__device__ __forceinline__ void hc_ct_round(u64 (&e)[16], const TW &tw, const HcQ &Q) {
-#pragma unroll
-    for (int s = 0; s < 4; s++) {
-        const int half = 8 >> s;
-#pragma unroll
-        for (int g = 0; g < (1 << s); g++) {
-            const HcTw w = tw((1 << s) - 1 + g);
-#pragma unroll
-            for (int k = 0; k < half; k++) {
-                const int a = g * 2 * half + k, b = a + half;
-                u64 X = e[a];
-                if (FM == HC_FM_ALT) X = hc_fold(X, Q.nq4);
-                const u64 T = hc_shoup4(e[b], w.w, w.ws, Q);
-                e[a] = X + T;
-                e[b] = (X + Q.q4) - T;
-            }
-        }
+template <int FM = 0> struct HcLazy {
+    typedef u64 elem;
+    typedef HcTw tw;
+    const HcQ &Q;
+    __device__ __forceinline__ void fwd(u64 &x, u64 &y, const HcTw &w) const {
+        static_assert(FM == HC_FM_FREE || FM == HC_FM_ALT, "HcLazy: a forward round needs its lazy-reduction mode");
+        u64 X = x;
+        if (FM == HC_FM_ALT) X = hc_fold(X, Q.nq4);
+        const u64 T = hc_shoup4(y, w.w, w.ws, Q);
+        x = X + T;
+        y = (X + Q.q4) - T;
     }
-}
+    __device__ __forceinline__ void fwd(u64 &x0, u64 &y0, u64 &x1, u64 &y1, const HcTw &w) const {
+        u64 X0 = x0, X1 = x1;
+        if (FM == HC_FM_ALT) { X0 = hc_fold(X0, Q.nq4); X1 = hc_fold(X1, Q.nq4); }
+        const u64 T0 = hc_shoup4(y0, w.w, w.ws, Q), T1 = hc_shoup4(y1, w.w, w.ws, Q);
+        x0 = X0 + T0; y0 = (X0 + Q.q4) - T0;
+        x1 = X1 + T1; y1 = (X1 + Q.q4) - T1;
+    }
+    __device__ __forceinline__ void inv(int, u64 &x0, u64 &y0, u64 &x1, u64 &y1, const HcTw &w) const {
+        const u64 X0 = x0, Y0 = y0, X1 = x1, Y1 = y1;
+        x0 = hc_fold(X0 + Y0, Q.nq4); y0 = hc_shoup4((X0 + Q.q4) - Y0, w.w, w.ws, Q);
+        x1 = hc_fold(X1 + Y1, Q.nq4); y1 = hc_shoup4((X1 + Q.q4) - Y1, w.w, w.ws, Q);
+    }
+};
 // canonical residue of a forward-transform output (FREE: < 70q -> short Barrett with mu = floor(2^64/q); ALT: < 8q)
 template <int FM>
 __device__ __forceinline__ u64 hc_fwd_canon(u64 x, const HcQ &Q, u64 mu) {
     if (FM == HC_FM_FREE) return hc_reduce64(x, mu, Q);
     return hc_canon8(x, Q);
 }
-// LAST: the final stage also multiplies by N^-1 (folded into the twiddle for the "-" output). In and out: [0,4q).
-template <bool LAST, class TW>
-__device__ __forceinline__ void hc_gs_round(u64 (&e)[16], const TW &tw, const HcQ &Q, HcTw ninv, HcTw w_last) {
+
+// Canonical 32-bit, for the limbs below 2^31 (round 5). Eleven of the bootstrapping chain's 28 limbs are ~30-bit primes. Every instruction class these kernels are made of issues
+// at one wave64 per 4 cycles whatever its width, so a butterfly costs its instruction count: 20-22 for the 64-bit lazy form above, 12 for this one - a Shoup
+// product is v_mul_hi_u32 + 2 v_mul_lo_u32 + a subtraction, every conditional correction is a subtraction and a v_min_u32 - and a thread's 16 residues take 16 registers, one LDS
+// word each (ONE exchange and barrier per pass instead of the two halves' three). The 32-bit companion of a table entry (w, w' = floor(w 2^64 / q)) is (low word of w, high word of
+// w'): floor(floor(w 2^64 / q) / 2^32) = floor(w 2^32 / q), so the 64-bit tables serve both forms. Everything is canonical, in and out: the same residues as the 64-bit
+// kernels, bit for bit. A workgroup takes this form as a WHOLE (its modulus is block-uniform): the 64-bit and 32-bit bodies share no live registers (round 4 switched per
+// butterfly inside one body and paid 108-132 VGPRs for 65-86: profiles/round4_chain_class_paths_ab.txt). Chosen at run time per modulus: HcRowMod::s32 (option small32).
+__device__ __forceinline__ HcTw32 hc_tw32(const HcTw &t) { return HcTw32{(u32)t.w, (u32)(t.ws >> 32)}; }
+__device__ __forceinline__ u32 hc_umulhi32(u32 a, u32 b) { return (u32)(((u64)a * b) >> 32); }
+__device__ __forceinline__ u32 hc_min32(u32 a, u32 b) { return a < b ? a : b; }
+__device__ __forceinline__ u32 hc_csub32(u32 x, u32 q) { return hc_min32(x, x - q); }                         // [0,2q) -> [0,q): x - q wraps above x when x < q
+__device__ __forceinline__ u32 hc_add32(u32 a, u32 b, u32 q) { return hc_csub32(a + b, q); }                   // a, b < q < 2^31
+__device__ __forceinline__ u32 hc_sub32(u32 a, u32 b, u32 q) { const u32 d = a - b; return hc_min32(d, d + q); }   // a < b: d wraps to 2^32 - (b - a) and d + q to the residue
+__device__ __forceinline__ u32 hc_mul32(u32 y, HcTw32 w, u32 q) { return hc_csub32(y * w.w - hc_umulhi32(y, w.ws) * q, q); }     // ANY y < 2^32; w < q
+struct HcCanon32 {
+    typedef u32 elem;
+    typedef HcTw32 tw;
+    u32 q;
+    __device__ __forceinline__ void fwd(u32 &x, u32 &y, const HcTw32 &w) const {
+        const u32 X = x, T = hc_mul32(y, w, q);
+        x = hc_add32(X, T, q);
+        y = hc_sub32(X, T, q);
+    }
+};
+
+// The forward skeleton. tw(slot): the twiddle of a slot (HcTwA / HcTwB below, or a caller's own).
+template <class P, class TW>
+__device__ __forceinline__ void hc_ct_round(const P &pol, const TW &tw, typename P::elem (&e)[16]) {
+#pragma unroll
+    for (int s = 0; s < 4; s++) {
+        const int half = 8 >> s;
+#pragma unroll
+        for (int g = 0; g < (1 << s); g++) {
+            const typename P::tw w = tw((1 << s) - 1 + g);
+#pragma unroll
+            for (int k = 0; k < half; k++) {
+                const int a = g * 2 * half + k, b = a + half;
+                pol.fwd(e[a], e[b], w);
+            }
+        }
+    }
+}
+// The inverse rounds, written out per arithmetic: through one skeleton over inverse butterflies of the policies the kernels of the 64-bit lazy form come out rescheduled and those of
+// the other two with commuted multiplies. LAST: the final stage also multiplies by N^-1 (folded into the twiddle w_last for the "-" output). 64-bit lazy, in and out [0,4q):
+template <bool LAST = false, int FM, class TW>
+__device__ __forceinline__ void hc_gs_round(const HcLazy<FM> &pol, const TW &tw, u64 (&e)[16], HcTw ninv = {}, HcTw w_last = {}) {
+    const HcQ &Q = pol.Q;
 #pragma unroll
     for (int s = 0; s < 4; s++) {
         const int dist = 1 << s;
@@ -129,7 +184,27 @@ __device__ __forceinline__ void hc_gs_round(u64 (&e)[16], const TW &tw, const Hc
         }
     }
 }
-
+// canonical 32-bit
+template <bool LAST = false, class TW>
+__device__ __forceinline__ void hc_gs_round(const HcCanon32 &pol, const TW &tw, u32 (&e)[16], HcTw32 ninv = {}, HcTw32 w_last = {}) {
+    const u32 q = pol.q;
+#pragma unroll
+    for (int s = 0; s < 4; s++) {
+        const int dist = 1 << s;
+#pragma unroll
+        for (int g = 0; g < (8 >> s); g++) {
+            HcTw32 w = tw((8 >> s) - 1 + g);
+            if (LAST && s == 3) w = w_last;
+#pragma unroll
+            for (int k = 0; k < dist; k++) {
+                const int a = g * 2 * dist + k, b = a + dist;
+                const u32 X = e[a], Y = e[b], u = hc_add32(X, Y, q), d = hc_sub32(X, Y, q);
+                e[a] = (LAST && s == 3) ? hc_mul32(u, ninv, q) : u;
+                e[b] = hc_mul32(d, w, q);
+            }
+        }
+    }
+}
 // fp64 form of the inverse round for a modulus below 2^49 (hc_arith.h): the table entries are {w, w/q} as doubles in the bit
 // patterns of an HcTw. Bounds: every value entering a round is below q in magnitude; sums are folded after stages 1 and 3 (where
 // they could reach 4q), differences go through hc_f64_mulmod (|input| < 4q < 2^51); every value leaving the round is below q.
@@ -155,7 +230,64 @@ __device__ __forceinline__ void hc_gs_round_f64(double (&e)[16], const TW &tw, H
         }
     }
 }
+// ---- two register tiles in lock step. Two transforms over the same 16 rows and the same modulus want the same twiddles - 15 rowsA pairs per row and 15 rowsB pairs per THREAD and
+// pass, 480 of the 608 bytes a thread loads in a rows pass. These forms run the butterflies of both tiles behind ONE load per twiddle slot: the same arithmetic on the same values
+// as the one-tile rounds, only the order of independent operations differs (bit-identical results). Used where one workgroup has both tiles anyway (hc_k_b3p: the two key components
+// of a node; hc_k_b5m: the two polynomials) or can take them (hc_k_a1p / hc_k_a3p: the two polynomials of a channel, which also share the kernel-plaintext tile). The two tiles
+// sit side by side inside the innermost iteration on purpose: as tile after tile (a loop or a pack over tiles) hc_k_b3p spilled and hc_k_a1p<0> lost an occupancy step.
+template <class P, class TW>
+__device__ __forceinline__ void hc_ct_round(const P &pol, const TW &tw, typename P::elem (&e0)[16], typename P::elem (&e1)[16]) {
+#pragma unroll
+    for (int s = 0; s < 4; s++) {
+        const int half = 8 >> s;
+#pragma unroll
+        for (int g = 0; g < (1 << s); g++) {
+            const typename P::tw w = tw((1 << s) - 1 + g);
+#pragma unroll
+            for (int k = 0; k < half; k++) {
+                const int a = g * 2 * half + k, b = a + half;
+                pol.fwd(e0[a], e0[b], e1[a], e1[b], w);
+            }
+        }
+    }
+}
+template <class P, class TW>
+__device__ __forceinline__ void hc_gs_round(const P &pol, const TW &tw, typename P::elem (&e0)[16], typename P::elem (&e1)[16]) {
+#pragma unroll
+    for (int s = 0; s < 4; s++) {
+        const int dist = 1 << s;
+#pragma unroll
+        for (int g = 0; g < (8 >> s); g++) {
+            const typename P::tw w = tw((8 >> s) - 1 + g);
+#pragma unroll
+            for (int k = 0; k < dist; k++) {
+                const int a = g * 2 * dist + k, b = a + dist;
+                pol.inv(s, e0[a], e0[b], e1[a], e1[b], w);
+            }
+        }
+    }
+}
 
+// hc_gs_round_f64<false> on two tiles
+template <class TW>
+__device__ __forceinline__ void hc_gs_round2_f64(double (&e0)[16], double (&e1)[16], const TW &tw, HcF64Mod m) {
+#pragma unroll
+    for (int s = 0; s < 4; s++) {
+        const int dist = 1 << s;
+#pragma unroll
+        for (int g = 0; g < (8 >> s); g++) {
+            const HcTw w = tw((8 >> s) - 1 + g);
+            const double ww = hc_u2d(w.w), wq = hc_u2d(w.ws);
+#pragma unroll
+            for (int k = 0; k < dist; k++) {
+                const int a = g * 2 * dist + k, b = a + dist;
+                const double X0 = e0[a], Y0 = e0[b], X1 = e1[a], Y1 = e1[b], u0 = X0 + Y0, u1 = X1 + Y1;
+                e0[a] = (s & 1) ? hc_f64_reduce(u0, m.q, m.qinv) : u0; e0[b] = hc_f64_mulmod(X0 - Y0, ww, wq, m.q);
+                e1[a] = (s & 1) ? hc_f64_reduce(u1, m.q, m.qinv) : u1; e1[b] = hc_f64_mulmod(X1 - Y1, ww, wq, m.q);
+            }
+        }
+    }
+}
 // ---------------------------------------------------------------- tile geometry
 // LDS holds 8-byte words; a ds_read/write_b64 is serviced per half-wave over 32 word slots (64 banks x 4 B), so a
 // layout is conflict-free when the 32 lanes of a half-wave hit 32 distinct values of (word index mod 32).
@@ -171,30 +303,52 @@ __device__ __forceinline__ void hc_gs_round_f64(double (&e)[16], const TW &tw, H
 #else
 #define HC_ROW_SYNC() do { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); } while (0)
 #endif
-__device__ __forceinline__ int hc_rows_lds(int rloc, int col) {
-    return rloc * 256 + ((col & 0xF0) ^ ((rloc & 1) << 4)) + ((col & 15) ^ ((col >> 5) & 7) ^ ((rloc & 1) << 3));
-}
 // cols kernels: thread t -> (c = t&15, tid = t>>4); a half-wave = 2 tids x 16 columns. Patterns: hi-local
 //   (row = hi*16+tid) and lo-local (row = tid*16+lo). Row bit 0 is XORed with row bit 4 so that the two tids of
 //   a half-wave land in different 16-word halves in both patterns.
-__device__ __forceinline__ int hc_cols_lds(int row, int c) { return ((row ^ ((row >> 4) & 1)) << 4) + c; }
+// ---- the same tiles as 4-byte words, HALF the LDS (an 8-byte element then goes through in two phases: hc_xchg). 32 KiB per 256-thread workgroup caps a CU at 5 workgroups =
+// 5 wavefronts per SIMD; the multi-modulus kernels of the chain wait on memory two thirds of the time at VALU busy 0.4-0.5 (rocprofv3 SQ counters,
+// profiles/round4_chain_valu_table.txt), their 44-56 VGPRs would admit 8. The 4-byte swizzles are the 8-byte ones with one more row bit folded in: a ds_*_b32 is serviced
+// over 64 banks for all 64 lanes, and the four rows (rows passes) / four tids (cols passes) of a wavefront must land in four different 16-word groups.
+#ifndef HC_MM_WAVES
+#define HC_MM_WAVES 7                  // wavefronts per SIMD the multi-modulus transform kernels are compiled for (VGPR budget 512 / HC_MM_WAVES)
+#endif
+#ifndef HC_MM_WAVES_EXT
+#define HC_MM_WAVES_EXT 5              // the passes with the basis extension in their prologue. Round 5, first half: the straight-line extension of full digits at 4 wavefronts (120 VGPRs) beat 5 with 96 bytes of scratch; since the tables' constants
+                                       // come through the constant address space into SGPRs (hc_const_copy) the kernels need 96-102 VGPRs: 5 wavefronts with 0 / 24 bytes of scratch, 16.93 vs 17.05 ms per ciphertext-layer
+#endif
+// measured (convReLU 5 1 tail, 8 images, profiles/round4_chain_occupancy_ab.txt): 8-byte exchange / 5 waves 189.5 ms; 4-byte exchange at 6 / 6 waves 183.2, 7 / 5 waves 166.7,
+// 7 / 4 180.8, 8 / 6 193.0 (spills), 7 / 7 with two-element extension groups 169.6
+// The convolution's transform kernels (61-bit P, 82-126 VGPRs: occupancy is set by registers, not LDS): measured per kernel (profiles/round4_conv33_lds32_ab.txt), the
+// 4-byte exchange pays in the cols kernels a2, b2, b4 (-2..4 % each) and costs in the rows kernels a3, b3 (two exchanges each, +14 %), which keep the 8-byte one.
+// So: u32 tiles in every multi-modulus kernel and in the convolution's cols kernels, u64 tiles in its rows kernels and in the standalone transforms.
+// L: the LDS word type of the tile (u64, the default, or u32)
+template <class L = u64>
+__device__ __forceinline__ int hc_rows_lds(int rloc, int col) {
+    if (sizeof(L) == 4) return rloc * 256 + ((col & 0xF0) ^ ((rloc & 1) << 4) ^ ((rloc & 2) << 4)) + ((col & 15) ^ ((col >> 5) & 7) ^ ((rloc & 1) << 3));
+    return rloc * 256 + ((col & 0xF0) ^ ((rloc & 1) << 4)) + ((col & 15) ^ ((col >> 5) & 7) ^ ((rloc & 1) << 3));
+}
+template <class L = u64>
+__device__ __forceinline__ int hc_cols_lds(int row, int c) { return ((row ^ ((row >> 4) & (sizeof(L) == 4 ? 3 : 1))) << 4) + c; }
 
 // Twiddle tables always live in device (global) memory. The multi-modulus kernels take their table pointers from a struct they load (HcRowMod), so the compiler only knows a
 // GENERIC pointer and emitted flat_load_dwordx4 for every twiddle - 30 per thread and pass - which count against lgkmcnt as well as vmcnt and so tie every twiddle fetch to
 // the LDS exchange waits. The explicit address space makes them global_load_dwordx4 (round 5; the convolution's kernels receive HcTwTab by value and always had global loads).
-#if defined(__HIP_DEVICE_COMPILE__)
-typedef const HcTw __attribute__((address_space(1))) *HcTwGlobalPtr;
-typedef const HcTw __attribute__((address_space(4))) *HcTwConstPtr;
-#define HC_TW_LOAD(p, i) (*((HcTwGlobalPtr)(p) + (i)))
-#define HC_TW_LOADK(p, i) (*((HcTwConstPtr)(p) + (i)))
-#else
-#define HC_TW_LOAD(p, i) ((p)[i])
-#define HC_TW_LOADK(p, i) ((p)[i])
-#endif
 // Tables the kernels only read - twiddles, the per-modulus rows of HcRowMod, the extension's constants - are read through the CONSTANT address space: a load whose address is
 // uniform then goes through the scalar cache into SGPRs whatever else the kernel does. As global-memory loads they depend on the compiler proving that no store of the kernel
 // can reach them, and with the 32-bit and 64-bit bodies side by side it stopped proving that for the second body: hc_k_cols_fwd_mm<1, 5> went from 267 s_load / 196
-// global_load to 30 / 596 - every constant fetched per lane into VGPRs - and lost 8 %. hc_const_copy: a table entry selected by blockIdx, copied into registers that way.
+// global_load to 30 / 596 - every constant fetched per lane into VGPRs - and lost 8 %.
+// HC_TW_LOAD / HC_TW_LOADK: entry i of a table of TW = HcTw or HcTw32 through the global / the CONSTANT address space (K: the batched multi-modulus kernels, whose 32-bit and 64-bit
+// bodies sit side by side). The convolution's kernels keep global loads: as constant-memory loads their twiddle fetches may be hoisted anywhere, and hc_k_b3p / hc_k_b5m - two
+// transforms each - then spill 430-530 bytes (-19 % conv/s)
+#if defined(__HIP_DEVICE_COMPILE__)
+#define HC_TW_LOAD(TW, p, i) (*((const TW __attribute__((address_space(1))) *)(p) + (i)))
+#define HC_TW_LOADK(TW, p, i) (*((const TW __attribute__((address_space(4))) *)(p) + (i)))
+#else
+#define HC_TW_LOAD(TW, p, i) ((p)[i])
+#define HC_TW_LOADK(TW, p, i) ((p)[i])
+#endif
+// hc_const_copy: a table entry selected by blockIdx, copied into registers through the constant address space.
 template <class T>
 __device__ __forceinline__ T hc_const_copy(const T *p) {
     T r;
@@ -209,96 +363,24 @@ __device__ __forceinline__ T hc_const_copy(const T *p) {
 #endif
     return r;
 }
-// KC: through the CONSTANT address space (the batched multi-modulus kernels, whose 32-bit and 64-bit bodies sit side by side: hc_const_copy). The convolution's kernels keep
-// global loads: as constant-memory loads their twiddle fetches may be hoisted anywhere, and hc_k_b3 / hc_k_b5m - two transforms each - then spill 430-530 bytes (-19 % conv/s)
-template <bool KC = false> struct HcRowsTwA { const HcTw *p; __device__ __forceinline__ HcTw operator()(int slot) const { if (KC) return HC_TW_LOADK(p, slot); else return HC_TW_LOAD(p, slot); } };
-template <bool KC = false> struct HcRowsTwB { const HcTw *p; __device__ __forceinline__ HcTw operator()(int slot) const { if (KC) return HC_TW_LOADK(p, slot * 16); else return HC_TW_LOAD(p, slot * 16); } };
+// the twiddle of a slot: A = the round on the high bits (16 consecutive entries), B = the round on the low bits (per thread: entries 16 apart)
+template <bool KC, class TW> struct HcTwA { const TW *p; __device__ __forceinline__ TW operator()(int slot) const { if (KC) return HC_TW_LOADK(TW, p, slot); else return HC_TW_LOAD(TW, p, slot); } };
+template <bool KC, class TW> struct HcTwB { const TW *p; __device__ __forceinline__ TW operator()(int slot) const { if (KC) return HC_TW_LOADK(TW, p, slot * 16); else return HC_TW_LOAD(TW, p, slot * 16); } };
 
-// forward rows pass on registers: in  e[hi] = element (row, hi*16+tid)  [lazy < 4q]
-//                                 out e[lo] = element (row, tid*16+lo)  [lazy, bound per forward mode]
-template <int FM, bool KC = false>
-__device__ __forceinline__ void hc_rows_fwd(u64 (&e)[16], u64 *lds, const HcTwTab &T, int row, int rloc, int tid, const HcQ &Q) {
-    hc_ct_round<FM>(e, HcRowsTwA<KC>{T.rowsA + row * 16}, Q);
+// ---------------------------------------------------------------- the exchange through LDS
+// Every tile element goes to word wa(i) and comes back from word ra(i); sync() between the two (HC_ROW_SYNC for the row-local exchanges, __syncthreads for the others).
+// Elements of the LDS word's own width (u64 through u64 words, u32 through u32 words):
+template <class E, class WA, class RA, class SY>
+__device__ __forceinline__ void hc_xchg(E *lds, WA wa, RA ra, SY sync, E (&e)[16]) {
 #pragma unroll
-    for (int hi = 0; hi < 16; hi++) lds[hc_rows_lds(rloc, hi * 16 + tid)] = e[hi];
-    HC_ROW_SYNC();
+    for (int i = 0; i < 16; i++) lds[wa(i)] = e[i];
+    sync();
 #pragma unroll
-    for (int lo = 0; lo < 16; lo++) e[lo] = lds[hc_rows_lds(rloc, tid * 16 + lo)];
-    hc_ct_round<FM>(e, HcRowsTwB<KC>{T.rowsB + row * 256 + tid}, Q);
+    for (int i = 0; i < 16; i++) e[i] = lds[ra(i)];
 }
-// inverse rows pass: in e[lo] = (row, tid*16+lo) [lazy < 4q]; out e[hi] = (row, hi*16+tid) [lazy < 4q]
-template <bool KC = false>
-__device__ __forceinline__ void hc_rows_inv(u64 (&e)[16], u64 *lds, const HcTwTab &T, int row, int rloc, int tid, const HcQ &Q) {
-    hc_gs_round<false>(e, HcRowsTwB<KC>{T.rowsB + row * 256 + tid}, Q, T.ninv, T.ninv);
-#pragma unroll
-    for (int lo = 0; lo < 16; lo++) lds[hc_rows_lds(rloc, tid * 16 + lo)] = e[lo];
-    HC_ROW_SYNC();
-#pragma unroll
-    for (int hi = 0; hi < 16; hi++) e[hi] = lds[hc_rows_lds(rloc, hi * 16 + tid)];
-    hc_gs_round<false>(e, HcRowsTwA<KC>{T.rowsA + row * 16}, Q, T.ninv, T.ninv);
-}
-// forward cols pass: in e[hi] = (hi*16+tid, c); out e[lo] = (tid*16+lo, c) [lazy, bounds per forward mode]
-template <int FM, bool KC = false>
-__device__ __forceinline__ void hc_cols_fwd(u64 (&e)[16], u64 *lds, const HcTwTab &T, int c, int tid, const HcQ &Q) {
-    hc_ct_round<FM>(e, HcRowsTwA<KC>{T.colsA}, Q);
-#pragma unroll
-    for (int hi = 0; hi < 16; hi++) lds[hc_cols_lds(hi * 16 + tid, c)] = e[hi];
-    __syncthreads();
-#pragma unroll
-    for (int lo = 0; lo < 16; lo++) e[lo] = lds[hc_cols_lds(tid * 16 + lo, c)];
-    hc_ct_round<FM>(e, HcRowsTwB<KC>{T.colsB + tid}, Q);
-}
-// inverse cols pass incl. N^-1 (SCALE = false: without it, for callers that folded N^-1 into a fixed multiplicand upstream):
-// in e[lo] = (tid*16+lo, c) [lazy < 4q]; out e[hi] = (hi*16+tid, c) [lazy < 4q]
-template <bool SCALE = true, bool KC = false>
-__device__ __forceinline__ void hc_cols_inv(u64 (&e)[16], u64 *lds, const HcTwTab &T, int c, int tid, const HcQ &Q) {
-    hc_gs_round<false>(e, HcRowsTwB<KC>{T.colsB + tid}, Q, T.ninv, T.ninv);
-#pragma unroll
-    for (int lo = 0; lo < 16; lo++) lds[hc_cols_lds(tid * 16 + lo, c)] = e[lo];
-    __syncthreads();
-#pragma unroll
-    for (int hi = 0; hi < 16; hi++) e[hi] = lds[hc_cols_lds(hi * 16 + tid, c)];
-    hc_gs_round<SCALE>(e, HcRowsTwA<KC>{T.colsA}, Q, T.ninv, T.w_last_ninv);
-}
-
-// rows tile <-> "linear" order (thread t holds column t of the 16 rows; k = local row) through LDS
-__device__ __forceinline__ void hc_rows_lin_to_lo(u64 (&e)[16], u64 *lds, int t, int rloc, int tid) {
-#pragma unroll
-    for (int k = 0; k < 16; k++) lds[hc_rows_lds(k, t)] = e[k];
-    __syncthreads();
-#pragma unroll
-    for (int lo = 0; lo < 16; lo++) e[lo] = lds[hc_rows_lds(rloc, tid * 16 + lo)];
-}
-__device__ __forceinline__ void hc_rows_lo_to_lin(u64 (&e)[16], u64 *lds, int t, int rloc, int tid) {
-#pragma unroll
-    for (int lo = 0; lo < 16; lo++) lds[hc_rows_lds(rloc, tid * 16 + lo)] = e[lo];
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < 16; k++) e[k] = lds[hc_rows_lds(k, t)];
-}
-
-// ---- the same exchanges through HALF the LDS (multi-modulus kernels of the chain): low words, then high words, over a 16 KiB tile of 4-byte words. 32 KiB per
-// 256-thread workgroup caps a CU at 5 workgroups = 5 wavefronts per SIMD; these kernels wait on memory two thirds of the time at VALU busy 0.4-0.5 (rocprofv3 SQ counters,
-// profiles/round4_chain_valu_table.txt), their 44-56 VGPRs would admit 8. The swizzles below are the 8-byte ones with one more row bit folded in: a ds_*_b32 is serviced
-// over 64 banks for all 64 lanes, and the four rows (rows passes) / four tids (cols passes) of a wavefront must land in four different 16-word groups.
-#ifndef HC_MM_WAVES
-#define HC_MM_WAVES 7                  // wavefronts per SIMD the multi-modulus transform kernels are compiled for (VGPR budget 512 / HC_MM_WAVES)
-#endif
-#ifndef HC_MM_WAVES_EXT
-#define HC_MM_WAVES_EXT 5              // the passes with the basis extension in their prologue. Round 5, first half: the straight-line extension of full digits at 4 wavefronts (120 VGPRs) beat 5 with 96 bytes of scratch; since the tables' constants
-                                       // come through the constant address space into SGPRs (hc_const_copy) the kernels need 96-102 VGPRs: 5 wavefronts with 0 / 24 bytes of scratch, 16.93 vs 17.05 ms per ciphertext-layer
-#endif
-// measured (convReLU 5 1 tail, 8 images, profiles/round4_chain_occupancy_ab.txt): 8-byte exchange / 5 waves 189.5 ms; 4-byte exchange at 6 / 6 waves 183.2, 7 / 5 waves 166.7,
-// 7 / 4 180.8, 8 / 6 193.0 (spills), 7 / 7 with two-element extension groups 169.6
-// The convolution's transform kernels (61-bit P, 82-126 VGPRs: occupancy is set by registers, not LDS): measured per kernel (profiles/round4_conv33_lds32_ab.txt), the
-// 4-byte exchange pays in the cols kernels a2, b2, b4 (-2..4 % each) and costs in the rows kernels a3, b3 (two exchanges each, +14 %), which keep the 8-byte one.
-// So: u32 tiles in every multi-modulus kernel and in the convolution's cols kernels, u64 tiles in its rows kernels and in the standalone transforms.
-__device__ __forceinline__ int hc_rows_lds32(int rloc, int col) {
-    return rloc * 256 + ((col & 0xF0) ^ ((rloc & 1) << 4) ^ ((rloc & 2) << 4)) + ((col & 15) ^ ((col >> 5) & 7) ^ ((rloc & 1) << 3));
-}
-__device__ __forceinline__ int hc_cols_lds32(int row, int c) { return ((row ^ ((row >> 4) & 3)) << 4) + c; }
+// 8-byte elements through 4-byte words: low words, then high words
 template <class WA, class RA, class SY>
-__device__ __forceinline__ void hc_xchg32(u64 (&e)[16], u32 *lds, WA wa, RA ra, SY sync) {
+__device__ __forceinline__ void hc_xchg(u32 *lds, WA wa, RA ra, SY sync, u64 (&e)[16]) {
     u32 lo[16];
 #pragma unroll
     for (int i = 0; i < 16; i++) lds[wa(i)] = (u32)e[i];
@@ -312,154 +394,145 @@ __device__ __forceinline__ void hc_xchg32(u64 (&e)[16], u32 *lds, WA wa, RA ra, 
 #pragma unroll
     for (int i = 0; i < 16; i++) e[i] = ((u64)lds[ra(i)] << 32) | lo[i];
 }
-template <int FM, bool KC = false>
-__device__ __forceinline__ void hc_rows_fwd(u64 (&e)[16], u32 *lds, const HcTwTab &T, int row, int rloc, int tid, const HcQ &Q) {
-    hc_ct_round<FM>(e, HcRowsTwA<KC>{T.rowsA + row * 16}, Q);
-    hc_xchg32(e, lds, [&](int hi) { return hc_rows_lds32(rloc, hi * 16 + tid); }, [&](int lo) { return hc_rows_lds32(rloc, tid * 16 + lo); }, [] { HC_ROW_SYNC(); });
-    hc_ct_round<FM>(e, HcRowsTwB<KC>{T.rowsB + row * 256 + tid}, Q);
+// Two tiles go through ONE LDS tile, one after the other (occupancy: two tiles side by side would halve the workgroups a CU holds)
+template <class L, class E, class WA, class RA, class SY>
+__device__ __forceinline__ void hc_xchg(L *lds, WA wa, RA ra, SY sync, E (&e0)[16], E (&e1)[16]) {
+    hc_xchg(lds, wa, ra, sync, e0);
+    sync();                                                                  // every word of the first tile has been read before the second lands on it
+    hc_xchg(lds, wa, ra, sync, e1);
 }
-template <bool KC = false>
-__device__ __forceinline__ void hc_rows_inv(u64 (&e)[16], u32 *lds, const HcTwTab &T, int row, int rloc, int tid, const HcQ &Q) {
-    hc_gs_round<false>(e, HcRowsTwB<KC>{T.rowsB + row * 256 + tid}, Q, T.ninv, T.ninv);
-    hc_xchg32(e, lds, [&](int lo) { return hc_rows_lds32(rloc, tid * 16 + lo); }, [&](int hi) { return hc_rows_lds32(rloc, hi * 16 + tid); }, [] { HC_ROW_SYNC(); });
-    hc_gs_round<false>(e, HcRowsTwA<KC>{T.rowsA + row * 16}, Q, T.ninv, T.ninv);
-}
-template <int FM, bool KC = false>
-__device__ __forceinline__ void hc_cols_fwd(u64 (&e)[16], u32 *lds, const HcTwTab &T, int c, int tid, const HcQ &Q) {
-    hc_ct_round<FM>(e, HcRowsTwA<KC>{T.colsA}, Q);
-    hc_xchg32(e, lds, [&](int hi) { return hc_cols_lds32(hi * 16 + tid, c); }, [&](int lo) { return hc_cols_lds32(tid * 16 + lo, c); }, [] { __syncthreads(); });
-    hc_ct_round<FM>(e, HcRowsTwB<KC>{T.colsB + tid}, Q);
-}
-template <bool SCALE = true, bool KC = false>
-__device__ __forceinline__ void hc_cols_inv(u64 (&e)[16], u32 *lds, const HcTwTab &T, int c, int tid, const HcQ &Q) {
-    hc_gs_round<false>(e, HcRowsTwB<KC>{T.colsB + tid}, Q, T.ninv, T.ninv);
-    hc_xchg32(e, lds, [&](int lo) { return hc_cols_lds32(tid * 16 + lo, c); }, [&](int hi) { return hc_cols_lds32(hi * 16 + tid, c); }, [] { __syncthreads(); });
-    hc_gs_round<SCALE>(e, HcRowsTwA<KC>{T.colsA}, Q, T.ninv, T.w_last_ninv);
-}
-// the same exchange for doubles: they travel as their bit patterns
-template <class WA, class RA, class SY>
-__device__ __forceinline__ void hc_xchg32_f64(double (&f)[16], u32 *lds, WA wa, RA ra, SY sync) {
+// doubles travel as their bit patterns
+template <class L, class WA, class RA, class SY>
+__device__ __forceinline__ void hc_xchg(L *lds, WA wa, RA ra, SY sync, double (&f)[16]) {
     u64 b[16];
 #pragma unroll
     for (int i = 0; i < 16; i++) b[i] = hc_d2u(f[i]);
-    hc_xchg32(b, lds, wa, ra, sync);
+    hc_xchg(lds, wa, ra, sync, b);
 #pragma unroll
     for (int i = 0; i < 16; i++) f[i] = hc_u2d(b[i]);
 }
-// fp64 form of the inverse cols pass (the rows pass is hc_rows_inv2_f64, through 8-byte words)
+
+// ---------------------------------------------------------------- the passes on registers
+// One definition per direction and geometry, over the policy (64-bit lazy, canonical 32-bit: P::elem tiles, P::tw tables), the LDS word type L and ONE OR TWO tiles e...
+// (two: the lock-step rounds, the tiles exchanged in turn). KC: twiddles through the constant address space. TAB: HcTwTab or HcTwTab32.
+// forward rows pass: in  e[hi] = element (row, hi*16+tid)  [64-bit lazy: < 4q]
+//                    out e[lo] = element (row, tid*16+lo)  [64-bit lazy: bound per forward mode]
+template <bool KC = false, class P, class L, class TAB, class... E>
+__device__ __forceinline__ void hc_rows_fwd(const P &pol, L *lds, const TAB &T, int row, int rloc, int tid, E (&...e)[16]) {
+    hc_ct_round(pol, HcTwA<KC, typename P::tw>{T.rowsA + row * 16}, e...);
+    hc_xchg(lds, [&](int hi) { return hc_rows_lds<L>(rloc, hi * 16 + tid); }, [&](int lo) { return hc_rows_lds<L>(rloc, tid * 16 + lo); }, [] { HC_ROW_SYNC(); }, e...);
+    hc_ct_round(pol, HcTwB<KC, typename P::tw>{T.rowsB + row * 256 + tid}, e...);
+}
+// inverse rows pass: in e[lo] = (row, tid*16+lo); out e[hi] = (row, hi*16+tid)  [64-bit lazy: < 4q both]
+template <bool KC = false, class P, class L, class TAB, class... E>
+__device__ __forceinline__ void hc_rows_inv(const P &pol, L *lds, const TAB &T, int row, int rloc, int tid, E (&...e)[16]) {
+    hc_gs_round(pol, HcTwB<KC, typename P::tw>{T.rowsB + row * 256 + tid}, e...);
+    hc_xchg(lds, [&](int lo) { return hc_rows_lds<L>(rloc, tid * 16 + lo); }, [&](int hi) { return hc_rows_lds<L>(rloc, hi * 16 + tid); }, [] { HC_ROW_SYNC(); }, e...);
+    hc_gs_round(pol, HcTwA<KC, typename P::tw>{T.rowsA + row * 16}, e...);
+}
+// forward cols pass: in e[hi] = (hi*16+tid, c); out e[lo] = (tid*16+lo, c)
+template <bool KC = false, class P, class L, class TAB>
+__device__ __forceinline__ void hc_cols_fwd(const P &pol, L *lds, const TAB &T, int c, int tid, typename P::elem (&e)[16]) {
+    hc_ct_round(pol, HcTwA<KC, typename P::tw>{T.colsA}, e);
+    hc_xchg(lds, [&](int hi) { return hc_cols_lds<L>(hi * 16 + tid, c); }, [&](int lo) { return hc_cols_lds<L>(tid * 16 + lo, c); }, [] { __syncthreads(); }, e);
+    hc_ct_round(pol, HcTwB<KC, typename P::tw>{T.colsB + tid}, e);
+}
+// inverse cols pass incl. N^-1 (SCALE = false: without it, for callers that folded N^-1 into a fixed multiplicand upstream): in e[lo] = (tid*16+lo, c); out e[hi] = (hi*16+tid, c)
+// ninv, w_last: HcTwTab's ninv and w_last_ninv in the policy's twiddle type
+template <bool SCALE = true, bool KC = false, class P, class L, class TAB>
+__device__ __forceinline__ void hc_cols_inv(const P &pol, L *lds, const TAB &T, int c, int tid, typename P::elem (&e)[16], const typename P::tw &ninv, const typename P::tw &w_last) {
+    hc_gs_round(pol, HcTwB<KC, typename P::tw>{T.colsB + tid}, e);
+    hc_xchg(lds, [&](int lo) { return hc_cols_lds<L>(tid * 16 + lo, c); }, [&](int hi) { return hc_cols_lds<L>(hi * 16 + tid, c); }, [] { __syncthreads(); }, e);
+    hc_gs_round<SCALE>(pol, HcTwA<KC, typename P::tw>{T.colsA}, e, ninv, w_last);
+}
+// rows tile <-> "linear" order (thread t holds column t of the 16 rows; k = local row) through LDS
+template <class L, class... E>
+__device__ __forceinline__ void hc_rows_lin_to_lo(L *lds, int t, int rloc, int tid, E (&...e)[16]) {
+    hc_xchg(lds, [&](int k) { return hc_rows_lds<L>(k, t); }, [&](int lo) { return hc_rows_lds<L>(rloc, tid * 16 + lo); }, [] { __syncthreads(); }, e...);
+}
+template <class L, class... E>
+__device__ __forceinline__ void hc_rows_lo_to_lin(L *lds, int t, int rloc, int tid, E (&...e)[16]) {
+    hc_xchg(lds, [&](int lo) { return hc_rows_lds<L>(rloc, tid * 16 + lo); }, [&](int k) { return hc_rows_lds<L>(k, t); }, [] { __syncthreads(); }, e...);
+}
+// One tile through 8-byte words: the same passes with their exchange written out. Written out, the address arithmetic is simplified together with the kernel's (tid, rloc < 16 known);
+// that of the lambdas handed to hc_xchg is simplified on its own first and comes out in another form, and the kernels of these passes (the standalone transforms, hc_k_b1, hc_k_b3p,
+// hc_k_b5) then get other, longer address code around their LDS accesses.
+template <class P>
+__device__ __forceinline__ void hc_rows_fwd(const P &pol, u64 *lds, const HcTwTab &T, int row, int rloc, int tid, u64 (&e)[16]) {
+    hc_ct_round(pol, HcTwA<false, HcTw>{T.rowsA + row * 16}, e);
+#pragma unroll
+    for (int hi = 0; hi < 16; hi++) lds[hc_rows_lds(rloc, hi * 16 + tid)] = e[hi];
+    HC_ROW_SYNC();
+#pragma unroll
+    for (int lo = 0; lo < 16; lo++) e[lo] = lds[hc_rows_lds(rloc, tid * 16 + lo)];
+    hc_ct_round(pol, HcTwB<false, HcTw>{T.rowsB + row * 256 + tid}, e);
+}
+template <class P>
+__device__ __forceinline__ void hc_rows_inv(const P &pol, u64 *lds, const HcTwTab &T, int row, int rloc, int tid, u64 (&e)[16]) {
+    hc_gs_round(pol, HcTwB<false, HcTw>{T.rowsB + row * 256 + tid}, e);
+#pragma unroll
+    for (int lo = 0; lo < 16; lo++) lds[hc_rows_lds(rloc, tid * 16 + lo)] = e[lo];
+    HC_ROW_SYNC();
+#pragma unroll
+    for (int hi = 0; hi < 16; hi++) e[hi] = lds[hc_rows_lds(rloc, hi * 16 + tid)];
+    hc_gs_round(pol, HcTwA<false, HcTw>{T.rowsA + row * 16}, e);
+}
+template <class P>
+__device__ __forceinline__ void hc_cols_fwd(const P &pol, u64 *lds, const HcTwTab &T, int c, int tid, u64 (&e)[16]) {
+    hc_ct_round(pol, HcTwA<false, HcTw>{T.colsA}, e);
+#pragma unroll
+    for (int hi = 0; hi < 16; hi++) lds[hc_cols_lds(hi * 16 + tid, c)] = e[hi];
+    __syncthreads();
+#pragma unroll
+    for (int lo = 0; lo < 16; lo++) e[lo] = lds[hc_cols_lds(tid * 16 + lo, c)];
+    hc_ct_round(pol, HcTwB<false, HcTw>{T.colsB + tid}, e);
+}
+// (always with N^-1: no caller without it)
+template <class P>
+__device__ __forceinline__ void hc_cols_inv(const P &pol, u64 *lds, const HcTwTab &T, int c, int tid, u64 (&e)[16], const HcTw &ninv, const HcTw &w_last) {
+    hc_gs_round(pol, HcTwB<false, HcTw>{T.colsB + tid}, e);
+#pragma unroll
+    for (int lo = 0; lo < 16; lo++) lds[hc_cols_lds(tid * 16 + lo, c)] = e[lo];
+    __syncthreads();
+#pragma unroll
+    for (int hi = 0; hi < 16; hi++) e[hi] = lds[hc_cols_lds(hi * 16 + tid, c)];
+    hc_gs_round<true>(pol, HcTwA<false, HcTw>{T.colsA}, e, ninv, w_last);
+}
+__device__ __forceinline__ void hc_rows_lin_to_lo(u64 *lds, int t, int rloc, int tid, u64 (&e)[16]) {
+#pragma unroll
+    for (int k = 0; k < 16; k++) lds[hc_rows_lds(k, t)] = e[k];
+    __syncthreads();
+#pragma unroll
+    for (int lo = 0; lo < 16; lo++) e[lo] = lds[hc_rows_lds(rloc, tid * 16 + lo)];
+}
+__device__ __forceinline__ void hc_rows_lo_to_lin(u64 *lds, int t, int rloc, int tid, u64 (&e)[16]) {
+#pragma unroll
+    for (int lo = 0; lo < 16; lo++) lds[hc_rows_lds(rloc, tid * 16 + lo)] = e[lo];
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < 16; k++) e[k] = lds[hc_rows_lds(k, t)];
+}
+// fp64 forms of the inverse cols pass (4-byte words) and of the inverse rows pass on two tiles (8-byte words)
 __device__ __forceinline__ void hc_cols_inv_f64(double (&e)[16], u32 *lds, const HcTwTab &T, int c, int tid, HcF64Mod m) {
-    hc_gs_round_f64<false>(e, HcRowsTwB<false>{T.colsB + tid}, m, T.ninv, T.ninv);
-    hc_xchg32_f64(e, lds, [&](int lo) { return hc_cols_lds32(tid * 16 + lo, c); }, [&](int hi) { return hc_cols_lds32(hi * 16 + tid, c); }, [] { __syncthreads(); });
-    hc_gs_round_f64<true>(e, HcRowsTwA<false>{T.colsA}, m, T.ninv, T.w_last_ninv);
+    hc_gs_round_f64<false>(e, HcTwB<false, HcTw>{T.colsB + tid}, m, T.ninv, T.ninv);
+    hc_xchg(lds, [&](int lo) { return hc_cols_lds<u32>(tid * 16 + lo, c); }, [&](int hi) { return hc_cols_lds<u32>(hi * 16 + tid, c); }, [] { __syncthreads(); }, e);
+    hc_gs_round_f64<true>(e, HcTwA<false, HcTw>{T.colsA}, m, T.ninv, T.w_last_ninv);
 }
-__device__ __forceinline__ void hc_rows_lin_to_lo(u64 (&e)[16], u32 *lds, int t, int rloc, int tid) {
-    hc_xchg32(e, lds, [&](int k) { return hc_rows_lds32(k, t); }, [&](int lo) { return hc_rows_lds32(rloc, tid * 16 + lo); }, [] { __syncthreads(); });
-}
-__device__ __forceinline__ void hc_rows_lo_to_lin(u64 (&e)[16], u32 *lds, int t, int rloc, int tid) {
-    hc_xchg32(e, lds, [&](int lo) { return hc_rows_lds32(rloc, tid * 16 + lo); }, [&](int k) { return hc_rows_lds32(k, t); }, [] { __syncthreads(); });
+__device__ __forceinline__ void hc_rows_inv2_f64(double (&f0)[16], double (&f1)[16], u64 *lds, const HcTwTab &T, int row, int rloc, int tid, HcF64Mod m) {
+    hc_gs_round2_f64(f0, f1, HcTwB<false, HcTw>{T.rowsB + row * 256 + tid}, m);
+    u64 b0[16], b1[16];
+#pragma unroll
+    for (int i = 0; i < 16; i++) { b0[i] = hc_d2u(f0[i]); b1[i] = hc_d2u(f1[i]); }
+    hc_xchg(lds, [&](int lo) { return hc_rows_lds(rloc, tid * 16 + lo); }, [&](int hi) { return hc_rows_lds(rloc, hi * 16 + tid); }, [] { HC_ROW_SYNC(); }, b0, b1);
+#pragma unroll
+    for (int i = 0; i < 16; i++) { f0[i] = hc_u2d(b0[i]); f1[i] = hc_u2d(b1[i]); }
+    hc_gs_round2_f64(f0, f1, HcTwA<false, HcTw>{T.rowsA + row * 16}, m);
 }
 
 // x mod q for x < 2^64 with mu = floor(2^64/q): result canonical
 __device__ __forceinline__ u64 hc_barrett64(u64 x, u64 q, u64 mu) {
     u64 r = x - hc_mulhi(x, mu) * q;   // in [0, 2q)
     return hc_csub(r, q);
-}
-
-// ================================================================ 32-bit transforms for the limbs below 2^31 (round 5)
-// Eleven of the bootstrapping chain's 28 limbs are ~30-bit primes. Every instruction class these kernels are made of issues at one wave64 per 4 cycles whatever its width
-// (DESIGN.md section 5), so a butterfly costs its instruction count: 20-22 for the 64-bit lazy forms above, 12 for the canonical 32-bit form below - a Shoup product is
-// v_mul_hi_u32 + 2 v_mul_lo_u32 + a subtraction, every conditional correction is a subtraction and a v_min_u32 - and a thread's 16 residues take 16 registers, one LDS word
-// each (ONE exchange and barrier per pass instead of the two halves' three). The 32-bit companion of a table entry (w, w' = floor(w 2^64 / q)) is (low word of w, high word of
-// w'): floor(floor(w 2^64 / q) / 2^32) = floor(w 2^32 / q), so the 64-bit tables serve both forms. Everything is canonical, in and out: the same residues as the 64-bit
-// kernels, bit for bit. A workgroup takes this form as a WHOLE (its modulus is block-uniform): the 64-bit and 32-bit bodies share no live registers (round 4 switched per
-// butterfly inside one body and paid 108-132 VGPRs for 65-86: profiles/round4_chain_class_paths_ab.txt). Chosen at run time per modulus: HcRowMod::s32 (option small32).
-__device__ __forceinline__ HcTw32 hc_tw32(const HcTw &t) { return HcTw32{(u32)t.w, (u32)(t.ws >> 32)}; }
-__device__ __forceinline__ u32 hc_umulhi32(u32 a, u32 b) { return (u32)(((u64)a * b) >> 32); }
-__device__ __forceinline__ u32 hc_min32(u32 a, u32 b) { return a < b ? a : b; }
-__device__ __forceinline__ u32 hc_csub32(u32 x, u32 q) { return hc_min32(x, x - q); }                         // [0,2q) -> [0,q): x - q wraps above x when x < q
-__device__ __forceinline__ u32 hc_add32(u32 a, u32 b, u32 q) { return hc_csub32(a + b, q); }                   // a, b < q < 2^31
-__device__ __forceinline__ u32 hc_sub32(u32 a, u32 b, u32 q) { const u32 d = a - b; return hc_min32(d, d + q); }   // a < b: d wraps to 2^32 - (b - a) and d + q to the residue
-__device__ __forceinline__ u32 hc_mul32(u32 y, HcTw32 w, u32 q) { return hc_csub32(y * w.w - hc_umulhi32(y, w.ws) * q, q); }     // ANY y < 2^32; w < q
-template <class TW>
-__device__ __forceinline__ void hc_ct_round32(u32 (&e)[16], const TW &tw, u32 q) {
-#pragma unroll
-    for (int s = 0; s < 4; s++) {
-        const int half = 8 >> s;
-#pragma unroll
-        for (int g = 0; g < (1 << s); g++) {
-            const HcTw32 w = tw((1 << s) - 1 + g);
-#pragma unroll
-            for (int k = 0; k < half; k++) {
-                const int a = g * 2 * half + k, b = a + half;
-                const u32 X = e[a], T = hc_mul32(e[b], w, q);
-                e[a] = hc_add32(X, T, q);
-                e[b] = hc_sub32(X, T, q);
-            }
-        }
-    }
-}
-template <bool LAST, class TW>
-__device__ __forceinline__ void hc_gs_round32(u32 (&e)[16], const TW &tw, u32 q, HcTw32 ninv, HcTw32 w_last) {
-#pragma unroll
-    for (int s = 0; s < 4; s++) {
-        const int dist = 1 << s;
-#pragma unroll
-        for (int g = 0; g < (8 >> s); g++) {
-            HcTw32 w = tw((8 >> s) - 1 + g);
-            if (LAST && s == 3) w = w_last;
-#pragma unroll
-            for (int k = 0; k < dist; k++) {
-                const int a = g * 2 * dist + k, b = a + dist;
-                const u32 X = e[a], Y = e[b], u = hc_add32(X, Y, q), d = hc_sub32(X, Y, q);
-                e[a] = (LAST && s == 3) ? hc_mul32(u, ninv, q) : u;
-                e[b] = hc_mul32(d, w, q);
-            }
-        }
-    }
-}
-template <class WA, class RA, class SY>
-__device__ __forceinline__ void hc_xchg1(u32 (&e)[16], u32 *lds, WA wa, RA ra, SY sync) {
-#pragma unroll
-    for (int i = 0; i < 16; i++) lds[wa(i)] = e[i];
-    sync();
-#pragma unroll
-    for (int i = 0; i < 16; i++) e[i] = lds[ra(i)];
-}
-// the passes of hc_rows_fwd / hc_rows_inv / hc_cols_fwd / hc_cols_inv above on 32-bit residues: same element orders, same LDS address functions (4-byte words); twiddles from the
-// 8-byte tables, through the constant address space
-#if defined(__HIP_DEVICE_COMPILE__)
-#define HC_TW32_LOADK(p, i) (*((const HcTw32 __attribute__((address_space(4))) *)(p) + (i)))
-#else
-#define HC_TW32_LOADK(p, i) ((p)[i])
-#endif
-struct HcRowsTw32A { const HcTw32 *p; __device__ __forceinline__ HcTw32 operator()(int slot) const { return HC_TW32_LOADK(p, slot); } };
-struct HcRowsTw32B { const HcTw32 *p; __device__ __forceinline__ HcTw32 operator()(int slot) const { return HC_TW32_LOADK(p, slot * 16); } };
-__device__ __forceinline__ void hc_rows_fwd32(u32 (&e)[16], u32 *lds, const HcTwTab32 &T, int row, int rloc, int tid, u32 q) {
-    hc_ct_round32(e, HcRowsTw32A{T.rowsA + row * 16}, q);
-    hc_xchg1(e, lds, [&](int hi) { return hc_rows_lds32(rloc, hi * 16 + tid); }, [&](int lo) { return hc_rows_lds32(rloc, tid * 16 + lo); }, [] { HC_ROW_SYNC(); });
-    hc_ct_round32(e, HcRowsTw32B{T.rowsB + row * 256 + tid}, q);
-}
-__device__ __forceinline__ void hc_rows_inv32(u32 (&e)[16], u32 *lds, const HcTwTab32 &T, HcTw32 ni, int row, int rloc, int tid, u32 q) {
-    hc_gs_round32<false>(e, HcRowsTw32B{T.rowsB + row * 256 + tid}, q, ni, ni);
-    hc_xchg1(e, lds, [&](int lo) { return hc_rows_lds32(rloc, tid * 16 + lo); }, [&](int hi) { return hc_rows_lds32(rloc, hi * 16 + tid); }, [] { HC_ROW_SYNC(); });
-    hc_gs_round32<false>(e, HcRowsTw32A{T.rowsA + row * 16}, q, ni, ni);
-}
-__device__ __forceinline__ void hc_cols_fwd32(u32 (&e)[16], u32 *lds, const HcTwTab32 &T, int c, int tid, u32 q) {
-    hc_ct_round32(e, HcRowsTw32A{T.colsA}, q);
-    hc_xchg1(e, lds, [&](int hi) { return hc_cols_lds32(hi * 16 + tid, c); }, [&](int lo) { return hc_cols_lds32(tid * 16 + lo, c); }, [] { __syncthreads(); });
-    hc_ct_round32(e, HcRowsTw32B{T.colsB + tid}, q);
-}
-template <bool SCALE = true>
-__device__ __forceinline__ void hc_cols_inv32(u32 (&e)[16], u32 *lds, const HcTwTab32 &T, HcTw32 ni, HcTw32 w_last_ninv, int c, int tid, u32 q) {
-    hc_gs_round32<false>(e, HcRowsTw32B{T.colsB + tid}, q, ni, ni);
-    hc_xchg1(e, lds, [&](int lo) { return hc_cols_lds32(tid * 16 + lo, c); }, [&](int hi) { return hc_cols_lds32(hi * 16 + tid, c); }, [] { __syncthreads(); });
-    hc_gs_round32<SCALE>(e, HcRowsTw32A{T.colsA}, q, ni, w_last_ninv);
-}
-__device__ __forceinline__ void hc_rows_lin_to_lo32(u32 (&e)[16], u32 *lds, int t, int rloc, int tid) {
-    hc_xchg1(e, lds, [&](int k) { return hc_rows_lds32(k, t); }, [&](int lo) { return hc_rows_lds32(rloc, tid * 16 + lo); }, [] { __syncthreads(); });
-}
-__device__ __forceinline__ void hc_rows_lo_to_lin32(u32 (&e)[16], u32 *lds, int t, int rloc, int tid) {
-    hc_xchg1(e, lds, [&](int lo) { return hc_rows_lds32(rloc, tid * 16 + lo); }, [&](int k) { return hc_rows_lds32(k, t); }, [] { __syncthreads(); });
 }
 
 // ================================================================ standalone transforms (L0 API)
@@ -473,7 +546,7 @@ __global__ __launch_bounds__(HC_TPB) void hc_k_cols_fwd(const u64 *in, u64 *out,
     u64 e[16];
 #pragma unroll
     for (int hi = 0; hi < 16; hi++) e[hi] = in[base + (size_t)(hi * 16 + tid) * 256];
-    hc_cols_fwd<FM>(e, lds, T, c, tid, Q);
+    hc_cols_fwd(HcLazy<FM>{Q}, lds, T, c, tid, e);
 #pragma unroll
     for (int lo = 0; lo < 16; lo++) out[base + (size_t)(tid * 16 + lo) * 256] = e[lo];
 }
@@ -486,9 +559,9 @@ __global__ __launch_bounds__(HC_TPB) void hc_k_rows_fwd_canon(const u64 *in, u64
 #pragma unroll
     for (int hi = 0; hi < 16; hi++) e[hi] = in[pbase + (size_t)row * 256 + hi * 16 + tid];
     const HcQ Q = hc_q(q);
-    hc_rows_fwd<FM>(e, lds, T, row, rloc, tid, Q);
+    hc_rows_fwd(HcLazy<FM>{Q}, lds, T, row, rloc, tid, e);
     HC_ROW_SYNC();        // row-local: the reads before and the writes after stay inside the 16 lanes of a row
-    hc_rows_lo_to_lin(e, lds, t, rloc, tid);
+    hc_rows_lo_to_lin(lds, t, rloc, tid, e);
 #pragma unroll
     for (int k = 0; k < 16; k++) out[pbase + (size_t)(blockIdx.x * 16 + k) * 256 + t] = hc_fwd_canon<FM>(e[k], Q, mu);
 }
@@ -499,9 +572,9 @@ __global__ __launch_bounds__(HC_TPB) void hc_k_rows_inv(const u64 *in, u64 *out,
     u64 e[16];
 #pragma unroll
     for (int k = 0; k < 16; k++) e[k] = in[pbase + (size_t)(blockIdx.x * 16 + k) * 256 + t];
-    hc_rows_lin_to_lo(e, lds, t, rloc, tid);
+    hc_rows_lin_to_lo(lds, t, rloc, tid, e);
     HC_ROW_SYNC();        // row-local: the reads before and the writes after stay inside the 16 lanes of a row
-    hc_rows_inv(e, lds, T, row, rloc, tid, hc_q(q));
+    hc_rows_inv(HcLazy<>{hc_q(q)}, lds, T, row, rloc, tid, e);
 #pragma unroll
     for (int hi = 0; hi < 16; hi++) out[pbase + (size_t)row * 256 + hi * 16 + tid] = e[hi];
 }
@@ -513,7 +586,7 @@ __global__ __launch_bounds__(HC_TPB) void hc_k_cols_inv_canon(const u64 *in, u64
 #pragma unroll
     for (int lo = 0; lo < 16; lo++) e[lo] = in[base + (size_t)(tid * 16 + lo) * 256];
     const HcQ Q = hc_q(q);
-    hc_cols_inv(e, lds, T, c, tid, Q);
+    hc_cols_inv(HcLazy<>{Q}, lds, T, c, tid, e, T.ninv, T.w_last_ninv);
 #pragma unroll
     for (int hi = 0; hi < 16; hi++) out[base + (size_t)(hi * 16 + tid) * 256] = hc_canon4(e[hi], Q);
 }
@@ -785,109 +858,6 @@ __global__ __launch_bounds__(HC_TPB) void hc_k_rotate_finish(const u64 *d0, cons
     HC_ROW_DISPATCH(mods[l].row32, body);
 }
 
-// ---------------------------------------------------------------- two register tiles in lock step
-// Two transforms over the same 16 rows and the same modulus want the same twiddles - 15 rowsA pairs per row and 15 rowsB pairs per THREAD and pass, 480 of the 608 bytes a
-// thread loads in a rows pass. The forms below run the butterflies of both tiles behind ONE load per twiddle slot: the same lazy arithmetic on the same values as the one-tile
-// rounds, only the order of independent operations differs (bit-identical results). Used where one workgroup has both tiles anyway (hc_k_b3: the two key components of a
-// node; hc_k_b5m: the two polynomials) or can take them (hc_k_a1 / hc_k_a3: the two polynomials of a channel, which also share the kernel-plaintext tile).
-template <int FM, class TW>
-__device__ __forceinline__ void hc_ct_round2(u64 (&e0)[16], u64 (&e1)[16], const TW &tw, const HcQ &Q) {
-#pragma unroll
-    for (int s = 0; s < 4; s++) {
-        const int half = 8 >> s;
-#pragma unroll
-        for (int g = 0; g < (1 << s); g++) {
-            const HcTw w = tw((1 << s) - 1 + g);
-#pragma unroll
-            for (int k = 0; k < half; k++) {
-                const int a = g * 2 * half + k, b = a + half;
-                u64 X0 = e0[a], X1 = e1[a];
-                if (FM == HC_FM_ALT) { X0 = hc_fold(X0, Q.nq4); X1 = hc_fold(X1, Q.nq4); }
-                const u64 T0 = hc_shoup4(e0[b], w.w, w.ws, Q), T1 = hc_shoup4(e1[b], w.w, w.ws, Q);
-                e0[a] = X0 + T0; e0[b] = (X0 + Q.q4) - T0;
-                e1[a] = X1 + T1; e1[b] = (X1 + Q.q4) - T1;
-            }
-        }
-    }
-}
-// hc_gs_round<false> on two tiles
-template <class TW>
-__device__ __forceinline__ void hc_gs_round2(u64 (&e0)[16], u64 (&e1)[16], const TW &tw, const HcQ &Q) {
-#pragma unroll
-    for (int s = 0; s < 4; s++) {
-        const int dist = 1 << s;
-#pragma unroll
-        for (int g = 0; g < (8 >> s); g++) {
-            const HcTw w = tw((8 >> s) - 1 + g);
-#pragma unroll
-            for (int k = 0; k < dist; k++) {
-                const int a = g * 2 * dist + k, b = a + dist;
-                const u64 X0 = e0[a], Y0 = e0[b], X1 = e1[a], Y1 = e1[b];
-                e0[a] = hc_fold(X0 + Y0, Q.nq4); e0[b] = hc_shoup4((X0 + Q.q4) - Y0, w.w, w.ws, Q);
-                e1[a] = hc_fold(X1 + Y1, Q.nq4); e1[b] = hc_shoup4((X1 + Q.q4) - Y1, w.w, w.ws, Q);
-            }
-        }
-    }
-}
-// hc_gs_round_f64<false> on two tiles
-template <class TW>
-__device__ __forceinline__ void hc_gs_round2_f64(double (&e0)[16], double (&e1)[16], const TW &tw, HcF64Mod m) {
-#pragma unroll
-    for (int s = 0; s < 4; s++) {
-        const int dist = 1 << s;
-#pragma unroll
-        for (int g = 0; g < (8 >> s); g++) {
-            const HcTw w = tw((8 >> s) - 1 + g);
-            const double ww = hc_u2d(w.w), wq = hc_u2d(w.ws);
-#pragma unroll
-            for (int k = 0; k < dist; k++) {
-                const int a = g * 2 * dist + k, b = a + dist;
-                const double X0 = e0[a], Y0 = e0[b], X1 = e1[a], Y1 = e1[b], u0 = X0 + Y0, u1 = X1 + Y1;
-                e0[a] = (s & 1) ? hc_f64_reduce(u0, m.q, m.qinv) : u0; e0[b] = hc_f64_mulmod(X0 - Y0, ww, wq, m.q);
-                e1[a] = (s & 1) ? hc_f64_reduce(u1, m.q, m.qinv) : u1; e1[b] = hc_f64_mulmod(X1 - Y1, ww, wq, m.q);
-            }
-        }
-    }
-}
-// The exchanges of two tiles go through ONE 32 KiB LDS tile, one after the other (occupancy: two tiles side by side would halve the workgroups a CU holds).
-// SY: HC_ROW_SYNC for the row-local exchanges, __syncthreads for the ones to and from the linear order.
-template <class WA, class RA, class SY>
-__device__ __forceinline__ void hc_xchg2(u64 (&e0)[16], u64 (&e1)[16], u64 *lds, WA wa, RA ra, SY sync) {
-#pragma unroll
-    for (int i = 0; i < 16; i++) lds[wa(i)] = e0[i];
-    sync();
-#pragma unroll
-    for (int i = 0; i < 16; i++) e0[i] = lds[ra(i)];
-    sync();                                                                  // every word of the first tile has been read before the second lands on it
-#pragma unroll
-    for (int i = 0; i < 16; i++) lds[wa(i)] = e1[i];
-    sync();
-#pragma unroll
-    for (int i = 0; i < 16; i++) e1[i] = lds[ra(i)];
-}
-// hc_rows_fwd / hc_rows_inv / hc_rows_inv_f64 on two tiles: same element orders in and out
-template <int FM>
-__device__ __forceinline__ void hc_rows_fwd2(u64 (&e0)[16], u64 (&e1)[16], u64 *lds, const HcTwTab &T, int row, int rloc, int tid, const HcQ &Q) {
-    hc_ct_round2<FM>(e0, e1, HcRowsTwA<false>{T.rowsA + row * 16}, Q);
-    hc_xchg2(e0, e1, lds, [&](int hi) { return hc_rows_lds(rloc, hi * 16 + tid); }, [&](int lo) { return hc_rows_lds(rloc, tid * 16 + lo); }, [] { HC_ROW_SYNC(); });
-    hc_ct_round2<FM>(e0, e1, HcRowsTwB<false>{T.rowsB + row * 256 + tid}, Q);
-}
-__device__ __forceinline__ void hc_rows_inv2(u64 (&e0)[16], u64 (&e1)[16], u64 *lds, const HcTwTab &T, int row, int rloc, int tid, const HcQ &Q) {
-    hc_gs_round2(e0, e1, HcRowsTwB<false>{T.rowsB + row * 256 + tid}, Q);
-    hc_xchg2(e0, e1, lds, [&](int lo) { return hc_rows_lds(rloc, tid * 16 + lo); }, [&](int hi) { return hc_rows_lds(rloc, hi * 16 + tid); }, [] { HC_ROW_SYNC(); });
-    hc_gs_round2(e0, e1, HcRowsTwA<false>{T.rowsA + row * 16}, Q);
-}
-__device__ __forceinline__ void hc_rows_inv2_f64(double (&f0)[16], double (&f1)[16], u64 *lds, const HcTwTab &T, int row, int rloc, int tid, HcF64Mod m) {
-    hc_gs_round2_f64(f0, f1, HcRowsTwB<false>{T.rowsB + row * 256 + tid}, m);
-    u64 b0[16], b1[16];
-#pragma unroll
-    for (int i = 0; i < 16; i++) { b0[i] = hc_d2u(f0[i]); b1[i] = hc_d2u(f1[i]); }
-    hc_xchg2(b0, b1, lds, [&](int lo) { return hc_rows_lds(rloc, tid * 16 + lo); }, [&](int hi) { return hc_rows_lds(rloc, hi * 16 + tid); }, [] { HC_ROW_SYNC(); });
-#pragma unroll
-    for (int i = 0; i < 16; i++) { f0[i] = hc_u2d(b0[i]); f1[i] = hc_u2d(b1[i]); }
-    hc_gs_round2_f64(f0, f1, HcRowsTwA<false>{T.rowsA + row * 16}, m);
-}
-
 // ================================================================ loop A (conv.go:525-531), fused
 // Per output channel i and ciphertext polynomial p:
 //   a_l = c'_p[l] (*) k_i[l]  (l = 0,1; c' = ct_in * MultByConst constant, kept as Shoup pairs: it is the FIXED operand of 2B products)
@@ -942,7 +912,7 @@ struct HcLoopA {
 };
 // KA1: a_1 = c'_p[1] (*) k_i[1] and its rows-inverse (mod Q1) for BOTH polynomials of a channel (jobs 2c and 2c + 1 of tmp): grid = (jobs / 2, 16, batch). F64 = 1: Q1 < 2^49, the transform
 // runs in fp64 (T1inv = the fp64 table) and tmp carries doubles (bit patterns) to KA2. The kernel-plaintext tile
-// k_i[1] is loaded once and every T1inv twiddle once for the two transforms (hc_rows_inv2 / hc_rows_inv2_f64); one LDS tile, used by the two polynomials in turn.
+// k_i[1] is loaded once and every T1inv twiddle once for the two transforms (hc_rows_inv on two tiles / hc_rows_inv2_f64); one LDS tile, used by the two polynomials in turn.
 template <int F64>
 __global__ __launch_bounds__(HC_TPB, HC_W_A1) void hc_k_a1p(HcLoopA A, HcTwTab T1inv) {
     __shared__ u64 lds[HC_ROWS_LDS];
@@ -960,7 +930,7 @@ __global__ __launch_bounds__(HC_TPB, HC_W_A1) void hc_k_a1p(HcLoopA A, HcTwTab T
         e1[kk] = hc_shoup4(kv, w1.w, w1.ws, Q);
     }
     u64 *o = A.tmp + ((size_t)z * A.njobs + 2 * ch) * 65536 + (size_t)row * 256;     // polynomial 1 is 65536 words on
-    hc_xchg2(e0, e1, lds, [&](int kk) { return hc_rows_lds(kk, t); }, [&](int lo) { return hc_rows_lds(rloc, tid * 16 + lo); }, [] { __syncthreads(); });
+    hc_xchg(lds, [&](int kk) { return hc_rows_lds(kk, t); }, [&](int lo) { return hc_rows_lds(rloc, tid * 16 + lo); }, [] { __syncthreads(); }, e0, e1);
     HC_ROW_SYNC();        // row-local: the reads before and the writes after stay inside the 16 lanes of a row
     if (F64) {
         const HcF64Mod m{(double)A.m1.q, 1.0 / (double)A.m1.q};
@@ -971,7 +941,7 @@ __global__ __launch_bounds__(HC_TPB, HC_W_A1) void hc_k_a1p(HcLoopA A, HcTwTab T
 #pragma unroll
         for (int hi = 0; hi < 16; hi++) { o[hi * 16 + tid] = hc_d2u(f0[hi]); o[65536 + hi * 16 + tid] = hc_d2u(f1[hi]); }
     } else {
-        hc_rows_inv2(e0, e1, lds, T1inv, row, rloc, tid, Q);
+        hc_rows_inv(HcLazy<>{Q}, lds, T1inv, row, rloc, tid, e0, e1);
 #pragma unroll
         for (int hi = 0; hi < 16; hi++) { o[hi * 16 + tid] = e0[hi]; o[65536 + hi * 16 + tid] = e1[hi]; }
     }
@@ -1001,7 +971,7 @@ __global__ __launch_bounds__(HC_TPB, HC_W_A2) void hc_k_a2(HcLoopA A, HcTwTab T1
         }
     } else {
         const HcQ Q1 = hc_q(A.m1.q);
-        hc_cols_inv(e, lds, T1inv, c, tid, Q1);
+        hc_cols_inv(HcLazy<>{Q1}, lds, T1inv, c, tid, e, T1inv.ninv, T1inv.w_last_ninv);
 #pragma unroll
         for (int hi = 0; hi < 16; hi++) {
             const u64 v = hc_csub(hc_canon4(e[hi], Q1) + A.h, A.m1.q);   // [t + h]_{Q1}
@@ -1009,12 +979,12 @@ __global__ __launch_bounds__(HC_TPB, HC_W_A2) void hc_k_a2(HcLoopA A, HcTwTab T1
         }
     }
     __syncthreads();
-    hc_cols_fwd<FM>(e, lds, T0fwd, c, tid, Q0);
+    hc_cols_fwd(HcLazy<FM>{Q0}, lds, T0fwd, c, tid, e);
 #pragma unroll
     for (int lo = 0; lo < 16; lo++) base[(size_t)(tid * 16 + lo) * 256] = e[lo];
 }
 // KA3: rows-forward mod Q0, then out = (a_0 - u) * Q1^-1 with a_0 = c'_p[0] (*) k_i[0], for both polynomials of a channel per workgroup, grid = (jobs / 2, 16, batch): k_i[0] loaded once (held across the transform: 32 VGPRs), every T0fwd twiddle once
-// (hc_rows_fwd2). The two c'_p[0] tiles are loaded behind the transform in row batches, as hc_k_b5m's epilogue loads its operands: two a_0 tiles formed before the transform
+// (hc_rows_fwd on two tiles). The two c'_p[0] tiles are loaded behind the transform in row batches, as hc_k_b5m's epilogue loads its operands: two a_0 tiles formed before the transform
 // (all loads up front, as the one-polynomial form of this kernel had them) would be 64 more registers across it.
 template <int FM>
 __global__ __launch_bounds__(HC_TPB, HC_W_A3) void hc_k_a3p(HcLoopA A, HcTwTab T0fwd) {
@@ -1031,9 +1001,9 @@ __global__ __launch_bounds__(HC_TPB, HC_W_A3) void hc_k_a3p(HcLoopA A, HcTwTab T
     for (int hi = 0; hi < 16; hi++) { e0[hi] = in[hi * 16 + tid]; e1[hi] = in[65536 + hi * 16 + tid]; }
 #pragma unroll
     for (int kk = 0; kk < 16; kk++) kv[kk] = k[kk * 256];
-    hc_rows_fwd2<FM>(e0, e1, lds, T0fwd, row, rloc, tid, Q);
+    hc_rows_fwd(HcLazy<FM>{Q}, lds, T0fwd, row, rloc, tid, e0, e1);
     HC_ROW_SYNC();        // row-local: the reads before and the writes after stay inside the 16 lanes of a row
-    hc_xchg2(e0, e1, lds, [&](int lo) { return hc_rows_lds(rloc, tid * 16 + lo); }, [&](int kk) { return hc_rows_lds(kk, t); }, [] { __syncthreads(); });
+    hc_xchg(lds, [&](int lo) { return hc_rows_lds(rloc, tid * 16 + lo); }, [&](int kk) { return hc_rows_lds(kk, t); }, [] { __syncthreads(); }, e0, e1);
 #pragma unroll
     for (int b = 0; b < 16; b += HC_A3_ROWS) {
         HcTw w0[HC_A3_ROWS], w1[HC_A3_ROWS];
@@ -1101,9 +1071,9 @@ __global__ __launch_bounds__(HC_TPB, HC_W_B1) void hc_k_b1(HcLoopB B, HcTwTab T0
 #pragma unroll
         for (int kk = 0; kk < 16; kk++) tt[kk * 256] = e[kk];
     }
-    hc_rows_lin_to_lo(e, lds, t, rloc, tid);
+    hc_rows_lin_to_lo(lds, t, rloc, tid, e);
     HC_ROW_SYNC();        // row-local: the reads before and the writes after stay inside the 16 lanes of a row
-    hc_rows_inv(e, lds, T0inv, row, rloc, tid, Q);
+    hc_rows_inv(HcLazy<>{Q}, lds, T0inv, row, rloc, tid, e);
     u64 *__restrict__ o = B.tmpC + (size_t)job * 65536 + (size_t)row * 256;
 #pragma unroll
     for (int hi = 0; hi < 16; hi++) o[hi * 16 + tid] = e[hi];
@@ -1118,15 +1088,15 @@ __global__ __launch_bounds__(HC_TPB, HC_W_B2) void hc_k_b2(HcLoopB B, HcTwTab T0
     u64 e[16];
 #pragma unroll
     for (int lo = 0; lo < 16; lo++) e[lo] = base[(size_t)(tid * 16 + lo) * 256];
-    hc_cols_inv(e, lds, T0inv, c, tid, Q0);
+    hc_cols_inv(HcLazy<>{Q0}, lds, T0inv, c, tid, e, T0inv.ninv, T0inv.w_last_ninv);
 #pragma unroll
     for (int hi = 0; hi < 16; hi++) e[hi] = hc_canon4(e[hi], Q0);          // the integer in [0, Q0) is what is read modulo P
     __syncthreads();
-    hc_cols_fwd<FMP>(e, lds, TPfwd, c, tid, QP);
+    hc_cols_fwd(HcLazy<FMP>{QP}, lds, TPfwd, c, tid, e);
 #pragma unroll
     for (int lo = 0; lo < 16; lo++) base[(size_t)(tid * 16 + lo) * 256] = e[lo];
 }
-// KB3: rows-forward mod P, multiply by b_P and a_P, rows-inverse mod P of both in lock step, every TPinv twiddle loaded once (hc_rows_inv2). grid = (batch*nodes, 16)
+// KB3: rows-forward mod P, multiply by b_P and a_P, rows-inverse mod P of both in lock step, every TPinv twiddle loaded once (hc_rows_inv on two tiles). grid = (batch*nodes, 16)
 template <int FMP>
 __global__ __launch_bounds__(HC_TPB, HC_W_B3) void hc_k_b3p(HcLoopB B, HcTwTab TPfwd, HcTwTab TPinv) {
     __shared__ u64 lds[HC_ROWS_LDS];
@@ -1139,7 +1109,7 @@ __global__ __launch_bounds__(HC_TPB, HC_W_B3) void hc_k_b3p(HcLoopB B, HcTwTab T
         u64 cp[16];
 #pragma unroll
         for (int hi = 0; hi < 16; hi++) cp[hi] = in[hi * 16 + tid];
-        hc_rows_fwd<FMP>(cp, lds, TPfwd, row, rloc, tid, Q);
+        hc_rows_fwd(HcLazy<FMP>{Q}, lds, TPfwd, row, rloc, tid, cp);
         const HcTw *__restrict__ ev = B.evkP + (size_t)HC_TILE * 4096 + t;                 // b_P rows ; a_P is 65536 pairs on
 #pragma unroll
         for (int lo = 0; lo < 16; lo++) {
@@ -1149,7 +1119,7 @@ __global__ __launch_bounds__(HC_TPB, HC_W_B3) void hc_k_b3p(HcLoopB B, HcTwTab T
         }
     }
     HC_ROW_SYNC();             // row-local (the forward pass's reads of this row, then the inverse pass's writes): hc_k_b3 has no workgroup barrier
-    hc_rows_inv2(e0, e1, lds, TPinv, row, rloc, tid, Q);
+    hc_rows_inv(HcLazy<>{Q}, lds, TPinv, row, rloc, tid, e0, e1);
     u64 *o = B.tmpE + (size_t)node * 2 * 65536 + (size_t)row * 256;
 #pragma unroll
     for (int hi = 0; hi < 16; hi++) { o[hi * 16 + tid] = e0[hi]; o[65536 + hi * 16 + tid] = e1[hi]; }
@@ -1165,7 +1135,7 @@ __global__ __launch_bounds__(HC_TPB, HC_W_B4) void hc_k_b4(HcLoopB B, HcTwTab TP
     u64 e[16];
 #pragma unroll
     for (int lo = 0; lo < 16; lo++) e[lo] = base[(size_t)(tid * 16 + lo) * 256];
-    hc_cols_inv<false>(e, lds, TPinv, c, tid, QP);                 // N^-1 mod P is inside the key rows (hc_evk_load)
+    hc_cols_inv<false>(HcLazy<>{QP}, lds, TPinv, c, tid, e, TPinv.ninv, TPinv.w_last_ninv);                 // N^-1 mod P is inside the key rows (hc_evk_load)
 #pragma unroll
     for (int hi = 0; hi < 16; hi++) {
         const u64 yv = hc_canon4(e[hi], QP);                       // [d]_P in [0,P)
@@ -1178,7 +1148,7 @@ __global__ __launch_bounds__(HC_TPB, HC_W_B4) void hc_k_b4(HcLoopB B, HcTwTab TP
         e[hi] = r;
     }
     __syncthreads();
-    hc_cols_fwd<FM>(e, lds, T0fwd, c, tid, Q);
+    hc_cols_fwd(HcLazy<FM>{Q}, lds, T0fwd, c, tid, e);
 #pragma unroll
     for (int lo = 0; lo < 16; lo++) base[(size_t)(tid * 16 + lo) * 256] = e[lo];
 }
@@ -1230,9 +1200,9 @@ __global__ __launch_bounds__(HC_TPB, 3) void hc_k_b5(HcLoopB B, HcTwTab T0fwd, H
     u64 e[16];
 #pragma unroll
     for (int hi = 0; hi < 16; hi++) e[hi] = in[hi * 16 + tid];
-    hc_rows_fwd<FM>(e, lds, T0fwd, row, rloc, tid, Q);
+    hc_rows_fwd(HcLazy<FM>{Q}, lds, T0fwd, row, rloc, tid, e);
     HC_ROW_SYNC();        // row-local: the reads before and the writes after stay inside the 16 lanes of a row
-    hc_rows_lo_to_lin(e, lds, t, rloc, tid);          // e[kk] = n = NTT(ext * P^-1) at (row kk, column t)
+    hc_rows_lo_to_lin(lds, t, rloc, tid, e);          // e[kk] = n = NTT(ext * P^-1) at (row kk, column t)
     __syncthreads();
     {
         u64 t1[16];
@@ -1289,13 +1259,13 @@ __global__ __launch_bounds__(HC_TPB, 3) void hc_k_b5(HcLoopB B, HcTwTab T0fwd, H
 // hc_rows_fwd on two polynomials (tiles l0, l1 of LDS), then hc_rows_lo_to_lin on both: out e_k[kk] = n_k at (row kk, column t)
 template <int FM>
 __device__ __forceinline__ void hc_rows_fwd2_lin(u64 (&e0)[16], u64 (&e1)[16], u64 *l0, u64 *l1, const HcTwTab &T, int row, int rloc, int tid, int t, const HcQ &Q) {
-    hc_ct_round2<FM>(e0, e1, HcRowsTwA<false>{T.rowsA + row * 16}, Q);
+    hc_ct_round(HcLazy<FM>{Q}, HcTwA<false, HcTw>{T.rowsA + row * 16}, e0, e1);
 #pragma unroll
     for (int hi = 0; hi < 16; hi++) { const int a = hc_rows_lds(rloc, hi * 16 + tid); l0[a] = e0[hi]; l1[a] = e1[hi]; }
     HC_ROW_SYNC();
 #pragma unroll
     for (int lo = 0; lo < 16; lo++) { const int a = hc_rows_lds(rloc, tid * 16 + lo); e0[lo] = l0[a]; e1[lo] = l1[a]; }
-    hc_ct_round2<FM>(e0, e1, HcRowsTwB<false>{T.rowsB + row * 256 + tid}, Q);
+    hc_ct_round(HcLazy<FM>{Q}, HcTwB<false, HcTw>{T.rowsB + row * 256 + tid}, e0, e1);
     HC_ROW_SYNC();        // row-local: the reads before and the writes after stay inside the 16 lanes of a row
 #pragma unroll
     for (int lo = 0; lo < 16; lo++) { const int a = hc_rows_lds(rloc, tid * 16 + lo); l0[a] = e0[lo]; l1[a] = e1[lo]; }
@@ -1888,7 +1858,7 @@ __device__ __forceinline__ void hc_cols_fwd_mm_small(const u64 *in, u64 *out, u3
 #pragma unroll
         for (int hi = 0; hi < 16; hi++) e[hi] = (u32)in[(size_t)y * 65536 + (size_t)(blockIdx.x * 16 + c) + (size_t)(hi * 16 + tid) * 256];
     }
-    hc_cols_fwd32(e, lds, R.fwd32, c, tid, q);
+    hc_cols_fwd<true>(HcCanon32{q}, lds, R.fwd32, c, tid, e);
     if (A.pk_out) {
 #pragma unroll
         for (int lo = 0; lo < 16; lo++) hc_st32(out + (size_t)y * 65536, (size_t)(blockIdx.x * 16 + c) + (size_t)(tid * 16 + lo) * 256, e[lo]);
@@ -1925,7 +1895,7 @@ __device__ __forceinline__ void hc_cols_fwd_mm_big(const u64 *in, u64 *out, u32 
         for (int hi = 0; hi < 16; hi++) e[hi] = hc_ldp(in + (size_t)y * 65536, (size_t)(blockIdx.x * 16 + c) + (size_t)(hi * 16 + tid) * 256, in32);
     }
     const HcQ Qf = hc_q(R.q);
-    hc_cols_fwd<HC_FM_ALT, true>(e, lds, R.fwd, c, tid, Qf);
+    hc_cols_fwd<true>(HcLazy<HC_FM_ALT>{Qf}, lds, R.fwd, c, tid, e);
     if (A.pk_out && HC_SMALL_Q(R.q)) {                                        // block-uniform: the seam row as 4-byte words (lazy values < 8q -> < 2q < 2^32)
 #pragma unroll
         for (int lo = 0; lo < 16; lo++) hc_st32(out + (size_t)y * 65536, (size_t)(blockIdx.x * 16 + c) + (size_t)(tid * 16 + lo) * 256, hc_fold(hc_fold(e[lo], Qf.nq4), Qf.nq2));
@@ -1960,9 +1930,9 @@ __device__ __forceinline__ void hc_rows_fwd_canon_mm_small(const u64 *in, u64 *o
 #pragma unroll
         for (int hi = 0; hi < 16; hi++) e[hi] = (u32)in[pbase + (size_t)row * 256 + hi * 16 + tid];
     }
-    hc_rows_fwd32(e, lds, R.fwd32, row, rloc, tid, q);
+    hc_rows_fwd<true>(HcCanon32{q}, lds, R.fwd32, row, rloc, tid, e);
     HC_ROW_SYNC();
-    hc_rows_lo_to_lin32(e, lds, t, rloc, tid);
+    hc_rows_lo_to_lin(lds, t, rloc, tid, e);
     const size_t lj = (size_t)(bx * 16) * 256 + t;                           // element index of (row bx * 16, column t) inside the limb's row
     if (A.epi_x != nullptr) {                                                // block-uniform: (x - result) * c (+ addend [* c']), hc_k_rows_fwd_canon_mm's epilogue
         const u64 *x = A.epi_x + (size_t)zi * A.epi_x_zs + (size_t)img * A.epi_x_is + pbase;
@@ -2020,9 +1990,9 @@ __global__ __launch_bounds__(HC_TPB, HC_MM_WAVES_RF) void hc_k_rows_fwd_canon_mm
 #pragma unroll
     for (int hi = 0; hi < 16; hi++) e[hi] = hc_ldp(in + pbase, (size_t)row * 256 + hi * 16 + tid, A.pk_in && small);
     const HcQ Q = hc_q(rq);
-    hc_rows_fwd<HC_FM_ALT, true>(e, lds, R.fwd, row, rloc, tid, Q);
+    hc_rows_fwd<true>(HcLazy<HC_FM_ALT>{Q}, lds, R.fwd, row, rloc, tid, e);
     HC_ROW_SYNC();        // row-local: the reads before and the writes after stay inside the 16 lanes of a row
-    hc_rows_lo_to_lin(e, lds, t, rloc, tid);
+    hc_rows_lo_to_lin(lds, t, rloc, tid, e);
 #pragma unroll
     for (int k = 0; k < 16; k++) e[k] = hc_fwd_canon<HC_FM_ALT>(e[k], Q, rmu);
     const size_t lin = pbase + (size_t)(bx * 16) * 256 + t;
@@ -2092,9 +2062,9 @@ __device__ __forceinline__ void hc_rows_inv_mm_small(const u64 *in, u64 *out, u3
 #pragma unroll
         for (int k = 0; k < 16; k++) e[k] = (u32)in[pbase + (size_t)(bx * 16 + k) * 256 + t];
     }
-    hc_rows_lin_to_lo32(e, lds, t, rloc, tid);
+    hc_rows_lin_to_lo(lds, t, rloc, tid, e);
     HC_ROW_SYNC();
-    hc_rows_inv32(e, lds, R.inv32, hc_tw32(R.inv.ninv), row, rloc, tid, q);
+    hc_rows_inv<true>(HcCanon32{q}, lds, R.inv32, row, rloc, tid, e);
     if (A.pk_out) {
 #pragma unroll
         for (int hi = 0; hi < 16; hi++) hc_st32(out + pbase, (size_t)row * 256 + hi * 16 + tid, e[hi]);
@@ -2115,9 +2085,9 @@ __device__ __forceinline__ void hc_cols_inv_canon_mm_small(const u64 *in, u64 *o
 #pragma unroll
         for (int lo = 0; lo < 16; lo++) e[lo] = (u32)in[pbase + col + (size_t)(tid * 16 + lo) * 256];
     }
-    hc_cols_inv32(e, lds, R.inv32, hc_tw32(R.inv.ninv), hc_tw32(R.inv.w_last_ninv), c, tid, q);
+    hc_cols_inv<true, true>(HcCanon32{q}, lds, R.inv32, c, tid, e, hc_tw32(R.inv.ninv), hc_tw32(R.inv.w_last_ninv));
     if (scale != nullptr) {                                                   // uniform: y_i = x_i (S/s_i)^-1 (hc_cols_inv_canon_mm_body)
-        const HcTw32 w = hc_tw32(HC_TW_LOADK(scale, 0));
+        const HcTw32 w = hc_tw32(HC_TW_LOADK(HcTw, scale, 0));
 #pragma unroll
         for (int hi = 0; hi < 16; hi++) e[hi] = hc_mul32(e[hi], w, q);
     }
@@ -2140,10 +2110,10 @@ __global__ __launch_bounds__(HC_TPB, HC_MM_WAVES_INV) void hc_k_rows_inv_mm(cons
     const bool in32 = A.pk_in && HC_SMALL_Q(R.q);                             // block-uniform (a caller's NTT-domain polynomial under pack32 = 2)
 #pragma unroll
     for (int k = 0; k < 16; k++) e[k] = hc_ldp(in + pbase, (size_t)(bx * 16 + k) * 256 + t, in32);
-    hc_rows_lin_to_lo(e, lds, t, rloc, tid);
+    hc_rows_lin_to_lo(lds, t, rloc, tid, e);
     HC_ROW_SYNC();        // row-local: the reads before and the writes after stay inside the 16 lanes of a row
     const HcQ Q = hc_q(R.q);
-    hc_rows_inv<true>(e, lds, R.inv, row, rloc, tid, Q);
+    hc_rows_inv<true>(HcLazy<>{Q}, lds, R.inv, row, rloc, tid, e);
     if (A.pk_out && HC_SMALL_Q(R.q)) {                                       // block-uniform: the seam row as 4-byte words (lazy values < 4q -> < 2q < 2^32)
 #pragma unroll
         for (int hi = 0; hi < 16; hi++) hc_st32(out + pbase, (size_t)row * 256 + hi * 16 + tid, hc_fold(e[hi], Q.nq2));
@@ -2162,9 +2132,9 @@ __device__ __forceinline__ void hc_cols_inv_canon_mm_body(const u64 *in, u64 *ou
 #pragma unroll
     for (int lo = 0; lo < 16; lo++) e[lo] = IN32 ? hc_ld32(in + (size_t)y * 65536, (size_t)(blockIdx.x * 16 + c) + (size_t)(tid * 16 + lo) * 256) : in[base + (size_t)(tid * 16 + lo) * 256];
     const HcQ Q = hc_q(R.q);
-    hc_cols_inv<true, true>(e, lds, R.inv, c, tid, Q);
+    hc_cols_inv<true, true>(HcLazy<>{Q}, lds, R.inv, c, tid, e, R.inv.ninv, R.inv.w_last_ninv);
     if (scale != nullptr) {                                                   // uniform
-        const HcTw w = HC_TW_LOADK(scale, 0);
+        const HcTw w = HC_TW_LOADK(HcTw, scale, 0);
 #pragma unroll
         for (int hi = 0; hi < 16; hi++) e[hi] = hc_mul_shoup(e[hi], w.w, w.ws, R.q);
     } else {
@@ -2231,7 +2201,7 @@ __global__ __launch_bounds__(HC_STPB) void hc_k_cols_inv_canon_mm_s(const u64 *i
     const size_t obase = (size_t)yo * 65536;
     HcTw sc{0, 0};
     const bool scaled = A.epi_mul != nullptr;                                // y_i = x_i (S/s_i)^-1 (hc_cols_inv_canon_mm_body)
-    if (scaled) sc = HC_TW_LOADK(A.epi_mul + y, 0);
+    if (scaled) sc = HC_TW_LOADK(HcTw, A.epi_mul + y, 0);
 #pragma unroll
     for (int k = 0; k < 4; k++) {
         const int r = k * 64 + u;

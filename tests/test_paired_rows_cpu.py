@@ -42,7 +42,7 @@ def test_big_level_kernels_in_a_batch_of_three(env, max_ob, chunk):
 @pytest.mark.parametrize("q0,q1", [(Q0, Q60), (Q60, Q1), (Q60, Q0)], ids=["integer-a1", "alt-a3-b5m", "alt-and-integer-a1"])
 @pytest.mark.parametrize("small", [0, 16])
 def test_other_modulus_sizes(monkeypatch, q0, q1, small):
-    """Q1 above 2^49: hc_k_a1p<0> (hc_rows_inv2); Q0 at or above 2^57: HC_FM_ALT in hc_k_a3p and hc_k_b5m. The parity case draws its inputs below the moduli it finds in its module."""
+    """Q1 above 2^49: hc_k_a1p<0> (hc_rows_inv on two tiles); Q0 at or above 2^57: HC_FM_ALT in hc_k_a3p and hc_k_b5m. The parity case draws its inputs below the moduli it finds in its module."""
     subprocess.check_call(["make", "-s", "-C", EMU_DIR, EMU_LIB])
     monkeypatch.setattr(pc, "Q0", q0)
     monkeypatch.setattr(pc, "Q1", q1)

@@ -10,9 +10,9 @@ template <int MODE> __global__ __launch_bounds__(256) void k_round(u64 *out, con
 #pragma unroll
     for (int j = 0; j < 16; j++) { e[j] = (u64)threadIdx.x * 977 + j * 131 + blockIdx.x; T.t[j] = tw[j]; }
     for (int it = 0; it < iters; it++) {
-        if (MODE == 0) hc_ct_round<HC_FM_ALT>(e, T, q);
-        else if (MODE == 1) hc_ct_round<HC_FM_FREE>(e, T, q);
-        else { hc_gs_round<false>(e, T, q, T.t[0], T.t[1]); }
+        if (MODE == 0) hc_ct_round(HcLazy<HC_FM_ALT>{q}, T, e);
+        else if (MODE == 1) hc_ct_round(HcLazy<HC_FM_FREE>{q}, T, e);
+        else { hc_gs_round(HcLazy<>{q}, T, e); }
         if (MODE == 1) { // keep values bounded like the real pipeline does once per transform
             if ((it & 3) == 3) {
 #pragma unroll

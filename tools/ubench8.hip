@@ -22,7 +22,7 @@ __global__ __launch_bounds__(256) void k_valu_round(u64 *sink, u64 seed) {
     for (int i = 0; i < 16; i++) e[i] = (seed * (threadIdx.x + 1) + i * 0x9E3779B97F4A7C15ull) % Q0;
     // a wave holds 64 lanes x 16 residues = 1024 outputs per round: TILES_PER_WAVE tiles of 256 = TILES_PER_WAVE / 4 rounds
     for (int r = 0; r < TILES_PER_WAVE / 4; r++) {
-        hc_ct_round<HC_FM_FREE>(e, tw, Q);
+        hc_ct_round(HcLazy<HC_FM_FREE>{Q}, tw, e);
 #pragma unroll
         for (int i = 0; i < 16; i++) e[i] = hc_reduce64(e[i], 0x1ffffffffull, Q);     // keep the lazy range bounded as the real pass does between rounds (one reduction per round: generous)
         acc += e[r & 15];

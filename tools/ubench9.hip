@@ -78,7 +78,7 @@ __global__ __launch_bounds__(1024) void k_fwd1(const u64 *__restrict__ in, u64 *
                 e[hb + h] = X + hc_shoup4(Y, w2.w, w2.ws, Q);                    // ALT: < 8q; FREE: < 9q
             }
         }
-        hc_ct_round<FM>(e, U9Tw{psi, 4, qd}, Q);
+        hc_ct_round(HcLazy<FM>{Q}, U9Tw{psi, 4, qd}, e);
 #pragma unroll
         for (int h = 0; h < 16; h++) lds[h * 1024 + u9_p1(T)] = e[h];
     }
@@ -87,7 +87,7 @@ __global__ __launch_bounds__(1024) void k_fwd1(const u64 *__restrict__ in, u64 *
     u64 *__restrict__ row = lds + w * 1024;
 #pragma unroll
     for (int r = 0; r < 16; r++) e[r] = row[u9_p1((r << 6) | lane)];
-    hc_ct_round<FM>(e, U9Tw{psi, 64, qw}, Q);                                    // stages 7-10 (bits 9..6 in registers): wave-uniform twiddles
+    hc_ct_round(HcLazy<FM>{Q}, U9Tw{psi, 64, qw}, e);                                    // stages 7-10 (bits 9..6 in registers): wave-uniform twiddles
     HC_ROW_SYNC();
 #pragma unroll
     for (int r = 0; r < 16; r++) row[u9_p1((r << 6) | lane)] = e[r];
@@ -95,7 +95,7 @@ __global__ __launch_bounds__(1024) void k_fwd1(const u64 *__restrict__ in, u64 *
     const int u = lane >> 2, v = lane & 3;
 #pragma unroll
     for (int r = 0; r < 16; r++) e[r] = row[u9_p1((u << 6) | (r << 2) | v)];
-    hc_ct_round<FM>(e, U9Tw{psi, 1024, (qw << 4) | u}, Q);                       // stages 11-14 (bits 5..2 in registers)
+    hc_ct_round(HcLazy<FM>{Q}, U9Tw{psi, 1024, (qw << 4) | u}, e);                       // stages 11-14 (bits 5..2 in registers)
     HC_ROW_SYNC();
 #pragma unroll
     for (int r = 0; r < 16; r++) row[u9_p3((u << 6) | (r << 2) | v)] = e[r];
