@@ -47,7 +47,7 @@ typedef struct hc_ker hc_ker; /* device-resident kernel plaintexts pl_ker[0..max
 int hc_ctx_create(hc_ctx **out, int logN, const uint64_t *q, int nq, const uint64_t *p, int np, int device);
 void hc_ctx_destroy(hc_ctx *ctx);
 const char *hc_last_error(const hc_ctx *ctx); /* ctx may be NULL: error of the last failed hc_ctx_create */
-int hc_version(void);   /* 3: hc_prep_ker_ex (transposed kernels); 4: hc_prep_ker_ex2 (dilated, channel-strided kernels) */
+int hc_version(void);   /* 3: hc_prep_ker_ex (transposed kernels); 4: hc_prep_ker_ex2 (dilated, channel-strided kernels); 5: hc_encode_coeffs, hc_encrypt_sk, hc_decrypt_decode_coeffs */
 
 /* ---- device memory ---- */
 int hc_malloc(hc_ctx *ctx, size_t bytes, void **dptr);
@@ -91,8 +91,8 @@ int hc_permute(hc_ctx *ctx, uint64_t galEl, const uint64_t *in, uint64_t *out, i
  * hc_lv_mul_acc_plain, b0 of HC_LV_MUL_PLAIN / HC_LV_MUL_ACC_PLAIN (hc_lv_op2, hc_qp_op2), the plaintexts of hc_qp_mul_sum*, every constant vector - it is read once per launch;
  * switching keys likewise (one fetch of a key row serves all images and both key components). (Until round 5 hc_lv_mul always shared b and hc_lv_op2 inferred a plaintext
  * from b0 == b1: a per-image second operand gave wrong residues for images above 0 without an error.) Results are bit-identical to n separate calls.
- * n = 1 (default) restores single-ciphertext behaviour; the L0 one-row primitives above, hc_permute and the L1 convolution (which has its own
- * batch entry point) ignore the setting. A decomposition held by hc_keyswitch_decompose belongs to the batch it was taken under.
+ * n = 1 (default) restores single-ciphertext behaviour; the L0 one-row primitives above, hc_permute, the L1 convolution (which has its own
+ * batch entry point) and hc_encode_coeffs / hc_encrypt_sk / hc_decrypt_decode_coeffs (which carry their own `count`) ignore the setting. A decomposition held by hc_keyswitch_decompose belongs to the batch it was taken under.
  * The setting is context STATE (calls on one hc_ctx are serialised by the caller): a binding must hold it in a scope that restores n = 1 on every way out - INTEGRATION.md 3d
  * (`Batched` with a deferred reset), `Context.batch()` in abi.py, `Boot::Batch` in the C++ host. Under n > 1 every entry point checks the strides against the footprint of its
  * operands at the call's level - poly_stride >= (level+1) N, qp_stride >= 2 (level+1+np) N where it takes extended-basis pairs - and fails with HC_ERR_ARG otherwise (images
@@ -290,6 +290,22 @@ int hc_pack_ctxts_strided(hc_ctx *ctx, uint64_t *cts, int count, int stride_log2
  * Encode; level: rows 0..level (moduli 0..level) are produced; to_ntt != 0: the rows are left in the NTT domain. out: DEVICE
  * [count][level+1][N]. IEEE fp64 without contraction in the reference's operand order: the same residues as the CPU encoder. */
 int hc_encode_slots(hc_ctx *ctx, double *values, int count, int level, double scale, int to_ntt, uint64_t *out);
+/* ckks.Encoder.EncodeCoeffs (+ ToNTT), the coefficient-domain sibling of hc_encode_slots (hc_version() >= 5). values: DEVICE [count][nvals] doubles (not modified), nvals <= N
+ * (coefficients past nvals are 0); out: DEVICE [count][level+1][N]. scaleUpVecExact's rounding, uint64(|v| * scale + 0.5) mod q_l and q_l - . for negative v, in plain IEEE
+ * fp64: the same residues as the CPU encoder. HC_ERR_UNSUPPORTED if any |value * scale| > 2^64 or is not finite (the reference's big-float branch is not built; the context
+ * stays usable, out is unspecified). Under pack32 = 2 the rows of hc_row_is32 limbs are written as 4-byte words, as hc_encode_slots writes them. The call reads a one-word
+ * flag back from the device before it returns. */
+int hc_encode_coeffs(hc_ctx *ctx, const double *values, int count, int nvals, int level, double scale, int to_ntt, uint64_t *out);
+/* HARNESS ONLY (as hc_swk_generate; a Lattigo host encrypts and decrypts with its own keys): count sk-encryptions in one set of launches, level 0 or 1 (HC_ERR_UNSUPPORTED
+ * above). pt: DEVICE [count][level+1][N] coefficient-domain rows (hc_encode_coeffs / hc_encode_slots with to_ntt = 0); sk_ntt as in hc_swk_generate; ct_out: HOST array of
+ * count device pointers, each [2][level+1][N], NTT domain, canonical: c1 uniform in [0, q_l), c0 = NTT(e + m) - c1 s, e one integer polynomial per image under every limb
+ * (sigma 3.2, |e| <= 19: hc_swk_generate's sampler). Draws are ChaCha20 blocks keyed by seed8 and addressed by (stream_id < 2^40, image, limb, coefficient), in a domain
+ * no hc_swk_generate draw under the same seed shares: the same (seed8, stream_id) gives the same ciphertexts; a caller never reuses a stream_id under one seed. */
+int hc_encrypt_sk(hc_ctx *ctx, int count, int level, const uint64_t *pt, const uint64_t *sk_ntt, const uint32_t *seed8, uint64_t stream_id, uint64_t *const *ct_out);
+/* HARNESS ONLY: Decrypt + DecodeCoeffs of count ciphertexts (ct: HOST array of count device pointers, each [2][level+1][N]) at level 0 or 1 (HC_ERR_UNSUPPORTED above);
+ * out: DEVICE [count][N] doubles. Level 0: c0 + c1 s, inverse transform, centred in (-q/2, q/2], divided by scale. Level 1: the CRT over q0 q1, centred, the magnitude
+ * (up to 116 bits) rounded to the nearest double (ties to even), divided by scale: the doubles the host's (double)(unsigned __int128) / scale gives. */
+int hc_decrypt_decode_coeffs(hc_ctx *ctx, int count, int level, const uint64_t *const *ct, const uint64_t *sk_ntt, double scale, double *out);
 /* conv.go:167-172 in one launch: out[2][level+1][N] = sum over t < ntaps (<= 64) of ciphertext cts[t] ([2][level+1][N], device) x
  * plaintext pts[t] ([level+1][N], NTT domain, device [ntaps][level+1][N]); cts is a HOST array of device pointers. Exact modular
  * sums: the same residues as the reference's MulNew + Add chain. */
@@ -308,7 +324,8 @@ int hc_bl_post_ker_slots(hc_ctx *ctx, const double *max_ker_rs, int in_wid, int 
  *      level), the extended-basis pairs of hc_keyswitch_qp*, hc_mod_down2*, hc_qp_*, the plaintexts they multiply by, hc_encode_slots' output. hc_row_is32(ctx, mod) tells which
  *      limbs that concerns; a caller converts at its own boundary only (what it uploads into / downloads from such rows: the C++ host's Boot::put_rows / get_rows; ciphertexts
  *      enter and leave the chain at levels 0 / 1, whose limbs are large, so the hot path converts nothing). The L0 one-row primitives (hc_ntt ... hc_permute with an explicit
- *      modulus or row count), the level-0/1 convolution path and hc_swk_generate's secret-key rows keep 8-byte rows. Same residues, bit for bit, in every setting.
+ *      modulus or row count), the level-0/1 convolution path, hc_encrypt_sk / hc_decrypt_decode_coeffs (level 0 / 1 only) and hc_swk_generate's secret-key rows keep 8-byte rows;
+ *      hc_encode_coeffs' output follows hc_encode_slots'. Same residues, bit for bit, in every setting.
  *   0: off. Keys are stored per the setting in force when they are loaded: switch between 0 and 1 / 2 only on a context without keys (HC_ERR_STATE otherwise).
  * Setting 2 never applies to limbs 0 and 1 (the convolution's level-0 / 1 entry points and the secret-key rows read them as 8-byte rows whatever their size).
  * The library reads NO configuration from the environment (a cgo host would inherit its shell's): every switch is an hc_set_option; this repo's CLI translates

@@ -93,6 +93,9 @@ SYMBOLS = {
     "hc_conv_then_pack_sharded": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_void_p), C.c_double, C.POINTER(C.c_void_p), C.c_double, C.c_int,
                                             C.c_double, C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]),
     "hc_encode_slots": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_int, C.c_void_p]),
+    "hc_encode_coeffs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_void_p]),
+    "hc_encrypt_sk": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32), C.c_uint64, C.POINTER(C.c_void_p)]),
+    "hc_decrypt_decode_coeffs": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.c_void_p, C.c_double, C.c_void_p]),
     "hc_bl_post_ker_slots": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "hc_lv_mul_sum": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.c_void_p, C.c_int, C.c_void_p]),
     "hc_device_count": (C.c_int, [C.POINTER(C.c_int)]),
@@ -559,6 +562,54 @@ class Context:
         res = out.download((count, level + 1, self.N))
         dv.free(); out.free()
         return res
+
+    def encode_coeffs(self, values, level, scale, to_ntt=True):
+        """hc_encode_coeffs: values float64 [count][nvals] (host; one vector if 1-D) -> uint64 [count][level+1][N]; under pack32 = 2 the 4-byte rows come back as 8-byte words"""
+        v = np.asarray(values, dtype=np.float64)
+        v = np.ascontiguousarray(v.reshape(1, -1) if v.ndim == 1 else v)
+        count, nvals = v.shape
+        dv = self.buf(nwords=max(1, v.size))
+        if v.size:
+            dv.upload(v.reshape(-1).view(np.uint64))
+        out = self.buf(nwords=count * (level + 1) * self.N)
+        try:
+            self._ck(self.L.hc_encode_coeffs(self.h, dv.ptr, count, nvals, level, scale, 1 if to_ntt else 0, out.ptr))
+            return self.unpack_rows(out.download((count, level + 1, self.N)), level + 1)
+        finally:
+            dv.free(); out.free()
+
+    def sk_rows(self, sk):
+        """NTT(s) modulo every modulus of the context, [nq + np][N]: the sk_ntt operand of hc_swk_generate / hc_encrypt_sk / hc_decrypt_decode_coeffs (sk: signed int64 [N])"""
+        sk = np.ascontiguousarray(sk, dtype=np.int64)
+        mods = self.q + self.p
+        return np.stack([self.ntt(m, np.where(sk >= 0, sk, sk + mods[m]).astype(np.uint64)).reshape(-1) for m in range(len(mods))])
+
+    def encrypt_sk(self, pt, level, sk_ntt, seed8, stream_id):
+        """hc_encrypt_sk (harness only): pt uint64 [count][level+1][N] coefficient-domain rows -> ciphertexts uint64 [count][2][level+1][N]"""
+        pt = np.ascontiguousarray(pt, dtype=np.uint64).reshape(-1, level + 1, self.N)
+        count = pt.shape[0]
+        dp, ds = self.buf(pt), self.buf(sk_ntt)
+        cts = [self.buf(nwords=2 * (level + 1) * self.N) for _ in range(count)]
+        try:
+            self._ck(self.L.hc_encrypt_sk(self.h, count, level, dp.ptr, ds.ptr, (C.c_uint32 * 8)(*[int(x) for x in seed8]), C.c_uint64(int(stream_id)),
+                                          (C.c_void_p * count)(*[b.ptr for b in cts])))
+            return np.stack([b.download((2, level + 1, self.N)) for b in cts])
+        finally:
+            for b in [dp, ds] + cts:
+                b.free()
+
+    def decrypt_decode_coeffs(self, cts, level, sk_ntt, scale):
+        """hc_decrypt_decode_coeffs (harness only): cts uint64 [count][2][level+1][N] -> float64 [count][N]"""
+        cts = np.ascontiguousarray(cts, dtype=np.uint64).reshape(-1, 2, level + 1, self.N)
+        count = cts.shape[0]
+        bufs = [self.buf(ct) for ct in cts]
+        ds, out = self.buf(sk_ntt), self.buf(nwords=count * self.N)
+        try:
+            self._ck(self.L.hc_decrypt_decode_coeffs(self.h, count, level, (C.c_void_p * count)(*[b.ptr for b in bufs]), ds.ptr, scale, out.ptr))
+            return out.download((count, self.N)).view(np.float64)
+        finally:
+            for b in bufs + [ds, out]:
+                b.free()
 
     @staticmethod
     def conv_then_pack_sharded_dev(ctxs, ct_in_bufs, ct_scale, kers, ker_scale, max_ob, out_scale, bias_buf, out_buf):

@@ -2692,6 +2692,13 @@ __device__ __forceinline__ void hc_chacha_block(const u32 (&key)[8], u32 c0, u32
     out[0] = x0 | ((u64)x1 << 32); out[1] = x2 | ((u64)x3 << 32); out[2] = x4 | ((u64)x5 << 32); out[3] = x6 | ((u64)x7 << 32);
     out[4] = x8 | ((u64)x9 << 32); out[5] = x10 | ((u64)x11 << 32); out[6] = x12 | ((u64)x13 << 32); out[7] = x14 | ((u64)x15 << 32);
 }
+// the error sampler: one discrete Gaussian draw (sigma 3.2, 0 beyond 6 sigma, so |e| <= 19) from the first two words of a block, Box-Muller on two 53-bit uniforms
+__device__ __forceinline__ long hc_gauss_e(const u64 (&w)[8]) {
+    const double u1 = ((double)(w[0] >> 11) + 1.0) / 9007199254740993.0, u2 = (double)(w[1] >> 11) / 9007199254740992.0;
+    double g = sqrt(-2.0 * log(u1)) * 3.2 * cos(6.283185307179586 * u2);
+    if (fabs(g) > 19.2) g = 0;
+    return (long)llrint(g);
+}
 // rows: [beta][2][nt][N]; writes a (component 1, final values before the Montgomery factor) and e mod q_T (component 0, coefficient domain). grid = (64, nt, beta)
 __global__ __launch_bounds__(HC_TPB) void hc_k_swk_sample(u64 *rows, const HcMod *mods, HcKeyGen G) {
     const int T = blockIdx.y, d = blockIdx.z; const u64 q = mods[T < G.nl ? T : G.nq + (T - G.nl)].q;
@@ -2715,10 +2722,7 @@ __global__ __launch_bounds__(HC_TPB) void hc_k_swk_sample(u64 *rows, const HcMod
         a_row[j] = a;
         // the digit's error polynomial: the same stream for every limb T (tag 0xE0 in the nonce instead of the limb)
         hc_chacha_block(G.key, j, 0, G.id_lo, G.id_hi ^ ((u32)(d * 64 + 63) << 8) ^ 0xE0000000u, w);
-        const double u1 = ((double)(w[0] >> 11) + 1.0) / 9007199254740993.0, u2 = (double)(w[1] >> 11) / 9007199254740992.0;
-        double g = sqrt(-2.0 * log(u1)) * 3.2 * cos(6.283185307179586 * u2);
-        if (fabs(g) > 19.2) g = 0;
-        const long e = (long)llrint(g);
+        const long e = hc_gauss_e(w);
         b_row[j] = e >= 0 ? (u64)e : q - (u64)(-e);
     }
 }
@@ -2846,5 +2850,96 @@ __global__ __launch_bounds__(HC_TPB) void hc_k_lv_mul_sum(HcTapPtrs cts, const u
             acc = hc_addmod(acc, hc_mont(cts.ct[t][row + i], y, m.q, m.qinv), m.q);
         }
         out[row + i] = acc;
+    }
+}
+
+// ================================================================ coefficient encoder (ckks.Encoder.EncodeCoeffs), harness sk-encryptor and decryptor + DecodeCoeffs
+// hc_encode_coeffs: scaleUpVecExact on its |v * scale| < 2^64 branch, one thread per coefficient and all limbs of the level from it:
+//     neg = v < 0 ;  x = neg ? -scale * v : scale * v  (plain fp64, no contraction) ;  xi = uint64(x + 0.5) ;  word = neg ? q_l - (xi mod q_l) : xi mod q_l
+// (q_l itself for a negative value that rounds to 0, as upstream leaves it: the transform canonicalises it). Coefficients past nvals are 0. A value beyond 2^64, a NaN or
+// an infinity raises *flag (the reference's big-float branch is not built: the call fails). values: [count][nvals]; out: [count][nl][N]. grid = (64, count)
+__global__ __launch_bounds__(HC_TPB) void hc_k_coeffs_round(const double *values, u64 *out, const HcMod *mods, int nl, int nvals, double scale, u32 *flag) {
+#pragma clang fp contract(off)
+    const double *v = values + (size_t)blockIdx.y * nvals; u64 *o = out + (size_t)blockIdx.y * nl * 65536;
+    for (int i = blockIdx.x * HC_TPB + threadIdx.x; i < 65536; i += gridDim.x * HC_TPB) {
+        const double val = i < nvals ? v[i] : 0.0;
+        const bool neg = val < 0; const double x = neg ? -scale * val : scale * val;
+        const bool bad = !(x <= 1.8446744073709552e+19);                     // above 2^64, NaN or infinite
+        if (bad) *flag = 1;
+        const u64 xi = bad ? 0 : (u64)(x + 0.5);
+        for (int l = 0; l < nl; l++) {
+            const u64 q = mods[l].q, r = xi % q, vv = neg ? q - r : r;
+            if (mods[l].row32) hc_st32(o + (size_t)l * 65536, (size_t)i, vv); else o[(size_t)l * 65536 + i] = vv;
+        }
+    }
+}
+// hc_encrypt_sk: rlwe's sk-encryption for the C++ harness, count images and all limbs per launch: c1 uniform mod q_l, c0 = NTT(e + m) - c1 s, e ONE integer polynomial
+// per image (hc_gauss_e) under every limb. Draws are ChaCha20 blocks addressed by (stream id | image, limb or error tag, coefficient, attempt); bit 28 of the last nonce
+// word (HC_ENC_DOMAIN) is set in every encryption draw and in no switching-key draw (hc_k_swk_sample uses bits 0..19 and 29..31 there), so that no block of one
+// coincides with a block of the other under the same seed. Level 0 / 1 only: limbs 0 and 1 are 8-byte rows under every pack32.
+#define HC_ENC_DOMAIN 0x10000000u
+#define HC_MAXCTS 64
+struct HcCtPtrs { u64 *p[HC_MAXCTS]; };
+struct HcEnc { u32 key[8]; u32 id_lo, id_hi; int nl, z0; };                 // z0: number of the first image of this launch within the call
+// t = e + m, coefficient domain. pt, t: [images][nl][N]. grid = (64, images)
+__global__ __launch_bounds__(HC_TPB) void hc_k_enc_sample(const u64 *pt, u64 *t, const HcMod *mods, HcEnc E) {
+    const size_t base = (size_t)blockIdx.y * E.nl * 65536; const u32 img = (u32)(E.z0 + blockIdx.y) << 16;
+    for (u32 j = blockIdx.x * HC_TPB + threadIdx.x; j < 65536; j += gridDim.x * HC_TPB) {
+        u64 w[8];
+        hc_chacha_block(E.key, img | j, 0, E.id_lo, E.id_hi ^ (63u << 8) ^ 0xE0000000u ^ HC_ENC_DOMAIN, w);
+        const long e = hc_gauss_e(w);
+        for (int l = 0; l < E.nl; l++) {
+            const u64 q = mods[l].q;
+            t[base + (size_t)l * 65536 + j] = hc_addmod(e >= 0 ? (u64)e : q - (u64)(-e), pt[base + (size_t)l * 65536 + j] % q, q);
+        }
+    }
+}
+// after the transform of t: c1 by rejection on ceil(log2 q) bits (the key generator's rule), c0 = t - c1 s. out.p[z]: [2][nl][N]; sk_ntt: [nq + np][N]. grid = (64, nl, images)
+__global__ __launch_bounds__(HC_TPB) void hc_k_enc_finish(const u64 *t, const u64 *sk_ntt, HcCtPtrs out, const HcMod *mods, HcEnc E) {
+    const int l = blockIdx.y, z = blockIdx.z; const HcMod m = mods[l]; const u32 img = (u32)(E.z0 + z) << 16;
+    const u64 *tr = t + ((size_t)z * E.nl + l) * 65536, *s = sk_ntt + (size_t)l * 65536;
+    u64 *c0 = out.p[z] + (size_t)l * 65536, *c1 = out.p[z] + (size_t)(E.nl + l) * 65536;
+    const int bits = 64 - __builtin_clzll(m.q); const u64 mask = bits >= 64 ? ~0ull : ((1ull << bits) - 1);
+    for (u32 j = blockIdx.x * HC_TPB + threadIdx.x; j < 65536; j += gridDim.x * HC_TPB) {
+        u64 w[8]; u64 a = 0; bool found = false;
+        for (u32 attempt = 0; !found; attempt++) {                           // each word is accepted with probability q / 2^bits > 1/2
+            hc_chacha_block(E.key, img | j, attempt, E.id_lo, E.id_hi ^ ((u32)l << 8) ^ HC_ENC_DOMAIN, w);
+#pragma unroll
+            for (int k = 0; k < 8; k++) if (!found && (w[k] & mask) < m.q) { a = w[k] & mask; found = true; }
+        }
+        c1[j] = a;
+        c0[j] = hc_submod(tr[j], hc_mont(hc_mont(a, m.r2, m.q, m.qinv), s[j], m.q, m.qinv), m.q);
+    }
+}
+// hc_decrypt_decode_coeffs, first half: t = c0 + c1 s. ct.p[z]: [2][nl][N]; t: [images][nl][N]. grid = (64, nl, images)
+__global__ __launch_bounds__(HC_TPB) void hc_k_dec_combine(HcCtPtrs ct, const u64 *sk_ntt, u64 *t, const HcMod *mods, int nl) {
+    const int l = blockIdx.y, z = blockIdx.z; const HcMod m = mods[l];
+    const u64 *c0 = ct.p[z] + (size_t)l * 65536, *c1 = ct.p[z] + (size_t)(nl + l) * 65536, *s = sk_ntt + (size_t)l * 65536;
+    u64 *tr = t + ((size_t)z * nl + l) * 65536;
+    for (u32 j = blockIdx.x * HC_TPB + threadIdx.x; j < 65536; j += gridDim.x * HC_TPB)
+        tr[j] = hc_addmod(c0[j], hc_mont(hc_mont(c1[j], m.r2, m.q, m.qinv), s[j], m.q, m.qinv), m.q);
+}
+// a magnitude below 2^128 as the nearest double, ties to even: the top 64 bits with everything below them folded into bit 0 (a sticky bit: the 53-bit rounding of the
+// 64-bit word sees eleven bits below its last place, so a set bit 0 can only break a false tie), one correctly rounded 64-bit conversion, an exact power of two
+__device__ __forceinline__ double hc_u128_to_f64(u128 x) {
+    const u64 hi = (u64)(x >> 64), lo = (u64)x;
+    if (!hi) return (double)lo;
+    const int sh = 64 - __builtin_clzll(hi);                                 // 1 .. 64: x >> sh has its leading one at bit 63
+    const u64 top = sh == 64 ? hi : ((hi << (64 - sh)) | (lo >> sh)), rest = sh == 64 ? lo : (lo << (64 - sh));
+    return ldexp((double)(top | (rest ? 1ull : 0ull)), sh);
+}
+// second half, after the inverse transform: DecodeCoeffs. One limb: centre in (-q/2, q/2], / scale. Two limbs: CRT over q0 q1 (x = a0 + q0 ((a1 - a0) q0^-1 mod q1)), centre
+// in (-q0 q1 / 2, q0 q1 / 2], the magnitude (up to 116 bits) to the nearest double, / scale. q0inv_m: q0^-1 mod q1 in Montgomery form. t: [images][nl][N]; out: [images][N]. grid = (64, images)
+__global__ __launch_bounds__(HC_TPB) void hc_k_dec_decode(const u64 *t, double *out, const HcMod *mods, int nl, double scale, u64 q0inv_m) {
+#pragma clang fp contract(off)
+    const u64 *a = t + (size_t)blockIdx.y * nl * 65536; double *o = out + (size_t)blockIdx.y * 65536;
+    const u64 q0 = mods[0].q;
+    for (u32 j = blockIdx.x * HC_TPB + threadIdx.x; j < 65536; j += gridDim.x * HC_TPB) {
+        const u64 a0 = a[j];
+        if (nl == 1) { o[j] = a0 > q0 / 2 ? -(double)(q0 - a0) / scale : (double)a0 / scale; continue; }
+        const HcMod m1 = mods[1]; const u64 q1 = m1.q;
+        const u64 d = hc_submod(a[65536 + j] % q1, a0 % q1, q1);
+        const u128 QQ = (u128)q0 * q1, x = (u128)a0 + (u128)q0 * hc_mont(d, q0inv_m, q1, m1.qinv);
+        o[j] = x > (QQ >> 1) ? -hc_u128_to_f64(QQ - x) / scale : hc_u128_to_f64(x) / scale;
     }
 }

@@ -139,6 +139,7 @@ struct hc_ctx {
     long chunk_nodes = 64;
     hipEvent_t ev_fork = nullptr;
     HcCplx *enc_roots = nullptr; int *enc_rot_group = nullptr;      // slot encoder tables (hc_encode_slots), built at first use
+    u32 *d_flag = nullptr;                                          // hc_encode_coeffs: the word its kernel raises for a value it refuses
     hipEvent_t ev_shard = nullptr;     // hc_conv_then_pack_sharded: this device's partial ciphertext is complete / has been collected
     u64 *ws_gather = nullptr; size_t ws_gather_rows = 0;
     long small_levels = 16;               // pack-tree launches of at most this many nodes (summed over the batch) run on the 1024-thread S kernels; 0 = never
@@ -324,7 +325,7 @@ static int hc_build_tables(hc_ctx *c, HcModHost *mh, bool inverse) {
     return HC_OK;
 }
 
-extern "C" int hc_version(void) { return 4; }      // 2: a plaintext shared by the images of a batch is said by the operation (HC_LV_MUL_PLAIN), never inferred from b0 == b1; 3: hc_prep_ker_ex (transposed kernels); 4: hc_prep_ker_ex2 (dilated, channel-strided kernels)
+extern "C" int hc_version(void) { return 5; }      // 2: a plaintext shared by the images of a batch is said by the operation (HC_LV_MUL_PLAIN), never inferred from b0 == b1; 3: hc_prep_ker_ex (transposed kernels); 4: hc_prep_ker_ex2 (dilated, channel-strided kernels); 5: hc_encode_coeffs, hc_encrypt_sk, hc_decrypt_decode_coeffs
 extern "C" const char *hc_last_error(const hc_ctx *c) { return c ? c->err.c_str() : g_create_err.c_str(); }
 
 // the per-modulus table of the batched transforms (HcRowMod); again after option small32 changes
@@ -399,7 +400,7 @@ extern "C" void hc_ctx_destroy(hc_ctx *c) {
     F(c->idx_pairs); F(c->ws_cts); F(c->ws_cts2); F(c->ws_gather);
     if (c->ev_fork) D(hipEventDestroy(c->ev_fork), "hipEventDestroy");
     if (c->ev_shard) D(hipEventDestroy(c->ev_shard), "hipEventDestroy");
-    F(c->enc_roots); F(c->enc_rot_group);
+    F(c->enc_roots); F(c->enc_rot_group); F(c->d_flag);
     F(c->ws_ctc); F(c->ws_tmp); F(c->d_mods); F(c->d_rowmods); F(c->ws_mm); F(c->ws_accm);
     for (auto &kv : c->ks_plan) { F(kv.second.bx); F(kv.second.bxdown); F(kv.second.pinv); F(kv.second.pmod); F(kv.second.pinv_qlinv); }
     for (auto &kv : c->rescale_plan) F(kv.second);
@@ -1867,6 +1868,70 @@ extern "C" int hc_encode_slots(hc_ctx *c, double *values, int count, int level, 
     HC_TRY(hc_launch(c, "sfft_inv_b", hc_k_sfft_inv_b, dim3(16, (unsigned)count), (const HcCplx *)v, v, E));
     HC_TRY(hc_launch(c, "slots_round", hc_k_slots_round, dim3(64, (unsigned)count), (const HcCplx *)v, (u64 *)out, (const HcMod *)c->d_mods, level + 1, scale));
     if (to_ntt) { c->hoist_cx = nullptr; HC_TRY(hc_ntt_mm(c, (const u64 *)out, (u64 *)out, level + 1, level + 1, 0, 0, count, (size_t)(level + 1) * HC_N, (size_t)(level + 1) * HC_N)); }
+    return HC_OK;
+}
+// ckks.Encoder.EncodeCoeffs (+ ToNTT): one launch rounds every coefficient into all limbs of the level, the batched forward transform follows. The one-word flag the kernel
+// raises for a value scaleUpVecExact would hand to its big-float branch is read back before the call returns (the only host synchronisation of the call)
+extern "C" int hc_encode_coeffs(hc_ctx *c, const double *values, int count, int nvals, int level, double scale, int to_ntt, uint64_t *out) {
+    HC_ENTER(c);
+    if (!out || count < 1 || count > 65535 || nvals < 0 || nvals > HC_N || (!values && nvals) || level < 0 || level >= c->nq)
+        return hc_fail(c, HC_ERR_ARG, "hc_encode_coeffs: bad arguments (count >= 1, 0 <= nvals <= N, 0 <= level < %d, non-null pointers)", c->nq);
+    if (!c->d_flag) HC_HIP(c, hcx_malloc(c, (void **)&c->d_flag, sizeof(u32)));
+    HC_HIP(c, hipMemsetAsync(c->d_flag, 0, sizeof(u32), c->stream));
+    HC_TRY(hc_launch(c, "coeffs_round", hc_k_coeffs_round, dim3(64, (unsigned)count), values, (u64 *)out, (const HcMod *)c->d_mods, level + 1, nvals, scale, c->d_flag));
+    u32 flag = 0;
+    HC_HIP(c, hipMemcpyAsync(&flag, c->d_flag, sizeof flag, hipMemcpyDeviceToHost, c->stream));
+    HC_HIP(c, hipStreamSynchronize(c->stream));
+    if (flag) return hc_fail(c, HC_ERR_UNSUPPORTED, "hc_encode_coeffs: a value times the scale exceeds 2^64 or is not finite (scaleUpVecExact's big-float branch is not built)");
+    if (to_ntt) { c->hoist_cx = nullptr; HC_TRY(hc_ntt_mm(c, (const u64 *)out, (u64 *)out, level + 1, level + 1, 0, 0, count, (size_t)(level + 1) * HC_N, (size_t)(level + 1) * HC_N)); }
+    return HC_OK;
+}
+// Harness-side sk-encryption (include/hconv.h): per chunk of at most HC_MAXCTS images one launch forms e + m for all limbs, one batched transform takes it to the NTT
+// domain, one launch draws c1 and writes c0 = NTT(e + m) - c1 s into the callers' ciphertexts
+extern "C" int hc_encrypt_sk(hc_ctx *c, int count, int level, const uint64_t *pt, const uint64_t *sk_ntt, const uint32_t *seed8, uint64_t stream_id, uint64_t *const *ct_out) {
+    HC_ENTER(c);
+    if (!pt || !sk_ntt || !seed8 || !ct_out || count < 1 || count > 65535 || level < 0 || level >= c->nq) return hc_fail(c, HC_ERR_ARG, "hc_encrypt_sk: bad arguments (1 <= count <= 65535, 0 <= level < %d, non-null pointers)", c->nq);
+    if (level > 1) return hc_fail(c, HC_ERR_UNSUPPORTED, "hc_encrypt_sk: level 0 or 1 only (ciphertexts enter at the levels whose rows are 8-byte words)");
+    if (stream_id >> 40) return hc_fail(c, HC_ERR_ARG, "hc_encrypt_sk: stream id %llu does not fit the 40 bits of the ChaCha nonce that tell calls apart", (unsigned long long)stream_id);
+    for (int z = 0; z < count; z++) if (!ct_out[z]) return hc_fail(c, HC_ERR_ARG, "hc_encrypt_sk: null ciphertext %d", z);
+    const int nl = level + 1;
+    HcEnc E; memset(&E, 0, sizeof E); memcpy(E.key, seed8, sizeof E.key); E.id_lo = (u32)stream_id; E.id_hi = (u32)(stream_id >> 32) & 0xFFu; E.nl = nl;
+    HcScratch S(c);
+    const int chunk = count < HC_MAXCTS ? count : HC_MAXCTS;
+    u64 *t = nullptr; HC_HIP(c, S.alloc(&t, (size_t)chunk * nl * HC_N * sizeof(u64)));
+    HcMmFuse Fraw; Fraw.raw = true;                                          // limbs 0 and 1: 8-byte rows under every pack32
+    c->hoist_cx = nullptr;
+    for (int z0 = 0; z0 < count; z0 += chunk) {
+        const int n = count - z0 < chunk ? count - z0 : chunk;
+        HcCtPtrs O; memset(&O, 0, sizeof O); for (int z = 0; z < n; z++) O.p[z] = (u64 *)ct_out[z0 + z];
+        E.z0 = z0;
+        HC_TRY(hc_launch(c, "enc_sample", hc_k_enc_sample, dim3(64, (unsigned)n), (const u64 *)pt + (size_t)z0 * nl * HC_N, t, (const HcMod *)c->d_mods, E));
+        HC_TRY(hc_ntt_mm(c, t, t, nl, nl, 0, 0, n, (size_t)nl * HC_N, (size_t)nl * HC_N, 0, 1, 0, 0, "ntt", &Fraw));
+        HC_TRY(hc_launch(c, "enc_finish", hc_k_enc_finish, dim3(64, (unsigned)nl, (unsigned)n), (const u64 *)t, (const u64 *)sk_ntt, O, (const HcMod *)c->d_mods, E));
+    }
+    return HC_OK;
+}
+// Harness-side Decrypt + DecodeCoeffs at level 0 or 1: t = c0 + c1 s for all images and limbs, one batched inverse transform, one launch centres (after the CRT at level 1),
+// converts and divides by the scale
+extern "C" int hc_decrypt_decode_coeffs(hc_ctx *c, int count, int level, const uint64_t *const *ct, const uint64_t *sk_ntt, double scale, double *out) {
+    HC_ENTER(c);
+    if (!ct || !sk_ntt || !out || count < 1 || count > 65535 || level < 0 || level >= c->nq) return hc_fail(c, HC_ERR_ARG, "hc_decrypt_decode_coeffs: bad arguments (1 <= count <= 65535, 0 <= level < %d, non-null pointers)", c->nq);
+    if (level > 1) return hc_fail(c, HC_ERR_UNSUPPORTED, "hc_decrypt_decode_coeffs: level 0 or 1 only (DecodeCoeffs above level 1 is not built)");
+    for (int z = 0; z < count; z++) if (!ct[z]) return hc_fail(c, HC_ERR_ARG, "hc_decrypt_decode_coeffs: null ciphertext %d", z);
+    const int nl = level + 1;
+    u64 q0inv_m = 0;
+    if (level == 1) { const u64 q0 = c->mods[0].m.q, q1 = c->mods[1].m.q; q0inv_m = (u64)((((u128)h_inv(q0 % q1, q1)) << 64) % q1); }
+    HcScratch S(c);
+    const int chunk = count < HC_MAXCTS ? count : HC_MAXCTS;
+    u64 *t = nullptr; HC_HIP(c, S.alloc(&t, (size_t)chunk * nl * HC_N * sizeof(u64)));
+    c->hoist_cx = nullptr;
+    for (int z0 = 0; z0 < count; z0 += chunk) {
+        const int n = count - z0 < chunk ? count - z0 : chunk;
+        HcCtPtrs I; memset(&I, 0, sizeof I); for (int z = 0; z < n; z++) I.p[z] = (u64 *)ct[z0 + z];
+        HC_TRY(hc_launch(c, "dec_combine", hc_k_dec_combine, dim3(64, (unsigned)nl, (unsigned)n), I, (const u64 *)sk_ntt, t, (const HcMod *)c->d_mods, nl));
+        HC_TRY(hc_intt_mm(c, t, t, nl, nl, n, (size_t)nl * HC_N, (size_t)nl * HC_N));
+        HC_TRY(hc_launch(c, "dec_decode", hc_k_dec_decode, dim3(64, (unsigned)n), (const u64 *)t, out + (size_t)z0 * HC_N, (const HcMod *)c->d_mods, nl, scale, q0inv_m));
+    }
     return HC_OK;
 }
 // out[2][level+1][N] = sum over t < ntaps of cts[t] (ciphertext [2][level+1][N]) x pts[t] (plaintext [level+1][N], NTT domain): the

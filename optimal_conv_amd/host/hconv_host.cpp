@@ -195,6 +195,12 @@ Context *newContext(int logN, int ker_wid, const std::vector<int> &in_wids, cons
     if (resnetReplaySeed()) c->sk = replay::gen_sk(resnetReplaySeed(), 192);       // the oracle network's key: Ckks(seed).sk = or_gen_sk(seed, 192)
     else { auto &g = rng(c); int placed = 0; while (placed < 192) { uint64_t r = g(); int pos = (int)(r % N); if (!c->sk[pos]) { c->sk[pos] = (r >> 40) & 1 ? 1 : -1; placed++; } } }
     for (int m = 0; m < 3; m++) c->sk_ntt[m] = gpu_ntt(c, m, signed_row(c->sk, MODQ[m]));
+    if (deviceEncrypt()) {      // the secret key on the device once, and the key of the encryptor's draws (the host stream is left as it is when the device path is off)
+        c->d_sk = dev_rows(c, 3);
+        for (int m = 0; m < 3; m++) HC(c->hc, hc_upload(c->hc, c->d_sk + (size_t)m * N, c->sk_ntt[m].data(), (size_t)N * 8));
+        for (uint32_t &w : c->enc_seed8) w = (uint32_t)rng(c)();
+        printf("Encryption and decryption on the device (hc_encrypt_sk / hc_decrypt_decode_coeffs)\n");
+    }
     printf("Num Rotations:  %d\n", c->num_rotations);                                                  // main.go:412
     // gen_idxNlogs (conv.go:241-261): idx[i] = NTT(X^(2^i)) on the device; Galois keys for 2^(i+1)+1, i < logN
     for (hc_ctx *h : c->shards) HC(h, hc_idx_load(h, nullptr));
@@ -304,7 +310,51 @@ std::vector<uint64_t> EncodeCoeffs(const std::vector<double> &coeffs, int level,
     }
     return out;
 }
+bool deviceEncrypt() {
+    static const bool v = [] {
+        bool replay = resnetReplaySeed() != 0;
+        for (const char *n : {"HCONV_CHAIN_REPLAY", "HCONV_CHAIN_REPLAY_BL"}) if (testOnlyEnv(n)) replay = true;
+        if (replay) return false;                                             // every committed digest depends on the oracle harness' host draws
+        if (const char *e = getenv("HCONV_DEVICE_ENCRYPT")) return atoi(e) != 0;
+        return false;                                                         // unset: the host path, until the device path is measured against it (profiles/LEDGER.md)
+    }();
+    return v;
+}
+std::vector<Ciphertext> EncryptCoeffsBatch(Context *c, const std::vector<const std::vector<double> *> &inputs, int level, double scale) {
+    std::vector<Ciphertext> out; const int n = (int)inputs.size();
+    if (!deviceEncrypt()) { for (const auto *in : inputs) out.push_back(EncryptNew(c, EncodeCoeffs(*in, level, scale), level, scale)); return out; }
+    size_t nvals = 0; for (const auto *in : inputs) nvals = std::max(nvals, in->size());
+    if ((int)nvals > N) panic("cannot EncodeCoeffs: too many coefficients");
+    std::vector<double> vals((size_t)n * nvals, 0.0);
+    for (int z = 0; z < n; z++) std::copy(inputs[(size_t)z]->begin(), inputs[(size_t)z]->end(), vals.begin() + (size_t)z * nvals);
+    void *dv = nullptr; HC(c->hc, hc_malloc(c->hc, std::max<size_t>(8, vals.size() * 8), &dv));
+    HC(c->hc, hc_upload(c->hc, dv, vals.data(), vals.size() * 8));
+    uint64_t *pt = dev_rows(c, (size_t)n * (level + 1));
+    HC(c->hc, hc_encode_coeffs(c->hc, (const double *)dv, n, (int)nvals, level, scale, 0, pt));       // HC_ERR_UNSUPPORTED where EncodeCoeffs panics (|value * scale| beyond 2^64)
+    std::vector<uint64_t *> ptrs;
+    for (int z = 0; z < n; z++) { Ciphertext r; r.d = dev_rows(c, (size_t)2 * (level + 1)); r.level = level; r.Scale = scale; out.push_back(r); ptrs.push_back(r.d); }
+    HC(c->hc, hc_encrypt_sk(c->hc, n, level, pt, c->d_sk, c->enc_seed8, c->enc_stream++, ptrs.data()));
+    HC(c->hc, hc_free(c->hc, dv)); HC(c->hc, hc_free(c->hc, pt));
+    return out;
+}
+std::vector<std::vector<double>> DecryptDecodeCoeffsBatch(Context *c, const std::vector<Ciphertext> &cts) {
+    std::vector<std::vector<double>> out; const int n = (int)cts.size();
+    if (!deviceEncrypt()) { for (const Ciphertext &ct : cts) out.push_back(DecryptDecodeCoeffs(c, ct)); return out; }
+    std::vector<const uint64_t *> ptrs;
+    for (const Ciphertext &ct : cts) { if (ct.level != 0 || ct.Scale != cts[0].Scale) panic("DecryptDecodeCoeffs: level 0 and one scale expected on the conv path"); ptrs.push_back(ct.d); }
+    void *dv = nullptr; HC(c->hc, hc_malloc(c->hc, (size_t)n * N * 8, &dv));
+    HC(c->hc, hc_decrypt_decode_coeffs(c->hc, n, 0, ptrs.data(), c->d_sk, cts[0].Scale, (double *)dv));
+    std::vector<double> all((size_t)n * N); HC(c->hc, hc_download(c->hc, all.data(), dv, all.size() * 8)); HC(c->hc, hc_free(c->hc, dv));
+    for (int z = 0; z < n; z++) out.emplace_back(all.begin() + (size_t)z * N, all.begin() + (size_t)(z + 1) * N);
+    return out;
+}
 Ciphertext EncryptNew(Context *c, const std::vector<uint64_t> &pt_rows, int level, double scale) {    // sk-encryption: c0 = -c1*s + e + m
+    if (deviceEncrypt()) {                                                    // the same plaintext rows through hc_encrypt_sk (one image)
+        uint64_t *pt = dev_upload(c, pt_rows); Ciphertext r; r.d = dev_rows(c, (size_t)2 * (level + 1)); r.level = level; r.Scale = scale;
+        HC(c->hc, hc_encrypt_sk(c->hc, 1, level, pt, c->d_sk, c->enc_seed8, c->enc_stream++, &r.d));
+        HC(c->hc, hc_free(c->hc, pt));
+        return r;
+    }
     const uint64_t rs = resnetReplaySeed() ? 5 + 1000 * c->replay_encryptions++ : 0;          // replay: or_encrypt(seed 5) for the first image, as resnet_layer_digests encrypts it
     std::vector<int64_t> e; if (rs) replay::gauss(rs ^ 0xABCDEFull, e); else e = gaussian(c);
     std::vector<uint64_t> ct((size_t)2 * (level + 1) * N);
@@ -324,6 +374,7 @@ Ciphertext EncryptNew(Context *c, const std::vector<uint64_t> &pt_rows, int leve
 }
 std::vector<double> DecryptDecodeCoeffs(Context *c, const Ciphertext &ct) {       // Decrypt + DecodeCoeffs at level 0 (test.go:59-60)
     if (ct.level != 0) panic("DecryptDecodeCoeffs: level 0 expected on the conv path");
+    if (deviceEncrypt()) return DecryptDecodeCoeffsBatch(c, {ct})[0];
     std::vector<uint64_t> h = dev_download(c, ct.d, 2), m(N);
     const uint64_t q = MODQ[0];
     for (int j = 0; j < N; j++) m[(size_t)j] = addmod(h[(size_t)j], mulmod(h[(size_t)N + (size_t)j], c->sk_ntt[0][(size_t)j], q), q);
@@ -614,15 +665,16 @@ void testConv_in(int in_batch, int in_wid, int ker_wid, int total_test_num, bool
         std::vector<double> bn_b = readTxt(pre + "bnb" + suf, raw_out_batch);
         std::vector<double> input = prep_Input(raw_input, raw_in_wid, in_wid, cont->Nn, norm, trans, false);
         auto start = now();
-        Ciphertext ctxt_input = EncryptNew(cont, EncodeCoeffs(input, cont->ECD_LV, cont->scale), cont->ECD_LV, cont->scale);
+        // HCONV_IMAGE_BATCH = n > 1 with the bootstrapping chain: the n encryptions are ONE call on the device path
+        std::vector<Ciphertext> enc = EncryptCoeffsBatch(cont, std::vector<const std::vector<double> *>((size_t)(boot ? imageBatch() : 1), &input), cont->ECD_LV, cont->scale);
+        Ciphertext ctxt_input = enc[0];
         printf("Encryption done in %s \n", dur(start).c_str());
         if (boot) {                                                                                    // test.go:52-53, eval.go:272-607
             const double pow_ = 4.0, alpha = 0.0;                                                      // test.go:22
             const double out_scale = exp2(round(log2((double)MODQ[0]) - (pow_ + 8)));                  // eval.go:433
             // HCONV_IMAGE_BATCH = n > 1 (not a reference feature): n independent encryptions of the input go through the layer as ONE set of launches
             const int nimg = imageBatch();
-            std::vector<Ciphertext> ins{ctxt_input};
-            for (int z = 1; z < nimg; z++) ins.push_back(EncryptNew(cont, EncodeCoeffs(input, cont->ECD_LV, cont->scale), cont->ECD_LV, cont->scale));
+            std::vector<Ciphertext> ins = enc;
             std::vector<Ciphertext> ct_conv = evalConv_BN_batch(cont, ins, ker_in, bn_a, bn_b, in_wid, ker_wid, raw_in_batch, raw_out_batch, norm, out_scale, trans);
             HC(cont->hc, hc_sync(cont->hc));                                                           // hand-over to the bootstrapper's context (another stream)
             std::vector<const uint64_t *> conv_d; for (const Ciphertext &ct : ct_conv) conv_d.push_back(ct.d);
@@ -697,10 +749,9 @@ void testTransConv_in(int in_batch, int in_wid, int ker_wid, int total_test_num)
         std::vector<double> bn_b = readTxt(pre + "bnb" + suf, raw_out_batch);
         std::vector<double> input = prep_Input(raw_input, raw_in_wid, in_wid, cont->Nn, norm, trans, false);
         auto start = now();
-        std::vector<Ciphertext> ins{EncryptNew(cont, EncodeCoeffs(input, cont->ECD_LV, cont->scale), cont->ECD_LV, cont->scale)};
+        // HCONV_IMAGE_BATCH = n > 1: n independent encryptions of the input (ONE call on the device path) through ONE set of launches (evalConv_BN_batch)
+        std::vector<Ciphertext> ins = EncryptCoeffsBatch(cont, std::vector<const std::vector<double> *>((size_t)nimg, &input), cont->ECD_LV, cont->scale);
         printf("Encryption done in %s \n", dur(start).c_str());
-        // HCONV_IMAGE_BATCH = n > 1: n independent encryptions of the input through ONE set of launches (evalConv_BN_batch)
-        for (int z = 1; z < nimg; z++) ins.push_back(EncryptNew(cont, EncodeCoeffs(input, cont->ECD_LV, cont->scale), cont->ECD_LV, cont->scale));
         std::vector<Ciphertext> ct_result = evalConv_BN_batch(cont, ins, ker_in, bn_a, bn_b, in_wid, ker_wid, raw_in_batch, raw_out_batch, norm, (double)(1 << 30), trans);
         if (getenv("HCONV_PRINT_DIGEST")) {      // FNV-1a over the result ciphertext: lets tests compare code paths bit for bit
             std::vector<uint64_t> h = dev_download(cont, ct_result[0].d, 2); uint64_t f = 1469598103934665603ull;
@@ -708,12 +759,13 @@ void testTransConv_in(int in_batch, int in_wid, int ker_wid, int total_test_num)
             printf("ciphertext digest: %016llx\n", (unsigned long long)f);
         }
         start = now();
-        std::vector<double> test_out = out_channels(DecryptDecodeCoeffs(cont, ct_result[0]));
+        std::vector<std::vector<double>> dec = DecryptDecodeCoeffsBatch(cont, ct_result);
+        std::vector<double> test_out = out_channels(dec[0]);
         printf("Decryption Done in %s \n", dur(start).c_str());
         std::vector<double> real_out = readTxt(pre + "out" + suf, out_wid * out_wid * raw_out_batch);
         printDebugCfsPlain(test_out, real_out);
         for (int z = 1; z < nimg; z++) {                                                               // the other encryptions decrypt to the same values up to the scheme's noise
-            std::vector<double> cz = out_channels(DecryptDecodeCoeffs(cont, ct_result[(size_t)z]));
+            std::vector<double> cz = out_channels(dec[(size_t)z]);
             double mx = 0, mr = 0; for (size_t i = 0; i < cz.size(); i++) { mx = std::max(mx, fabs(cz[i] - test_out[i])); mr = std::max(mr, fabs(cz[i] - real_out[i])); }
             printf("image %d of the batch: max |difference| to image 0 = %.3g, to the expected output = %.3g\n", z, mx, mr);
         }

@@ -92,6 +92,9 @@ struct Context {
     Seed256 seed;                             // key of this context's generators (hconv_prng.hpp)
     ChaChaRng g;                              // this context's own generator: secret key, Galois keys, encryption randomness
     uint64_t replay_encryptions = 0;          // HCONV_RESNET_REPLAY: encryptions so far (the i-th takes the oracle harness' seed 5 + 1000 i)
+    uint64_t *d_sk = nullptr;                 // device [3][N]: NTT(s) mod Q0, Q1, P, the sk_ntt operand of hc_encrypt_sk / hc_decrypt_decode_coeffs (uploaded once)
+    uint32_t enc_seed8[8] = {0};              // key of the device encryptor's draws: eight draws of g at context creation
+    uint64_t enc_stream = 0;                  // hc_encrypt_sk's stream id: one per call, never reused
     std::map<int, std::vector<std::vector<int>>> ext_idx;   // kind "Resnet_crop_fast": ext_idx[step][ul], the keep masks of the "inside" layers (main.go:123-136)
 };
 
@@ -129,6 +132,13 @@ void set_Variables(int batch, int raw_in_wid, int in_wid, int ker_wid, const std
 std::vector<uint64_t> EncodeCoeffs(const std::vector<double> &coeffs, int level, double scale);   // host rows, coefficient domain
 Ciphertext EncryptNew(Context *cont, const std::vector<uint64_t> &pt_rows, int level, double scale);
 std::vector<double> DecryptDecodeCoeffs(Context *cont, const Ciphertext &ct);
+// HCONV_DEVICE_ENCRYPT: 1 = hc_encode_coeffs + hc_encrypt_sk / hc_decrypt_decode_coeffs, 0 or unset = the host encryptor and decryptor (every
+// existing run keeps the stream it has; the default waits for the measurement profiles/LEDGER.md asks for). Under HCONV_RESNET_REPLAY / HCONV_CHAIN_REPLAY* the draws are always the host's.
+bool deviceEncrypt();
+// EncodeCoeffs + EncryptNew of n inputs: ONE hc_encode_coeffs and ONE hc_encrypt_sk call on the device path, n EncryptNew calls otherwise
+std::vector<Ciphertext> EncryptCoeffsBatch(Context *cont, const std::vector<const std::vector<double> *> &inputs, int level, double scale);
+// Decrypt + DecodeCoeffs of n level-0 ciphertexts: ONE hc_decrypt_decode_coeffs call on the device path
+std::vector<std::vector<double>> DecryptDecodeCoeffsBatch(Context *cont, const std::vector<Ciphertext> &cts);
 void freeCt(Context *cont, Ciphertext &ct);
 
 // kernel plaintexts: handle to the B device-resident plaintexts
