@@ -328,6 +328,9 @@ static int hc_build_tables(hc_ctx *c, HcModHost *mh, bool inverse) {
 extern "C" int hc_version(void) { return 5; }      // 2: a plaintext shared by the images of a batch is said by the operation (HC_LV_MUL_PLAIN), never inferred from b0 == b1; 3: hc_prep_ker_ex (transposed kernels); 4: hc_prep_ker_ex2 (dilated, channel-strided kernels); 5: hc_encode_coeffs, hc_encrypt_sk, hc_decrypt_decode_coeffs
 extern "C" const char *hc_last_error(const hc_ctx *c) { return c ? c->err.c_str() : g_create_err.c_str(); }
 
+// HcMod::row32 of modulus i of the context's nmods (Q then P): under pack32 = 2 the rows of a modulus below 2^31 in the caller's leveled operands are 4-byte words - except
+// limbs 0 and 1, which are what the convolution's entry points, hc_div_round_last_n's level-1 branch and hc_swk_generate's sk rows read as 8-byte rows
+static int hc_row32(int pack32, u64 q, size_t i, size_t nmods) { return pack32 == 2 && q < (1ull << 31) && !(i < 2 && nmods > 1); }
 // the per-modulus table of the batched transforms (HcRowMod); again after option small32 changes
 static int hc_upload_rowmods(hc_ctx *c) {
     std::vector<HcRowMod> hr;
@@ -366,7 +369,7 @@ extern "C" int hc_ctx_create(hc_ctx **out, int logN, const uint64_t *q, int nq, 
         mh.m.r2 = h_mulmod(r, r, qi);
         mh.m.ninv = h_inv(HC_N, qi); mh.m.ninv_s = h_shoup(mh.m.ninv, qi);
         mh.m.mu = (u64)((((u128)1) << 64) / qi);
-        mh.m.row32 = (c->pack32 == 2 && qi < (1ull << 31)) ? 1 : 0;
+        mh.m.row32 = hc_row32(c->pack32, qi, (size_t)i, c->mods.size());     // pack32 is 1 here: no 4-byte rows until the option asks
         u64 g = h_primitive_root(qi), power = (qi - 1) / (2ull * HC_N);
         mh.psi = h_powmod(g, power, qi); mh.psi_inv = h_powmod(g, (qi - 1) - power, qi);
         int rc = hc_build_tables(c, &mh, false); if (!rc) rc = hc_build_tables(c, &mh, true);
@@ -466,14 +469,25 @@ static int hc_check_mod(hc_ctx *c, int mod, const char *fn) {
 }
 static dim3 hc_pw_grid(size_t n) { size_t b = (n + HC_TPB - 1) / HC_TPB; if (b > 4096) b = 4096; return dim3((unsigned)b); }
 
-static int hc_ensure_tmp(hc_ctx *c, size_t rows) {
-    if (c->ws_tmp_rows >= rows) return HC_OK;
+// workspace growth: (ws, cap) is one of the context's workspaces and its capacity in units of unit_bytes; a workspace too small for `units` is replaced (its contents are lost)
+template <class T>
+static int hc_ensure(hc_ctx *c, T *&ws, size_t &cap, size_t units, size_t unit_bytes) {
+    if (cap >= units) return HC_OK;
     HC_HIP(c, hipStreamSynchronize(c->stream));
-    if (c->ws_tmp) HC_HIP(c, hcx_free(c, c->ws_tmp));
-    c->ws_tmp = nullptr; c->ws_tmp_rows = 0;
-    HC_HIP(c, hcx_malloc(c, (void **)&c->ws_tmp, rows * HC_N * sizeof(u64)));
-    c->ws_tmp_rows = rows;
+    if (ws) HC_HIP(c, hcx_free(c, ws));
+    ws = nullptr; cap = 0;
+    HC_HIP(c, hcx_malloc(c, (void **)&ws, units * unit_bytes));
+    cap = units;
     return HC_OK;
+}
+static int hc_ensure_tmp(hc_ctx *c, size_t rows) { return hc_ensure(c, c->ws_tmp, c->ws_tmp_rows, rows, HC_N * sizeof(u64)); }
+static int hc_ensure_cts(hc_ctx *c, size_t rows) { return hc_ensure(c, c->ws_cts, c->ws_cts_rows, rows, HC_N * sizeof(u64)); }
+static int hc_ensure_ctc(hc_ctx *c, size_t nct) { return hc_ensure(c, c->ws_ctc, c->ws_ctc_cts, nct, 4 * HC_N * sizeof(HcTw)); }
+static int hc_ensure_mm(hc_ctx *c, size_t rows) {
+    const size_t had = c->ws_mm_rows;
+    const int rc = hc_ensure(c, c->ws_mm, c->ws_mm_rows, rows, HC_N * sizeof(u64));
+    if (c->ws_mm_rows != had) c->hoist_cx = nullptr;        // the old block is gone, and the decomposition it held with it
+    return rc;
 }
 
 extern "C" int hc_ntt(hc_ctx *c, int mod, const uint64_t *in, uint64_t *out, int count) {
@@ -619,85 +633,110 @@ extern "C" int hc_lv_add(hc_ctx *c, int level, const uint64_t *a, const uint64_t
 extern "C" int hc_lv_sub(hc_ctx *c, int level, const uint64_t *a, const uint64_t *b, uint64_t *out) { return hc_lv_pw<HC_PW_SUB>(c, "hc_lv_sub", level, a, b, out, nullptr); }
 extern "C" int hc_lv_mul_const(hc_ctx *c, int level, const uint64_t *a, const uint64_t *consts, uint64_t *out) { return hc_lv_pw<HC_PW_MULC>(c, "hc_lv_mul_const", level, a, nullptr, out, consts); }
 extern "C" int hc_lv_add_const(hc_ctx *c, int level, const uint64_t *a, const uint64_t *consts, uint64_t *out) { return hc_lv_pw<HC_PW_ADDC>(c, "hc_lv_add_const", level, a, nullptr, out, consts); }
-// batched transforms over rows of different moduli (row y <-> modulus y < nl ? y : nq + y - nl); z operands zs words apart, n images is words apart.
-// fuse: optional prologue of the first pass (lift_level: Rescale's lift of t, see HcMm) and epilogue of the second (epi_x: (x - result) * epi_mul (+ epi_add))
+// ---- batched transforms over rows of different moduli (row y <-> modulus y < nl ? y : nq + y - nl), two passes through the seam ws_tmp
+// What the rows of an operand are. Rows of a modulus below 2^31 are 4-byte words in some arrays and under some settings of option pack32 (include/hconv.h "4-byte rows"):
+enum HcRows { HC_ROWS_USER,        // a caller's leveled operand, and the library's NTT-domain arrays laid out like one (a key switch's acc and ext): 4-byte rows under pack32 = 2
+              HC_ROWS_LIB8,        // a coefficient-domain scratch array of the library (t, S.yv, S.pc): 8-byte rows under every pack32
+              HC_ROWS_PACKED,      // a library array read only by kernels that expect 4-byte rows for the small moduli (the digits of a key switch): 4-byte rows unless pack32 = 0
+              HC_ROWS_RAW,         // 8-byte rows whatever the option: the rows of a switching key while it is being generated, limbs 0 and 1 in the encryptor
+              HC_ROWS_SEAM };      // ws_tmp between the two passes, which never leaves the library: follows pack32
+// HcMm::pk_in / pk_out / pk_epi for rows of that kind (the kernels test them for non-zero, together with HC_SMALL_Q of the row's modulus). The one place that decides a width.
+// Per call site, under pack32 = 0 / 1 / 2 (-: the kernel does not read the field there: a fused prologue forms the input, or there is no epilogue):
+//                                                                              pass 1 (in -> seam)   pass 2 (seam -> out)
+//   forward (hc_ntt_mm)                         in        out                  pk_in    pk_out       pk_in    pk_out   pk_epi
+//   hc_lv_ntt, hc_lv_mod_raise, hc_encode_*     USER      USER (= in)          0/0/1    0/1/1        0/1/1    0/0/1    -
+//   Rescale (hc_div_round_last_n)               LIB8 t    USER                 -        0/1/1        0/1/1    0/0/1    0/0/1
+//   hc_swk_generate, hc_encrypt_sk              RAW       RAW (= in)           0/0/0    0/1/1        0/1/1    0/0/0    -
+//   decomposition (hc_ks_decompose_into)        LIB8 yv   PACKED digits        -        0/1/1        0/1/1    0/1/1    -
+//   ModDown before a rotation                   LIB8 yv   USER S.ext           -        0/1/1        0/1/1    0/0/1    -
+//   ModDown, ModDown + Rescale                  LIB8      USER d0, d1          -        0/1/1        0/1/1    0/0/1    0/0/1
+//   inverse (hc_intt_mm)
+//   hc_lv_intt                                  USER      USER                 0/0/1    0/1/1        0/1/1    0/0/1    0
+//   hc_lv_mod_raise, Rescale, decomposition,    USER      LIB8                 0/0/1    0/1/1        0/1/1    0/0/0    0
+//   ModDown (+ Rescale), hc_decrypt_decode_coeffs (its t is read as USER rows)
+// Known disagreement (the medium finding; its fix belongs here): under pack32 = 2 on a context whose limb 0 or 1 is below 2^31, hc_row32 says 8-byte rows for those
+// two limbs - what every kernel that goes by HcMod::row32 reads and writes - while USER below says 4-byte rows for every small modulus. The contexts the product builds have
+// large limbs 0 and 1.
+static int hc_pk(const hc_ctx *c, HcRows rows) {
+    switch (rows) { case HC_ROWS_USER: return c->pack32 == 2; case HC_ROWS_PACKED: case HC_ROWS_SEAM: return c->pack32 != 0; case HC_ROWS_LIB8: case HC_ROWS_RAW: break; }
+    return 0;
+}
+// the inner products' `pk` (hc_k_ks_mac_all / _multi, tested for non-zero): bit 0 the digits (HC_ROWS_PACKED), bit 1 the switching key's rows (hc_k_pack32_rows, under the same rule)
+static int hc_pk_mac(const hc_ctx *c) { return hc_pk(c, HC_ROWS_PACKED) ? 3 : 0; }
+// one operand of a batched transform: blockIdx.z = operand + nz * image, the nz operands of an image zs words apart, the images is words apart
+template <class W> struct HcMmOperand { W *p; size_t zs, is; HcRows rows; };
+// fuse: optional prologue of the first pass (lift_level: Rescale's lift of t, see HcMm) and epilogue of the second (epi_x: (x - result) * epi_mul (+ epi_add)); x, add and the result are HC_ROWS_USER
 struct HcMmFuse { const HcBasisExt *ext_bs = nullptr; int ext_rows = 0; int lift_level = 0; const u64 *epi_x = nullptr; size_t epi_x_zs = 0, epi_x_is = 0; const HcTw *epi_mul = nullptr; const u64 *epi_add = nullptr; size_t epi_add_zs = 0, epi_add_is = 0;
-                  const u64 *lift_t = nullptr; size_t lift_t_zs = 0, lift_t_is = 0; const HcTw *lift_pmul = nullptr, *epi_add_mul = nullptr;      // lift_t: ModDown + Rescale in one transform (HcMm)
-                  bool out_packed = false;       // out is a library-internal array read only by kernels that expect 4-byte rows for the small moduli (the digits of a key switch)
-                  bool raw = false; };           // in / out are plain 8-byte rows whatever the context's pack32 (the rows of a switching key while it is being generated)
-static int hc_ntt_mm(hc_ctx *c, const u64 *in, u64 *out, int rows, int nl, int skip_lo, int skip_hi, int z, size_t zs_in, size_t zs_out, int z_alpha = 0, int n = 1, size_t is_in = 0, size_t is_out = 0, const char *tag = "ntt",
-                     const HcMmFuse *fuse = nullptr) {
+                  const u64 *lift_t = nullptr; size_t lift_t_zs = 0, lift_t_is = 0; const HcTw *lift_pmul = nullptr, *epi_add_mul = nullptr; };     // lift_t: ModDown + Rescale in one transform (HcMm)
+struct HcMmCall { int rows = 0, nl = 0, nz = 1, images = 1; HcMmOperand<const u64> in = {nullptr, 0, 0, HC_ROWS_USER}; HcMmOperand<u64> out = {nullptr, 0, 0, HC_ROWS_USER}; const char *tag = nullptr; };
+struct HcNttCall : HcMmCall { int z_alpha = 0; const HcMmFuse *fuse = nullptr; };       // z_alpha > 0: operand z is digit z of a key switch, whose own limbs are not transformed (hc_mm_skip)
+struct HcInttCall : HcMmCall { int skip_lo = 0, skip_hi = 0, out_first_row = 0;            // rows [skip_lo, skip_hi) have nothing to do; out.p is where row out_first_row goes (the rows below it are skipped: out holds rows out_first_row .. rows - 1 only)
+                               const HcTw *out_scale = nullptr; int out_gap = 0; };        // the result leaves as the y_i rows of a basis extension (HcMm::out_gap, hc_cols_inv_canon_mm_body)
+static int hc_ntt_mm(hc_ctx *c, const HcNttCall &m) {
+    const int rows = m.rows, z = m.nz, n = m.images; const HcMmFuse *fuse = m.fuse; const char *tag = m.tag ? m.tag : "ntt";
     HC_TRY(hc_ensure_tmp(c, (size_t)rows * z * n));
-    HcMm A; memset(&A, 0, sizeof A); A.M = c->d_rowmods; A.nl = nl; A.nq = c->nq; A.skip_lo = skip_lo; A.skip_hi = skip_hi; A.z_alpha = z_alpha; A.nz = z; A.mods = c->d_mods;
+    HcMm A; memset(&A, 0, sizeof A); A.M = c->d_rowmods; A.nl = m.nl; A.nq = c->nq; A.skip_lo = 0; A.skip_hi = 0; A.z_alpha = m.z_alpha; A.nz = z; A.mods = c->d_mods;
     char n1[48], n2[48]; snprintf(n1, sizeof n1, "%s:cols_fwd_mm", tag); snprintf(n2, sizeof n2, "%s:rows_fwd_canon_mm", tag);
     const size_t zt = (size_t)rows * HC_N, it = zt * (size_t)z;
     if (rows > 48) return hc_fail(c, HC_ERR_UNSUPPORTED, "batched transform over more than 48 rows");
     A.gap_lo = rows; A.gap_len = 0;                                          // every row is in the grid
     const dim3 grid(16, (unsigned)rows, (unsigned)(z * n));
-    A.zs_in = zs_in; A.is_in = is_in; A.zs_out = zt; A.is_out = it;
+    A.zs_in = m.in.zs; A.is_in = m.in.is; A.zs_out = zt; A.is_out = it;
     if (fuse && fuse->lift_level > 0) { A.lift_level = fuse->lift_level; if (!fuse->lift_t) { A.zs_in = (size_t)HC_N; A.is_in = (size_t)z * HC_N; } }
     if (fuse && fuse->ext_bs) { A.ext_bs = fuse->ext_bs; A.ext_rows = fuse->ext_rows; }
     if (fuse && fuse->lift_t) { A.lift_t = fuse->lift_t; A.lift_t_zs = fuse->lift_t_zs; A.lift_t_is = fuse->lift_t_is; A.lift_pmul = fuse->lift_pmul; }
     // the extension's operand registers are sized by the most source limbs a digit / ModDown can have: the context's number of special primes (hc_basis_ext_tile)
-#define HC_COLS_EXT(E) (c->np <= 2 ? hc_launch(c, c->profile ? n1 : "cols_fwd_mm", hc_k_cols_fwd_mm<E, 2>, grid, in, c->ws_tmp, A) : hc_launch(c, c->profile ? n1 : "cols_fwd_mm", hc_k_cols_fwd_mm<E, HC_MAX_NP>, grid, in, c->ws_tmp, A))
-    const bool user32 = c->pack32 == 2 && !(fuse && fuse->raw);              // pack32 = 2: the caller's polynomials (a plain input, the output, the epilogue's operands) carry 4-byte rows too
-    A.pk_in = user32; A.pk_out = c->pack32;                                  // the seam between the two passes (ws_tmp) never leaves the library
+#define HC_COLS_EXT(E) (c->np <= 2 ? hc_launch(c, c->profile ? n1 : "cols_fwd_mm", hc_k_cols_fwd_mm<E, 2>, grid, m.in.p, c->ws_tmp, A) : hc_launch(c, c->profile ? n1 : "cols_fwd_mm", hc_k_cols_fwd_mm<E, HC_MAX_NP>, grid, m.in.p, c->ws_tmp, A))
+    A.pk_in = hc_pk(c, m.in.rows); A.pk_out = hc_pk(c, HC_ROWS_SEAM);
     if (A.ext_bs && A.lift_t) HC_TRY(HC_COLS_EXT(2));
     else if (A.ext_bs) HC_TRY(HC_COLS_EXT(1));
-    else HC_TRY(hc_launch(c, c->profile ? n1 : "cols_fwd_mm", hc_k_cols_fwd_mm<0>, grid, in, c->ws_tmp, A));
+    else HC_TRY(hc_launch(c, c->profile ? n1 : "cols_fwd_mm", hc_k_cols_fwd_mm<0>, grid, m.in.p, c->ws_tmp, A));
 #undef HC_COLS_EXT
-    A.lift_level = 0; A.ext_bs = nullptr; A.lift_t = nullptr; A.zs_in = zt; A.is_in = it; A.zs_out = zs_out; A.is_out = is_out;
-    A.pk_in = c->pack32; A.pk_out = ((c->pack32 && fuse && fuse->out_packed) || user32) ? 1 : 0; A.pk_epi = user32;
-    if (fuse && fuse->epi_x) { A.epi_x = fuse->epi_x; A.epi_x_zs = fuse->epi_x_zs; A.epi_x_is = fuse->epi_x_is; A.epi_mul = fuse->epi_mul; A.epi_add = fuse->epi_add; A.epi_add_zs = fuse->epi_add_zs; A.epi_add_is = fuse->epi_add_is; A.epi_add_mul = fuse->epi_add_mul; }
+    A.lift_level = 0; A.ext_bs = nullptr; A.lift_t = nullptr; A.zs_in = zt; A.is_in = it; A.zs_out = m.out.zs; A.is_out = m.out.is;
+    A.pk_in = hc_pk(c, HC_ROWS_SEAM); A.pk_out = hc_pk(c, m.out.rows);
+    if (fuse && fuse->epi_x) { A.epi_x = fuse->epi_x; A.epi_x_zs = fuse->epi_x_zs; A.epi_x_is = fuse->epi_x_is; A.epi_mul = fuse->epi_mul; A.epi_add = fuse->epi_add; A.epi_add_zs = fuse->epi_add_zs; A.epi_add_is = fuse->epi_add_is; A.epi_add_mul = fuse->epi_add_mul; A.pk_epi = hc_pk(c, HC_ROWS_USER); }
     A.xcd = c->xcd_rows; A.nzn = z * n;
     // a second pass of at most about a round of 16-row workgroups: on quarter tiles (hc_k_rows_fwd_canon_mm_s)
-    if ((long)16 * rows * z * n <= c->small_mm_wgs) { A.xcd = 0; HC_TRY(hc_launch<HC_STPB>(c, c->profile ? n2 : "rows_fwd_canon_mm", hc_k_rows_fwd_canon_mm_s, dim3(HC_STILES, (unsigned)rows, (unsigned)(z * n)), (const u64 *)c->ws_tmp, out, A)); return HC_OK; }
-    HC_TRY(hc_launch(c, c->profile ? n2 : "rows_fwd_canon_mm", hc_k_rows_fwd_canon_mm, A.xcd ? dim3(16u * (unsigned)rows * (unsigned)(z * n)) : grid, (const u64 *)c->ws_tmp, out, A));
+    if ((long)16 * rows * z * n <= c->small_mm_wgs) { A.xcd = 0; HC_TRY(hc_launch<HC_STPB>(c, c->profile ? n2 : "rows_fwd_canon_mm", hc_k_rows_fwd_canon_mm_s, dim3(HC_STILES, (unsigned)rows, (unsigned)(z * n)), (const u64 *)c->ws_tmp, m.out.p, A)); return HC_OK; }
+    HC_TRY(hc_launch(c, c->profile ? n2 : "rows_fwd_canon_mm", hc_k_rows_fwd_canon_mm, A.xcd ? dim3(16u * (unsigned)rows * (unsigned)(z * n)) : grid, (const u64 *)c->ws_tmp, m.out.p, A));
     return HC_OK;
 }
-// out_user: out is a polynomial of the caller's (hc_lv_intt), not one of the library's coefficient-domain scratch arrays (which keep 8-byte rows under every pack32)
-// out_scale / out_gap: the result leaves as the y_i rows of a basis extension (HcMm::out_gap, hc_cols_inv_canon_mm_body)
-static int hc_intt_mm(hc_ctx *c, const u64 *in, u64 *out, int rows, int nl, int z, size_t zs_in, size_t zs_out, int skip_lo = 0, int skip_hi = 0, int n = 1, size_t is_in = 0, size_t is_out = 0, const char *tag = "intt", bool out_user = false,
-                      const HcTw *out_scale = nullptr, int out_gap = 0) {
+static int hc_intt_mm(hc_ctx *c, const HcInttCall &m) {
+    const int rows = m.rows, z = m.nz, n = m.images; const char *tag = m.tag ? m.tag : "intt";
     HC_TRY(hc_ensure_tmp(c, (size_t)rows * z * n));
-    HcMm A; memset(&A, 0, sizeof A); A.M = c->d_rowmods; A.nl = nl; A.nq = c->nq; A.skip_lo = skip_lo; A.skip_hi = skip_hi; A.z_alpha = 0; A.nz = z;
+    HcMm A; memset(&A, 0, sizeof A); A.M = c->d_rowmods; A.nl = m.nl; A.nq = c->nq; A.skip_lo = m.skip_lo; A.skip_hi = m.skip_hi; A.z_alpha = 0; A.nz = z;
     char n1[48], n2[48]; snprintf(n1, sizeof n1, "%s:rows_inv_mm", tag); snprintf(n2, sizeof n2, "%s:cols_inv_canon_mm", tag);
     const size_t zt = (size_t)rows * HC_N, it = zt * (size_t)z;
     if (rows > 48) return hc_fail(c, HC_ERR_UNSUPPORTED, "batched transform over more than 48 rows");
     // rows in [skip_lo, skip_hi) have nothing to do: not in the grid
-    const int s_lo = skip_lo < 0 ? 0 : (skip_lo > rows ? rows : skip_lo), s_hi = skip_hi < s_lo ? s_lo : (skip_hi > rows ? rows : skip_hi);
+    const int s_lo = m.skip_lo < 0 ? 0 : (m.skip_lo > rows ? rows : m.skip_lo), s_hi = m.skip_hi < s_lo ? s_lo : (m.skip_hi > rows ? rows : m.skip_hi);
     const int cnt = rows - (s_hi - s_lo);
+    if (m.out_first_row && (s_lo > 0 || s_hi < m.out_first_row)) return hc_fail(c, HC_ERR_ARG, "batched transform: rows below the first output row must be skipped");
     A.gap_lo = s_lo; A.gap_len = s_hi - s_lo;
     const dim3 grid(16, (unsigned)cnt, (unsigned)(z * n));
-    A.zs_in = zs_in; A.is_in = is_in; A.zs_out = zt; A.is_out = it; A.xcd = c->xcd_rows; A.nzn = z * n;
-    A.pk_in = c->pack32 == 2; A.pk_out = c->pack32;                          // the caller's NTT-domain rows; the seam (ws_tmp)
+    A.zs_in = m.in.zs; A.is_in = m.in.is; A.zs_out = zt; A.is_out = it; A.xcd = c->xcd_rows; A.nzn = z * n;
+    A.pk_in = hc_pk(c, m.in.rows); A.pk_out = hc_pk(c, HC_ROWS_SEAM);
     // a launch of a few hundred workgroups costs what ONE workgroup takes: quarter tiles (four residues per thread, four times the workgroups) then
     const bool quarter = (long)16 * cnt * z * n <= c->small_mm_wgs;
     const dim3 sgrid(HC_STILES, (unsigned)cnt, (unsigned)(z * n));
-    if (quarter) { A.xcd = 0; HC_TRY(hc_launch<HC_STPB>(c, c->profile ? n1 : "rows_inv_mm", hc_k_rows_inv_mm_s, sgrid, in, c->ws_tmp, A)); }
-    else HC_TRY(hc_launch(c, c->profile ? n1 : "rows_inv_mm", hc_k_rows_inv_mm, A.xcd ? dim3(16u * (unsigned)cnt * (unsigned)(z * n)) : grid, in, c->ws_tmp, A));
-    A.xcd = 0; A.pk_in = c->pack32; A.pk_out = (c->pack32 == 2 && out_user) ? 1 : 0; A.epi_mul = out_scale; A.out_gap = out_gap;
-    A.zs_in = zt; A.is_in = it; A.zs_out = zs_out; A.is_out = is_out;
+    if (quarter) { A.xcd = 0; HC_TRY(hc_launch<HC_STPB>(c, c->profile ? n1 : "rows_inv_mm", hc_k_rows_inv_mm_s, sgrid, m.in.p, c->ws_tmp, A)); }
+    else HC_TRY(hc_launch(c, c->profile ? n1 : "rows_inv_mm", hc_k_rows_inv_mm, A.xcd ? dim3(16u * (unsigned)cnt * (unsigned)(z * n)) : grid, m.in.p, c->ws_tmp, A));
+    A.xcd = 0; A.pk_in = hc_pk(c, HC_ROWS_SEAM); A.pk_out = hc_pk(c, m.out.rows); A.epi_mul = m.out_scale; A.out_gap = m.out_gap;
+    A.zs_in = zt; A.is_in = it; A.zs_out = m.out.zs; A.is_out = m.out.is;
+    // the kernels store row y of an operand at out + y * N, y the row's absolute number: the address of row 0 is what they take, whether or not row 0 is stored. It lies
+    // before the array when out holds rows from out_first_row only - formed in integers, so that no pointer leaves its allocation here
+    u64 *out = reinterpret_cast<u64 *>(reinterpret_cast<uintptr_t>(m.out.p) - (uintptr_t)m.out_first_row * HC_N * sizeof(u64));
     if (quarter) HC_TRY(hc_launch<HC_STPB>(c, c->profile ? n2 : "cols_inv_canon_mm", hc_k_cols_inv_canon_mm_s, sgrid, (const u64 *)c->ws_tmp, out, A));
     else HC_TRY(hc_launch(c, c->profile ? n2 : "cols_inv_canon_mm", hc_k_cols_inv_canon_mm, grid, (const u64 *)c->ws_tmp, out, A));
     return HC_OK;
 }
-static int hc_ensure_mm(hc_ctx *c, size_t rows) {
-    if (c->ws_mm_rows >= rows) return HC_OK;
-    HC_HIP(c, hipStreamSynchronize(c->stream));
-    if (c->ws_mm) HC_HIP(c, hcx_free(c, c->ws_mm));
-    c->ws_mm = nullptr; c->ws_mm_rows = 0; c->hoist_cx = nullptr;
-    HC_HIP(c, hcx_malloc(c, (void **)&c->ws_mm, rows * HC_N * sizeof(u64)));
-    c->ws_mm_rows = rows;
-    return HC_OK;
-}
 extern "C" int hc_lv_ntt(hc_ctx *c, int level, const uint64_t *in, uint64_t *out) {
     HC_ENTER(c); HC_TRY(hc_lv_check(c, "hc_lv_ntt", level, in, out));
-    return hc_ntt_mm(c, in, out, level + 1, level + 1, 0, 0, 1, 0, 0, 0, c->nb, c->bs_poly, c->bs_poly);
+    HcNttCall m; m.rows = m.nl = level + 1; m.images = c->nb; m.in = {in, 0, c->bs_poly, HC_ROWS_USER}; m.out = {out, 0, c->bs_poly, HC_ROWS_USER}; return hc_ntt_mm(c, m);
 }
 extern "C" int hc_lv_intt(hc_ctx *c, int level, const uint64_t *in, uint64_t *out) {
     HC_ENTER(c); HC_TRY(hc_lv_check(c, "hc_lv_intt", level, in, out));
-    return hc_intt_mm(c, in, out, level + 1, level + 1, 1, 0, 0, 0, 0, c->nb, c->bs_poly, c->bs_poly, "intt", true);
+    HcInttCall m; m.rows = m.nl = level + 1; m.images = c->nb; m.in = {in, 0, c->bs_poly, HC_ROWS_USER}; m.out = {out, 0, c->bs_poly, HC_ROWS_USER}; return hc_intt_mm(c, m);
 }
 extern "C" int hc_lv_mul_tensor(hc_ctx *c, int level, const uint64_t *a0, const uint64_t *a1, const uint64_t *b0, const uint64_t *b1, uint64_t *d0, uint64_t *d1, uint64_t *d2) {
     HC_ENTER(c); HC_TRY(hc_lv_check(c, "hc_lv_mul_tensor", level, a0, d0));
@@ -725,9 +764,9 @@ extern "C" int hc_lv_mod_raise(hc_ctx *c, int level, const uint64_t *in_q0, uint
     if ((const void *)in_q0 == (const void *)out) return hc_fail(c, HC_ERR_ARG, "hc_lv_mod_raise: in and out must differ");
     HC_TRY(hc_ensure_mm(c, (size_t)c->nb)); c->hoist_cx = nullptr;
     u64 *t = c->ws_mm;                                                                  // one coefficient row per image
-    HC_TRY(hc_intt_mm(c, in_q0, t, 1, 1, 1, 0, 0, 0, 0, c->nb, c->bs_poly, (size_t)HC_N));
+    HcInttCall mi; mi.rows = mi.nl = 1; mi.images = c->nb; mi.in = {in_q0, 0, c->bs_poly, HC_ROWS_USER}; mi.out = {t, 0, (size_t)HC_N, HC_ROWS_LIB8}; HC_TRY(hc_intt_mm(c, mi));
     HC_TRY(hc_launch(c, "mod_raise", hc_k_mod_raise, dim3(HC_GX_LV, (unsigned)(level + 1), (unsigned)c->nb), (const u64 *)t, (u64 *)out, (const HcMod *)c->d_mods, c->bs_poly));
-    return hc_ntt_mm(c, out, out, level + 1, level + 1, 0, 0, 1, 0, 0, 0, c->nb, c->bs_poly, c->bs_poly);
+    HcNttCall m; m.rows = m.nl = level + 1; m.images = c->nb; m.in = {out, 0, c->bs_poly, HC_ROWS_USER}; m.out = {out, 0, c->bs_poly, HC_ROWS_USER}; return hc_ntt_mm(c, m);
 }
 
 // getConstAndScale + scaleUpExact of the reference's dependency: a float64 constant with a
@@ -765,15 +804,6 @@ static int hc_fill_loopA(hc_ctx *c, HcLoopA *A, const HcPtrs &kers, u64 *cts, si
 
 // ct_in (2x2 rows) of n ciphertexts times per-limb constants -> ws_ctc as Shoup pairs: c' is the fixed operand of the 2B products
 // of loop A, so its companion floor(c' * 2^64 / q) is computed once per conv (4 rows per ciphertext)
-static int hc_ensure_ctc(hc_ctx *c, size_t nct) {
-    if (c->ws_ctc_cts >= nct) return HC_OK;
-    HC_HIP(c, hipStreamSynchronize(c->stream));
-    if (c->ws_ctc) HC_HIP(c, hcx_free(c, c->ws_ctc));
-    c->ws_ctc = nullptr; c->ws_ctc_cts = 0;
-    HC_HIP(c, hcx_malloc(c, (void **)&c->ws_ctc, nct * 4 * HC_N * sizeof(HcTw)));
-    c->ws_ctc_cts = nct;
-    return HC_OK;
-}
 static int hc_prepare_ctc(hc_ctx *c, const HcPtrs &ct_in, int n, const u64 cst[2]) {
     HC_TRY(hc_ensure_ctc(c, (size_t)n));
     HcCtc K; K.m0 = c->mods[0].m; K.m1 = c->mods[1].m;
@@ -841,11 +871,11 @@ static int hc_div_round_last_n(hc_ctx *c, int level, const u64 *x, size_t xs, u6
         c->hoist_cx = nullptr;                                   // the scratch is shared with the key switch's decomposition
         u64 *t = c->ws_mm;                                         // t[z][N], z = polynomial + np * image
         // InvNTT of the last limb of every polynomial: the multi-modulus kernels over rows 0..level with rows below `level` skipped
-        HC_TRY(hc_intt_mm(c, x, t - (size_t)level * HC_N, level + 1, level + 1, np, xs, (size_t)HC_N, 0, level, nb, c->bs_poly, (size_t)np * HC_N, "rescale"));
+        HcInttCall mi; mi.rows = mi.nl = level + 1; mi.skip_hi = mi.out_first_row = level; mi.nz = np; mi.images = nb; mi.in = {x, xs, c->bs_poly, HC_ROWS_USER}; mi.out = {t, (size_t)HC_N, (size_t)np * HC_N, HC_ROWS_LIB8}; mi.tag = "rescale"; HC_TRY(hc_intt_mm(c, mi));
         // the lift of t into every lower modulus happens where the forward transform reads its input, (x - NTT(lift)) / q_L where it writes its output: two launches,
         // x read once, the result written once (round 3: lift, two transform passes over a scratch, a finishing pass)
         HcMmFuse F; F.lift_level = level; F.epi_x = x; F.epi_x_zs = xs; F.epi_x_is = c->bs_poly; F.epi_mul = qlinv;
-        return hc_ntt_mm(c, t, out, level, level, 0, 0, np, (size_t)HC_N, os, 0, nb, (size_t)np * HC_N, c->bs_poly, "rescale", &F);
+        HcNttCall m; m.rows = m.nl = level; m.nz = np; m.images = nb; m.in = {t, (size_t)HC_N, (size_t)np * HC_N, HC_ROWS_LIB8}; m.out = {out, os, c->bs_poly, HC_ROWS_USER}; m.tag = "rescale"; m.fuse = &F; return hc_ntt_mm(c, m);
     }
     if (c->nb > 1) {           // level 1 in a batch: image by image through the fused level-1 path below (not on the batched chain's route: its rescales end at level 1)
         const int nb = c->nb; const size_t bs = c->bs_poly; int rc = HC_OK;
@@ -1289,8 +1319,8 @@ static int hc_swk_generate_impl(hc_ctx *c, uint64_t key_id, int level, uint64_t 
     const dim3 grid(64, (unsigned)nt, (unsigned)beta);
     HC_TRY(hc_launch(c, "swk_sample", hc_k_swk_sample, grid, k.rows, (const HcMod *)c->d_mods, G));
     c->hoist_cx = nullptr;
-    { HcMmFuse Fraw; Fraw.raw = true;                                                                          // key rows are 8-byte words until hc_k_pack32_rows below
-      HC_TRY(hc_ntt_mm(c, k.rows, k.rows, nt, nl, 0, 0, beta, (size_t)2 * nt * HC_N, (size_t)2 * nt * HC_N, 0, 1, 0, 0, "ntt", &Fraw)); }      // the e rows (component 0 of every digit), all limbs
+    // the e rows (component 0 of every digit), all limbs, in place; key rows are 8-byte words until hc_k_pack32_rows below
+    HcNttCall m; m.rows = nt; m.nl = nl; m.nz = beta; m.in = {k.rows, (size_t)2 * nt * HC_N, 0, HC_ROWS_RAW}; m.out = {k.rows, (size_t)2 * nt * HC_N, 0, HC_ROWS_RAW}; HC_TRY(hc_ntt_mm(c, m));
     HC_TRY(hc_launch(c, "swk_finish", hc_k_swk_finish, grid, k.rows, (const u64 *)sk_ntt, (const HcMod *)c->d_mods, (const HcTw *)pm, G));
     if (c->pack32) HC_TRY(hc_launch(c, "pack32_rows", hc_k_pack32_rows, dim3((unsigned)(beta * 2 * nt)), k.rows, (const HcMod *)c->d_mods, nl, c->nq, nt));
     HC_HIP(c, hipStreamSynchronize(c->stream));
@@ -1370,17 +1400,18 @@ static int hc_ks_decompose_into(hc_ctx *c, int level, const u64 *cx, const HcKsS
     // at row l + l / alpha); one pass over them adds the v rows; the target side is taken inside the first pass of the digits' forward transforms (blockIdx.z = digit + beta *
     // image): neither the coefficients of cx nor the extended digits exist in memory in the coefficient domain
     const size_t yz = (size_t)(alpha + 1) * HC_N;
-    HC_TRY(hc_intt_mm(c, cx, S.yv, nl, nl, 1, 0, 0, 0, 0, nb, c->bs_poly, (size_t)beta * yz, "decomp", false, P->yinv, alpha));
+    HcInttCall mi; mi.rows = mi.nl = nl; mi.images = nb; mi.in = {cx, 0, c->bs_poly, HC_ROWS_USER}; mi.out = {S.yv, 0, (size_t)beta * yz, HC_ROWS_LIB8}; mi.tag = "decomp"; mi.out_scale = P->yinv; mi.out_gap = alpha; HC_TRY(hc_intt_mm(c, mi));
     HC_TRY(hc_launch(c, "decomp:basis_v", hc_k_basis_v, dim3(HC_GX_YV, (unsigned)(beta * nb)), S.yv, alpha + 1, (const HcBasisExt *)P->bx, nt, alpha, beta));
-    HcMmFuse F; F.ext_bs = P->bx; F.ext_rows = nt; F.out_packed = true;            // the digits are read by the inner products only (hc_k_ks_mac_all / _multi)
-    return hc_ntt_mm(c, S.yv, S.digits, nt, nl, 0, 0, beta, yz, (size_t)nt * HC_N, alpha, nb, (size_t)beta * yz, S.digits_is, "decomp", &F);
+    HcMmFuse F; F.ext_bs = P->bx; F.ext_rows = nt;
+    HcNttCall m; m.rows = nt; m.nl = nl; m.nz = beta; m.z_alpha = alpha; m.images = nb; m.in = {S.yv, yz, (size_t)beta * yz, HC_ROWS_LIB8}; m.tag = "decomp"; m.fuse = &F;
+    m.out = {S.digits, (size_t)nt * HC_N, S.digits_is, HC_ROWS_PACKED}; return hc_ntt_mm(c, m);            // the digits are read by the inner products only (hc_k_ks_mac_all / _multi)
 }
 // the inner product with both components of the key, all images: acc [img][2][nt][N], images acc_is words apart
 static int hc_ks_mac(hc_ctx *c, const HcSwk &key, int level, const u64 *cx, const HcKsScratch &S, u64 *acc, size_t acc_is, const HcMacPrep *prep = nullptr) {
     HcMacPrep PR; memset(&PR, 0, sizeof PR); if (prep) PR = *prep;
     const int alpha = c->np, nl = level + 1, nt = nl + alpha;
     const int nb = c->nb, NB = nb <= 1 ? 1 : nb <= 2 ? 2 : HC_MAC_NB;                 // images per thread; more images = more image groups (blockIdx.z), each reading the key once
-#define HC_MAC_ALL(NN) hc_launch(c, "ks_mac_all", hc_k_ks_mac_all<NN>, dim3(HC_GX_MAC, (unsigned)nt, (unsigned)((nb + NN - 1) / NN)), (const u64 *)key.rows, cx, c->bs_poly, (const u64 *)S.digits, S.digits_is, acc, acc_is, (const HcMod *)c->d_mods, nl, c->nq, nt, alpha, key.beta, nb, PR, c->pack32 ? 3 : 0)
+#define HC_MAC_ALL(NN) hc_launch(c, "ks_mac_all", hc_k_ks_mac_all<NN>, dim3(HC_GX_MAC, (unsigned)nt, (unsigned)((nb + NN - 1) / NN)), (const u64 *)key.rows, cx, c->bs_poly, (const u64 *)S.digits, S.digits_is, acc, acc_is, (const HcMod *)c->d_mods, nl, c->nq, nt, alpha, key.beta, nb, PR, hc_pk_mac(c))
     return NB == 1 ? HC_MAC_ALL(1) : NB == 2 ? HC_MAC_ALL(2) : NB == 4 ? HC_MAC_ALL(4) : HC_MAC_ALL(8);
 #undef HC_MAC_ALL
 }
@@ -1391,18 +1422,20 @@ static int hc_ks_moddown(hc_ctx *c, int level, const u64 *acc, size_t acc_is, co
     const int alpha = c->np, nl = level + 1, nt = nl + alpha, nb = c->nb;
     // InvNTT of the P rows of both components: rows y -> modulus nq + y (nl = 0)
     const size_t yz = (size_t)(alpha + 1) * HC_N;
-    HC_TRY(hc_intt_mm(c, acc + (size_t)nl * HC_N, S.yv, alpha, 0, 2, (size_t)nt * HC_N, yz, 0, 0, nb, acc_is, 2 * yz, "moddown", false, P->yinv + nl, 0));      // as the y_i rows of the extension {P} -> Q (hc_ks_decompose_into)
+    HcInttCall mi; mi.rows = alpha; mi.nl = 0; mi.nz = 2; mi.images = nb; mi.in = {acc + (size_t)nl * HC_N, (size_t)nt * HC_N, acc_is, HC_ROWS_USER}; mi.out = {S.yv, yz, 2 * yz, HC_ROWS_LIB8}; mi.tag = "moddown";
+    mi.out_scale = P->yinv + nl; HC_TRY(hc_intt_mm(c, mi));         // as the y_i rows of the extension {P} -> Q (hc_ks_decompose_into)
     HC_TRY(hc_launch(c, "moddown:basis_v", hc_k_basis_v, dim3(HC_GX_YV, 2u * (unsigned)nb), S.yv, alpha + 1, (const HcBasisExt *)P->bxdown, nl, 0, 2));
     HcMmFuse F; F.ext_bs = P->bxdown; F.ext_rows = nl;            // {P} -> every Q limb inside the forward transform's first pass
+    HcNttCall m; m.rows = m.nl = nl; m.nz = 2; m.images = nb; m.in = {S.yv, yz, 2 * yz, HC_ROWS_LIB8}; m.tag = "moddown"; m.fuse = &F;
     if (rot_gal) {   // a rotation: + c0 and the permutation ride in ModDown's last pass (d0, d1 = the rotated ciphertext)
-        HC_TRY(hc_ntt_mm(c, S.yv, S.ext, nl, nl, 0, 0, 2, yz, (size_t)nl * HC_N, 0, nb, 2 * yz, S.ext_is, "moddown", &F));
+        m.out = {S.ext, (size_t)nl * HC_N, S.ext_is, HC_ROWS_USER}; HC_TRY(hc_ntt_mm(c, m));
         return hc_launch(c, "ks_moddown_rotate_mm", hc_k_ks_moddown_rotate_mm, dim3(HC_GX_ROT, (unsigned)nl, 2u * (unsigned)nb), (const u64 *)acc, (size_t)nt * HC_N, (const u64 *)S.ext, (size_t)nl * HC_N, rot_c0, d0, d1, (const HcMod *)c->d_mods, (const HcTw *)P->pinv, (u32)(rot_gal & 0x1FFFF),
                          acc_is, S.ext_is, c->bs_poly);
     }
     // (acc - NTT(ext)) / P, plus the addend if there is one (relinearisation: d_k + its key-switched part), in the epilogue of the extension's forward transform: d_k written once
     F.epi_x = acc; F.epi_x_zs = (size_t)nt * HC_N; F.epi_x_is = acc_is; F.epi_mul = P->pinv;
     if (add0) { F.epi_add = add0; F.epi_add_zs = (size_t)(add1 - add0); F.epi_add_is = c->bs_poly; }
-    return hc_ntt_mm(c, S.yv, d0, nl, nl, 0, 0, 2, yz, (size_t)(d1 - d0), 0, nb, 2 * yz, c->bs_poly, "moddown", &F);
+    m.out = {d0, (size_t)(d1 - d0), c->bs_poly, HC_ROWS_USER}; return hc_ntt_mm(c, m);
 }
 // ModDownSplitNTTPQ and the DivRoundByLastModulusNTT behind it as ONE forward transform per limb (relinearisation followed by Rescale: most multiplications of the
 // sine and the ReLU polynomials): d_k = Rescale((acc_k - NTT(ext_k)) / P + add_k), level -> level - 1. Both steps subtract a forward transform from the same limb:
@@ -1417,14 +1450,15 @@ static int hc_ks_moddown_rescale(hc_ctx *c, int level, u64 *acc, size_t acc_is, 
     if (!prepped)       // (the inner product of hc_keyswitch_add_rescale leaves row `level` as acc_L / P + add_L already: HcMacPrep)
     HC_TRY(hc_launch(c, "moddown:mdrs_prep", hc_k_mdrs_prep, dim3(HC_GX_YV, 2u * (unsigned)nb), acc, (size_t)nt * HC_N, acc_is, add0, add0 ? (size_t)(add1 - add0) : (size_t)0, c->bs_poly, level, (const HcTw *)P->pinv, (const HcMod *)c->d_mods));
     // InvNTT of row `level` and of the P rows of both components in one pair of launches: pc[z] = [u | the alpha P rows]
-    HC_TRY(hc_intt_mm(c, acc, S.pc - (size_t)level * HC_N, nt, nl, 2, (size_t)nt * HC_N, tz, 0, level, nb, acc_is, S.pc_is, "moddown", false, P->yinv1, 0));       // the P rows leave as y_i (hc_ks_decompose_into), row `level` as it is
+    HcInttCall mi; mi.rows = nt; mi.nl = nl; mi.skip_hi = mi.out_first_row = level; mi.nz = 2; mi.images = nb; mi.in = {acc, (size_t)nt * HC_N, acc_is, HC_ROWS_USER}; mi.out = {S.pc, tz, S.pc_is, HC_ROWS_LIB8}; mi.tag = "moddown";
+    mi.out_scale = P->yinv1; HC_TRY(hc_intt_mm(c, mi));             // the P rows leave as y_i (hc_ks_decompose_into), row `level` as it is
     // v of the P rows' extension and, with each coefficient's y_i / v in registers, t = u - ext_L / P on the row before them (what hc_k_mdrs_last did in a launch of its own)
     HC_TRY(hc_launch(c, "moddown:basis_yv", hc_k_basis_yv<true, true>, dim3(HC_GX_YV, 2u * (unsigned)nb), (const u64 *)(S.pc + HC_N), (size_t)HC_N, S.pc + HC_N, alpha + 2, (const HcBasisExt *)P->bxdown, nl, tz, 0, 2, S.pc_is,
                      (const HcBasisExt *)(P->bxdown + level), (const HcTw *)(P->pinv + level)));
     HcMmFuse F; F.ext_bs = P->bxdown; F.ext_rows = nl; F.lift_level = level; F.lift_t = S.pc; F.lift_t_zs = tz; F.lift_t_is = S.pc_is; F.lift_pmul = P->pmod;
     F.epi_x = acc; F.epi_x_zs = (size_t)nt * HC_N; F.epi_x_is = acc_is; F.epi_mul = P->pinv_qlinv;
     if (add0) { F.epi_add = add0; F.epi_add_zs = (size_t)(add1 - add0); F.epi_add_is = c->bs_poly; F.epi_add_mul = qlinv; }
-    return hc_ntt_mm(c, S.pc + HC_N, d0, level, level, 0, 0, 2, tz, (size_t)(d1 - d0), 0, nb, S.pc_is, c->bs_poly, "moddown", &F);
+    HcNttCall m; m.rows = m.nl = level; m.nz = 2; m.images = nb; m.in = {S.pc + HC_N, tz, S.pc_is, HC_ROWS_LIB8}; m.out = {d0, (size_t)(d1 - d0), c->bs_poly, HC_ROWS_USER}; m.tag = "moddown"; m.fuse = &F; return hc_ntt_mm(c, m);
 }
 // phase 2: inner product with the key (both components), then ModDownSplitNTTPQ
 static int hc_ks_apply_from(hc_ctx *c, const HcSwk &key, int level, const u64 *cx, const HcKsScratch &S, u64 *d0, u64 *d1, uint64_t rot_gal = 0, const u64 *rot_c0 = nullptr, const u64 *add0 = nullptr, const u64 *add1 = nullptr) {
@@ -1584,7 +1618,7 @@ extern "C" int hc_keyswitch_qp_rotate_many(hc_ctx *c, int nrot, const uint64_t *
             }
             F.pc0 = (const u64 *)pc0; F.pc0_is = c->bs_poly; F.out_is = c->bs_qp;
         }
-#define HC_MAC_MULTI(RR, NN) hc_launch(c, "ks_mac_multi", beta >= 3 ? (c->rot_fuse ? hc_k_ks_mac_multi<RR, NN, true, true> : hc_k_ks_mac_multi<RR, NN, false, true>) : (c->rot_fuse ? hc_k_ks_mac_multi<RR, NN, true, false> : hc_k_ks_mac_multi<RR, NN, false, false>), grid, K, nr, (const u64 *)cx, c->bs_poly, (const u64 *)S.digits, S.digits_is, c->ws_accm, acc_rs, acc_is, (const HcMod *)c->d_mods, nl, c->nq, nt, alpha, beta, nb, c->pack32 ? 3 : 0, F)
+#define HC_MAC_MULTI(RR, NN) hc_launch(c, "ks_mac_multi", beta >= 3 ? (c->rot_fuse ? hc_k_ks_mac_multi<RR, NN, true, true> : hc_k_ks_mac_multi<RR, NN, false, true>) : (c->rot_fuse ? hc_k_ks_mac_multi<RR, NN, true, false> : hc_k_ks_mac_multi<RR, NN, false, false>), grid, K, nr, (const u64 *)cx, c->bs_poly, (const u64 *)S.digits, S.digits_is, c->ws_accm, acc_rs, acc_is, (const HcMod *)c->d_mods, nl, c->nq, nt, alpha, beta, nb, hc_pk_mac(c), F)
         if (NB == 8) HC_TRY(HC_MAC_MULTI(2, 8)); else if (NB == 4) HC_TRY(HC_MAC_MULTI(4, 4)); else if (NB == 2) HC_TRY(HC_MAC_MULTI(8, 2)); else HC_TRY(HC_MAC_MULTI(8, 1));
 #undef HC_MAC_MULTI
         if (!c->rot_fuse)
@@ -1691,15 +1725,6 @@ extern "C" int hc_qp_mul_sum2(hc_ctx *c, int level, int nterms, const uint64_t *
 }
 
 // ------------------------------------------------------------------ L1
-static int hc_ensure_cts(hc_ctx *c, size_t rows) {
-    if (c->ws_cts_rows >= rows) return HC_OK;
-    HC_HIP(c, hipStreamSynchronize(c->stream));
-    if (c->ws_cts) HC_HIP(c, hcx_free(c, c->ws_cts));
-    c->ws_cts = nullptr; c->ws_cts_rows = 0;
-    HC_HIP(c, hcx_malloc(c, (void **)&c->ws_cts, rows * HC_N * sizeof(u64)));
-    c->ws_cts_rows = rows;
-    return HC_OK;
-}
 // scale bookkeeping of conv.go:527-528 (MulNew, SetScale = MultByConst + Rescale) -> per-limb constants
 static int hc_loopA_consts(hc_ctx *c, double ct_scale, double ker_scale, int max_ob, int norm, double out_scale, u64 cst[2], double *target) {
     if (c->nq < 2) return hc_fail(c, HC_ERR_STATE, "conv: needs the level-1 modulus chain (nq >= 2)");
@@ -1867,7 +1892,8 @@ extern "C" int hc_encode_slots(hc_ctx *c, double *values, int count, int level, 
     HC_TRY(hc_launch(c, "sfft_inv_a", hc_k_sfft_inv_a, dim3(16, (unsigned)count), (const HcCplx *)v, v, E));
     HC_TRY(hc_launch(c, "sfft_inv_b", hc_k_sfft_inv_b, dim3(16, (unsigned)count), (const HcCplx *)v, v, E));
     HC_TRY(hc_launch(c, "slots_round", hc_k_slots_round, dim3(64, (unsigned)count), (const HcCplx *)v, (u64 *)out, (const HcMod *)c->d_mods, level + 1, scale));
-    if (to_ntt) { c->hoist_cx = nullptr; HC_TRY(hc_ntt_mm(c, (const u64 *)out, (u64 *)out, level + 1, level + 1, 0, 0, count, (size_t)(level + 1) * HC_N, (size_t)(level + 1) * HC_N)); }
+    HcNttCall m; m.rows = m.nl = level + 1; m.nz = count; m.in = {out, (size_t)(level + 1) * HC_N, 0, HC_ROWS_USER}; m.out = {out, (size_t)(level + 1) * HC_N, 0, HC_ROWS_USER};
+    if (to_ntt) { c->hoist_cx = nullptr; HC_TRY(hc_ntt_mm(c, m)); }
     return HC_OK;
 }
 // ckks.Encoder.EncodeCoeffs (+ ToNTT): one launch rounds every coefficient into all limbs of the level, the batched forward transform follows. The one-word flag the kernel
@@ -1883,7 +1909,8 @@ extern "C" int hc_encode_coeffs(hc_ctx *c, const double *values, int count, int 
     HC_HIP(c, hipMemcpyAsync(&flag, c->d_flag, sizeof flag, hipMemcpyDeviceToHost, c->stream));
     HC_HIP(c, hipStreamSynchronize(c->stream));
     if (flag) return hc_fail(c, HC_ERR_UNSUPPORTED, "hc_encode_coeffs: a value times the scale exceeds 2^64 or is not finite (scaleUpVecExact's big-float branch is not built)");
-    if (to_ntt) { c->hoist_cx = nullptr; HC_TRY(hc_ntt_mm(c, (const u64 *)out, (u64 *)out, level + 1, level + 1, 0, 0, count, (size_t)(level + 1) * HC_N, (size_t)(level + 1) * HC_N)); }
+    HcNttCall m; m.rows = m.nl = level + 1; m.nz = count; m.in = {out, (size_t)(level + 1) * HC_N, 0, HC_ROWS_USER}; m.out = {out, (size_t)(level + 1) * HC_N, 0, HC_ROWS_USER};
+    if (to_ntt) { c->hoist_cx = nullptr; HC_TRY(hc_ntt_mm(c, m)); }
     return HC_OK;
 }
 // Harness-side sk-encryption (include/hconv.h): per chunk of at most HC_MAXCTS images one launch forms e + m for all limbs, one batched transform takes it to the NTT
@@ -1899,14 +1926,14 @@ extern "C" int hc_encrypt_sk(hc_ctx *c, int count, int level, const uint64_t *pt
     HcScratch S(c);
     const int chunk = count < HC_MAXCTS ? count : HC_MAXCTS;
     u64 *t = nullptr; HC_HIP(c, S.alloc(&t, (size_t)chunk * nl * HC_N * sizeof(u64)));
-    HcMmFuse Fraw; Fraw.raw = true;                                          // limbs 0 and 1: 8-byte rows under every pack32
     c->hoist_cx = nullptr;
     for (int z0 = 0; z0 < count; z0 += chunk) {
         const int n = count - z0 < chunk ? count - z0 : chunk;
         HcCtPtrs O; memset(&O, 0, sizeof O); for (int z = 0; z < n; z++) O.p[z] = (u64 *)ct_out[z0 + z];
         E.z0 = z0;
         HC_TRY(hc_launch(c, "enc_sample", hc_k_enc_sample, dim3(64, (unsigned)n), (const u64 *)pt + (size_t)z0 * nl * HC_N, t, (const HcMod *)c->d_mods, E));
-        HC_TRY(hc_ntt_mm(c, t, t, nl, nl, 0, 0, n, (size_t)nl * HC_N, (size_t)nl * HC_N, 0, 1, 0, 0, "ntt", &Fraw));
+        HcNttCall m; m.rows = m.nl = nl; m.nz = n; m.in = {t, (size_t)nl * HC_N, 0, HC_ROWS_RAW}; m.out = {t, (size_t)nl * HC_N, 0, HC_ROWS_RAW};      // limbs 0 and 1: 8-byte rows under every pack32
+        HC_TRY(hc_ntt_mm(c, m));
         HC_TRY(hc_launch(c, "enc_finish", hc_k_enc_finish, dim3(64, (unsigned)nl, (unsigned)n), (const u64 *)t, (const u64 *)sk_ntt, O, (const HcMod *)c->d_mods, E));
     }
     return HC_OK;
@@ -1929,7 +1956,8 @@ extern "C" int hc_decrypt_decode_coeffs(hc_ctx *c, int count, int level, const u
         const int n = count - z0 < chunk ? count - z0 : chunk;
         HcCtPtrs I; memset(&I, 0, sizeof I); for (int z = 0; z < n; z++) I.p[z] = (u64 *)ct[z0 + z];
         HC_TRY(hc_launch(c, "dec_combine", hc_k_dec_combine, dim3(64, (unsigned)nl, (unsigned)n), I, (const u64 *)sk_ntt, t, (const HcMod *)c->d_mods, nl));
-        HC_TRY(hc_intt_mm(c, t, t, nl, nl, n, (size_t)nl * HC_N, (size_t)nl * HC_N));
+        HcInttCall m; m.rows = m.nl = nl; m.nz = n; m.in = {t, (size_t)nl * HC_N, 0, HC_ROWS_USER}; m.out = {t, (size_t)nl * HC_N, 0, HC_ROWS_LIB8};      // t: limbs 0 and 1, written by HcMod::row32 and read as a caller's rows
+        HC_TRY(hc_intt_mm(c, m));
         HC_TRY(hc_launch(c, "dec_decode", hc_k_dec_decode, dim3(64, (unsigned)n), (const u64 *)t, out + (size_t)z0 * HC_N, (const HcMod *)c->d_mods, nl, scale, q0inv_m));
     }
     return HC_OK;
@@ -1982,11 +2010,7 @@ extern "C" int hc_set_option(hc_ctx *c, const char *name, long value) {
         if (((value == 0) != (c->pack32 == 0)) && !c->swk.empty()) return hc_fail(c, HC_ERR_STATE, "pack32: switching keys are already stored in the other form");
         HC_ENTER(c); HC_HIP(c, hipStreamSynchronize(c->stream));
         c->pack32 = (int)value; c->hoist_cx = nullptr;
-        std::vector<HcMod> hm; for (auto &mh : c->mods) { mh.m.row32 = (value == 2 && mh.m.q < (1ull << 31)) ? 1 : 0; hm.push_back(mh.m); }
-        // limbs 0 and 1 are what the convolution's entry points, hc_div_round_last_n's level-1 branch and hc_swk_generate's sk rows read as 8-byte rows
-        if (value == 2 && c->mods.size() > 1 && (hm[0].row32 || hm[1].row32)) {
-            for (size_t l = 0; l < 2; l++) { c->mods[l].m.row32 = 0; hm[l].row32 = 0; }
-        }
+        std::vector<HcMod> hm; for (auto &mh : c->mods) { mh.m.row32 = hc_row32(c->pack32, mh.m.q, hm.size(), c->mods.size()); hm.push_back(mh.m); }
         HC_HIP(c, hcx_h2d(c, c->d_mods, hm.data(), hm.size() * sizeof(HcMod)));
         return HC_OK;
     }

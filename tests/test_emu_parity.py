@@ -303,3 +303,44 @@ def test_the_library_reads_no_environment_and_refuses_more_than_five_special_pri
     six = pc.P_CHAIN + [0x1FFFFFFFFF380001]
     with pytest.raises(HconvError, match="at most 5"):
         Context(pc.Q_MIX[:3], six, lib_path=EMU_LIB)
+
+
+_WIDTH_CHAIN = (pc.Q_MIX[:4], pc.P_CHAIN[:1])      # limbs 0 and 1 large, limbs 2 and 3 below 2^31, one special prime: the smallest context on which every kind of row exists
+_width_reference = {}
+
+
+def _width_case():
+    """inputs and the oracle's residues of the row-width test below, computed once for its three settings"""
+    if not _width_reference:
+        import numpy as np
+        from oracle_lib import splitmix_rows
+        (Q, P), level, N = _WIDTH_CHAIN, 3, pc.N
+        O = Oracle(q=Q, p=P)
+        a, b = (np.stack([splitmix_rows(0x41D7 + 97 * s + l, Q[l], N) for l in range(level + 1)]) for s in (1, 2))
+        evk = np.stack([np.stack([np.stack([splitmix_rows(0x6000 + (d * 2 + k) * 16 + T, (Q + P)[T], N) for T in range(level + 2)]) for k in range(2)]) for d in range(level + 1)])
+        rows = lambda fn, x: np.stack([np.asarray(fn(l, x[l])).reshape(-1) for l in range(level + 1)])
+        _width_reference.update(a=a, b=b, evk=evk, ntt=rows(O.ntt, a), intt=rows(O.intt, a), rescale=(O.div_round_last(level, a), O.div_round_last(level, b)), ks=O.keyswitch(level, a, evk))
+    return _width_reference
+
+
+@pytest.mark.parametrize("pack32", [0, 1, 2])
+def test_row_widths_of_the_batched_transforms(pack32):
+    """The truth table above hc_pk (hconv.hip), pinned under every setting of option pack32 on the smallest context where all its branches are live: a caller's operands into
+    and out of both transforms (hc_lv_ntt, hc_lv_intt), a coefficient-domain scratch array between an inverse transform and a forward transform with the lift prologue and
+    the epilogue (Rescale at level 3), the packed digits and the extension's y_i rows (one key switch at level 3: four digits, ModDown). The binding converts a caller's
+    4-byte rows at the boundary, so the oracle's residues must come back under every setting. (Limbs 0 and 1 are large here: what a context with a small limb 0 or 1
+    does under pack32 = 2 is ADVICE.md's open finding and is not stated.)"""
+    subprocess.check_call(["make", "-s", "-C", EMU_DIR, EMU_LIB])
+    (Q, P), level, R = _WIDTH_CHAIN, 3, _width_case()
+    assert [q < 1 << 31 for q in Q] == [False, False, True, True] and P[0] > 1 << 31
+    ctx = Context(Q, P, lib_path=EMU_LIB)
+    ctx.set_option("pack32", pack32)
+    assert ctx.row32() == [False, False, pack32 == 2, pack32 == 2] and not ctx.L.hc_row_is32(ctx.h, 4)
+    pc.eq(ctx.lv_ntt(level, R["a"]), R["ntt"], f"lv_ntt pack32={pack32}")
+    pc.eq(ctx.lv_intt(level, R["a"]), R["intt"], f"lv_intt pack32={pack32}")
+    d = ctx.div_round_last2(level, R["a"], R["b"])
+    pc.eq(d[0], R["rescale"][0], f"div_round_last2 [0] pack32={pack32}"); pc.eq(d[1], R["rescale"][1], f"div_round_last2 [1] pack32={pack32}")
+    ctx.swk_load(5, level, R["evk"])
+    g0, g1 = ctx.keyswitch(5, level, R["a"])
+    pc.eq(g0, R["ks"][0], f"keyswitch d0 pack32={pack32}"); pc.eq(g1, R["ks"][1], f"keyswitch d1 pack32={pack32}")
+    ctx.close()
