@@ -241,22 +241,25 @@ class Context:
             self._row32 = None
 
     # ---- 4-byte rows (include/hconv.h; option pack32 = 2): the numpy-in / numpy-out conveniences below convert at the boundary, as a binding must. `nl` = the Q rows per
-    # polynomial (rows nl .. per-1 of each group of `per` rows are special primes: large); row r of a group <-> limb r
+    # polynomial (rows nl .. per-1 of each group of `per` rows are the special primes); row r of a group <-> limb r, or special prime r - nl
     def row32(self):
         if getattr(self, "_row32", None) is None:
             self._row32 = [bool(self.L.hc_row_is32(self.h, m)) for m in range(len(self.q))]
         return self._row32
 
+    def _group_row32(self, nl, per):
+        """row32 of the `per` rows of one group: nl limbs, then special primes"""
+        return self.row32()[:nl] + [bool(self.L.hc_row_is32(self.h, len(self.q) + j)) for j in range(per - nl)]
+
     def pack_rows(self, arr, nl, per=None):
         a = np.ascontiguousarray(arr, dtype=np.uint64).reshape(-1, self.N).copy()
-        r32 = self.row32()
-        if not any(r32[:nl]):
-            return a.reshape(np.shape(arr))
         per = per or nl
+        r32 = self._group_row32(nl, per)
+        if not any(r32):
+            return a.reshape(np.shape(arr))
         v = a.view(np.uint32).reshape(a.shape[0], 2 * self.N)
         for r in range(a.shape[0]):
-            T = r % per
-            if T < nl and r32[T]:
+            if r32[r % per]:
                 low = (a[r] & np.uint64(0xFFFFFFFF)).astype(np.uint32)
                 v[r, : self.N] = low
                 v[r, self.N:] = 0xDEADBEEF          # the unused half of the slot: poisoned so that a kernel that reads 8-byte words there cannot pass
@@ -264,14 +267,13 @@ class Context:
 
     def unpack_rows(self, arr, nl, per=None):
         a = np.ascontiguousarray(arr, dtype=np.uint64).reshape(-1, self.N).copy()
-        r32 = self.row32()
-        if not any(r32[:nl]):
-            return a.reshape(np.shape(arr))
         per = per or nl
+        r32 = self._group_row32(nl, per)
+        if not any(r32):
+            return a.reshape(np.shape(arr))
         v = np.ascontiguousarray(arr, dtype=np.uint64).reshape(-1, self.N).view(np.uint32).reshape(a.shape[0], 2 * self.N)
         for r in range(a.shape[0]):
-            T = r % per
-            if T < nl and r32[T]:
+            if r32[r % per]:
                 a[r] = v[r, : self.N].astype(np.uint64)
         return a.reshape(np.shape(arr))
 

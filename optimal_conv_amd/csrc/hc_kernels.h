@@ -1778,14 +1778,16 @@ __device__ __forceinline__ void hc_basis_ext_tile32(u32 (&e)[16], const u64 *yv,
 }
 struct HcRowMod { HcTwTab fwd, inv; u64 q, mu;
                   HcTwTab32 fwd32, inv32;   // moduli below 2^31 (null otherwise)
-                  u64 s32; };            // nonzero: the batched transforms take their 32-bit form for rows of this modulus: q < 2^31 and option small32 (in the table the
+                  u64 s32;               // nonzero: the batched transforms take their 32-bit form for rows of this modulus: q < 2^31 and option small32 (in the table the
                                          // kernels read their moduli from, so that the option costs no launch argument; the kernels test HC_SMALL_Q(q) && s32)
+                  u64 row32; };          // HcMod::row32 of this modulus: its rows in a caller's leveled operand are 4-byte words (HC_PK_ROW, hc_mm_row_widths)
 // blockIdx.z = operand + nz * image: `nz` operands zs_* words apart (the two polynomials of a ciphertext, the digits of a key switch), and the
 // images of a batch (hc_set_batch) is_* words apart
 struct HcMm { const HcRowMod *M; int nl, nq, skip_lo, skip_hi; size_t zs_in, zs_out; int z_alpha; int nz; size_t is_in, is_out;
               int xcd, nzn;                  // rows passes: XCD-aware 1-D grid over nzn = nz * images operands (HC_MM_PROLOGUE_ROWS)
               int out_gap;                   // hc_k_cols_inv_canon_mm: > 0: row y of the output goes to row y + y / out_gap (one free row after every out_gap rows: the v row of a digit's y_i rows)
-              int pk_in, pk_out, pk_epi;     // the rows of `in` / `out` / the epilogue's operands (epi_x, epi_add and the result) whose modulus is below 2^31 are 4-byte words
+              int pk_in, pk_out, pk_epi;     // the rows of `in` / `out` / the epilogue's operands (epi_x, epi_add and the result) whose modulus is below 2^31 are 4-byte words:
+                                             // HC_PK_ALL for every such modulus, HC_PK_ROW for those whose HcRowMod::row32 is set (after hc_mm_row_widths: non-zero or zero)
               int gap_lo, gap_len;           // blockIdx.y -> row: y + (y >= gap_lo ? gap_len : 0) - the rows [gap_lo, gap_lo + gap_len) a launch has nothing to do for are left out of the
                                              // grid. (Arithmetic since round 6: as a 48-byte table in the kernel arguments the lookup was a vector load and a full wait in front of every
                                              // workgroup's first load: -1.1 % per ciphertext-layer at 4 images per launch set, -2.3 % at one.)
@@ -1810,9 +1812,16 @@ __device__ __forceinline__ bool hc_mm_skip(const HcMm &A, int y, int zi) {
     return y >= A.skip_lo && y < A.skip_hi;
 }
 __device__ __forceinline__ int hc_mm_mod(const HcMm &A, int y) { return y < A.nl ? y : A.nq + (y - A.nl); }
+// pk_in / pk_out / pk_epi as the host sets them, and as the bodies below test them once the row's modulus is known. NOTE for a reader of a body: every kernel here takes
+// `HcMm A` BY VALUE and its HC_MM_PROLOGUE(_ROWS) rewrites A.pk_* for the workgroup's row (hc_mm_row_widths) before any body runs; the bodies take `const HcMm &` and so see
+// "this row's words are 4 bytes wide" as non-zero, whatever kind of array the host named (HC_PK_ROW is gone by then unless the row's HcRowMod::row32 is set)
+enum { HC_PK_ALL = 1, HC_PK_ROW = 2 };
+__device__ __forceinline__ void hc_mm_row_widths(HcMm &A, const HcRowMod &R) {          // block-uniform
+    if (!R.row32) { A.pk_in &= HC_PK_ALL; A.pk_out &= HC_PK_ALL; A.pk_epi &= HC_PK_ALL; }
+}
 #define HC_MM_PROLOGUE \
     const int y = (int)blockIdx.y + ((int)blockIdx.y >= A.gap_lo ? A.gap_len : 0), zi = (int)blockIdx.z % A.nz, img = (int)blockIdx.z / A.nz; if (hc_mm_skip(A, y, zi)) return; \
-    const HcRowMod R = hc_const_copy(&A.M[hc_mm_mod(A, y)]); \
+    const HcRowMod R = hc_const_copy(&A.M[hc_mm_mod(A, y)]); hc_mm_row_widths(A, R); \
     in += (size_t)zi * A.zs_in + (size_t)img * A.is_in; out += (size_t)zi * A.zs_out + (size_t)img * A.is_out;
 // The rows passes read PER-ROW twiddles: 255 (w, w') pairs = 4 KB for every 2 KB row of data, the same for every operand and image of the launch. With the operand index in
 // blockIdx.z the workgroups sharing a twiddle slice were a whole (tiles x rows) sweep apart and, consecutive workgroup ids going round-robin over the 8 XCDs, on different L2s:
@@ -1823,7 +1832,7 @@ __device__ __forceinline__ int hc_mm_mod(const HcMm &A, int y) { return y < A.nl
     if (A.xcd) { const unsigned id = blockIdx.x, rest = id >> 3, p = (rest / (unsigned)A.nzn) * 8 + (id & 7); bx = (int)(p & 15); by_ = (int)(p >> 4); bz_ = (int)(rest % (unsigned)A.nzn); } \
     else { bx = (int)blockIdx.x; by_ = (int)blockIdx.y; bz_ = (int)blockIdx.z; } \
     const int y = by_ + (by_ >= A.gap_lo ? A.gap_len : 0), zi = bz_ % A.nz, img = bz_ / A.nz; if (hc_mm_skip(A, y, zi)) return; \
-    const HcRowMod R = hc_const_copy(&A.M[hc_mm_mod(A, y)]); \
+    const HcRowMod R = hc_const_copy(&A.M[hc_mm_mod(A, y)]); hc_mm_row_widths(A, R); \
     in += (size_t)zi * A.zs_in + (size_t)img * A.is_in; out += (size_t)zi * A.zs_out + (size_t)img * A.is_out;
 // (Round 4, measured and not kept - profiles/round4_chain_class_paths_ab.txt: butterflies per modulus class inside these kernels - 32-bit canonical arithmetic for the
 // chain's eleven ~30-bit limbs, the fold-free 64-bit form below 2^57 - as a block-uniform switch cost 108-132 VGPRs against 65-86 and only won the lost occupancy back;

@@ -331,10 +331,10 @@ extern "C" const char *hc_last_error(const hc_ctx *c) { return c ? c->err.c_str(
 // HcMod::row32 of modulus i of the context's nmods (Q then P): under pack32 = 2 the rows of a modulus below 2^31 in the caller's leveled operands are 4-byte words - except
 // limbs 0 and 1, which are what the convolution's entry points, hc_div_round_last_n's level-1 branch and hc_swk_generate's sk rows read as 8-byte rows
 static int hc_row32(int pack32, u64 q, size_t i, size_t nmods) { return pack32 == 2 && q < (1ull << 31) && !(i < 2 && nmods > 1); }
-// the per-modulus table of the batched transforms (HcRowMod); again after option small32 changes
+// the per-modulus table of the batched transforms (HcRowMod); again after option small32 or pack32 changes
 static int hc_upload_rowmods(hc_ctx *c) {
     std::vector<HcRowMod> hr;
-    for (auto &mh : c->mods) { HcRowMod r; r.fwd = mh.fwd; r.inv = mh.inv; r.fwd32 = mh.fwd32; r.inv32 = mh.inv32; r.q = mh.m.q; r.mu = mh.m.mu; r.s32 = (c->small32 && mh.m.q < (1ull << 31)) ? 1 : 0; hr.push_back(r); }
+    for (auto &mh : c->mods) { HcRowMod r; r.fwd = mh.fwd; r.inv = mh.inv; r.fwd32 = mh.fwd32; r.inv32 = mh.inv32; r.q = mh.m.q; r.mu = mh.m.mu; r.s32 = (c->small32 && mh.m.q < (1ull << 31)) ? 1 : 0; r.row32 = mh.m.row32 ? 1 : 0; hr.push_back(r); }
     return hcx_h2d(c, c->d_rowmods, hr.data(), hr.size() * sizeof(HcRowMod)) == hipSuccess ? HC_OK : HC_ERR_HIP;
 }
 extern "C" int hc_ctx_create(hc_ctx **out, int logN, const uint64_t *q, int nq, const uint64_t *p, int np, int device) {
@@ -640,7 +640,7 @@ enum HcRows { HC_ROWS_USER,        // a caller's leveled operand, and the librar
               HC_ROWS_PACKED,      // a library array read only by kernels that expect 4-byte rows for the small moduli (the digits of a key switch): 4-byte rows unless pack32 = 0
               HC_ROWS_RAW,         // 8-byte rows whatever the option: the rows of a switching key while it is being generated, limbs 0 and 1 in the encryptor
               HC_ROWS_SEAM };      // ws_tmp between the two passes, which never leaves the library: follows pack32
-// HcMm::pk_in / pk_out / pk_epi for rows of that kind (the kernels test them for non-zero, together with HC_SMALL_Q of the row's modulus). The one place that decides a width.
+// HcMm::pk_in / pk_out / pk_epi for rows of that kind (the kernels reduce them by the row's modulus - hc_mm_row_widths - and then test them for non-zero, together with HC_SMALL_Q of that modulus). The one place that decides a width.
 // Per call site, under pack32 = 0 / 1 / 2 (-: the kernel does not read the field there: a fused prologue forms the input, or there is no epilogue):
 //                                                                              pass 1 (in -> seam)   pass 2 (seam -> out)
 //   forward (hc_ntt_mm)                         in        out                  pk_in    pk_out       pk_in    pk_out   pk_epi
@@ -654,11 +654,12 @@ enum HcRows { HC_ROWS_USER,        // a caller's leveled operand, and the librar
 //   hc_lv_intt                                  USER      USER                 0/0/1    0/1/1        0/1/1    0/0/1    0
 //   hc_lv_mod_raise, Rescale, decomposition,    USER      LIB8                 0/0/1    0/1/1        0/1/1    0/0/0    0
 //   ModDown (+ Rescale), hc_decrypt_decode_coeffs (its t is read as USER rows)
-// Known disagreement (the medium finding; its fix belongs here): under pack32 = 2 on a context whose limb 0 or 1 is below 2^31, hc_row32 says 8-byte rows for those
-// two limbs - what every kernel that goes by HcMod::row32 reads and writes - while USER below says 4-byte rows for every small modulus. The contexts the product builds have
-// large limbs 0 and 1.
+// A 1 in the table is HC_PK_ALL for PACKED and SEAM rows - every modulus below 2^31 - and HC_PK_ROW for USER rows: the moduli whose HcMod::row32 is set, which the kernels
+// read from their own table (HcRowMod::row32, a copy of HcMod::row32: hc_upload_rowmods). So a USER row has the width that hc_row32 gives its modulus, in the transforms as
+// in every kernel that goes by HcMod::row32: limbs 0 and 1 of a context with more than one modulus are 8-byte rows under pack32 = 2 whatever their size
+// (tests/test_emu_chain_edges.py, tests/test_gpu_a_chain_edges.py: chains whose limb 0 or 1 is below 2^31).
 static int hc_pk(const hc_ctx *c, HcRows rows) {
-    switch (rows) { case HC_ROWS_USER: return c->pack32 == 2; case HC_ROWS_PACKED: case HC_ROWS_SEAM: return c->pack32 != 0; case HC_ROWS_LIB8: case HC_ROWS_RAW: break; }
+    switch (rows) { case HC_ROWS_USER: return c->pack32 == 2 ? HC_PK_ROW : 0; case HC_ROWS_PACKED: case HC_ROWS_SEAM: return c->pack32 != 0 ? HC_PK_ALL : 0; case HC_ROWS_LIB8: case HC_ROWS_RAW: break; }
     return 0;
 }
 // the inner products' `pk` (hc_k_ks_mac_all / _multi, tested for non-zero): bit 0 the digits (HC_ROWS_PACKED), bit 1 the switching key's rows (hc_k_pack32_rows, under the same rule)
@@ -2012,7 +2013,7 @@ extern "C" int hc_set_option(hc_ctx *c, const char *name, long value) {
         c->pack32 = (int)value; c->hoist_cx = nullptr;
         std::vector<HcMod> hm; for (auto &mh : c->mods) { mh.m.row32 = hc_row32(c->pack32, mh.m.q, hm.size(), c->mods.size()); hm.push_back(mh.m); }
         HC_HIP(c, hcx_h2d(c, c->d_mods, hm.data(), hm.size() * sizeof(HcMod)));
-        return HC_OK;
+        return hc_upload_rowmods(c);
     }
     return hc_fail(c, HC_ERR_ARG, "unknown option %s", name);
 }

@@ -299,23 +299,71 @@ Q1_BL = 0x10000000006E0001
 Q_MIX = [Q0, Q1_BL, 0x3FFC0001, 0x40080001, 0x1000000000B00001, 0x3FFFFE80001, 0x3FAC0001]
 P_CHAIN = [0x1FFFFFFFFFE00001, 0x1FFFFFFFFFC80001, 0x1FFFFFFFFFB40001, 0x1FFFFFFFFF500001, 0x1FFFFFFFFF420001]
 
+# Chains (Q, P) for the leveled entry points beyond the three the product builds: hc_ctx_create takes any NTT-friendly primes below 2^61, in any order. Every modulus is
+# prime and 1 mod 2^17.
+CHAIN_SMALL01 = ([0x3FFC0001, 0x40080001, 0x3FAC0001, Q_MIX[4]], P_CHAIN[:1])              # limbs 0 and 1 below 2^31: 8-byte rows under every pack32 (hc_row32's exception)
+CHAIN_SMALL0 = ([0x3FFC0001, Q1_BL, 0x40080001, Q_MIX[5]], P_CHAIN[:2])                    # only limb 0 small
+CHAIN_ALLSMALL = ([0x7FFE0001, 0x7FF80001, 0x3FFC0001, 0x40080001], [P_CHAIN[0], 0x120001])      # no large limb at all, one 21-bit special prime
+_Q_EDGES = [Q0, Q1_BL, 0x7FFE0001, 0x80140001, 0xC0001, 0x7FF80001]                         # just below 2^31 (the top of the 32-bit class), just above (the smallest q on the 64-bit bodies), 20 bits
+CHAIN_EDGES = (_Q_EDGES, P_CHAIN[:1])
+CHAIN_EDGES2 = (_Q_EDGES, P_CHAIN[:2])                                                      # two-limb digits that mix the classes
+CHAIN_SIZES = ([Q0, Q1_BL, 0xFFF00001, 0x100180001, 0x1FFFFFFEA0001, 0x20000001A0001, 0x1FFFFFFFFFC0001, 0x2000000003A0001],      # either side of 2^32, 2^49, 2^57
+               [0x3FFFFFFFFBE0001, 0x400000000360001])                                      # either side of 2^58: the inner products' lazy-sum branch
+CHAIN_ONE = ([0x7FFE0001], [])                                                              # nmods == 1: the other arm of hc_row32's exception; no special prime, so no key switch
+CHAINS = {"small01": CHAIN_SMALL01, "small0": CHAIN_SMALL0, "allsmall": CHAIN_ALLSMALL, "edges": CHAIN_EDGES, "edges2": CHAIN_EDGES2, "sizes": CHAIN_SIZES, "one": CHAIN_ONE}
 
-def case_keyswitch_general(make_ctx, make_oracle, shapes=((1, 2), (0, 1), (2, 2), (3, 2), (4, 3), (4, 5)), chain=None):
+
+def expected_row32(chain, pack32):
+    """HcMod::row32 of the chain's Q limbs, as the comment above hc_pk (hconv.hip) states it: under pack32 = 2 a modulus below 2^31 has 4-byte rows, except limbs 0 and 1 of a
+    context with more than one modulus"""
+    Q, P = chain
+    return [pack32 == 2 and q < 1 << 31 and not (i < 2 and len(Q) + len(P) > 1) for i, q in enumerate(Q)]
+
+
+def edge_row(seed, q):
+    """one operand row of the rows="edge" mode: all 0, all q-1, alternating 0 / q-1 in either phase, or one of the rows edge_rows(q) holds, chosen by the seed; q-1 rows are the most
+    frequent, since they are what the lazy sums and the 4-byte seams have to hold"""
+    k = (int(seed) * 0x9E3779B1 >> 11) % 8
+    if k < 3:
+        return np.full(N, q - 1, dtype=np.uint64)
+    if k == 3:
+        return np.zeros(N, dtype=np.uint64)
+    if k == 4:
+        r = np.full(N, q - 1, dtype=np.uint64); r[::2] = 0
+        return r
+    r = np.zeros(N, dtype=np.uint64)
+    if k == 5:
+        r[:] = q - 1
+    elif k == 6:
+        r[N - 1] = 1                           # edge_rows(q)'s single 1
+    else:
+        r[::2] = q - 1                         # and its q-1 at the even places
+    return r
+
+
+def row_source(rows):
+    """rows="random": uniform residues (splitmix_rows); rows="edge": edge_row"""
+    assert rows in ("random", "edge"), rows
+    return (lambda seed, q: splitmix_rows(seed, q, N)) if rows == "random" else edge_row
+
+
+def case_keyswitch_general(make_ctx, make_oracle, shapes=((1, 2), (0, 1), (2, 2), (3, 2), (4, 3), (4, 5)), chain=None, rows="random"):
     """hc_keyswitch vs or_keyswitch for (level, alpha): single- and multi-limb digits, several digits, targets smaller
     than sources (30-bit limbs), and the level-0/one-prime case that must also equal the fused path's key switch.
     chain = (Q, P): other moduli than the mixed test chain (e.g. the bootstrapping chain with two special primes: seven and more digits, where the inner product's 128-bit
-    sums are folded between digits)"""
+    sums are folded between digits); rows: row_source"""
+    gen = row_source(rows)
     for level, alpha in shapes:
         Q, P = (chain[0][: level + 1], chain[1][:alpha]) if chain else (Q_MIX[: level + 1], P_CHAIN[:alpha])
         ctx, O = make_ctx(Q, P), make_oracle(Q, P)
         beta = (level + 1 + alpha - 1) // alpha
-        cx = np.stack([splitmix_rows(900 + 7 * level + l, Q[l], N) for l in range(level + 1)])
+        cx = np.stack([gen(900 + 7 * level + l, Q[l]) for l in range(level + 1)])
         evk = np.empty((beta, 2, level + 1 + alpha, N), dtype=np.uint64)
         for d in range(beta):
             for k in range(2):
                 for T in range(level + 1 + alpha):
                     q = Q[T] if T <= level else P[T - level - 1]
-                    evk[d, k, T] = splitmix_rows(5000 + ((d * 2 + k) * 64 + T) * 3 + alpha, q, N)
+                    evk[d, k, T] = gen(5000 + ((d * 2 + k) * 64 + T) * 3 + alpha, q)
         ctx.swk_load(77, level, evk)
         g0, g1 = ctx.keyswitch(77, level, cx)
         w0, w1 = O.keyswitch(level, cx, evk)
@@ -323,13 +371,23 @@ def case_keyswitch_general(make_ctx, make_oracle, shapes=((1, 2), (0, 1), (2, 2)
         ctx.close()
 
 
-def case_keyswitch_hoisted(make_ctx, make_oracle, level=4, alpha=3, nkeys=3):
+def _chain_shape(chain, level, alpha):
+    """(Q, P, level, alpha) of a case: the whole of `chain` = (Q, P) where one is given, the mixed test chain cut to (level, alpha) otherwise"""
+    if chain is None:
+        return Q_MIX[: level + 1], P_CHAIN[:alpha], level, alpha
+    Q, P = list(chain[0]), list(chain[1])
+    return Q, P, len(Q) - 1, len(P)
+
+
+def case_keyswitch_hoisted(make_ctx, make_oracle, level=4, alpha=3, nkeys=3, chain=None, rows="random"):
     """hc_keyswitch_decompose + hc_keyswitch_hoisted (evaluator.RotateHoisted): one decomposition, several keys; every result
-    must equal the oracle's (and hence hc_keyswitch's) bit for bit, and a stale decomposition must be refused"""
-    Q, P = Q_MIX[: level + 1], P_CHAIN[:alpha]
+    must equal the oracle's (and hence hc_keyswitch's) bit for bit, and a stale decomposition must be refused.
+    chain = (Q, P): level and alpha are the chain's; rows: row_source"""
+    Q, P, level, alpha = _chain_shape(chain, level, alpha)
+    gen = row_source(rows)
     ctx, O = make_ctx(Q, P), make_oracle(Q, P)
     beta = (level + 1 + alpha - 1) // alpha
-    cx = np.stack([splitmix_rows(1900 + l, Q[l], N) for l in range(level + 1)])
+    cx = np.stack([gen(1900 + l, Q[l]) for l in range(level + 1)])
     evks = []
     for kid in range(nkeys):
         evk = np.empty((beta, 2, level + 1 + alpha, N), dtype=np.uint64)
@@ -337,7 +395,7 @@ def case_keyswitch_hoisted(make_ctx, make_oracle, level=4, alpha=3, nkeys=3):
             for k in range(2):
                 for T in range(level + 1 + alpha):
                     q = Q[T] if T <= level else P[T - level - 1]
-                    evk[d, k, T] = splitmix_rows(7000 + 1000 * kid + ((d * 2 + k) * 16 + T), q, N)
+                    evk[d, k, T] = gen(7000 + 1000 * kid + ((d * 2 + k) * 16 + T), q)
         ctx.swk_load(10 + kid, level, evk)
         evks.append(evk)
     outs = ctx.keyswitch_hoisted([10 + kid for kid in range(nkeys)], level, cx)
@@ -347,14 +405,16 @@ def case_keyswitch_hoisted(make_ctx, make_oracle, level=4, alpha=3, nkeys=3):
     ctx.close()
 
 
-def case_keyswitch_qp_mod_down(make_ctx, make_oracle, level=4, alpha=3, nkeys=2):
+def case_keyswitch_qp_mod_down(make_ctx, make_oracle, level=4, alpha=3, nkeys=2, chain=None, rows="random"):
     """hc_keyswitch_qp (hoisted and not), hc_mod_down2, hc_qp_op2 and hc_permute on QP rows against the oracle's or_keyswitch_qp / or_mod_down:
-    the pieces of the reference's MultiplyByDiagMatrixBSGS; hc_keyswitch_qp followed by hc_mod_down2 must equal hc_keyswitch"""
-    Q, P = Q_MIX[: level + 1], P_CHAIN[:alpha]
+    the pieces of the reference's MultiplyByDiagMatrixBSGS; hc_keyswitch_qp followed by hc_mod_down2 must equal hc_keyswitch.
+    chain = (Q, P): level and alpha are the chain's; rows: row_source"""
+    Q, P, level, alpha = _chain_shape(chain, level, alpha)
+    gen = row_source(rows)
     ctx, O = make_ctx(Q, P), make_oracle(Q, P)
     beta, nt = (level + 1 + alpha - 1) // alpha, level + 1 + alpha
     mods = list(range(level + 1)) + [len(Q) + j for j in range(alpha)]
-    cx = np.stack([splitmix_rows(2900 + l, Q[l], N) for l in range(level + 1)])
+    cx = np.stack([gen(2900 + l, Q[l]) for l in range(level + 1)])
     evks = []
     for kid in range(nkeys):
         evk = np.empty((beta, 2, nt, N), dtype=np.uint64)
@@ -362,7 +422,7 @@ def case_keyswitch_qp_mod_down(make_ctx, make_oracle, level=4, alpha=3, nkeys=2)
             for k in range(2):
                 for T in range(nt):
                     q = Q[T] if T <= level else P[T - level - 1]
-                    evk[d, k, T] = splitmix_rows(8000 + 1000 * kid + ((d * 2 + k) * 16 + T), q, N)
+                    evk[d, k, T] = gen(8000 + 1000 * kid + ((d * 2 + k) * 16 + T), q)
         ctx.swk_load(20 + kid, level, evk)
         evks.append(evk)
     want = [O.keyswitch_qp(level, cx, e) for e in evks]
@@ -375,7 +435,7 @@ def case_keyswitch_qp_mod_down(make_ctx, make_oracle, level=4, alpha=3, nkeys=2)
     w0, w1 = O.keyswitch(level, cx, evks[0])
     eq(down[0], w0, "keyswitch_qp + mod_down2 == keyswitch (d0)"); eq(down[1], w1, "keyswitch_qp + mod_down2 == keyswitch (d1)")
     # arithmetic over the QP rows: product with a plaintext (shared), accumulate, add; permutation of QP rows
-    pt = np.stack([splitmix_rows(3300 + t, (Q + P)[t] if t <= level else P[t - level - 1], N) for t in range(nt)])
+    pt = np.stack([gen(3300 + t, (Q + P)[t] if t <= level else P[t - level - 1]) for t in range(nt)])
     ref_mul = np.stack([np.stack([O.mul(mods[t], want[0][k, t], pt[t]).reshape(-1) for t in range(nt)]) for k in range(2)])
     eq(ctx.qp_op2(0, level, want[0], pt, shared_b=True), ref_mul, "qp mul by a plaintext")
     ref_mac = np.stack([np.stack([O.add(mods[t], want[1][k, t], ref_mul[k, t]).reshape(-1) for t in range(nt)]) for k in range(2)])
@@ -388,37 +448,40 @@ def case_keyswitch_qp_mod_down(make_ctx, make_oracle, level=4, alpha=3, nkeys=2)
     ctx.close()
 
 
-def case_leveled_rows(make_ctx, make_oracle, level=5, alpha=3, seed=0x4B17):
+def case_leveled_rows(make_ctx, make_oracle, level=5, alpha=3, seed=0x4B17, chain=None, rows="random"):
     """Every numpy-in / numpy-out leveled entry point against the oracle's row functions, on a chain that mixes 60-bit and ~30-bit limbs (the bootstrapping chain's
     shape). With option pack32 = 2 the binding packs the small limbs' rows to 4-byte words on upload (the other half of each slot poisoned) and widens them on download,
-    so the same residues must come back in either mode."""
-    Q, P = Q_MIX[: level + 1], P_CHAIN[:alpha]
+    so the same residues must come back in either mode.
+    chain = (Q, P): level and alpha are the chain's (a chain of one limb has no Rescale, one without special primes no key switch: those parts are left out); rows: row_source"""
+    Q, P, level, alpha = _chain_shape(chain, level, alpha)
+    gen = row_source(rows)
     ctx, O = make_ctx(Q, P), make_oracle(Q, P)
     nl = level + 1
-    rnd = lambda s: np.stack([splitmix_rows(seed + 97 * s + l, Q[l], N) for l in range(nl)])
+    rnd = lambda s: np.stack([gen(seed + 97 * s + l, Q[l]) for l in range(nl)])
     a, b, c = rnd(1), rnd(2), rnd(3)
-    rows = lambda fn, *xs: np.stack([np.asarray(fn(l, *[x[l] for x in xs])).reshape(-1) for l in range(nl)])
-    eq(ctx.lv_ntt(level, a), rows(O.ntt, a), "lv_ntt"); eq(ctx.lv_intt(level, a), rows(O.intt, a), "lv_intt")
+    per_limb = lambda fn, *xs: np.stack([np.asarray(fn(l, *[x[l] for x in xs])).reshape(-1) for l in range(nl)])
+    eq(ctx.lv_ntt(level, a), per_limb(O.ntt, a), "lv_ntt"); eq(ctx.lv_intt(level, a), per_limb(O.intt, a), "lv_intt")
     eq(ctx.lv_intt(level, ctx.lv_ntt(level, a)), a, "lv_intt(lv_ntt(x)) == x")
-    eq(ctx.lv_mul(level, a, b), rows(O.mul, a, b), "lv_mul"); eq(ctx.lv_add(level, a, b), rows(O.add, a, b), "lv_add"); eq(ctx.lv_sub(level, a, b), rows(O.sub, a, b), "lv_sub")
-    eq(ctx.lv_mul_acc(level, a, b, c), rows(O.add, c, rows(O.mul, a, b)), "lv_mul_acc")
+    eq(ctx.lv_mul(level, a, b), per_limb(O.mul, a, b), "lv_mul"); eq(ctx.lv_add(level, a, b), per_limb(O.add, a, b), "lv_add"); eq(ctx.lv_sub(level, a, b), per_limb(O.sub, a, b), "lv_sub")
+    eq(ctx.lv_mul_acc(level, a, b, c), per_limb(O.add, c, per_limb(O.mul, a, b)), "lv_mul_acc")
     cs = [int(x) % Q[l] for l, x in enumerate(splitmix_rows(seed + 5, 1 << 61, nl))]
     want = np.stack([np.asarray(O.mul_scalar(l, a[l], cs[l])).reshape(-1) for l in range(nl)])
     eq(ctx.lv_mul_const(level, a, cs), want, "lv_mul_const")
     want = np.stack([(a[l] + np.uint64(cs[l])) % np.uint64(Q[l]) for l in range(nl)])
     eq(ctx.lv_add_const(level, a, cs), want, "lv_add_const")
-    eq(ctx.div_round_last(level, a), O.div_round_last(level, a), "div_round_last")
-    d = ctx.div_round_last2(level, a, b)
-    eq(d[0], O.div_round_last(level, a), "div_round_last2 [0]"); eq(d[1], O.div_round_last(level, b), "div_round_last2 [1]")
+    if level > 0:
+        eq(ctx.div_round_last(level, a), O.div_round_last(level, a), "div_round_last")
+        d = ctx.div_round_last2(level, a, b)
+        eq(d[0], O.div_round_last(level, a), "div_round_last2 [0]"); eq(d[1], O.div_round_last(level, b), "div_round_last2 [1]")
     ct_a, ct_b = np.stack([a, b]), np.stack([c, rnd(4)])
     t = ctx.lv_mul_tensor(level, ct_a, ct_b)
-    eq(t[0], rows(O.mul, ct_a[0], ct_b[0]), "tensor d0"); eq(t[2], rows(O.mul, ct_a[1], ct_b[1]), "tensor d2")
-    eq(t[1], rows(O.add, rows(O.mul, ct_a[0], ct_b[1]), rows(O.mul, ct_a[1], ct_b[0])), "tensor d1")
-    eq(ctx.lv_op2(0, level, ct_a, ct_b), np.stack([rows(O.mul, ct_a[k], ct_b[k]) for k in range(2)]), "op2 mul")
-    eq(ctx.lv_op2(0, level, ct_a, c, shared_b=True), np.stack([rows(O.mul, ct_a[k], c) for k in range(2)]), "op2 mul by a plaintext")
-    eq(ctx.lv_op2(1, level, ct_a, ct_b), np.stack([rows(O.add, ct_a[k], ct_b[k]) for k in range(2)]), "op2 add")
-    eq(ctx.lv_op2(2, level, ct_a, ct_b), np.stack([rows(O.sub, ct_a[k], ct_b[k]) for k in range(2)]), "op2 sub")
-    eq(ctx.lv_op2(7, level, ct_a, c, out=ct_b, shared_b=True), np.stack([rows(O.add, ct_b[k], rows(O.mul, ct_a[k], c)) for k in range(2)]), "op2 mul-acc")
+    eq(t[0], per_limb(O.mul, ct_a[0], ct_b[0]), "tensor d0"); eq(t[2], per_limb(O.mul, ct_a[1], ct_b[1]), "tensor d2")
+    eq(t[1], per_limb(O.add, per_limb(O.mul, ct_a[0], ct_b[1]), per_limb(O.mul, ct_a[1], ct_b[0])), "tensor d1")
+    eq(ctx.lv_op2(0, level, ct_a, ct_b), np.stack([per_limb(O.mul, ct_a[k], ct_b[k]) for k in range(2)]), "op2 mul")
+    eq(ctx.lv_op2(0, level, ct_a, c, shared_b=True), np.stack([per_limb(O.mul, ct_a[k], c) for k in range(2)]), "op2 mul by a plaintext")
+    eq(ctx.lv_op2(1, level, ct_a, ct_b), np.stack([per_limb(O.add, ct_a[k], ct_b[k]) for k in range(2)]), "op2 add")
+    eq(ctx.lv_op2(2, level, ct_a, ct_b), np.stack([per_limb(O.sub, ct_a[k], ct_b[k]) for k in range(2)]), "op2 sub")
+    eq(ctx.lv_op2(7, level, ct_a, c, out=ct_b, shared_b=True), np.stack([per_limb(O.add, ct_b[k], per_limb(O.mul, ct_a[k], c)) for k in range(2)]), "op2 mul-acc")
     # modUp of the bootstrapping: the centred lift of a q_0 row to every limb
     x0 = a[0]
     cf = np.asarray(O.intt(0, x0)).reshape(-1)
@@ -428,18 +491,21 @@ def case_leveled_rows(make_ctx, make_oracle, level=5, alpha=3, seed=0x4B17):
         lifted = np.where(cf > half, (cf % np.uint64(Q[l]) + np.uint64(Q[l]) - np.uint64(Q[0] % Q[l])) % np.uint64(Q[l]), cf % np.uint64(Q[l]))
         want.append(np.asarray(O.ntt(l, lifted)).reshape(-1))
     eq(ctx.lv_mod_raise(level, x0), np.stack(want), "lv_mod_raise")
+    if alpha == 0:
+        ctx.close()
+        return
     # rotation: key switch + automorphism, fused and in two steps
     beta, nt = (nl + alpha - 1) // alpha, nl + alpha
     evk = np.empty((beta, 2, nt, N), dtype=np.uint64)
     for dd in range(beta):
         for k in range(2):
             for T in range(nt):
-                evk[dd, k, T] = splitmix_rows(seed + 9000 + ((dd * 2 + k) * 16 + T), Q[T] if T <= level else P[T - nl], N)
+                evk[dd, k, T] = gen(seed + 9000 + ((dd * 2 + k) * 16 + T), Q[T] if T <= level else P[T - nl])
     gal = pow(5, 7, 2 * N)
     ctx.swk_load(gal, level, evk)
     w0, w1 = O.keyswitch(level, b, evk)
     idx = O.permute_index(gal)
-    want0 = np.stack([O.permute(idx, r) for r in rows(O.add, w0, a)]); want1 = np.stack([O.permute(idx, r) for r in w1])
+    want0 = np.stack([O.permute(idx, r) for r in per_limb(O.add, w0, a)]); want1 = np.stack([O.permute(idx, r) for r in w1])
     for hoisted in (False, True):
         r0, r1 = ctx.keyswitch_rotate(gal, gal, level, a, b, hoisted=hoisted)
         eq(r0, want0, f"keyswitch_rotate c0 hoisted={hoisted}"); eq(r1, want1, f"keyswitch_rotate c1 hoisted={hoisted}")
@@ -451,7 +517,8 @@ def case_leveled_rows(make_ctx, make_oracle, level=5, alpha=3, seed=0x4B17):
 def case_batched_leveled(make_ctx, n=3, level=4, alpha=3, seed=0xBA7C4, make_oracle=None, chain=None):
     """hc_set_batch: every leveled entry point on n images per launch (operands `stride` words apart, plaintexts and keys shared) must give,
     for every image, the bits of the same call on that image alone (which the other cases pin to the oracle). Strides are padded so that an
-    addressing slip lands in the padding, outputs start from a non-zero fill, and the images' inputs differ."""
+    addressing slip lands in the padding, outputs start from a non-zero fill, and the images' inputs differ.
+    Under option pack32 = 2 the case converts the caller's rows at the boundary as the binding does (to_dev / from_dev: nothing to do under 0 and 1)."""
     import ctypes as C
     QC, PC = chain if chain is not None else (Q_MIX, P_CHAIN)      # chain = (Q, P) of a real parameter set: the shapes the bench times (level 27, alpha 5)
     Q, P = list(QC[: level + 2]), list(PC[:alpha])        # one modulus above the level (where the chain has one): rows and moduli must not be confused
@@ -475,20 +542,30 @@ def case_batched_leveled(make_ctx, n=3, level=4, alpha=3, seed=0xBA7C4, make_ora
     def qp():
         return np.stack([np.stack([np.stack([rnd(qp_mod(t)) for t in range(nt)]) for _ in range(2)]) for _ in range(n)])
 
+    def to_dev(x, kind):         # one image's operand as the device holds it: 'p' rows of limbs 0 .., 'q' groups of nt extended-basis rows, 's' either (by its row count)
+        x = np.ascontiguousarray(x, dtype=np.uint64).reshape(-1, N)
+        if kind == "q" or (kind == "s" and x.shape[0] == nt):
+            return ctx.pack_rows(x, nl, nt).reshape(-1)
+        return ctx.pack_rows(x, x.shape[0]).reshape(-1)
+
+    def from_dev(x, kind):
+        x = np.ascontiguousarray(x, dtype=np.uint64).reshape(-1, N)
+        return (ctx.unpack_rows(x, nl, nt) if kind == "q" else ctx.unpack_rows(x, x.shape[0])).reshape(-1)
+
     def put(arr, stride):        # (n, words...) -> one allocation, image z at z * stride
         b = ctx.buf(np.full(n * stride, 0xDEADBEEFCAFE, dtype=np.uint64))
         for z in range(n):
-            b.upload(arr[z].reshape(-1), z * stride)
+            b.upload(to_dev(arr[z], "q" if stride == QS else "p"), z * stride)
         return b
 
     def get(b, stride, words):
         full = b.download()
-        return np.stack([full[z * stride: z * stride + words] for z in range(n)])
+        return np.stack([from_dev(full[z * stride: z * stride + words], "q" if stride == QS else "p") for z in range(n)])
 
     def run(what, fn, ins, outs, init=None):
         """ins: [(array, 'p'|'q'|'s')] per-image polynomials / QP pairs / shared plaintexts; outs: ['p'|'q', words]"""
         st = {"p": PS, "q": QS, "s": 0}
-        ibufs = [(ctx.buf(a) if k == "s" else put(a, st[k]), st[k]) for a, k in ins]
+        ibufs = [(ctx.buf(to_dev(a, "s")) if k == "s" else put(a, st[k]), st[k]) for a, k in ins]
         res = []
         for mode in ("single", "batch"):
             obufs = [put(init[i] if init else np.full((n, w), 0x1234567, dtype=np.uint64), st[k]) for i, (k, w) in enumerate(outs)]
@@ -574,7 +651,7 @@ def case_batched_leveled(make_ctx, n=3, level=4, alpha=3, seed=0xBA7C4, make_ora
                 eq(got_lin[k_][z], np.stack(want_rows).reshape(-1), f"lv_lincomb2 == oracle (image {z}, polynomial {k_})")
     ctx.set_batch(1)
     for z in range(n):                       # the chain, image by image
-        bufs = [ctx.buf(x_[z]) for pair in As for x_ in pair]; o0, o1 = ctx.buf(nwords=PW), ctx.buf(nwords=PW)
+        bufs = [ctx.buf(to_dev(x_[z], "p")) for pair in As for x_ in pair]; o0, o1 = ctx.buf(nwords=PW), ctx.buf(nwords=PW)
         t0_, t1_ = ctx.buf(nwords=PW), ctx.buf(nwords=PW)
         for t in range(NL):
             ct_ = (C.c_uint64 * nl)(*[int(v) for v in cvals[t]])
@@ -583,7 +660,7 @@ def case_batched_leveled(make_ctx, n=3, level=4, alpha=3, seed=0xBA7C4, make_ora
             else:
                 ck(L.hc_lv_op2(h, 3, level, bufs[2 * t].ptr, bufs[2 * t + 1].ptr, None, None, t0_.ptr, t1_.ptr, ct_)); ck(L.hc_lv_op2(h, 1, level, o0.ptr, o1.ptr, t0_.ptr, t1_.ptr, o0.ptr, o1.ptr, None))
         ck(L.hc_lv_add_const(h, level, o0.ptr, addc, o0.ptr))
-        eq(got_lin[0][z], o0.download(), f"lincomb2 == MultByConst / Add chain, image {z}, polynomial 0"); eq(got_lin[1][z], o1.download(), f"lincomb2 == chain, image {z}, polynomial 1")
+        eq(got_lin[0][z], from_dev(o0.download(), "p"), f"lincomb2 == MultByConst / Add chain, image {z}, polynomial 0"); eq(got_lin[1][z], from_dev(o1.download(), "p"), f"lincomb2 == chain, image {z}, polynomial 1")
         for b_ in bufs + [o0, o1, t0_, t1_]:
             b_.free()
     run("lv_mul_tensor", lambda x0, x1, y0, y1, d0, d1, d2: ck(L.hc_lv_mul_tensor(h, level, x0, x1, y0, y1, d0, d1, d2)), [(a, "p"), (a1, "p"), (b, "p"), (b1, "p")], [("p", PW)] * 3)
@@ -690,17 +767,18 @@ def case_batched_leveled(make_ctx, n=3, level=4, alpha=3, seed=0xBA7C4, make_ora
     X = qp()
     md = run("mod_down2", lambda x, o0, o1: ck(L.hc_mod_down2(h, level, x, o0, o1)), [(acc, "q")], [("p", PW), ("p", PW)])
     eq(md[0], ks[0], "keyswitch_qp + mod_down2 == keyswitch (d0)"); eq(md[1], ks[1], "keyswitch_qp + mod_down2 == keyswitch (d1)")
-    def qp_rot_composed(c0p, x, o):          # hc_keyswitch_qp + add on the Q rows of component 0 + permutation, image by image (single mode only)
-        t = ctx.buf(nwords=2 * nt * N)
-        ck(L.hc_keyswitch_qp(h, K0, level, x, t.ptr, 0)); ck(L.hc_lv_add(h, level, t.ptr, c0p, t.ptr)); ck(L.hc_permute(h, C.c_uint64(gal), t.ptr, o, 2 * nt))
-        ctx.sync(); t.free()
+    def qp_rot_composed(c0p, x):             # hc_keyswitch_qp + add on the Q rows of component 0 + permutation, image by image (single mode only). hc_permute is a one-row
+        t = ctx.buf(nwords=2 * nt * N)       # primitive (8-byte rows under every pack32), so it permutes the rows as a caller holds them: downloaded and widened
+        ck(L.hc_keyswitch_qp(h, K0, level, x, t.ptr, 0)); ck(L.hc_lv_add(h, level, t.ptr, c0p, t.ptr))
+        ctx.sync(); rows_ = from_dev(t.download(), "q"); t.free()
+        return ctx.permute(gal, rows_).reshape(-1)
     qr = run("keyswitch_qp_rotate", lambda c0p, x, o: ck(L.hc_keyswitch_qp_rotate(h, K0, C.c_uint64(gal), level, c0p, x, o, 0, 0)), [(b, "p"), (a, "p")], [("q", QW)])
     ctx.set_batch(1)
     comp = []
     for z in range(n):
-        bi, ai, oi = ctx.buf(b[z]), ctx.buf(a[z]), ctx.buf(nwords=2 * nt * N)
-        qp_rot_composed(bi.ptr, ai.ptr, oi.ptr); comp.append(oi.download())
-        bi.free(); ai.free(); oi.free()
+        bi, ai = ctx.buf(to_dev(b[z], "p")), ctx.buf(to_dev(a[z], "p"))
+        comp.append(qp_rot_composed(bi.ptr, ai.ptr))
+        bi.free(); ai.free()
     eq(qr[0], np.stack(comp), "keyswitch_qp_rotate == keyswitch_qp + add + permute")
 
     # all baby steps in one call == the single hoisted rotations (5 rotations over two keys: more than one launch's worth at n >= 3)
@@ -736,7 +814,7 @@ def case_batched_leveled(make_ctx, n=3, level=4, alpha=3, seed=0xBA7C4, make_ora
                 want_ = np.stack([np.stack([O.permute(idx_, acc_[k_, t]) for t in range(nt)]) for k_ in range(2)])
                 eq(rm[i][z], want_.reshape(-1), f"keyswitch_qp_rotate_many == oracle hoisted key switch + P c0 + permutation (image {z}, rotation {i})")
     # error behaviour: no decomposition held -> refused before any launch; an unknown key among the rotations likewise
-    xa, xo = ctx.buf(a[0]), ctx.buf(nwords=2 * nt * N)
+    xa, xo = ctx.buf(to_dev(a[0], "p")), ctx.buf(nwords=2 * nt * N)
     ids1 = (C.c_uint64 * 1)(30); gs1 = (C.c_uint64 * 1)(gal); arr1 = (C.c_void_p * 1)(xo.ptr)
     ck(L.hc_keyswitch(h, K0, level, xa.ptr, xo.at(0), xo.at(PW)))                        # a plain key switch drops any held decomposition
     assert L.hc_keyswitch_qp_rotate_many(h, 1, ids1, gs1, level, None, xa.ptr, arr1) != 0, "rotate_many without a held decomposition must fail"
@@ -838,7 +916,8 @@ def case_batched_leveled(make_ctx, n=3, level=4, alpha=3, seed=0xBA7C4, make_ora
         pass
     ctx.sync()
     full = get(xo, PS, PW)
-    xo.upload(np.full(n * PS, 0x1234567, dtype=np.uint64))
+    for z in range(n):
+        xo.upload(to_dev(np.full(PW, 0x1234567, dtype=np.uint64), "p"), z * PS)
     ck(L.hc_lv_add(h, level, xa.ptr, xb.ptr, xo.ptr)); ctx.sync()
     after = get(xo, PS, PW)
     eq(after[0], full[0], "after a batch scope ended by an exception: image 0 is computed as before")
@@ -1376,4 +1455,105 @@ def case_bl_boot_relu(make_ctx, logN=16, seed=5, min_bits=9.0):
         err = np.abs(dec - np.maximum(x[k], 0))
         bits = -np.log2(np.median(err) + 1e-30)
         assert bits >= min_bits, f"baseline ReLU half {k}: median precision {bits:.2f} bits"
+    ctx.close()
+
+
+def _random_key(seed, Q, P, level):
+    """a switching key of uniform rows for `level` of the chain: (beta, 2, level+1+alpha, N)"""
+    nl, alpha = level + 1, len(P)
+    beta, nt = (nl + alpha - 1) // alpha, nl + alpha
+    evk = np.empty((beta, 2, nt, N), dtype=np.uint64)
+    for d in range(beta):
+        for k in range(2):
+            for T in range(nt):
+                evk[d, k, T] = splitmix_rows(seed + (d * 2 + k) * 64 + T, Q[T] if T < nl else P[T - nl], N)
+    return evk
+
+
+def rounding_point_poly(O, Q, level, seed):
+    """A polynomial at `level` in the NTT domain whose coefficients sit on DivRoundByLastModulusNTT's rounding point: the last limb's coefficients cycle through
+    0, 1, (q_L-1)/2, (q_L+1)/2 and q_L-1 (the centred remainder changes sign between the third and the fourth), the other limbs' through runs of five 0s, five q-1s and five
+    uniform residues, so that each of the five meets each of the three."""
+    qL = Q[level]
+    j = np.arange(N)
+    cyc = np.array([0, 1, (qL - 1) // 2, (qL + 1) // 2, qL - 1], dtype=np.uint64)
+    rows_ = []
+    for l in range(level):
+        kind = (j // 5 + l + seed) % 3
+        c = np.where(kind == 0, np.uint64(0), np.where(kind == 1, np.uint64(Q[l] - 1), splitmix_rows(seed + 31 * l, Q[l], N)))
+        rows_.append(O.ntt(l, c.astype(np.uint64)))
+    rows_.append(O.ntt(level, cyc[(j + seed) % 5]))
+    return np.stack(rows_)
+
+
+def case_rescale_rounding_point(make_ctx, make_oracle, chain, levels, seed=0x2E5C):
+    """hc_div_round_last, hc_div_round_last2 and hc_keyswitch_add_rescale on rounding_point_poly at each of `levels` (of one context over the whole chain), against the oracle's
+    DivRoundByLastModulusNTT. For the fused call the addends are the planted polynomials minus the oracle's key-switched parts, so that the sum that is rescaled is the
+    planted polynomial itself."""
+    import ctypes as C
+    Q, P = list(chain[0]), list(chain[1])
+    ctx, O = make_ctx(Q, P), make_oracle(Q, P)
+    for level in levels:
+        nl = level + 1
+        a, b = rounding_point_poly(O, Q, level, seed + level), rounding_point_poly(O, Q, level, seed + level + 2)
+        wa, wb = O.div_round_last(level, a), O.div_round_last(level, b)
+        eq(ctx.div_round_last(level, a), wa, f"div_round_last at the rounding point, level {level}")
+        d = ctx.div_round_last2(level, a, b)
+        eq(d[0], wa, f"div_round_last2 [0] at the rounding point, level {level}"); eq(d[1], wb, f"div_round_last2 [1] at the rounding point, level {level}")
+        if level < 2:            # hc_keyswitch_add_rescale is refused below level 2 (its message names the two calls to use instead)
+            continue
+        evk = _random_key(seed + 4000 + 100 * level, Q, P, level)
+        ctx.swk_load(40 + level, level, evk)
+        x = np.stack([splitmix_rows(seed + 700 + l, Q[l], N) for l in range(nl)])
+        w0, w1 = O.keyswitch(level, x, evk)
+        p0 = np.stack([O.sub(l, a[l], w0[l]) for l in range(nl)]); p1 = np.stack([O.sub(l, b[l], w1[l]) for l in range(nl)])
+        bufs = [ctx.buf(ctx.pack_rows(v, nl)) for v in (x, p0, p1)]
+        outs = [ctx.buf(nwords=level * N) for _ in range(2)]
+        ctx._ck(ctx.L.hc_keyswitch_add_rescale(ctx.h, C.c_uint64(40 + level), level, bufs[0].ptr, bufs[1].ptr, bufs[2].ptr, outs[0].ptr, outs[1].ptr))
+        got = [ctx.unpack_rows(o.download((level, N)), level) for o in outs]
+        for v in bufs + outs:
+            v.free()
+        eq(got[0], wa, f"keyswitch_add_rescale [0] at the rounding point, level {level}"); eq(got[1], wb, f"keyswitch_add_rescale [1] at the rounding point, level {level}")
+    ctx.close()
+
+
+def digit_edge_poly(O, Q, level, alpha, seed):
+    """A polynomial at `level` in the NTT domain whose digit residues y_i (the terms of the basis extension, digit by digit: limbs s_i = Q[d alpha ..]) are chosen directly:
+    coefficient j has, in every digit, all y_i = 0 (j % 4 == 0), all y_i = s_i - 1 (1: the fp64 overflow count's largest sum), one y_i = s_i - 1 and the rest 0 (2; which
+    one moves with j), or uniform y_i (3). x_i = y_i (S / s_i) mod s_i, S the product of the digit's limbs, is what decomposes into those y_i."""
+    nl = level + 1
+    j = np.arange(N)
+    rows_ = []
+    for l in range(nl):
+        d = l // alpha
+        limbs = list(range(d * alpha, min((d + 1) * alpha, nl)))
+        s = Q[l]
+        hat = 1
+        for i in limbs:
+            if i != l:
+                hat = hat * Q[i] % s
+        y = splitmix_rows(seed + 13 * l, s, N)
+        y = np.where(j % 4 == 0, np.uint64(0), y)
+        y = np.where(j % 4 == 1, np.uint64(s - 1), y)
+        y = np.where(j % 4 == 2, np.where((j // 4) % len(limbs) == l - limbs[0], np.uint64(s - 1), np.uint64(0)), y)
+        x = (y.astype(object) * hat % s).astype(np.uint64)
+        rows_.append(O.ntt(l, x))
+    return np.stack(rows_)
+
+
+def case_basis_ext_edges(make_ctx, make_oracle, chain, seed=0xD161):
+    """hc_keyswitch and hc_keyswitch_qp at the chain's top level on digit_edge_poly: the general basis extension's fp64 overflow count v at its smallest and largest sums, with
+    multi-limb digits where alpha > 1. The oracle restates the reference's expression for v; nothing here derives it."""
+    Q, P = list(chain[0]), list(chain[1])
+    level, alpha = len(Q) - 1, len(P)
+    ctx, O = make_ctx(Q, P), make_oracle(Q, P)
+    cx = digit_edge_poly(O, Q, level, alpha, seed)
+    evk = _random_key(seed + 500, Q, P, level)
+    ctx.swk_load(55, level, evk)
+    g0, g1 = ctx.keyswitch(55, level, cx)
+    w0, w1 = O.keyswitch(level, cx, evk)
+    eq(g0, w0, f"keyswitch d0 on planted digit residues, alpha={alpha}"); eq(g1, w1, f"keyswitch d1 on planted digit residues, alpha={alpha}")
+    want = O.keyswitch_qp(level, cx, evk)
+    for hoisted in (False, True):
+        eq(ctx.keyswitch_qp([55], level, cx, hoisted=hoisted)[0], want, f"keyswitch_qp on planted digit residues, alpha={alpha}, hoisted={hoisted}")
     ctx.close()

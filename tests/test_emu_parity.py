@@ -328,8 +328,7 @@ def test_row_widths_of_the_batched_transforms(pack32):
     """The truth table above hc_pk (hconv.hip), pinned under every setting of option pack32 on the smallest context where all its branches are live: a caller's operands into
     and out of both transforms (hc_lv_ntt, hc_lv_intt), a coefficient-domain scratch array between an inverse transform and a forward transform with the lift prologue and
     the epilogue (Rescale at level 3), the packed digits and the extension's y_i rows (one key switch at level 3: four digits, ModDown). The binding converts a caller's
-    4-byte rows at the boundary, so the oracle's residues must come back under every setting. (Limbs 0 and 1 are large here: what a context with a small limb 0 or 1
-    does under pack32 = 2 is ADVICE.md's open finding and is not stated.)"""
+    4-byte rows at the boundary, so the oracle's residues must come back under every setting."""
     subprocess.check_call(["make", "-s", "-C", EMU_DIR, EMU_LIB])
     (Q, P), level, R = _WIDTH_CHAIN, 3, _width_case()
     assert [q < 1 << 31 for q in Q] == [False, False, True, True] and P[0] > 1 << 31
