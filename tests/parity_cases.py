@@ -77,15 +77,22 @@ def case_rescale(ctx, O):
     eq(ctx.div_round_last(1, x2), O.div_round_last(1, x2), "div_round_last boundary")
 
 
-def seeded_evk(seed):
-    return np.stack([splitmix_rows(seed, Q0, N), splitmix_rows(seed + 1, Q0, N), splitmix_rows(seed + 2, P0, N), splitmix_rows(seed + 3, P0, N)])
+def conv_moduli(O=None):
+    """(Q0, Q1, P) of the conv path: those of the oracle a case was handed, so that its operands are residues of the moduli under test; without one, the product's"""
+    return (Q0, Q1, P0) if O is None else (O.q[0], O.q[1], O.p[0])
+
+
+def seeded_evk(seed, O=None):
+    q0, _, p0 = conv_moduli(O)
+    return np.stack([splitmix_rows(seed, q0, N), splitmix_rows(seed + 1, q0, N), splitmix_rows(seed + 2, p0, N), splitmix_rows(seed + 3, p0, N)])
 
 
 def case_keyswitch(ctx, O, gals=(513, 65537)):
+    q0 = conv_moduli(O)[0]
     for gal in gals:
-        evk4 = seeded_evk(600 + gal)
+        evk4 = seeded_evk(600 + gal, O)
         ctx.evk_load(gal, evk4)
-        ct = np.stack([splitmix_rows(61 + gal, Q0, N), splitmix_rows(62 + gal, Q0, N)])
+        ct = np.stack([splitmix_rows(61 + gal, q0, N), splitmix_rows(62 + gal, q0, N)])
         eq(ctx.rotate_gal_l0(gal, ct), O.rotate_gal_l0(ct, gal, evk4), f"rotate_gal gal={gal}")
         d0, d1 = ctx.keyswitch_l0(gal, ct[1])
         w0, w1 = O.keyswitch_l0(ct[1], evk4)
@@ -114,26 +121,30 @@ def case_modup_overflow(ctx, O):
     ctx.evk_load(gal, seeded_evk(600 + gal))
 
 
-def planted_conv_inputs(seed, max_ob):
+def planted_conv_inputs(seed, max_ob, O=None, inputs="random"):
+    """the ciphertext and the kernel plaintexts of a conv case; inputs="edge": rows of edge_row's patterns (all q - 1, alternating 0 and q - 1, a single spike) instead of
+    uniform residues"""
+    q0, q1, _ = conv_moduli(O)
+    row = row_source(inputs)
     ct_in = np.empty((2, 2, N), dtype=np.uint64)
     for p in range(2):
-        ct_in[p, 0] = splitmix_rows(seed + 10 + p, Q0, N)
-        ct_in[p, 1] = splitmix_rows(seed + 20 + p, Q1, N)
+        ct_in[p, 0] = row(seed + 10 + p, q0)
+        ct_in[p, 1] = row(seed + 20 + p, q1)
     ker = np.empty((max_ob, 2, N), dtype=np.uint64)
     for i in range(max_ob):
-        ker[i, 0] = splitmix_rows(seed + 100 + 2 * i, Q0, N)
-        ker[i, 1] = splitmix_rows(seed + 101 + 2 * i, Q1, N)
+        ker[i, 0] = row(seed + 100 + 2 * i, q0)
+        ker[i, 1] = row(seed + 101 + 2 * i, q1)
     return ct_in, ker
 
 
-def load_tree_keys(ctx, seed, max_ob, norm=1):
+def load_tree_keys(ctx, seed, max_ob, norm=1, O=None):
     """switching keys for the Galois elements pack_ctxts touches (conv.go:284-296); returns oracle evk array"""
     evk_all = np.zeros((16, 4, N), dtype=np.uint64)
     step = max_ob // 2
     j = 16 - (step.bit_length() - 1 if step > 0 else 0)
     while step >= norm and step >= 1:
         gal = (1 << j) + 1
-        evk4 = seeded_evk(seed + 7000 + 10 * j)
+        evk4 = seeded_evk(seed + 7000 + 10 * j, O)
         ctx.evk_load(gal, evk4)
         evk_all[j - 1] = evk4
         step //= 2
@@ -141,14 +152,15 @@ def load_tree_keys(ctx, seed, max_ob, norm=1):
     return evk_all
 
 
-def case_conv(ctx, O, max_ob, seed=0xBEEF, with_bias=True, chunk=None, norm=1, out_scale=2.0 ** 30):
+def case_conv(ctx, O, max_ob, seed=0xBEEF, with_bias=True, chunk=None, norm=1, out_scale=2.0 ** 30, inputs="random"):
     """norm > 1 = the sparse packing of the reference's *_sparse kinds (only channels i % norm == 0 are live,
-    conv.go:526, 286-287); out_scale = 2^43 is what evalConv_BNRelu_new asks of the same operator (eval.go:433)."""
-    ct_in, ker = planted_conv_inputs(seed, max_ob)
-    evk_all = load_tree_keys(ctx, seed, max_ob, norm)
+    conv.go:526, 286-287); out_scale = 2^43 is what evalConv_BNRelu_new asks of the same operator (eval.go:433).
+    Operands are residues of the oracle's moduli; inputs="edge": the ciphertext, kernel-plaintext and bias rows are edge_row's patterns."""
+    ct_in, ker = planted_conv_inputs(seed, max_ob, O, inputs)
+    evk_all = load_tree_keys(ctx, seed, max_ob, norm, O)
     idx = O.idx_plaintexts()
     ctx.idx_load(None)                      # derived on the device; must equal the oracle's (checked via the result)
-    bias = splitmix_rows(seed + 5, Q0, N) if with_bias else None
+    bias = row_source(inputs)(seed + 5, conv_moduli(O)[0]) if with_bias else None
     if chunk is not None:
         ctx.set_option("chunk_nodes", chunk)
     got, sc = ctx.conv_then_pack(ct_in, 2.0 ** 30, ker, 2.0 ** 30, max_ob, norm, out_scale, bias)
@@ -161,15 +173,15 @@ def case_conv(ctx, O, max_ob, seed=0xBEEF, with_bias=True, chunk=None, norm=1, o
 def case_conv_batch(ctx, O, max_ob, n, seed=0xBA7C, chunk=None, shared_ker=False, oracle_members=(0,)):
     """hc_conv_then_pack_batch: n independent ciphertexts (own inputs, own or shared kernel plaintexts, a bias on the even members
     only) through ONE launch set == n separate hc_conv_then_pack calls bit for bit, and == the oracle for `oracle_members`."""
-    evk_all = load_tree_keys(ctx, seed, max_ob, 1)
+    evk_all = load_tree_keys(ctx, seed, max_ob, 1, O)
     ctx.idx_load(None)
     if chunk is not None:
         ctx.set_option("chunk_nodes", chunk)
     ins, kers, biases = [], [], []
     for z in range(n):
-        ct_in, ker = planted_conv_inputs(seed + 17 * z, max_ob)
+        ct_in, ker = planted_conv_inputs(seed + 17 * z, max_ob, O)
         ins.append(ct_in); kers.append(kers[0] if (shared_ker and z) else ker)
-        biases.append(splitmix_rows(seed + 5 + z, Q0, N) if z % 2 == 0 else None)
+        biases.append(splitmix_rows(seed + 5 + z, conv_moduli(O)[0], N) if z % 2 == 0 else None)
     hk = [ctx.ker_load(k) for k in (kers[:1] if shared_ker else kers)]
     hk = hk * n if shared_ker else hk
     bin_ = [ctx.buf(x) for x in ins]
@@ -345,6 +357,71 @@ def row_source(rows):
     """rows="random": uniform residues (splitmix_rows); rows="edge": edge_row"""
     assert rows in ("random", "edge"), rows
     return (lambda seed, q: splitmix_rows(seed, q, N)) if rows == "random" else edge_row
+
+
+# ---- the conv path under every modulus-size class. The host picks each kernel's arithmetic from a modulus' size (hconv.hip): hc_fm_free(Q0) and hc_fm_free(P) - q < 2^57, the
+# unfolded forward rounds - and hc_f64_ok(Q1) - q < 2^49, the fp64 inverse transform of loop A. The product's own (Q0 ~ 2^55, Q1 just below 2^49, P ~ 2^61) take one side of each;
+# a host with another parameter set lands on the others. Every modulus is prime and 1 mod 2^17. (Q0, Q1, P, what the three predicates must say)
+def conv_branches(q0, q1, p):
+    return (q0 < 1 << 57, q1 < 1 << 49, p < 1 << 57)
+
+
+Q1_ABOVE_49 = 0x20000001A0001           # just above 2^49
+Q_ABOVE_57 = 0x2000000003A0001          # just above 2^57
+Q_BELOW_57 = 0x1FFFFFFFFFC0001          # the largest prime HC_FM_FREE takes
+CONV_TRIPLES = [
+    (Q0, Q1_ABOVE_49, P0, (True, False, False)),                    # hc_k_a1p<0>, hc_k_a2<FREE, 0>
+    (Q_ABOVE_57, Q1, P0, (False, True, False)),                     # hc_k_a2<ALT, 1>; a3p, b4, b5, b5m, sb4, sb5 as ALT
+    (Q1_BL, Q1_ABOVE_49, P0, (False, False, False)),                # hc_k_a2<ALT, 0>
+    (Q_BELOW_57, Q1, P0, (True, True, False)),                      # FREE at its edge
+    (Q0, Q1, Q_BELOW_57, (True, True, True)),                       # b2, b3p, sb2, sb3 as FREE
+    (Q_ABOVE_57, Q1_ABOVE_49, Q_BELOW_57, (False, False, True)),    # all three flipped, with P < Q0
+]
+CONV_TRIPLES_BATCH = [CONV_TRIPLES[1], CONV_TRIPLES[5]]
+
+
+def conv_triple_id(t):
+    return f"Q0_{t[0]:x}-Q1_{t[1]:x}-P_{t[2]:x}"
+
+
+_triple_oracles = {}
+
+
+def _triple_env(make_ctx, triple):
+    from oracle_lib import Oracle
+    q0, q1, p, want = triple
+    assert conv_branches(q0, q1, p) == want, f"{conv_triple_id(triple)} has drifted off its branch: {conv_branches(q0, q1, p)}, meant {want}"
+    if triple[:3] not in _triple_oracles:
+        _triple_oracles[triple[:3]] = Oracle(q=(q0, q1), p=(p,))
+    return make_ctx([q0, q1], [p]), _triple_oracles[triple[:3]]
+
+
+def case_conv_triple(make_ctx, triple, small_levels, inputs):
+    """one small convolution (4 channels, launches of 3 tree nodes) under the triple's moduli: small_levels 0 keeps the tree on the 256-thread kernels (b1 .. b4, b5m), 16 on the
+    small-level ones (sb*). The kernels branch per workgroup on the modulus only, so nothing larger is needed to execute an instantiation."""
+    ctx, O = _triple_env(make_ctx, triple)
+    try:
+        ctx.set_option("small_levels", small_levels)
+        case_conv(ctx, O, 4, chunk=3, inputs=inputs)
+    finally:
+        ctx.close()
+
+
+def case_keyswitch_triple(make_ctx, triple):
+    ctx, O = _triple_env(make_ctx, triple)
+    try:
+        case_keyswitch(ctx, O)
+    finally:
+        ctx.close()
+
+
+def case_conv_batch_triple(make_ctx, triple):
+    ctx, O = _triple_env(make_ctx, triple)
+    try:
+        ctx.set_option("small_levels", 0)
+        case_conv_batch(ctx, O, 4, 3, chunk=9)
+    finally:
+        ctx.close()
 
 
 def case_keyswitch_general(make_ctx, make_oracle, shapes=((1, 2), (0, 1), (2, 2), (3, 2), (4, 3), (4, 5)), chain=None, rows="random"):

@@ -41,17 +41,34 @@ def test_big_level_kernels_in_a_batch_of_three(env, max_ob, chunk):
 
 @pytest.mark.parametrize("q0,q1", [(Q0, Q60), (Q60, Q1), (Q60, Q0)], ids=["integer-a1", "alt-a3-b5m", "alt-and-integer-a1"])
 @pytest.mark.parametrize("small", [0, 16])
-def test_other_modulus_sizes(monkeypatch, q0, q1, small):
-    """Q1 above 2^49: hc_k_a1p<0> (hc_rows_inv on two tiles); Q0 at or above 2^57: HC_FM_ALT in hc_k_a3p and hc_k_b5m. The parity case draws its inputs below the moduli it finds in its module."""
+def test_other_modulus_sizes(q0, q1, small):
+    """Q1 above 2^49: hc_k_a1p<0> (hc_rows_inv on two tiles); Q0 at or above 2^57: HC_FM_ALT in hc_k_a3p and hc_k_b5m. The parity case draws its inputs below the moduli of the oracle it is handed."""
     subprocess.check_call(["make", "-s", "-C", EMU_DIR, EMU_LIB])
-    monkeypatch.setattr(pc, "Q0", q0)
-    monkeypatch.setattr(pc, "Q1", q1)
     ctx = Context([q0, q1], [P0], lib_path=EMU_LIB)
     ctx.set_option("small_levels", small)
     try:
         pc.case_conv(ctx, Oracle(q=(q0, q1), p=(P0,)), 4, chunk=3)
     finally:
         ctx.close()
+
+
+@pytest.mark.parametrize("inputs", ["random", "edge"])
+@pytest.mark.parametrize("small", [0, 16])
+@pytest.mark.parametrize("triple", pc.CONV_TRIPLES, ids=pc.conv_triple_id)
+def test_conv_under_every_modulus_size_class(triple, small, inputs):
+    """the six (Q0, Q1, P) of pc.CONV_TRIPLES: every branch the host takes on a modulus' size, a special prime below 2^57 and below Q0 included, on random and on edge rows"""
+    subprocess.check_call(["make", "-s", "-C", EMU_DIR, EMU_LIB])
+    pc.case_conv_triple(lambda Q, P: Context(Q, P, lib_path=EMU_LIB), triple, small, inputs)
+
+
+@pytest.mark.parametrize("triple", pc.CONV_TRIPLES, ids=pc.conv_triple_id)
+def test_keyswitch_under_every_modulus_size_class(triple):
+    pc.case_keyswitch_triple(lambda Q, P: Context(Q, P, lib_path=EMU_LIB), triple)
+
+
+@pytest.mark.parametrize("triple", pc.CONV_TRIPLES_BATCH, ids=pc.conv_triple_id)
+def test_conv_batch_under_other_modulus_sizes(triple):
+    pc.case_conv_batch_triple(lambda Q, P: Context(Q, P, lib_path=EMU_LIB), triple)
 
 
 def test_tile_local_galois_levels_still_read_b1s_t2c1(env):
