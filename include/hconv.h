@@ -47,7 +47,7 @@ typedef struct hc_ker hc_ker; /* device-resident kernel plaintexts pl_ker[0..max
 int hc_ctx_create(hc_ctx **out, int logN, const uint64_t *q, int nq, const uint64_t *p, int np, int device);
 void hc_ctx_destroy(hc_ctx *ctx);
 const char *hc_last_error(const hc_ctx *ctx); /* ctx may be NULL: error of the last failed hc_ctx_create */
-int hc_version(void);   /* 3: hc_prep_ker_ex (transposed kernels); 4: hc_prep_ker_ex2 (dilated, channel-strided kernels); 5: hc_encode_coeffs, hc_encrypt_sk, hc_decrypt_decode_coeffs */
+int hc_version(void);   /* 3: hc_prep_ker_ex (transposed kernels); 4: hc_prep_ker_ex2 (dilated, channel-strided kernels); 5: hc_encode_coeffs, hc_encrypt_sk, hc_decrypt_decode_coeffs; hc_encode_slots_ex came later without a new number: detect it by symbol (dlsym) */
 
 /* ---- device memory ---- */
 int hc_malloc(hc_ctx *ctx, size_t bytes, void **dptr);
@@ -92,7 +92,7 @@ int hc_permute(hc_ctx *ctx, uint64_t galEl, const uint64_t *in, uint64_t *out, i
  * switching keys likewise (one fetch of a key row serves all images and both key components). (Until round 5 hc_lv_mul always shared b and hc_lv_op2 inferred a plaintext
  * from b0 == b1: a per-image second operand gave wrong residues for images above 0 without an error.) Results are bit-identical to n separate calls.
  * n = 1 (default) restores single-ciphertext behaviour; the L0 one-row primitives above, hc_permute, the L1 convolution (which has its own
- * batch entry point) and hc_encode_coeffs / hc_encrypt_sk / hc_decrypt_decode_coeffs (which carry their own `count`) ignore the setting. A decomposition held by hc_keyswitch_decompose belongs to the batch it was taken under.
+ * batch entry point) and hc_encode_slots / hc_encode_slots_ex / hc_encode_coeffs / hc_encrypt_sk / hc_decrypt_decode_coeffs (which carry their own `count`) ignore the setting. A decomposition held by hc_keyswitch_decompose belongs to the batch it was taken under.
  * The setting is context STATE (calls on one hc_ctx are serialised by the caller): a binding must hold it in a scope that restores n = 1 on every way out - INTEGRATION.md 3d
  * (`Batched` with a deferred reset), `Context.batch()` in abi.py, `Boot::Batch` in the C++ host. Under n > 1 every entry point checks the strides against the footprint of its
  * operands at the call's level - poly_stride >= (level+1) N, qp_stride >= 2 (level+1+np) N where it takes extended-basis pairs - and fails with HC_ERR_ARG otherwise (images
@@ -290,6 +290,16 @@ int hc_pack_ctxts_strided(hc_ctx *ctx, uint64_t *cts, int count, int stride_log2
  * Encode; level: rows 0..level (moduli 0..level) are produced; to_ntt != 0: the rows are left in the NTT domain. out: DEVICE
  * [count][level+1][N]. IEEE fp64 without contraction in the reference's operand order: the same residues as the CPU encoder. */
 int hc_encode_slots(hc_ctx *ctx, double *values, int count, int level, double scale, int to_ntt, uint64_t *out);
+/* ckks.(*encoderComplex128).Embed + scaleUpVecExact (+ ToNTT) with sparse slots and rows modulo the special primes: what encodeDiagonal leaves of a linear transform's
+ * diagonal, and any plaintext of a sparse-slot bootstrapper (no new hc_version(): detected by symbol). values: DEVICE [count][2^log_slots] complex128 as (re, im) pairs,
+ * OVERWRITTEN; 0 <= log_slots <= 15. The special inverse FFT runs over n = 2^log_slots points (the sub-ring's roots are the full table's entries at the same angles),
+ * is divided by n and bit-reversed over log_slots bits; real parts go to coefficients i * gap, imaginary parts to N/2 + i * gap, gap = (N/2) / n, and every other
+ * coefficient is the word 0. out: DEVICE [count][level + 1 + (with_p ? np : 0)][N], rows Q_0..Q_level then P_0..P_{np-1}: the layout hc_qp_mul_sum* reads. to_ntt != 0
+ * leaves every row, the P rows included, in the NTT domain. Under pack32 = 2 the Q rows of hc_row_is32 limbs are 4-byte words, as hc_encode_slots writes them; P rows
+ * are 8-byte words (a row goes by hc_row_is32 of its modulus as in every extended-basis operand, and the special primes of every parameter set are above 2^31).
+ * hc_encode_slots(ctx, v, count, level, scale, to_ntt, out) is hc_encode_slots_ex(ctx, v, count, 15, level, 0, scale, to_ntt, out): one body, the same bits.
+ * Bad arguments return HC_ERR_ARG and leave the context usable. */
+int hc_encode_slots_ex(hc_ctx *ctx, double *values, int count, int log_slots, int level, int with_p, double scale, int to_ntt, uint64_t *out);
 /* ckks.Encoder.EncodeCoeffs (+ ToNTT), the coefficient-domain sibling of hc_encode_slots (hc_version() >= 5). values: DEVICE [count][nvals] doubles (not modified), nvals <= N
  * (coefficients past nvals are 0); out: DEVICE [count][level+1][N]. scaleUpVecExact's rounding, uint64(|v| * scale + 0.5) mod q_l and q_l - . for negative v, in plain IEEE
  * fp64: the same residues as the CPU encoder. HC_ERR_UNSUPPORTED if any |value * scale| > 2^64 or is not finite (the reference's big-float branch is not built; the context
@@ -321,7 +331,7 @@ int hc_bl_post_ker_slots(hc_ctx *ctx, const double *max_ker_rs, int in_wid, int 
  * pointer arithmetic of the caller changes; the second half of such a row's slot is simply unused).
  *   1 (default): inside the library only - the seam between the two passes of every transform, the extended digits of a key switch, the switching keys. Invisible at this ABI.
  *   2: ALSO in every LEVELED operand a caller hands in or gets back - the polynomials of hc_lv_*, hc_rotate_finish, hc_lv_permute, hc_keyswitch*, hc_div_round_last / 2 (general
- *      level), the extended-basis pairs of hc_keyswitch_qp*, hc_mod_down2*, hc_qp_*, the plaintexts they multiply by, hc_encode_slots' output. hc_row_is32(ctx, mod) tells which
+ *      level), the extended-basis pairs of hc_keyswitch_qp*, hc_mod_down2*, hc_qp_*, the plaintexts they multiply by, hc_encode_slots' and hc_encode_slots_ex' output. hc_row_is32(ctx, mod) tells which
  *      limbs that concerns; a caller converts at its own boundary only (what it uploads into / downloads from such rows: the C++ host's Boot::put_rows / get_rows; ciphertexts
  *      enter and leave the chain at levels 0 / 1, whose limbs are large, so the hot path converts nothing). The L0 one-row primitives (hc_ntt ... hc_permute with an explicit
  *      modulus or row count), the level-0/1 convolution path, hc_encrypt_sk / hc_decrypt_decode_coeffs (level 0 / 1 only) and hc_swk_generate's secret-key rows keep 8-byte rows;

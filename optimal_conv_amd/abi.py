@@ -93,6 +93,7 @@ SYMBOLS = {
     "hc_conv_then_pack_sharded": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_void_p), C.c_double, C.POINTER(C.c_void_p), C.c_double, C.c_int,
                                             C.c_double, C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]),
     "hc_encode_slots": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_int, C.c_void_p]),
+    "hc_encode_slots_ex": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_void_p]),
     "hc_encode_coeffs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_void_p]),
     "hc_encrypt_sk": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32), C.c_uint64, C.POINTER(C.c_void_p)]),
     "hc_decrypt_decode_coeffs": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.c_void_p, C.c_double, C.c_void_p]),
@@ -564,6 +565,20 @@ class Context:
         res = out.download((count, level + 1, self.N))
         dv.free(); out.free()
         return res
+
+    def encode_slots_ex(self, values, log_slots, level, with_p, scale, to_ntt=True):
+        """hc_encode_slots_ex: values complex128 [count][2^log_slots] (host) -> uint64 [count][level+1 (+ np if with_p)][N], rows Q_0..Q_level then the special primes;
+        under pack32 = 2 the 4-byte rows come back as 8-byte words"""
+        v = np.ascontiguousarray(values, dtype=np.complex128).reshape(-1, 1 << log_slots) if 0 <= log_slots <= 15 else np.zeros((1, 1), dtype=np.complex128)
+        count = v.shape[0]
+        per = level + 1 + (len(self.p) if with_p else 0)
+        dv = self.buf(v.view(np.float64).reshape(-1).view(np.uint64))
+        out = self.buf(nwords=max(1, count * per * self.N))
+        try:
+            self._ck(self.L.hc_encode_slots_ex(self.h, dv.ptr, count, log_slots, level, 1 if with_p else 0, scale, 1 if to_ntt else 0, out.ptr))
+            return self.unpack_rows(out.download((count, per, self.N)), level + 1, per)
+        finally:
+            dv.free(); out.free()
 
     def encode_coeffs(self, values, level, scale, to_ntt=True):
         """hc_encode_coeffs: values float64 [count][nvals] (host; one vector if 1-D) -> uint64 [count][level+1][N]; under pack32 = 2 the 4-byte rows come back as 8-byte words"""

@@ -2753,17 +2753,21 @@ __global__ __launch_bounds__(HC_TPB) void hc_k_swk_finish(u64 *rows, const u64 *
     }
 }
 
-// ================================================================ slot encoder (ckks.Encoder.Encode / EncodeNTT, full slots)
+// ================================================================ slot encoder (ckks.Encoder.Encode / EncodeNTT: Embed + scaleUpVecExact, full and sparse slots)
 // Lattigo's "special" inverse FFT over the rotation group 5^j (encoder.go invfft; restated on the host in hconv_encoder.hpp and, for
-// the tests, in tests/oracle_bl.py): n = N/2 = 2^15 complex values, stages len = n .. 2 (distance len/2, large first), butterfly
+// the tests, in tests/oracle_bl.py / tests/oracle_ckks.py): n = 2^log_slots <= N/2 complex values, stages len = n .. 2 (distance len/2,
+// large first), butterfly
 //     u = a + b ;  w = (a - b) * roots[(4 len - rotGroup[j] mod 4 len) * (2N / 4 len)],   j = position inside the block,
-// then division by n, the bit-reversal permutation, real parts -> coefficients [0, n), imaginary parts -> [n, N), and
-// scaleUpVecExact's rounding (uint64(|v| * scale + 0.5) mod q, q - . for negative v). Plain IEEE fp64 with NO contraction and the
-// reference's operand order, so the doubles -- and therefore the residues -- are the ones the reference's Go code produces: the
-// root table comes from hc_gomath.h (math.Cos / math.Sin as Go's runtime evaluates them; SHA-256 equal to the table inside the
-// reference binary), and tests/test_oracle_pin_encoder.py pins the oracle this kernel is compared with to the binary's own
-// invfft / Encode digests. n is viewed as 128 rows x 256 columns: pass A runs the 7 stages that pair
-// rows (tile = 128 rows x 16 columns = 32 KiB of LDS), pass B the 8 stages inside a row (tile = 8 rows x 256 columns).
+// then division by n, the bit-reversal permutation over log_slots bits, real parts -> coefficients i * gap, imaginary parts ->
+// N/2 + i * gap (gap = (N/2) / n; every other coefficient is the word 0), and scaleUpVecExact's rounding (uint64(|v| * scale + 0.5)
+// mod q, q - . for negative v). The root index does not depend on n: the roots of the ring with n slots are the full ring's table at
+// the same angles, and its rotation group is the full one modulo 4 len. Plain IEEE fp64 with NO contraction and the reference's
+// operand order, so the doubles -- and therefore the residues -- are the ones the reference's Go code produces: the root table comes
+// from hc_gomath.h (math.Cos / math.Sin as Go's runtime evaluates them; SHA-256 equal to the table inside the reference binary), and
+// tests/test_oracle_pin_encoder.py / test_oracle_pin_dft.py pin the oracle these kernels are compared with to the binary's own
+// invfft / Encode / encodeDiagonal digests. A vector of n > 2048 values is viewed as R = n / 256 rows x 256 columns: pass A runs the
+// log2 R stages that pair rows (tile = R rows x 16 columns, at most 32 KiB of LDS), pass B the 8 stages inside a row (tile = 8 rows x
+// 256 columns). A vector of n <= 2048 values fits one tile: pass B alone runs all its stages, 2048 / n vectors per workgroup.
 struct HcCplx { double re, im; };
 struct HcSlotEnc { const HcCplx *roots; const int *rot_group; };     // roots[0 .. 2N], rot_group[0 .. N/2)
 __device__ __forceinline__ void hc_sfft_inv_bfly(HcCplx &a, HcCplx &b, const HcSlotEnc &E, int j, int len) {
@@ -2774,57 +2778,65 @@ __device__ __forceinline__ void hc_sfft_inv_bfly(HcCplx &a, HcCplx &b, const HcS
     const double p0 = dr * r.re, p1 = di * r.im, p2 = dr * r.im, p3 = di * r.re;
     a.re = ur; a.im = ui; b.re = p0 - p1; b.im = p2 + p3;
 }
-// pass A: grid = (16 column tiles, count); in/out: [count][32768] complex, in place allowed
-__global__ __launch_bounds__(HC_TPB) void hc_k_sfft_inv_a(const HcCplx *in, HcCplx *out, HcSlotEnc E) {
-    __shared__ HcCplx lds[2048];                       // [128 rows][16 columns]
-    const int t = threadIdx.x, c0 = blockIdx.x * 16;
-    const size_t base = (size_t)blockIdx.y * 32768;
-    for (int e = t; e < 2048; e += HC_TPB) { const int r = e >> 4, c = e & 15; lds[e] = in[base + (size_t)r * 256 + c0 + c]; }
+// pass A (n = R x 256, R = 2^log_r in 16 .. 128): grid = (16 column tiles, count); in/out: [count][n] complex, in place allowed
+__global__ __launch_bounds__(HC_TPB) void hc_k_sfft_inv_a(const HcCplx *in, HcCplx *out, HcSlotEnc E, int log_r) {
+    __shared__ HcCplx lds[2048];                       // [R rows][16 columns]
+    const int t = threadIdx.x, c0 = blockIdx.x * 16, ne = 16 << log_r;
+    const size_t base = (size_t)blockIdx.y << (log_r + 8);
+    for (int e = t; e < ne; e += HC_TPB) { const int r = e >> 4, c = e & 15; lds[e] = in[base + (size_t)r * 256 + c0 + c]; }
     __syncthreads();
-    for (int Lh = 64; Lh >= 1; Lh >>= 1) {             // distance in rows; len = 2 * Lh * 256
-        for (int b = t; b < 1024; b += HC_TPB) {
-            const int c = b & 15, q = b >> 4;          // q: butterfly number among the 64 of a column
-            const int blk = q / Lh, rr = q - blk * Lh, r = blk * 2 * Lh + rr;
+    for (int s = log_r - 1; s >= 0; s--) {             // distance in rows Lh = 2^s; len = 2 * Lh * 256
+        const int Lh = 1 << s;
+        for (int b = t; b < (ne >> 1); b += HC_TPB) {
+            const int c = b & 15, q = b >> 4;          // q: butterfly number among the R / 2 of a column
+            const int blk = q >> s, rr = q & (Lh - 1), r = blk * 2 * Lh + rr;
             hc_sfft_inv_bfly(lds[r * 16 + c], lds[(r + Lh) * 16 + c], E, rr * 256 + c0 + c, 2 * Lh * 256);
         }
         __syncthreads();
     }
-    for (int e = t; e < 2048; e += HC_TPB) { const int r = e >> 4, c = e & 15; out[base + (size_t)r * 256 + c0 + c] = lds[e]; }
+    for (int e = t; e < ne; e += HC_TPB) { const int r = e >> 4, c = e & 15; out[base + (size_t)r * 256 + c0 + c] = lds[e]; }
 }
-// pass B: grid = (16 row tiles, count)
-__global__ __launch_bounds__(HC_TPB) void hc_k_sfft_inv_b(const HcCplx *in, HcCplx *out, HcSlotEnc E) {
-    __shared__ HcCplx lds[2048];                       // [8 rows][256 columns]
+// pass B: the stages len = 2^log_len .. 2 on tiles of 2048 consecutive values of the `total` = count x n (a multiple of 2^log_len; the last tile may be short):
+// 8 rows of a long vector (log_len = 8), or whole vectors of n = 2^log_len <= 2048 values. grid = ceil(total / 2048)
+__global__ __launch_bounds__(HC_TPB) void hc_k_sfft_inv_b(const HcCplx *in, HcCplx *out, HcSlotEnc E, size_t total, int log_len) {
+    __shared__ HcCplx lds[2048];
     const int t = threadIdx.x;
-    const size_t base = (size_t)blockIdx.y * 32768 + (size_t)blockIdx.x * 2048;
-    for (int e = t; e < 2048; e += HC_TPB) lds[e] = in[base + e];
+    const size_t base = (size_t)blockIdx.x * 2048;
+    const int ne = total - base < 2048 ? (int)(total - base) : 2048;
+    for (int e = t; e < ne; e += HC_TPB) lds[e] = in[base + e];
     __syncthreads();
-    for (int lenh = 128; lenh >= 1; lenh >>= 1) {
-        for (int b = t; b < 1024; b += HC_TPB) {
-            const int row = b >> 7, q = b & 127;       // 128 butterflies per row
-            const int blk = q / lenh, j = q - blk * lenh, cidx = blk * 2 * lenh + j;
-            hc_sfft_inv_bfly(lds[row * 256 + cidx], lds[row * 256 + cidx + lenh], E, j, 2 * lenh);
+    for (int s = log_len - 1; s >= 0; s--) {
+        const int lenh = 1 << s;
+        for (int b = t; b < (ne >> 1); b += HC_TPB) {
+            const int blk = b >> s, j = b & (lenh - 1), idx = blk * 2 * lenh + j;
+            hc_sfft_inv_bfly(lds[idx], lds[idx + lenh], E, j, 2 * lenh);
         }
         __syncthreads();
     }
-    for (int e = t; e < 2048; e += HC_TPB) out[base + e] = lds[e];
+    for (int e = t; e < ne; e += HC_TPB) out[base + e] = lds[e];
 }
-// division by n, bit reversal, real | imaginary split, scaleUpVecExact: w [count][32768] complex -> rows [count][nl][N], coefficient
-// domain, modulus of row l = mods[l]. grid = (64, count)
-__global__ __launch_bounds__(HC_TPB) void hc_k_slots_round(const HcCplx *w, u64 *out, const HcMod *mods, int nl, double scale) {
+// division by n, bit reversal, real | imaginary split at stride gap, scaleUpVecExact: w [count][n] complex -> rows [count][nl + np][N], coefficient domain; row l < nl is
+// modulo mods[l], row nl + j modulo the special prime mods[nq + j]; a row is 4-byte words where its modulus' HcMod::row32 says so, as in every extended-basis operand (the
+// special primes of every parameter set are above 2^31: 8-byte rows). grid = (64, count)
+__global__ __launch_bounds__(HC_TPB) void hc_k_slots_round(const HcCplx *w, u64 *out, const HcMod *mods, int nl, int np, int nq, int log_slots, double scale) {
 #pragma clang fp contract(off)
-    const HcCplx *v = w + (size_t)blockIdx.y * 32768; u64 *o = out + (size_t)blockIdx.y * nl * 65536;
+    const int lg = 15 - log_slots, nrows = nl + np;
+    const double inv_n = 1.0 / (double)(1 << log_slots);                                 // exact: a power of two
+    const HcCplx *v = w + ((size_t)blockIdx.y << log_slots); u64 *o = out + (size_t)blockIdx.y * nrows * 65536;
     for (int i = blockIdx.x * HC_TPB + threadIdx.x; i < 65536; i += gridDim.x * HC_TPB) {
-        const int tix = i & 32767, src = (int)(__brev((u32)tix) >> 17);
-        const double val = (i < 32768 ? v[src].re : v[src].im) * (1.0 / 32768.0);       // exact: a power of two
+        const int tix = i & 32767, k = tix >> lg, src = log_slots ? (int)(__brev((u32)k) >> (32 - log_slots)) : 0;
+        double val = 0.0;                                                                // off the gap grid: the word 0 in every row
+        if (!(tix & ((1 << lg) - 1))) val = (i < 32768 ? v[src].re : v[src].im) * inv_n;
         const bool neg = val < 0; const double x = neg ? -scale * val : scale * val;
-        for (int l = 0; l < nl; l++) {
-            const u64 q = mods[l].q; u64 r;
+        for (int l = 0; l < nrows; l++) {
+            const HcMod &m = mods[l < nl ? l : nq + (l - nl)];
+            const u64 q = m.q; u64 r;
             if (x > 1.8446744073709552e+19) {           // above 2^64: the 53-bit mantissa times 2^(e - 53), reduced by doubling
                 int e2; const double mant = frexp(x + 0.5, &e2); const u64 mi = (u64)ldexp(mant, 53); r = mi % q;
                 for (int sft = 0; sft < e2 - 53; sft++) { r += r; if (r >= q) r -= q; }
             } else r = (u64)(x + 0.5) % q;
             const u64 vv = neg ? q - r : r;                     // q itself when r == 0, as scaleUpVecExact leaves it (the NTT maps it to the same row as 0)
-            if (mods[l].row32) hc_st32(o + (size_t)l * 65536, (size_t)i, vv); else o[(size_t)l * 65536 + i] = vv;
+            if (m.row32) hc_st32(o + (size_t)l * 65536, (size_t)i, vv); else o[(size_t)l * 65536 + i] = vv;
         }
     }
 }

@@ -138,7 +138,7 @@ struct hc_ctx {
     const void *hoist_cx = nullptr; int hoist_level = -1;   // the polynomial whose digit decomposition ws_mm currently holds
     long chunk_nodes = 64;
     hipEvent_t ev_fork = nullptr;
-    HcCplx *enc_roots = nullptr; int *enc_rot_group = nullptr;      // slot encoder tables (hc_encode_slots), built at first use
+    HcCplx *enc_roots = nullptr; int *enc_rot_group = nullptr;      // slot encoder tables (hc_encode_slots*), built at first use
     u32 *d_flag = nullptr;                                          // hc_encode_coeffs: the word its kernel raises for a value it refuses
     hipEvent_t ev_shard = nullptr;     // hc_conv_then_pack_sharded: this device's partial ciphertext is complete / has been collected
     u64 *ws_gather = nullptr; size_t ws_gather_rows = 0;
@@ -325,7 +325,7 @@ static int hc_build_tables(hc_ctx *c, HcModHost *mh, bool inverse) {
     return HC_OK;
 }
 
-extern "C" int hc_version(void) { return 5; }      // 2: a plaintext shared by the images of a batch is said by the operation (HC_LV_MUL_PLAIN), never inferred from b0 == b1; 3: hc_prep_ker_ex (transposed kernels); 4: hc_prep_ker_ex2 (dilated, channel-strided kernels); 5: hc_encode_coeffs, hc_encrypt_sk, hc_decrypt_decode_coeffs
+extern "C" int hc_version(void) { return 5; }      // 2: a plaintext shared by the images of a batch is said by the operation (HC_LV_MUL_PLAIN), never inferred from b0 == b1; 3: hc_prep_ker_ex (transposed kernels); 4: hc_prep_ker_ex2 (dilated, channel-strided kernels); 5: hc_encode_coeffs, hc_encrypt_sk, hc_decrypt_decode_coeffs (hc_encode_slots_ex came later without a new number: detected by symbol)
 extern "C" const char *hc_last_error(const hc_ctx *c) { return c ? c->err.c_str() : g_create_err.c_str(); }
 
 // HcMod::row32 of modulus i of the context's nmods (Q then P): under pack32 = 2 the rows of a modulus below 2^31 in the caller's leveled operands are 4-byte words - except
@@ -1866,7 +1866,7 @@ extern "C" int hc_conv_then_pack_sharded(hc_ctx *const *ctxs, int G, const uint6
     return HC_OK;
 }
 
-// ------------------------------------------------------------------ slot encoder (ckks.Encoder.EncodeNTT), BL baseline's plaintexts
+// ------------------------------------------------------------------ slot encoder (ckks.Encoder.EncodeNTT): the chain's diagonals and masks, the BL baseline's plaintexts
 static int hc_enc_tables(hc_ctx *c) {
     if (c->enc_roots) return HC_OK;
     const int m = 2 * HC_N, slots = HC_N / 2;
@@ -1883,19 +1883,34 @@ static int hc_enc_tables(hc_ctx *c) {
     c->enc_roots = d_roots; c->enc_rot_group = d_rg;
     return HC_OK;
 }
-// values: DEVICE [count][N/2] complex128 (re, im); overwritten (the transform runs in place). out: DEVICE [count][level+1][N]
-extern "C" int hc_encode_slots(hc_ctx *c, double *values, int count, int level, double scale, int to_ntt, uint64_t *out) {
-    HC_ENTER(c);
-    if (!values || !out || count < 1 || count > 65535 || level < 0 || level >= c->nq) return hc_fail(c, HC_ERR_ARG, "hc_encode_slots: bad arguments");
+// ckks.(*encoderComplex128).Embed + scaleUpVecExact (+ ToNTT) for count vectors of 2^log_slots values. values: DEVICE [count][2^log_slots] complex128 (re, im); overwritten
+// (the transform runs in place). out: DEVICE [count][level + 1 + (with_p ? np : 0)][N], rows Q_0..Q_level then P_0..P_{np-1}. One or two transform launches (a vector of
+// at most 2048 values is one LDS tile), one rounding launch, and ONE batched forward transform over the Q and P rows of every vector (as hc_swk_generate transforms a key's)
+static int hc_encode_slots_impl(hc_ctx *c, const char *fn, double *values, int count, int log_slots, int level, int with_p, double scale, int to_ntt, uint64_t *out) {
+    if (!values || !out || count < 1 || count > 65535 || log_slots < 0 || log_slots > 15 || level < 0 || level >= c->nq)
+        return hc_fail(c, HC_ERR_ARG, "%s: bad arguments (1 <= count <= 65535, 0 <= log_slots <= 15, 0 <= level < %d, non-null pointers)", fn, c->nq);
     HC_TRY(hc_enc_tables(c));
     HcSlotEnc E; E.roots = c->enc_roots; E.rot_group = c->enc_rot_group;
     HcCplx *v = (HcCplx *)values;
-    HC_TRY(hc_launch(c, "sfft_inv_a", hc_k_sfft_inv_a, dim3(16, (unsigned)count), (const HcCplx *)v, v, E));
-    HC_TRY(hc_launch(c, "sfft_inv_b", hc_k_sfft_inv_b, dim3(16, (unsigned)count), (const HcCplx *)v, v, E));
-    HC_TRY(hc_launch(c, "slots_round", hc_k_slots_round, dim3(64, (unsigned)count), (const HcCplx *)v, (u64 *)out, (const HcMod *)c->d_mods, level + 1, scale));
-    HcNttCall m; m.rows = m.nl = level + 1; m.nz = count; m.in = {out, (size_t)(level + 1) * HC_N, 0, HC_ROWS_USER}; m.out = {out, (size_t)(level + 1) * HC_N, 0, HC_ROWS_USER};
-    if (to_ntt) { c->hoist_cx = nullptr; HC_TRY(hc_ntt_mm(c, m)); }
+    const int nl = level + 1, np = with_p ? c->np : 0, nt = nl + np;
+    const size_t total = (size_t)count << log_slots;
+    if (log_slots > 11) HC_TRY(hc_launch(c, "sfft_inv_a", hc_k_sfft_inv_a, dim3(16, (unsigned)count), (const HcCplx *)v, v, E, log_slots - 8));
+    if (log_slots > 0) HC_TRY(hc_launch(c, "sfft_inv_b", hc_k_sfft_inv_b, dim3((unsigned)((total + 2047) / 2048)), (const HcCplx *)v, v, E, total, log_slots > 11 ? 8 : log_slots));
+    HC_TRY(hc_launch(c, "slots_round", hc_k_slots_round, dim3(64, (unsigned)count), (const HcCplx *)v, (u64 *)out, (const HcMod *)c->d_mods, nl, np, c->nq, log_slots, scale));
+    if (!to_ntt) return HC_OK;
+    c->hoist_cx = nullptr;
+    HcNttCall m; m.rows = nt; m.nl = nl; m.nz = count; m.in = {out, (size_t)nt * HC_N, 0, HC_ROWS_USER}; m.out = {out, (size_t)nt * HC_N, 0, HC_ROWS_USER};       // row nl + j: special prime j
+    HC_TRY(hc_ntt_mm(c, m));
     return HC_OK;
+}
+extern "C" int hc_encode_slots_ex(hc_ctx *c, double *values, int count, int log_slots, int level, int with_p, double scale, int to_ntt, uint64_t *out) {
+    HC_ENTER(c);
+    return hc_encode_slots_impl(c, "hc_encode_slots_ex", values, count, log_slots, level, with_p, scale, to_ntt, out);
+}
+// full slots, rows Q_0..Q_level: the BL baseline's plaintexts
+extern "C" int hc_encode_slots(hc_ctx *c, double *values, int count, int level, double scale, int to_ntt, uint64_t *out) {
+    HC_ENTER(c);
+    return hc_encode_slots_impl(c, "hc_encode_slots", values, count, 15, level, 0, scale, to_ntt, out);
 }
 // ckks.Encoder.EncodeCoeffs (+ ToNTT): one launch rounds every coefficient into all limbs of the level, the batched forward transform follows. The one-word flag the kernel
 // raises for a value scaleUpVecExact would hand to its big-float branch is read back before the call returns (the only host synchronisation of the call)

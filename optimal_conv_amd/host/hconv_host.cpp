@@ -320,6 +320,13 @@ bool deviceEncrypt() {
     }();
     return v;
 }
+bool deviceEncode() {
+    static const bool v = [] {
+        if (const char *e = getenv("HCONV_DEVICE_ENCODE")) return atoi(e) != 0;
+        return true;                                                          // unset: the device path (set-up times against the host path: profiles/LEDGER.md)
+    }();
+    return v;
+}
 std::vector<Ciphertext> EncryptCoeffsBatch(Context *c, const std::vector<const std::vector<double> *> &inputs, int level, double scale) {
     std::vector<Ciphertext> out; const int n = (int)inputs.size();
     if (!deviceEncrypt()) { for (const auto *in : inputs) out.push_back(EncryptNew(c, EncodeCoeffs(*in, level, scale), level, scale)); return out; }
@@ -694,6 +701,7 @@ void testConv_in(int in_batch, int in_wid, int ker_wid, int total_test_num, bool
             }
             long nk, nks; bootStats(cont->btp, &nk, &nks);
             if (getenv("HCONV_BOOT_STATS")) printf("boot stats: %ld switching keys generated, %ld key switches\n", nk, nks);
+            if (getenv("HCONV_BOOT_STATS")) { long nd, nm; bool dev; bootEncodeStats(cont->btp, &nd, &nm, &dev); printf("boot stats: %ld diagonals and %ld masks encoded on the %s\n", nd, nm, dev ? "device" : "host"); }
             for (Ciphertext &ct : ins) freeCt(cont, ct);
             for (Ciphertext &ct : ct_conv) freeCt(cont, ct);
             for (BootCiphertext &ct : ct_res) freeBootCt(cont->btp, ct);

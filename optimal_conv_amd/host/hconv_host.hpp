@@ -135,6 +135,9 @@ std::vector<double> DecryptDecodeCoeffs(Context *cont, const Ciphertext &ct);
 // HCONV_DEVICE_ENCRYPT: 1 = hc_encode_coeffs + hc_encrypt_sk / hc_decrypt_decode_coeffs, 0 or unset = the host encryptor and decryptor (every
 // existing run keeps the stream it has; the default waits for the measurement profiles/LEDGER.md asks for). Under HCONV_RESNET_REPLAY / HCONV_CHAIN_REPLAY* the draws are always the host's.
 bool deviceEncrypt();
+// HCONV_DEVICE_ENCODE: 1 = the bootstrappers' DFT diagonals and slot masks are encoded by hc_encode_slots_ex from uploaded VALUE vectors (all diagonals of a matrix in a few
+// calls), 0 = by hconv_encoder.hpp on the host, a diagonal at a time. The same words either way: no replay, digest or seeded stream depends on the switch.
+bool deviceEncode();
 // EncodeCoeffs + EncryptNew of n inputs: ONE hc_encode_coeffs and ONE hc_encrypt_sk call on the device path, n EncryptNew calls otherwise
 std::vector<Ciphertext> EncryptCoeffsBatch(Context *cont, const std::vector<const std::vector<double> *> &inputs, int level, double scale);
 // Decrypt + DecodeCoeffs of n level-0 ciphertexts: ONE hc_decrypt_decode_coeffs call on the device path
@@ -167,6 +170,7 @@ std::vector<BootCiphertext> evalConv_BNRelu_tail_batch(Boot *B, const std::strin
 std::vector<double> bootDecryptDecodeCoeffs(Boot *B, const BootCiphertext &ct);
 void freeBootCt(Boot *B, BootCiphertext &ct);
 void bootStats(Boot *B, long *keys, long *keyswitches);
+void bootEncodeStats(Boot *B, long *diagonals, long *masks, bool *device);   // plaintexts encoded since the bootstrapper was built, and where (deviceEncode)
 // ---- the baseline's bootstrapping + ReLU (test_BL.go:113-168) on parameter set [7]: cont.btp.Bootstrapp (the stock full-slot
 // bootstrapper), imaginary packing / unpacking, evalReLU + MulByPow2 + SetScale on both halves
 Boot *newBootBL(const std::vector<int64_t> &sk, const Seed256 &seed, int device);

@@ -90,6 +90,8 @@ struct Boot {
     std::map<int, Encoder> sub_enc;                                    // encoders of the rings with fewer slots (sparse embedding), by log2 of their degree
     std::vector<double> sine;
     long n_keyswitch = 0, n_keys = 0;
+    const bool dev_encode = deviceEncode();                  // HCONV_DEVICE_ENCODE: diagonals and masks through hc_encode_slots_ex (the same words as hconv_encoder.hpp gives)
+    long n_enc_diag = 0, n_enc_mask = 0;
     bool parts_merged = false;                               // ctos_fork returned ONE ciphertext of 2 nb images (both halves): see merge2
     // algorithmic traffic of what has been evaluated, in rows of N residues (SURVEY.md 8(d)'s convention carried to the chain: every evaluator operation reads its
     // ciphertext operands once and writes its result once, temporaries stay on chip; switching keys, diagonals and masks are read once per operation and - being common
@@ -405,7 +407,21 @@ struct Boot {
         std::vector<cplx> tmp((size_t)N / 2, cplx(0, 0)); for (size_t i = 0; i < idx.size(); i++) tmp[i] = cplx((double)idx[i], 0);
         return pt_cache.emplace(k, encode(tmp, level, scale)).first->second;
     }
+    // count slot vectors of 2^log_slots values each (vals[z]) -> out: DEVICE [count][level + 1 (+ np with_p)][N], NTT domain, in the row widths the context reads: the
+    // VALUES are uploaded (512 KiB per full-slot vector) and ONE hc_encode_slots_ex call embeds, rounds and transforms them all
+    void encode_device(const std::vector<const std::vector<cplx> *> &vals, int level, bool with_p, double scale, uint64_t *out) {
+        const size_t n = vals[0]->size(); int lg = 0; while (((size_t)1 << lg) < n) lg++;
+        if (((size_t)1 << lg) != n || lg > LOGN - 1) panic("encode_device: a slot vector of 2^k <= N/2 values expected");
+        std::vector<cplx> flat(vals.size() * n);
+        for (size_t z = 0; z < vals.size(); z++) { if (vals[z]->size() != n) panic("encode_device: vectors of one length expected"); std::copy(vals[z]->begin(), vals[z]->end(), flat.begin() + z * n); }
+        void *dv = nullptr; HCR(hc_malloc(hc, flat.size() * sizeof(cplx), &dv));
+        HCR(hc_upload(hc, dv, flat.data(), flat.size() * sizeof(cplx)));
+        HCR(hc_encode_slots_ex(hc, (double *)dv, (int)vals.size(), lg, level, with_p ? 1 : 0, scale, 1, out));
+        HCR(hc_free(hc, dv));
+    }
     DPt encode(const std::vector<cplx> &slots, int level, double scale) {
+        n_enc_mask++;
+        if (dev_encode) { DPt pt; pt.level = level; pt.scale = scale; pt.p = block1(); encode_device({&slots}, level, false, scale, pt.p.get()); return pt; }
         std::vector<uint64_t> rows = enc.Encode(slots, scale, Q.data(), level + 1);
         Single one(this);
         DPt pt; pt.level = level; pt.scale = scale; pt.p = block1();
@@ -581,29 +597,47 @@ struct Boot {
             if (best < 0 || cost < best) { best = cost; lt.n1 = n1; }
         }
         if (lattigo_split) lt.n1 = lattigo_n1(M, n);
+        // every linear transform of a bootstrapper runs in the extended basis (linear_transform_qp): the diagonals are encoded mod Q_0..Q_level and mod every P. On the
+        // host path one at a time (encode_qp); on the device path a call encodes as many as fit about 256 rows, into ONE allocation the DPts of the batch share
+        struct Diag { int k, g, b; std::vector<cplx> rolled; };
+        const size_t nt = (size_t)level + 1 + P.size(), per_call = dev_encode ? std::max<size_t>(1, 256 / nt) : 1;
+        std::vector<Diag> diags; size_t left = M.size();
+        lt.qp = true; n_enc_diag += (long)M.size();
         for (auto &e : M) {
-            const int k = e.first, g = k - k % lt.n1, b = k % lt.n1;
-            std::vector<cplx> rolled((size_t)n); for (int p = 0; p < n; p++) rolled[(size_t)p] = e.second[(size_t)(((p - g) % n + n) % n)];     // np.roll(diag, g) = the fork's rotate(v, -N1*j)
-            lt.giant[g][b] = encode_qp(rolled, level, pt_scale);      // every bootstrapper's linear transforms run in the extended basis (linear_transform_qp)
-            lt.qp = true;
-            if (dft_digests) {      // what the reference's encodeDiagonal receives and returns (mod Q): values; NTT rows in Montgomery form + the spare zero limb
-                Sha256 hv; hv.update(rolled.data(), rolled.size() * sizeof(cplx));
-                std::vector<uint64_t> rows((size_t)(level + 1) * N), zero((size_t)N, 0);
-                HCR(hc_download(hc, rows.data(), lt.giant[g][b].p.get(), rows.size() * 8));
-                unpack_rows(rows, level + 1);
-                for (int l = 0; l <= level; l++) { const uint64_t q = Q[(size_t)l], r = (uint64_t)((((u128)1) << 64) % q); for (int j = 0; j < N; j++) rows[(size_t)l * N + j] = mulmod(rows[(size_t)l * N + j], r, q); }
-                Sha256 hq; hq.update(rows.data(), rows.size() * 8); hq.update(zero.data(), zero.size() * 8);
-                std::string mp = "";
-                if (lt.qp) {            // ... and mod P
-                    const int np = (int)P.size(); std::vector<uint64_t> prow((size_t)np * N);
-                    HCR(hc_download(hc, prow.data(), lt.giant[g][b].p.get() + (size_t)(level + 1) * N, prow.size() * 8));
-                    for (int j = 0; j < np; j++) { const uint64_t q = P[(size_t)j], r = (uint64_t)((((u128)1) << 64) % q); for (int i = 0; i < N; i++) prow[(size_t)j * N + i] = mulmod(prow[(size_t)j * N + i], r, q); }
-                    Sha256 hp; hp.update(prow.data(), prow.size() * 8); mp = hp.hex();
-                }
-                fprintf(dft_digests, "{\"matrix\": \"%s\", \"chain\": %d, \"level\": %d, \"scale\": %.17g, \"N1\": %d, \"k\": %d, \"values\": \"%s\", \"mQ\": \"%s\", \"mP\": \"%s\"}\n", tag, chain, level, pt_scale, lt.n1, k, hv.hex().c_str(), hq.hex().c_str(), mp.c_str());
+            Diag d; d.k = e.first; d.g = d.k - d.k % lt.n1; d.b = d.k % lt.n1; d.rolled.resize((size_t)n);
+            for (int p = 0; p < n; p++) d.rolled[(size_t)p] = e.second[(size_t)(((p - d.g) % n + n) % n)];     // np.roll(diag, g) = the fork's rotate(v, -N1*j)
+            diags.push_back(std::move(d)); left--;
+            if (diags.size() < per_call && left) continue;
+            if (!dev_encode) lt.giant[diags[0].g][diags[0].b] = encode_qp(diags[0].rolled, level, pt_scale);
+            else {
+                void *v = nullptr; HCR(hc_malloc(hc, diags.size() * nt * N * 8, &v)); hc_ctx *h = hc;
+                std::shared_ptr<uint64_t> base((uint64_t *)v, [h](uint64_t *x) { hc_free(h, x); });
+                std::vector<const std::vector<cplx> *> vals; for (auto &x : diags) vals.push_back(&x.rolled);
+                encode_device(vals, level, true, pt_scale, base.get());
+                for (size_t z = 0; z < diags.size(); z++) { DPt pt; pt.level = level; pt.scale = pt_scale; pt.p = std::shared_ptr<uint64_t>(base, base.get() + z * nt * N); lt.giant[diags[z].g][diags[z].b] = pt; }
             }
+            for (auto &x : diags) digest_line(lt, x.k, x.g, x.b, x.rolled, level, pt_scale, tag);
+            diags.clear();
         }
         return lt;
+    }
+    // HCONV_DFT_DIGESTS: what the reference's encodeDiagonal receives and returns (mod Q): values; NTT rows in Montgomery form + the spare zero limb
+    void digest_line(const LT &lt, int k, int g, int b, const std::vector<cplx> &rolled, int level, double pt_scale, const char *tag) {
+        if (!dft_digests) return;
+        Sha256 hv; hv.update(rolled.data(), rolled.size() * sizeof(cplx));
+        std::vector<uint64_t> rows((size_t)(level + 1) * N), zero((size_t)N, 0);
+        HCR(hc_download(hc, rows.data(), lt.giant.at(g).at(b).p.get(), rows.size() * 8));
+        unpack_rows(rows, level + 1);
+        for (int l = 0; l <= level; l++) { const uint64_t q = Q[(size_t)l], r = (uint64_t)((((u128)1) << 64) % q); for (int j = 0; j < N; j++) rows[(size_t)l * N + j] = mulmod(rows[(size_t)l * N + j], r, q); }
+        Sha256 hq; hq.update(rows.data(), rows.size() * 8); hq.update(zero.data(), zero.size() * 8);
+        std::string mp = "";
+        if (lt.qp) {            // ... and mod P
+            const int np = (int)P.size(); std::vector<uint64_t> prow((size_t)np * N);
+            HCR(hc_download(hc, prow.data(), lt.giant.at(g).at(b).p.get() + (size_t)(level + 1) * N, prow.size() * 8));
+            for (int j = 0; j < np; j++) { const uint64_t q = P[(size_t)j], r = (uint64_t)((((u128)1) << 64) % q); for (int i = 0; i < N; i++) prow[(size_t)j * N + i] = mulmod(prow[(size_t)j * N + i], r, q); }
+            Sha256 hp; hp.update(prow.data(), prow.size() * 8); mp = hp.hex();
+        }
+        fprintf(dft_digests, "{\"matrix\": \"%s\", \"chain\": %d, \"level\": %d, \"scale\": %.17g, \"N1\": %d, \"k\": %d, \"values\": \"%s\", \"mQ\": \"%s\", \"mP\": \"%s\"}\n", tag, chain, level, pt_scale, lt.n1, k, hv.hex().c_str(), hq.hex().c_str(), mp.c_str());
     }
     // ckks.(*evaluator).LinearTransform -> MultiplyByDiagMatrixBSGS exactly as the reference's fork computes it (test_run @52a580; tests/lattigo_lt.py
     // is the same algorithm on the oracle and reproduces the binary's ModDown inputs / outputs and result on planted data, tests/test_oracle_pin_lt.py;
@@ -1462,5 +1496,6 @@ std::vector<double> bootDecryptDecodeCoeffs(Boot *B, const BootCiphertext &ct) {
 }
 void freeBootCt(Boot *B, BootCiphertext &ct) { hc_ctx *hc = B->hc; if (ct.d) HCR(hc_free(hc, ct.d)); ct.d = nullptr; }
 void bootStats(Boot *B, long *keys, long *keyswitches) { *keys = B->n_keys; *keyswitches = B->n_keyswitch; }
+void bootEncodeStats(Boot *B, long *diagonals, long *masks, bool *device) { *diagonals = B->n_enc_diag; *masks = B->n_enc_mask; *device = B->dev_encode; }
 
 }  // namespace hconv
