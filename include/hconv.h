@@ -47,7 +47,7 @@ typedef struct hc_ker hc_ker; /* device-resident kernel plaintexts pl_ker[0..max
 int hc_ctx_create(hc_ctx **out, int logN, const uint64_t *q, int nq, const uint64_t *p, int np, int device);
 void hc_ctx_destroy(hc_ctx *ctx);
 const char *hc_last_error(const hc_ctx *ctx); /* ctx may be NULL: error of the last failed hc_ctx_create */
-int hc_version(void);   /* 3: hc_prep_ker_ex (transposed kernels); 4: hc_prep_ker_ex2 (dilated, channel-strided kernels); 5: hc_encode_coeffs, hc_encrypt_sk, hc_decrypt_decode_coeffs; hc_encode_slots_ex came later without a new number: detect it by symbol (dlsym) */
+int hc_version(void);   /* 3: hc_prep_ker_ex (transposed kernels); 4: hc_prep_ker_ex2 (dilated, channel-strided kernels); 5: hc_encode_coeffs, hc_encrypt_sk, hc_decrypt_decode_coeffs; hc_encode_slots_ex came later without a new number: detect it by symbol (dlsym); so did hc_decode_slots and hc_decrypt_decode_slots: detect them by symbol too */
 
 /* ---- device memory ---- */
 int hc_malloc(hc_ctx *ctx, size_t bytes, void **dptr);
@@ -92,7 +92,7 @@ int hc_permute(hc_ctx *ctx, uint64_t galEl, const uint64_t *in, uint64_t *out, i
  * switching keys likewise (one fetch of a key row serves all images and both key components). (Until round 5 hc_lv_mul always shared b and hc_lv_op2 inferred a plaintext
  * from b0 == b1: a per-image second operand gave wrong residues for images above 0 without an error.) Results are bit-identical to n separate calls.
  * n = 1 (default) restores single-ciphertext behaviour; the L0 one-row primitives above, hc_permute, the L1 convolution (which has its own
- * batch entry point) and hc_encode_slots / hc_encode_slots_ex / hc_encode_coeffs / hc_encrypt_sk / hc_decrypt_decode_coeffs (which carry their own `count`) ignore the setting. A decomposition held by hc_keyswitch_decompose belongs to the batch it was taken under.
+ * batch entry point) and hc_encode_slots / hc_encode_slots_ex / hc_encode_coeffs / hc_encrypt_sk / hc_decrypt_decode_coeffs / hc_decode_slots / hc_decrypt_decode_slots (which carry their own `count`) ignore the setting. A decomposition held by hc_keyswitch_decompose belongs to the batch it was taken under.
  * The setting is context STATE (calls on one hc_ctx are serialised by the caller): a binding must hold it in a scope that restores n = 1 on every way out - INTEGRATION.md 3d
  * (`Batched` with a deferred reset), `Context.batch()` in abi.py, `Boot::Batch` in the C++ host. Under n > 1 every entry point checks the strides against the footprint of its
  * operands at the call's level - poly_stride >= (level+1) N, qp_stride >= 2 (level+1+np) N where it takes extended-basis pairs - and fails with HC_ERR_ARG otherwise (images
@@ -316,6 +316,16 @@ int hc_encrypt_sk(hc_ctx *ctx, int count, int level, const uint64_t *pt, const u
  * out: DEVICE [count][N] doubles. Level 0: c0 + c1 s, inverse transform, centred in (-q/2, q/2], divided by scale. Level 1: the CRT over q0 q1, centred, the magnitude
  * (up to 116 bits) rounded to the nearest double (ties to even), divided by scale: the doubles the host's (double)(unsigned __int128) / scale gives. */
 int hc_decrypt_decode_coeffs(hc_ctx *ctx, int count, int level, const uint64_t *const *ct, const uint64_t *sk_ntt, double scale, double *out);
+/* ckks.Encoder.Decode's float half: values[i] = c[i*gap] + i c[N/2 + i*gap], then the forward special FFT over 2^log_slots points. (No new hc_version(): detected by
+ * symbol.) coeffs: DEVICE [count][N] doubles - what a host's own CRT, centring and division by the scale leave, at any level - not modified, and not overlapping the
+ * output; only the coefficients on the gap grid, gap = (N/2) / 2^log_slots, are read. values_out: DEVICE [count][2^log_slots] complex128 as (re, im) pairs; 0 <= log_slots
+ * <= 15. The transform is hc_encode_slots_ex' run backwards - bit reversal over log_slots bits, stages len = 2 .. 2^log_slots, t = b * root, (a + t, a - t), no division -
+ * on the same root table, in IEEE fp64 without contraction and in the reference's operand order: the doubles encoder.Decode produces, bit for bit. Bad arguments return
+ * HC_ERR_ARG and leave the context usable. */
+int hc_decode_slots(hc_ctx *ctx, const double *coeffs, int count, int log_slots, double *values_out);
+/* HARNESS ONLY: hc_decrypt_decode_coeffs followed by hc_decode_slots, in one call; level 0 or 1 as there. The bits of the two calls composed (the coefficient doubles pass
+ * through a workspace of the context); hc_decrypt_decode_coeffs' argument checks, HC_ERR_UNSUPPORTED above level 1, centring and rounding. */
+int hc_decrypt_decode_slots(hc_ctx *ctx, int count, int level, const uint64_t *const *ct, const uint64_t *sk_ntt, double scale, int log_slots, double *values_out);
 /* conv.go:167-172 in one launch: out[2][level+1][N] = sum over t < ntaps (<= 64) of ciphertext cts[t] ([2][level+1][N], device) x
  * plaintext pts[t] ([level+1][N], NTT domain, device [ntaps][level+1][N]); cts is a HOST array of device pointers. Exact modular
  * sums: the same residues as the reference's MulNew + Add chain. */

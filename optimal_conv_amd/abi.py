@@ -97,6 +97,8 @@ SYMBOLS = {
     "hc_encode_coeffs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_void_p]),
     "hc_encrypt_sk": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32), C.c_uint64, C.POINTER(C.c_void_p)]),
     "hc_decrypt_decode_coeffs": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.c_void_p, C.c_double, C.c_void_p]),
+    "hc_decode_slots": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "hc_decrypt_decode_slots": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.c_void_p, C.c_double, C.c_int, C.c_void_p]),
     "hc_bl_post_ker_slots": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "hc_lv_mul_sum": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.c_void_p, C.c_int, C.c_void_p]),
     "hc_device_count": (C.c_int, [C.POINTER(C.c_int)]),
@@ -624,6 +626,30 @@ class Context:
         try:
             self._ck(self.L.hc_decrypt_decode_coeffs(self.h, count, level, (C.c_void_p * count)(*[b.ptr for b in bufs]), ds.ptr, scale, out.ptr))
             return out.download((count, self.N)).view(np.float64)
+        finally:
+            for b in bufs + [ds, out]:
+                b.free()
+
+    def decode_slots(self, coeffs, log_slots):
+        """hc_decode_slots: coeffs float64 [count][N] (host; one vector if 1-D) -> complex128 [count][2^log_slots]"""
+        cf = np.ascontiguousarray(coeffs, dtype=np.float64).reshape(-1, self.N)
+        count, n = cf.shape[0], 1 << log_slots if 0 <= log_slots <= 15 else 1
+        dc, out = self.buf(cf.reshape(-1).view(np.uint64)), self.buf(nwords=count * n * 2)
+        try:
+            self._ck(self.L.hc_decode_slots(self.h, dc.ptr, count, log_slots, out.ptr))
+            return out.download().view(np.complex128).reshape(count, n)
+        finally:
+            dc.free(); out.free()
+
+    def decrypt_decode_slots(self, cts, level, sk_ntt, scale, log_slots):
+        """hc_decrypt_decode_slots (harness only): cts uint64 [count][2][level+1][N] -> complex128 [count][2^log_slots]"""
+        cts = np.ascontiguousarray(cts, dtype=np.uint64).reshape(-1, 2, level + 1, self.N)
+        count, n = cts.shape[0], 1 << log_slots if 0 <= log_slots <= 15 else 1
+        bufs = [self.buf(ct) for ct in cts]
+        ds, out = self.buf(sk_ntt), self.buf(nwords=count * n * 2)
+        try:
+            self._ck(self.L.hc_decrypt_decode_slots(self.h, count, level, (C.c_void_p * count)(*[b.ptr for b in bufs]), ds.ptr, scale, log_slots, out.ptr))
+            return out.download().view(np.complex128).reshape(count, n)
         finally:
             for b in bufs + [ds, out]:
                 b.free()

@@ -2840,6 +2840,63 @@ __global__ __launch_bounds__(HC_TPB) void hc_k_slots_round(const HcCplx *w, u64 
         }
     }
 }
+// ---- slot decoder (ckks.Encoder.Decode's float half: plaintextToComplex + encoder.fft). The forward special FFT is the inverse one run backwards: the bit-reversal
+// permutation over log_slots bits first, then stages len = 2 .. n (small first), butterfly
+//     t = b * roots[(rotGroup[j] mod 4 len) * (2N / 4 len)] ;  a' = a + t ;  b' = a - t,   j = position inside the block's lower half,
+// with no division. Same tables, same arithmetic rules (plain fp64, no contraction, the complex product as four rounded products, one subtraction, one addition), and the
+// same two views of a vector as above, in the opposite order: pass B first (it also gathers: value k of a vector is (c[brev(k) gap], c[N/2 + brev(k) gap]), so coefficients
+// off the gap grid are never read, as in plaintextToComplex), then for n > 2048 pass A over the R rows.
+__device__ __forceinline__ void hc_sfft_fwd_bfly(HcCplx &a, HcCplx &b, const HcSlotEnc &E, int j, int len) {
+#pragma clang fp contract(off)
+    const int lenq = len << 2, gap = 131072 / lenq;
+    const HcCplx r = E.roots[(E.rot_group[j] % lenq) * gap];
+    const double p0 = b.re * r.re, p1 = b.im * r.im, p2 = b.re * r.im, p3 = b.im * r.re;
+    const double tr = p0 - p1, ti = p2 + p3, ar = a.re, ai = a.im;
+    a.re = ar + tr; a.im = ai + ti; b.re = ar - tr; b.im = ai - ti;
+}
+// forward pass B: gathers tiles of 2048 consecutive values of the `total` = count x n (n = 2^log_slots; the last tile may be short) from coeffs [count][N] and runs the
+// stages len = 2 .. min(n, 256) (n > 2048: 8 rows of a long vector) or 2 .. n (whole vectors of n <= 2048 values; n = 1: no stage). grid = ceil(total / 2048)
+__global__ __launch_bounds__(HC_TPB) void hc_k_sfft_fwd_b(const double *coeffs, HcCplx *out, HcSlotEnc E, size_t total, int log_slots) {
+    __shared__ HcCplx lds[2048];
+    const int t = threadIdx.x, log_len = log_slots > 11 ? 8 : log_slots, lg = 15 - log_slots;
+    const size_t base = (size_t)blockIdx.x * 2048;
+    const int ne = total - base < 2048 ? (int)(total - base) : 2048;
+    for (int e = t; e < ne; e += HC_TPB) {
+        const size_t g = base + e, z = g >> log_slots;
+        const u32 k = (u32)(g - (z << log_slots)), src = log_slots ? __brev(k) >> (32 - log_slots) : 0;
+        const double *c = coeffs + z * 65536 + ((size_t)src << lg);
+        HcCplx v; v.re = c[0]; v.im = c[32768]; lds[e] = v;
+    }
+    __syncthreads();
+    for (int s = 0; s < log_len; s++) {
+        const int lenh = 1 << s;
+        for (int b = t; b < (ne >> 1); b += HC_TPB) {
+            const int blk = b >> s, j = b & (lenh - 1), idx = blk * 2 * lenh + j;
+            hc_sfft_fwd_bfly(lds[idx], lds[idx + lenh], E, j, 2 * lenh);
+        }
+        __syncthreads();
+    }
+    for (int e = t; e < ne; e += HC_TPB) out[base + e] = lds[e];
+}
+// forward pass A (n = R x 256, R = 2^log_r in 16 .. 128), after pass B: the log2 R stages that pair rows, distance 1 row first. grid = (16 column tiles, count); in/out:
+// [count][n] complex, in place allowed
+__global__ __launch_bounds__(HC_TPB) void hc_k_sfft_fwd_a(const HcCplx *in, HcCplx *out, HcSlotEnc E, int log_r) {
+    __shared__ HcCplx lds[2048];                       // [R rows][16 columns]
+    const int t = threadIdx.x, c0 = blockIdx.x * 16, ne = 16 << log_r;
+    const size_t base = (size_t)blockIdx.y << (log_r + 8);
+    for (int e = t; e < ne; e += HC_TPB) { const int r = e >> 4, c = e & 15; lds[e] = in[base + (size_t)r * 256 + c0 + c]; }
+    __syncthreads();
+    for (int s = 0; s < log_r; s++) {                  // distance in rows Lh = 2^s; len = 2 * Lh * 256
+        const int Lh = 1 << s;
+        for (int b = t; b < (ne >> 1); b += HC_TPB) {
+            const int c = b & 15, q = b >> 4;
+            const int blk = q >> s, rr = q & (Lh - 1), r = blk * 2 * Lh + rr;
+            hc_sfft_fwd_bfly(lds[r * 16 + c], lds[(r + Lh) * 16 + c], E, rr * 256 + c0 + c, 2 * Lh * 256);
+        }
+        __syncthreads();
+    }
+    for (int e = t; e < ne; e += HC_TPB) { const int r = e >> 4, c = e & 15; out[base + (size_t)r * 256 + c0 + c] = lds[e]; }
+}
 // conv.go:150-164 on the device: the slot vectors postKer of ALL kernel taps (i, j) of one output rotation `rot`
 //   postKer[k*in_wid^2 + ki*in_wid + kj] = max_ker_rs[i][j][k][(k - rot) mod max_batch]  when tap (i, j) of position (ki, kj) lies
 //   inside the (in_wid - pad)^2 image, else 0.        out: [ker_wid^2][32768] complex (imaginary parts 0). grid = (128, ker_wid^2)

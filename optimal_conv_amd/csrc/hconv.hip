@@ -325,7 +325,7 @@ static int hc_build_tables(hc_ctx *c, HcModHost *mh, bool inverse) {
     return HC_OK;
 }
 
-extern "C" int hc_version(void) { return 5; }      // 2: a plaintext shared by the images of a batch is said by the operation (HC_LV_MUL_PLAIN), never inferred from b0 == b1; 3: hc_prep_ker_ex (transposed kernels); 4: hc_prep_ker_ex2 (dilated, channel-strided kernels); 5: hc_encode_coeffs, hc_encrypt_sk, hc_decrypt_decode_coeffs (hc_encode_slots_ex came later without a new number: detected by symbol)
+extern "C" int hc_version(void) { return 5; }      // 2: a plaintext shared by the images of a batch is said by the operation (HC_LV_MUL_PLAIN), never inferred from b0 == b1; 3: hc_prep_ker_ex (transposed kernels); 4: hc_prep_ker_ex2 (dilated, channel-strided kernels); 5: hc_encode_coeffs, hc_encrypt_sk, hc_decrypt_decode_coeffs (hc_encode_slots_ex, then hc_decode_slots and hc_decrypt_decode_slots, came later without a new number: detected by symbol)
 extern "C" const char *hc_last_error(const hc_ctx *c) { return c ? c->err.c_str() : g_create_err.c_str(); }
 
 // HcMod::row32 of modulus i of the context's nmods (Q then P): under pack32 = 2 the rows of a modulus below 2^31 in the caller's leveled operands are 4-byte words - except
@@ -1956,11 +1956,13 @@ extern "C" int hc_encrypt_sk(hc_ctx *c, int count, int level, const uint64_t *pt
 }
 // Harness-side Decrypt + DecodeCoeffs at level 0 or 1: t = c0 + c1 s for all images and limbs, one batched inverse transform, one launch centres (after the CRT at level 1),
 // converts and divides by the scale
-extern "C" int hc_decrypt_decode_coeffs(hc_ctx *c, int count, int level, const uint64_t *const *ct, const uint64_t *sk_ntt, double scale, double *out) {
-    HC_ENTER(c);
-    if (!ct || !sk_ntt || !out || count < 1 || count > 65535 || level < 0 || level >= c->nq) return hc_fail(c, HC_ERR_ARG, "hc_decrypt_decode_coeffs: bad arguments (1 <= count <= 65535, 0 <= level < %d, non-null pointers)", c->nq);
-    if (level > 1) return hc_fail(c, HC_ERR_UNSUPPORTED, "hc_decrypt_decode_coeffs: level 0 or 1 only (DecodeCoeffs above level 1 is not built)");
-    for (int z = 0; z < count; z++) if (!ct[z]) return hc_fail(c, HC_ERR_ARG, "hc_decrypt_decode_coeffs: null ciphertext %d", z);
+static int hc_decrypt_decode_check(hc_ctx *c, const char *fn, int count, int level, const uint64_t *const *ct, const uint64_t *sk_ntt, const void *out) {
+    if (!ct || !sk_ntt || !out || count < 1 || count > 65535 || level < 0 || level >= c->nq) return hc_fail(c, HC_ERR_ARG, "%s: bad arguments (1 <= count <= 65535, 0 <= level < %d, non-null pointers)", fn, c->nq);
+    if (level > 1) return hc_fail(c, HC_ERR_UNSUPPORTED, "%s: level 0 or 1 only (DecodeCoeffs above level 1 is not built)", fn);
+    for (int z = 0; z < count; z++) if (!ct[z]) return hc_fail(c, HC_ERR_ARG, "%s: null ciphertext %d", fn, z);
+    return HC_OK;
+}
+static int hc_decrypt_decode_coeffs_impl(hc_ctx *c, int count, int level, const uint64_t *const *ct, const uint64_t *sk_ntt, double scale, double *out) {
     const int nl = level + 1;
     u64 q0inv_m = 0;
     if (level == 1) { const u64 q0 = c->mods[0].m.q, q1 = c->mods[1].m.q; q0inv_m = (u64)((((u128)h_inv(q0 % q1, q1)) << 64) % q1); }
@@ -1977,6 +1979,37 @@ extern "C" int hc_decrypt_decode_coeffs(hc_ctx *c, int count, int level, const u
         HC_TRY(hc_launch(c, "dec_decode", hc_k_dec_decode, dim3(64, (unsigned)n), (const u64 *)t, out + (size_t)z0 * HC_N, (const HcMod *)c->d_mods, nl, scale, q0inv_m));
     }
     return HC_OK;
+}
+extern "C" int hc_decrypt_decode_coeffs(hc_ctx *c, int count, int level, const uint64_t *const *ct, const uint64_t *sk_ntt, double scale, double *out) {
+    HC_ENTER(c);
+    HC_TRY(hc_decrypt_decode_check(c, "hc_decrypt_decode_coeffs", count, level, ct, sk_ntt, out));
+    return hc_decrypt_decode_coeffs_impl(c, count, level, ct, sk_ntt, scale, out);
+}
+// ckks.Encoder.Decode's float half for count coefficient vectors: pass B gathers (bit reversal folded in) and runs the stages inside 2048-value tiles straight into
+// values_out, pass A (n > 2048) finishes there in place: one or two launches, no work array beside the output
+static int hc_decode_slots_impl(hc_ctx *c, const double *coeffs, int count, int log_slots, double *values_out) {
+    HC_TRY(hc_enc_tables(c));
+    HcSlotEnc E; E.roots = c->enc_roots; E.rot_group = c->enc_rot_group;
+    HcCplx *v = (HcCplx *)values_out;
+    const size_t total = (size_t)count << log_slots;
+    HC_TRY(hc_launch(c, "sfft_fwd_b", hc_k_sfft_fwd_b, dim3((unsigned)((total + 2047) / 2048)), coeffs, v, E, total, log_slots));
+    if (log_slots > 11) HC_TRY(hc_launch(c, "sfft_fwd_a", hc_k_sfft_fwd_a, dim3(16, (unsigned)count), (const HcCplx *)v, v, E, log_slots - 8));
+    return HC_OK;
+}
+extern "C" int hc_decode_slots(hc_ctx *c, const double *coeffs, int count, int log_slots, double *values_out) {
+    HC_ENTER(c);
+    if (!coeffs || !values_out || count < 1 || count > 65535 || log_slots < 0 || log_slots > 15) return hc_fail(c, HC_ERR_ARG, "hc_decode_slots: bad arguments (1 <= count <= 65535, 0 <= log_slots <= 15, non-null pointers)");
+    return hc_decode_slots_impl(c, coeffs, count, log_slots, values_out);
+}
+// hc_decrypt_decode_coeffs into the context's ciphertext workspace (idle outside a convolution), hc_decode_slots from there: the two calls' launches, the two calls' bits
+extern "C" int hc_decrypt_decode_slots(hc_ctx *c, int count, int level, const uint64_t *const *ct, const uint64_t *sk_ntt, double scale, int log_slots, double *values_out) {
+    HC_ENTER(c);
+    HC_TRY(hc_decrypt_decode_check(c, "hc_decrypt_decode_slots", count, level, ct, sk_ntt, values_out));
+    if (log_slots < 0 || log_slots > 15) return hc_fail(c, HC_ERR_ARG, "hc_decrypt_decode_slots: bad arguments (0 <= log_slots <= 15)");
+    HC_TRY(hc_ensure_cts(c, (size_t)count));
+    double *coeffs = (double *)c->ws_cts;
+    HC_TRY(hc_decrypt_decode_coeffs_impl(c, count, level, ct, sk_ntt, scale, coeffs));
+    return hc_decode_slots_impl(c, coeffs, count, log_slots, values_out);
 }
 // out[2][level+1][N] = sum over t < ntaps of cts[t] (ciphertext [2][level+1][N]) x pts[t] (plaintext [level+1][N], NTT domain): the
 // MulNew / Add chain of conv.go:167-172 in one launch. cts: HOST array of ntaps device pointers; pts: device, [ntaps][level+1][N]

@@ -57,6 +57,9 @@ struct BLContext {
     double scale = (double)(1 << 30);
     Boot *btp = nullptr;          // cont.btp (main.go:476): the stock bootstrapper over parameter set [7], only for convReLU
     Seed256 seed;
+    uint64_t *d_sk = nullptr;     // deviceEncrypt(): NTT(s) modulo Q0, Q1, P0, P1 on the device, uploaded once
+    uint32_t enc_seed8[8] = {0};  // key of the device encryptor's draws: eight draws of g at context creation
+    uint64_t enc_stream = 0;      // hc_encrypt_sk's stream id: one per call, never reused
 };
 struct BLCt { uint64_t *d = nullptr; double Scale = 0; };     // level-1 ciphertext: device [poly 2][limb 2][N]
 
@@ -247,6 +250,12 @@ static BLContext *bl_newContext(int logN, int ker_wid, int in_wid, bool boot) {
     c->sk.assign(N, 0);
     { int placed = 0; while (placed < 192) { uint64_t r = c->g(); int pos = (int)(r % N); if (!c->sk[(size_t)pos]) { c->sk[(size_t)pos] = (r >> 40) & 1 ? 1 : -1; placed++; } } }
     for (int m = 0; m < 4; m++) c->sk_ntt[m] = bl_ntt(c, m, signed_row(c->sk, BLQ[m]));
+    if (deviceEncrypt()) {      // as newContext does for the Ours column: the secret key on the device once, and the key of the encryptor's draws (g is left as it is when the device path is off)
+        c->d_sk = bl_rows(c, 4);
+        for (int m = 0; m < 4; m++) HCB(c->hc, hc_upload(c->hc, c->d_sk + (size_t)m * N, c->sk_ntt[m].data(), (size_t)N * 8));
+        for (uint32_t &w : c->enc_seed8) w = (uint32_t)c->g();
+        printf("Base Line: encryption and decryption on the device (hc_encode_slots / hc_encrypt_sk / hc_decrypt_decode_slots)\n");
+    }
     // main.go:101-112: rotations {k*W + k2} and {r * W^2}; removeDuplicateInt
     std::vector<int> rotations; std::set<int> seen;
     auto push = [&](int r) { if (!seen.count(r)) { seen.insert(r); rotations.push_back(r); } };
@@ -297,6 +306,31 @@ static std::vector<cplx> bl_decrypt_decode(BLContext *c, const Encoder &enc, con
     return vals;
 }
 
+// deviceEncrypt(): the codec of both halves on the device. Encoder.Encode + sk-encryption of the two slot vectors: one upload, hc_encode_slots (coefficient domain, level
+// 1), hc_encrypt_sk (count = 2)
+static void bl_encrypt_device(BLContext *c, const std::vector<cplx> &v1, const std::vector<cplx> &v2, BLCt &ct1, BLCt &ct2) {
+    if (v1.size() != (size_t)N / 2 || v2.size() != (size_t)N / 2) panic("bl_encrypt_device: full-slot vectors expected");
+    void *vp = nullptr; HCB(c->hc, hc_malloc(c->hc, (size_t)2 * (N / 2) * 16, &vp)); double *d_vals = (double *)vp;            // [2][N/2] complex128
+    HCB(c->hc, hc_upload(c->hc, d_vals, v1.data(), v1.size() * 16)); HCB(c->hc, hc_upload(c->hc, d_vals + N, v2.data(), v2.size() * 16));
+    uint64_t *pt = bl_rows(c, 4);                                                                                                 // [2][limb 2][N]
+    HCB(c->hc, hc_encode_slots(c->hc, d_vals, 2, 1, c->scale, 0, pt));
+    ct1 = bl_alloc(c, c->scale); ct2 = bl_alloc(c, c->scale);
+    uint64_t *ptrs[2] = {ct1.d, ct2.d};
+    HCB(c->hc, hc_encrypt_sk(c->hc, 2, 1, pt, c->d_sk, c->enc_seed8, c->enc_stream++, ptrs));
+    HCB(c->hc, hc_sync(c->hc));                                                                                                   // the caller times the encryption
+    HCB(c->hc, hc_free(c->hc, d_vals)); HCB(c->hc, hc_free(c->hc, pt));
+}
+// Decrypt at level 1 + encoder.Decode of both results: hc_decrypt_decode_slots (count = 2), one download
+static void bl_decrypt_decode_device(BLContext *c, const BLCt &a, const BLCt &b, std::vector<cplx> &va, std::vector<cplx> &vb) {
+    if (a.Scale != b.Scale) panic("bl_decrypt_decode_device: one scale expected");
+    void *vp = nullptr; HCB(c->hc, hc_malloc(c->hc, (size_t)2 * (N / 2) * 16, &vp)); double *d_vals = (double *)vp;
+    const uint64_t *ptrs[2] = {a.d, b.d};
+    HCB(c->hc, hc_decrypt_decode_slots(c->hc, 2, 1, ptrs, c->d_sk, a.Scale, LOGN - 1, d_vals));
+    va.resize((size_t)N / 2); vb.resize((size_t)N / 2);
+    HCB(c->hc, hc_download(c->hc, va.data(), d_vals, va.size() * 16)); HCB(c->hc, hc_download(c->hc, vb.data(), d_vals + N, vb.size() * 16));
+    HCB(c->hc, hc_free(c->hc, d_vals));
+}
+
 // ---------------------------------------------------------------- test_BL.go:16-185 (boot = false)
 void testConv_BL_in(int real_batch, int in_wid, int ker_wid, int total_test_num, bool boot) {
     const std::string test_dir = "test_conv_data/";
@@ -331,8 +365,12 @@ void testConv_BL_in(int real_batch, int in_wid, int ker_wid, int total_test_num,
                 ker_in_sep[out][in][(size_t)(k * hb * hb + i * hb + j)] = ker_in[(size_t)(k * real_batch * real_batch + (i + in * hb) * real_batch + out * hb + j)];
         }
         auto start = now();
-        BLCt ct_input1 = bl_encrypt(cont, enc.Encode(reshape_input_BL(pad_input1, in_wid), cont->scale, BLQ, 2), cont->scale);
-        BLCt ct_input2 = bl_encrypt(cont, enc.Encode(reshape_input_BL(pad_input2, in_wid), cont->scale, BLQ, 2), cont->scale);
+        BLCt ct_input1, ct_input2;
+        if (deviceEncrypt()) bl_encrypt_device(cont, reshape_input_BL(pad_input1, in_wid), reshape_input_BL(pad_input2, in_wid), ct_input1, ct_input2);
+        else {
+            ct_input1 = bl_encrypt(cont, enc.Encode(reshape_input_BL(pad_input1, in_wid), cont->scale, BLQ, 2), cont->scale);
+            ct_input2 = bl_encrypt(cont, enc.Encode(reshape_input_BL(pad_input2, in_wid), cont->scale, BLQ, 2), cont->scale);
+        }
         printf("Encryption done in %s \n", dur(start).c_str());
         auto start_eval = now();
         BLCt ct_res[2];
@@ -351,7 +389,9 @@ void testConv_BL_in(int real_batch, int in_wid, int ker_wid, int total_test_num,
             o0.Scale = o1.Scale = sc; ct_res[0] = o0; ct_res[1] = o1;
         }
         start = now();
-        std::vector<cplx> vals_tmp1 = bl_decrypt_decode(cont, enc, ct_res[0]), vals_tmp2 = bl_decrypt_decode(cont, enc, ct_res[1]);
+        std::vector<cplx> vals_tmp1, vals_tmp2;
+        if (deviceEncrypt()) bl_decrypt_decode_device(cont, ct_res[0], ct_res[1], vals_tmp1, vals_tmp2);
+        else { vals_tmp1 = bl_decrypt_decode(cont, enc, ct_res[0]); vals_tmp2 = bl_decrypt_decode(cont, enc, ct_res[1]); }
         printf("Decryption Done in %s \n", dur(start).c_str());
         std::vector<double> test_out = post_trim_BL(vals_tmp1, raw_in_wid, in_wid), t2 = post_trim_BL(vals_tmp2, raw_in_wid, in_wid);
         test_out.insert(test_out.end(), t2.begin(), t2.end());
@@ -360,6 +400,7 @@ void testConv_BL_in(int real_batch, int in_wid, int ker_wid, int total_test_num,
         bl_free(cont, ct_input1); bl_free(cont, ct_input2); bl_free(cont, ct_res[0]); bl_free(cont, ct_res[1]);
     }
     if (cont->btp) freeBoot(cont->btp);
+    if (cont->d_sk) HCB(cont->hc, hc_free(cont->hc, cont->d_sk));
     hc_ctx_destroy(cont->hc); delete cont;
 }
 
