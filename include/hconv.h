@@ -47,7 +47,7 @@ typedef struct hc_ker hc_ker; /* device-resident kernel plaintexts pl_ker[0..max
 int hc_ctx_create(hc_ctx **out, int logN, const uint64_t *q, int nq, const uint64_t *p, int np, int device);
 void hc_ctx_destroy(hc_ctx *ctx);
 const char *hc_last_error(const hc_ctx *ctx); /* ctx may be NULL: error of the last failed hc_ctx_create */
-int hc_version(void);   /* 3: hc_prep_ker_ex (transposed kernels); 4: hc_prep_ker_ex2 (dilated, channel-strided kernels); 5: hc_encode_coeffs, hc_encrypt_sk, hc_decrypt_decode_coeffs; hc_encode_slots_ex came later without a new number: detect it by symbol (dlsym); so did hc_decode_slots and hc_decrypt_decode_slots: detect them by symbol too */
+int hc_version(void);   /* 3: hc_prep_ker_ex (transposed kernels); 4: hc_prep_ker_ex2 (dilated, channel-strided kernels); 5: hc_encode_coeffs, hc_encrypt_sk, hc_decrypt_decode_coeffs; hc_encode_slots_ex came later without a new number: detect it by symbol (dlsym); so did hc_decode_slots and hc_decrypt_decode_slots, and after them hc_decode_coeffs and hc_decrypt_decode_lv: detect them by symbol too */
 
 /* ---- device memory ---- */
 int hc_malloc(hc_ctx *ctx, size_t bytes, void **dptr);
@@ -92,7 +92,7 @@ int hc_permute(hc_ctx *ctx, uint64_t galEl, const uint64_t *in, uint64_t *out, i
  * switching keys likewise (one fetch of a key row serves all images and both key components). (Until round 5 hc_lv_mul always shared b and hc_lv_op2 inferred a plaintext
  * from b0 == b1: a per-image second operand gave wrong residues for images above 0 without an error.) Results are bit-identical to n separate calls.
  * n = 1 (default) restores single-ciphertext behaviour; the L0 one-row primitives above, hc_permute, the L1 convolution (which has its own
- * batch entry point) and hc_encode_slots / hc_encode_slots_ex / hc_encode_coeffs / hc_encrypt_sk / hc_decrypt_decode_coeffs / hc_decode_slots / hc_decrypt_decode_slots (which carry their own `count`) ignore the setting. A decomposition held by hc_keyswitch_decompose belongs to the batch it was taken under.
+ * batch entry point) and hc_encode_slots / hc_encode_slots_ex / hc_encode_coeffs / hc_encrypt_sk / hc_decrypt_decode_coeffs / hc_decode_slots / hc_decrypt_decode_slots / hc_decode_coeffs / hc_decrypt_decode_lv (which carry their own `count`) ignore the setting. A decomposition held by hc_keyswitch_decompose belongs to the batch it was taken under.
  * The setting is context STATE (calls on one hc_ctx are serialised by the caller): a binding must hold it in a scope that restores n = 1 on every way out - INTEGRATION.md 3d
  * (`Batched` with a deferred reset), `Context.batch()` in abi.py, `Boot::Batch` in the C++ host. Under n > 1 every entry point checks the strides against the footprint of its
  * operands at the call's level - poly_stride >= (level+1) N, qp_stride >= 2 (level+1+np) N where it takes extended-basis pairs - and fails with HC_ERR_ARG otherwise (images
@@ -326,6 +326,21 @@ int hc_decode_slots(hc_ctx *ctx, const double *coeffs, int count, int log_slots,
 /* HARNESS ONLY: hc_decrypt_decode_coeffs followed by hc_decode_slots, in one call; level 0 or 1 as there. The bits of the two calls composed (the coefficient doubles pass
  * through a workspace of the context); hc_decrypt_decode_coeffs' argument checks, HC_ERR_UNSUPPORTED above level 1, centring and rounding. */
 int hc_decrypt_decode_slots(hc_ctx *ctx, int count, int level, const uint64_t *const *ct, const uint64_t *sk_ntt, double scale, int log_slots, double *values_out);
+/* ckks.Encoder.DecodeCoeffs at ANY level of the context, the sibling of hc_encode_coeffs (no new hc_version(): detected by symbol). pt: DEVICE [count][level+1][N], rows in the
+ * widths of a caller's leveled operand (hc_row_is32), not modified; from_ntt != 0: the rows are in the NTT domain (one batched inverse transform per chunk of 64 plaintexts
+ * into a scratch array), from_ntt = 0: coefficient domain. out: DEVICE [count][N] doubles. Per coefficient, in exact integer arithmetic: the unique x in [0, Q), Q = q_0 ..
+ * q_level, with x = a_l mod q_l (Garner's mixed-radix digits, then a multi-word sum); centred by the rule of hc_decrypt_decode_coeffs - x > Q >> 1 gives -(Q - x), so
+ * (Q - 1) / 2 stays positive: the project's rule at levels 0 and 1 kept for every level (the fork's own DecodeCoeffs could not be compared on this point); the magnitude rounded
+ * to the nearest double, ties to even, +-infinity where it rounds to 2^1024 or beyond (Q of ckks.DefaultBootstrapParams[6] exceeds 2^1024 from level 23 on); one IEEE division
+ * by scale. Levels 0 and 1 give hc_decrypt_decode_coeffs' bits (its kernel). HC_ERR_UNSUPPORTED for a level of more than 28 limbs or a Q above 1280 bits (no parameter set of the
+ * reference goes there); bad arguments return HC_ERR_ARG; the context stays usable after either. A decomposition held by hc_keyswitch_decompose survives the call. */
+int hc_decode_coeffs(hc_ctx *ctx, const uint64_t *pt, int count, int level, int from_ntt, double scale, double *out);
+/* HARNESS ONLY (as hc_decrypt_decode_coeffs): Decrypt + DecodeCoeffs (+ Decode) of count ciphertexts at any level, as the leveled chain holds them: c0, c1: HOST arrays of count
+ * device pointers, c0[z] and c1[z] each [level+1][N] NTT-domain rows in caller widths (hc_row_is32; the two polynomials need not be adjacent); sk_ntt: the 8-byte rows
+ * hc_encrypt_sk takes. log_slots = -1: out is DEVICE [count][N] doubles, hc_decode_coeffs of c0 + c1 s. 0 <= log_slots <= 15: hc_decode_slots' launches run behind it (the
+ * coefficient doubles pass through a workspace of the context) and out is DEVICE [count][2^log_slots] complex128 as (re, im) pairs. Levels 0 and 1 give the bits of
+ * hc_decrypt_decode_coeffs / hc_decrypt_decode_slots. Errors as hc_decode_coeffs'; any other log_slots is HC_ERR_ARG. */
+int hc_decrypt_decode_lv(hc_ctx *ctx, int count, int level, const uint64_t *const *c0, const uint64_t *const *c1, const uint64_t *sk_ntt, double scale, int log_slots, double *out);
 /* conv.go:167-172 in one launch: out[2][level+1][N] = sum over t < ntaps (<= 64) of ciphertext cts[t] ([2][level+1][N], device) x
  * plaintext pts[t] ([level+1][N], NTT domain, device [ntaps][level+1][N]); cts is a HOST array of device pointers. Exact modular
  * sums: the same residues as the reference's MulNew + Add chain. */

@@ -99,6 +99,8 @@ SYMBOLS = {
     "hc_decrypt_decode_coeffs": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.c_void_p, C.c_double, C.c_void_p]),
     "hc_decode_slots": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "hc_decrypt_decode_slots": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.c_void_p, C.c_double, C.c_int, C.c_void_p]),
+    "hc_decode_coeffs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_void_p]),
+    "hc_decrypt_decode_lv": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_void_p, C.c_double, C.c_int, C.c_void_p]),
     "hc_bl_post_ker_slots": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "hc_lv_mul_sum": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.c_void_p, C.c_int, C.c_void_p]),
     "hc_device_count": (C.c_int, [C.POINTER(C.c_int)]),
@@ -652,6 +654,35 @@ class Context:
             return out.download().view(np.complex128).reshape(count, n)
         finally:
             for b in bufs + [ds, out]:
+                b.free()
+
+    def decode_coeffs(self, pt, level, scale, from_ntt=True):
+        """hc_decode_coeffs: pt uint64 [count][level+1][N] (host, 8-byte words; packed into the caller widths of pack32 = 2 here) -> float64 [count][N]"""
+        pt = np.ascontiguousarray(pt, dtype=np.uint64).reshape(-1, level + 1, self.N)
+        count = pt.shape[0]
+        dp, out = self.buf(self.pack_rows(pt, level + 1)), self.buf(nwords=count * self.N)
+        try:
+            self._ck(self.L.hc_decode_coeffs(self.h, dp.ptr, count, level, 1 if from_ntt else 0, scale, out.ptr))
+            return out.download((count, self.N)).view(np.float64)
+        finally:
+            dp.free(); out.free()
+
+    def decrypt_decode_lv(self, c0, c1, level, sk_ntt, scale, log_slots=-1):
+        """hc_decrypt_decode_lv (harness only): c0, c1 uint64 [count][level+1][N] NTT rows, each polynomial in an allocation of its own -> float64 [count][N] (log_slots = -1)
+        or complex128 [count][2^log_slots]"""
+        c0 = np.ascontiguousarray(c0, dtype=np.uint64).reshape(-1, level + 1, self.N)
+        c1 = np.ascontiguousarray(c1, dtype=np.uint64).reshape(-1, level + 1, self.N)
+        count = c0.shape[0]
+        n = 1 << log_slots if 0 <= log_slots <= 15 else 1
+        b0 = [self.buf(self.pack_rows(x, level + 1)) for x in c0]
+        b1 = [self.buf(self.pack_rows(x, level + 1)) for x in c1]
+        ds, out = self.buf(sk_ntt), self.buf(nwords=count * (self.N if log_slots < 0 else 2 * n))
+        try:
+            self._ck(self.L.hc_decrypt_decode_lv(self.h, count, level, (C.c_void_p * count)(*[b.ptr for b in b0]), (C.c_void_p * count)(*[b.ptr for b in b1]), ds.ptr, scale,
+                                                 log_slots, out.ptr))
+            return out.download((count, self.N)).view(np.float64) if log_slots < 0 else out.download().view(np.complex128).reshape(count, n)
+        finally:
+            for b in b0 + b1 + [ds, out]:
                 b.free()
 
     @staticmethod

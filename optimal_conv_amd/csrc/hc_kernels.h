@@ -3021,3 +3021,81 @@ __global__ __launch_bounds__(HC_TPB) void hc_k_dec_decode(const u64 *t, double *
         o[j] = x > (QQ >> 1) ? -hc_u128_to_f64(QQ - x) / scale : hc_u128_to_f64(x) / scale;
     }
 }
+// ================================================================ DecodeCoeffs at any level of the context (hc_decode_coeffs, hc_decrypt_decode_lv)
+// hc_k_dec_decode above stays the kernel of nl <= 2. From nl = level + 1 coefficient-domain residues a_l (any 64-bit words congruent to the coefficient; canonical in the
+// library's own t), per coefficient and in exact integer arithmetic:
+//   Garner's mixed-radix digits  v_0 = a_0,  v_i = (..((a_i - v_0) q_0^-1 - v_1) q_1^-1 .. - v_(i-1)) q_(i-1)^-1 mod q_i   (all of it in Montgomery form modulo q_i:
+//                                HcCrt::ginv holds q_k^-1 mod q_i times 2^64),  so that  x = v_0 + v_1 q_0 + v_2 q_0 q_1 + ...  is THE x in [0, Q), Q = q_0 .. q_level;
+//   a multi-word Horner sum      x = (..(v_(nl-1) q_(nl-2) + v_(nl-2)) q_(nl-3) + ..) q_0 + v_0   over NW 64-bit words (Q of level 27 of ckks.DefaultBootstrapParams[6]
+//                                has 1248 bits: 20 words);
+//   the centring of hc_k_dec_decode:  x > Q >> 1  gives  -(Q - x).  (THE PROJECT'S RULE, kept: whether the fork's DecodeCoeffs sends x == (Q - 1) / 2 to the other side
+//                                could not be compared, its source being absent; both levels the project decoded so far use this rule, and so does every level now);
+//   the magnitude to the nearest double, ties to even (hc_words_to_f64, hc_u128_to_f64 over NW words); one that rounds to 2^1024 or beyond gives an infinity (Q exceeds
+//                                2^1024 from level 23 of that chain on);
+//   the sign, then ONE IEEE division by the scale, without contraction.
+// The digits live in LDS (one column per thread: a limb count known at run time would send a register array to scratch), the sum's words in registers: the kernel is
+// instantiated on the word counts hc_dec_decode_any picks from. t: [images][nl][N], 8-byte rows, or - user_rows != 0 - a caller's leveled operand, whose rows go by
+// HcMod::row32; out: [images][N]. grid = (64, images)
+#define HC_CRT_MAXL 28
+#define HC_CRT_MAXW 20
+struct HcCrt { const u64 *ginv, *qw, *half; int nq; };     // ginv[i * nq + k], k < i: q_k^-1 mod q_i in Montgomery form; qw / half[level * HC_CRT_MAXW + w]: the words of Q_level and of Q_level >> 1, least significant first, zero above
+// a magnitude of NW words as the nearest double, ties to even: hc_u128_to_f64's argument over more words - the 64 bits from the leading one on, every bit below them folded
+// into bit 0, one correctly rounded 64-bit conversion, an exact power of two (ldexp overflows to an infinity)
+template <int NW> __device__ __forceinline__ double hc_words_to_f64(const u64 *x) {
+    u64 hi = 0, lo = 0, below = 0; int top = 0;
+#pragma unroll
+    for (int k = NW - 1; k >= 0; k--) {
+        if (hi) { if (k < top - 1) below |= x[k]; }
+        else if (x[k]) { hi = x[k]; lo = k ? x[k ? k - 1 : 0] : 0; top = k; }
+    }
+    if (!top) return (double)hi;
+    const int lz = __builtin_clzll(hi);
+    const u64 t64 = lz ? ((hi << lz) | (lo >> (64 - lz))) : hi, rest = (lz ? (lo << lz) : lo) | below;
+    return ldexp((double)(t64 | (rest ? 1ull : 0ull)), 64 * top - lz);
+}
+template <int NW>
+__global__ __launch_bounds__(HC_TPB) void hc_k_dec_decode_crt(const u64 *t, double *out, const HcMod *mods, HcCrt T, int nl, int user_rows, double scale) {
+#pragma clang fp contract(off)
+    __shared__ u64 dg[HC_CRT_MAXL * HC_TPB];                                 // digit i of this thread's coefficient: dg[i * HC_TPB + thread]
+    const u64 *a = t + (size_t)blockIdx.y * nl * 65536; double *o = out + (size_t)blockIdx.y * 65536;
+    const u64 *Qw = T.qw + (size_t)(nl - 1) * HC_CRT_MAXW, *Hw = T.half + (size_t)(nl - 1) * HC_CRT_MAXW;
+    u64 *v = dg + threadIdx.x;
+    for (u32 j = blockIdx.x * HC_TPB + threadIdx.x; j < 65536; j += gridDim.x * HC_TPB) {
+        for (int i = 0; i < nl; i++) {
+            const HcMod m = mods[i]; const u64 *row = a + (size_t)i * 65536, *g = T.ginv + (size_t)i * T.nq;
+            u64 tm = hc_mont((user_rows && m.row32) ? hc_ld32(row, j) : row[j], m.r2, m.q, m.qinv);
+            for (int k = 0; k < i; k++) tm = hc_mont(hc_submod(tm, hc_mont(v[k * HC_TPB], m.r2, m.q, m.qinv), m.q), g[k], m.q, m.qinv);
+            v[i * HC_TPB] = hc_mont(tm, 1, m.q, m.qinv);
+        }
+        u64 x[NW];
+#pragma unroll
+        for (int w = 0; w < NW; w++) x[w] = 0;
+        x[0] = v[(nl - 1) * HC_TPB];
+        for (int i = nl - 2; i >= 0; i--) {
+            const u64 q = mods[i].q; u64 carry = v[i * HC_TPB];
+#pragma unroll
+            for (int w = 0; w < NW; w++) { const u128 p = (u128)x[w] * q + carry; x[w] = (u64)p; carry = (u64)(p >> 64); }
+        }
+        bool neg = false, decided = false;
+#pragma unroll
+        for (int w = NW - 1; w >= 0; w--) { const u64 h = Hw[w]; if (!decided && x[w] != h) { neg = x[w] > h; decided = true; } }
+        if (neg) {
+            u64 borrow = 0;
+#pragma unroll
+            for (int w = 0; w < NW; w++) { const u128 d = (u128)Qw[w] - x[w] - borrow; x[w] = (u64)d; borrow = (u64)(d >> 64) & 1; }
+        }
+        const double mag = hc_words_to_f64<NW>(x);
+        o[j] = (neg ? -mag : mag) / scale;
+    }
+}
+// hc_decrypt_decode_lv, first half: t = c0 + c1 s over the rows of a caller's leveled operands (c0.p[z], c1.p[z]: [nl][N], rows by HcMod::row32; sk_ntt: 8-byte rows);
+// t: [images][nl][N], 8-byte rows. grid = (64, nl, images)
+__global__ __launch_bounds__(HC_TPB) void hc_k_dec_combine_lv(HcCtPtrs c0, HcCtPtrs c1, const u64 *sk_ntt, u64 *t, const HcMod *mods, int nl) {
+    const int l = blockIdx.y, z = blockIdx.z; const HcMod m = mods[l];
+    const u64 *r0 = c0.p[z] + (size_t)l * 65536, *r1 = c1.p[z] + (size_t)l * 65536, *s = sk_ntt + (size_t)l * 65536;
+    u64 *tr = t + ((size_t)z * nl + l) * 65536;
+    for (u32 j = blockIdx.x * HC_TPB + threadIdx.x; j < 65536; j += gridDim.x * HC_TPB) {
+        const u64 x0 = m.row32 ? hc_ld32(r0, j) : r0[j], x1 = m.row32 ? hc_ld32(r1, j) : r1[j];
+        tr[j] = hc_addmod(x0, hc_mont(hc_mont(x1, m.r2, m.q, m.qinv), s[j], m.q, m.qinv), m.q);
+    }
+}

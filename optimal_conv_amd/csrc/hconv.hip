@@ -140,6 +140,7 @@ struct hc_ctx {
     hipEvent_t ev_fork = nullptr;
     HcCplx *enc_roots = nullptr; int *enc_rot_group = nullptr;      // slot encoder tables (hc_encode_slots*), built at first use
     u32 *d_flag = nullptr;                                          // hc_encode_coeffs: the word its kernel raises for a value it refuses
+    u64 *crt_tab = nullptr; std::vector<int> crt_words;             // DecodeCoeffs above level 1 (hc_crt_tables), built at first use: HcCrt's three arrays in one block; crt_words[level]: the 64-bit words of Q_level, for the levels the kernel is built for
     hipEvent_t ev_shard = nullptr;     // hc_conv_then_pack_sharded: this device's partial ciphertext is complete / has been collected
     u64 *ws_gather = nullptr; size_t ws_gather_rows = 0;
     long small_levels = 16;               // pack-tree launches of at most this many nodes (summed over the batch) run on the 1024-thread S kernels; 0 = never
@@ -325,7 +326,7 @@ static int hc_build_tables(hc_ctx *c, HcModHost *mh, bool inverse) {
     return HC_OK;
 }
 
-extern "C" int hc_version(void) { return 5; }      // 2: a plaintext shared by the images of a batch is said by the operation (HC_LV_MUL_PLAIN), never inferred from b0 == b1; 3: hc_prep_ker_ex (transposed kernels); 4: hc_prep_ker_ex2 (dilated, channel-strided kernels); 5: hc_encode_coeffs, hc_encrypt_sk, hc_decrypt_decode_coeffs (hc_encode_slots_ex, then hc_decode_slots and hc_decrypt_decode_slots, came later without a new number: detected by symbol)
+extern "C" int hc_version(void) { return 5; }      // 2: a plaintext shared by the images of a batch is said by the operation (HC_LV_MUL_PLAIN), never inferred from b0 == b1; 3: hc_prep_ker_ex (transposed kernels); 4: hc_prep_ker_ex2 (dilated, channel-strided kernels); 5: hc_encode_coeffs, hc_encrypt_sk, hc_decrypt_decode_coeffs (hc_encode_slots_ex, then hc_decode_slots and hc_decrypt_decode_slots, then hc_decode_coeffs and hc_decrypt_decode_lv, came later without a new number: detected by symbol)
 extern "C" const char *hc_last_error(const hc_ctx *c) { return c ? c->err.c_str() : g_create_err.c_str(); }
 
 // HcMod::row32 of modulus i of the context's nmods (Q then P): under pack32 = 2 the rows of a modulus below 2^31 in the caller's leveled operands are 4-byte words - except
@@ -403,7 +404,7 @@ extern "C" void hc_ctx_destroy(hc_ctx *c) {
     F(c->idx_pairs); F(c->ws_cts); F(c->ws_cts2); F(c->ws_gather);
     if (c->ev_fork) D(hipEventDestroy(c->ev_fork), "hipEventDestroy");
     if (c->ev_shard) D(hipEventDestroy(c->ev_shard), "hipEventDestroy");
-    F(c->enc_roots); F(c->enc_rot_group); F(c->d_flag);
+    F(c->enc_roots); F(c->enc_rot_group); F(c->d_flag); F(c->crt_tab);
     F(c->ws_ctc); F(c->ws_tmp); F(c->d_mods); F(c->d_rowmods); F(c->ws_mm); F(c->ws_accm);
     for (auto &kv : c->ks_plan) { F(kv.second.bx); F(kv.second.bxdown); F(kv.second.pinv); F(kv.second.pmod); F(kv.second.pinv_qlinv); }
     for (auto &kv : c->rescale_plan) F(kv.second);
@@ -2010,6 +2011,103 @@ extern "C" int hc_decrypt_decode_slots(hc_ctx *c, int count, int level, const ui
     double *coeffs = (double *)c->ws_cts;
     HC_TRY(hc_decrypt_decode_coeffs_impl(c, count, level, ct, sk_ntt, scale, coeffs));
     return hc_decode_slots_impl(c, coeffs, count, log_slots, values_out);
+}
+// ------------------------------------------------------------------ DecodeCoeffs at any level (hc_k_dec_decode_crt): hc_decode_coeffs, hc_decrypt_decode_lv
+// The per-context constants of the CRT, built at first use like hc_enc_tables' and kept on the device: q_k^-1 mod q_i (Montgomery form, the operand of Garner's products),
+// and the words of Q_level and Q_level >> 1 for every level whose Q fits HC_CRT_MAXW words (and HC_CRT_MAXL limbs: the digits' LDS columns). A prefix of the chain has a
+// prefix of the tables, so one set serves every level.
+static int hc_crt_tables(hc_ctx *c) {
+    if (c->crt_tab) return HC_OK;
+    const int nq = c->nq;
+    std::vector<u64> tab((size_t)nq * nq + 2 * (size_t)nq * HC_CRT_MAXW, 0);
+    u64 *ginv = tab.data(), *qw = ginv + (size_t)nq * nq, *half = qw + (size_t)nq * HC_CRT_MAXW;
+    for (int i = 0; i < nq; i++) for (int k = 0; k < i; k++) { const u64 qi = c->mods[(size_t)i].m.q; ginv[(size_t)i * nq + k] = (u64)((((u128)h_inv(c->mods[(size_t)k].m.q % qi, qi)) << 64) % qi); }
+    std::vector<int> words;
+    std::vector<u64> Q(HC_CRT_MAXW + 1, 0); Q[0] = 1;
+    for (int l = 0; l < nq && l < HC_CRT_MAXL; l++) {
+        u64 carry = 0; const u64 q = c->mods[(size_t)l].m.q;
+        for (int w = 0; w <= HC_CRT_MAXW; w++) { const u128 p = (u128)Q[(size_t)w] * q + carry; Q[(size_t)w] = (u64)p; carry = (u64)(p >> 64); }
+        if (Q[HC_CRT_MAXW] || carry) break;                                  // Q_l no longer fits: this level and every one above it is not built
+        int nw = 1; for (int w = 0; w < HC_CRT_MAXW; w++) if (Q[(size_t)w]) nw = w + 1;
+        words.push_back(nw);
+        for (int w = 0; w < HC_CRT_MAXW; w++) { qw[(size_t)l * HC_CRT_MAXW + w] = Q[(size_t)w]; half[(size_t)l * HC_CRT_MAXW + w] = (Q[(size_t)w] >> 1) | (Q[(size_t)w + 1] << 63); }
+    }
+    HcScratch S(c);
+    u64 *d = nullptr;
+    HC_HIP(c, S.alloc(&d, tab.size() * sizeof(u64)));
+    HC_HIP(c, hcx_h2d(c, d, tab.data(), tab.size() * sizeof(u64)));
+    S.keep(d);
+    c->crt_tab = d; c->crt_words = words;
+    return HC_OK;
+}
+// the second half of every decoder: n images of nl rows -> n x N doubles. nl <= 2 over 8-byte rows is hc_k_dec_decode, the kernel (and the bits) of hc_decrypt_decode_coeffs;
+// everything else is hc_k_dec_decode_crt on the smallest word count that holds Q_level
+static int hc_dec_decode_any(hc_ctx *c, const u64 *t, int n, int nl, int user_rows, double scale, double *out) {
+    bool any32 = false; for (int l = 0; l < nl; l++) any32 = any32 || (user_rows && c->mods[(size_t)l].m.row32);
+    if (nl <= 2 && !any32) {
+        u64 q0inv_m = 0;
+        if (nl == 2) { const u64 q0 = c->mods[0].m.q, q1 = c->mods[1].m.q; q0inv_m = (u64)((((u128)h_inv(q0 % q1, q1)) << 64) % q1); }
+        return hc_launch(c, "dec_decode", hc_k_dec_decode, dim3(64, (unsigned)n), t, out, (const HcMod *)c->d_mods, nl, scale, q0inv_m);
+    }
+    HcCrt T; T.ginv = c->crt_tab; T.qw = c->crt_tab + (size_t)c->nq * c->nq; T.half = T.qw + (size_t)c->nq * HC_CRT_MAXW; T.nq = c->nq;
+    const int nw = c->crt_words[(size_t)(nl - 1)];
+#define HC_CRT_GO(NW) hc_launch(c, "dec_decode_crt", hc_k_dec_decode_crt<NW>, dim3(64, (unsigned)n), t, out, (const HcMod *)c->d_mods, T, nl, user_rows, scale)
+    if (nw <= 4) return HC_CRT_GO(4);
+    if (nw <= 8) return HC_CRT_GO(8);
+    if (nw <= 12) return HC_CRT_GO(12);
+    if (nw <= 16) return HC_CRT_GO(16);
+    return HC_CRT_GO(HC_CRT_MAXW);
+#undef HC_CRT_GO
+}
+// the levels the CRT kernel is built for (after hc_crt_tables)
+static int hc_crt_check(hc_ctx *c, const char *fn, int level) {
+    HC_TRY(hc_crt_tables(c));
+    if (level >= (int)c->crt_words.size()) return hc_fail(c, HC_ERR_UNSUPPORTED, "%s: level %d: DecodeCoeffs is built for at most %d limbs and a Q of at most %d bits (this context: up to level %d)", fn, level, HC_CRT_MAXL, 64 * HC_CRT_MAXW, (int)c->crt_words.size() - 1);
+    return HC_OK;
+}
+// ckks.Encoder.DecodeCoeffs (include/hconv.h): per chunk of at most HC_MAXCTS plaintexts one batched inverse transform into 8-byte rows (from_ntt) and one decode launch;
+// coefficient-domain input is decoded where it lies, its rows read in the caller's widths. A held hc_keyswitch_decompose survives (the transform's seam is its only scratch).
+extern "C" int hc_decode_coeffs(hc_ctx *c, const uint64_t *pt, int count, int level, int from_ntt, double scale, double *out) {
+    HC_ENTER(c);
+    if (!pt || !out || count < 1 || count > 65535 || level < 0 || level >= c->nq) return hc_fail(c, HC_ERR_ARG, "hc_decode_coeffs: bad arguments (1 <= count <= 65535, 0 <= level < %d, non-null pointers)", c->nq);
+    HC_TRY(hc_crt_check(c, "hc_decode_coeffs", level));
+    const int nl = level + 1;
+    HcScratch S(c);
+    const int chunk = count < HC_MAXCTS ? count : HC_MAXCTS;
+    u64 *t = nullptr; if (from_ntt) HC_HIP(c, S.alloc(&t, (size_t)chunk * nl * HC_N * sizeof(u64)));
+    for (int z0 = 0; z0 < count; z0 += chunk) {
+        const int n = count - z0 < chunk ? count - z0 : chunk;
+        const u64 *src = (const u64 *)pt + (size_t)z0 * nl * HC_N;
+        if (from_ntt) { HcInttCall m; m.rows = m.nl = nl; m.nz = n; m.in = {src, (size_t)nl * HC_N, 0, HC_ROWS_USER}; m.out = {t, (size_t)nl * HC_N, 0, HC_ROWS_LIB8}; HC_TRY(hc_intt_mm(c, m)); }
+        HC_TRY(hc_dec_decode_any(c, from_ntt ? (const u64 *)t : src, n, nl, from_ntt ? 0 : 1, scale, out + (size_t)z0 * HC_N));
+    }
+    return HC_OK;
+}
+// Harness-side Decrypt + DecodeCoeffs (+ Decode) at any level, the two polynomials of a ciphertext in separate allocations as the chain holds them: per chunk t = c0 + c1 s
+// for all images and limbs, one batched inverse transform, one decode launch; then, log_slots >= 0, hc_decode_slots' launches from the context's ciphertext workspace
+extern "C" int hc_decrypt_decode_lv(hc_ctx *c, int count, int level, const uint64_t *const *c0, const uint64_t *const *c1, const uint64_t *sk_ntt, double scale, int log_slots, double *out) {
+    HC_ENTER(c);
+    if (!c0 || !c1 || !sk_ntt || !out || count < 1 || count > 65535 || level < 0 || level >= c->nq || log_slots < -1 || log_slots > 15)
+        return hc_fail(c, HC_ERR_ARG, "hc_decrypt_decode_lv: bad arguments (1 <= count <= 65535, 0 <= level < %d, -1 <= log_slots <= 15, non-null pointers)", c->nq);
+    for (int z = 0; z < count; z++) if (!c0[z] || !c1[z]) return hc_fail(c, HC_ERR_ARG, "hc_decrypt_decode_lv: null ciphertext %d", z);
+    HC_TRY(hc_crt_check(c, "hc_decrypt_decode_lv", level));
+    const int nl = level + 1;
+    double *coeffs = out;
+    if (log_slots >= 0) { HC_TRY(hc_ensure_cts(c, (size_t)count)); coeffs = (double *)c->ws_cts; }
+    HcScratch S(c);
+    const int chunk = count < HC_MAXCTS ? count : HC_MAXCTS;
+    u64 *t = nullptr; HC_HIP(c, S.alloc(&t, (size_t)chunk * nl * HC_N * sizeof(u64)));
+    for (int z0 = 0; z0 < count; z0 += chunk) {
+        const int n = count - z0 < chunk ? count - z0 : chunk;
+        HcCtPtrs A, B; memset(&A, 0, sizeof A); memset(&B, 0, sizeof B);
+        for (int z = 0; z < n; z++) { A.p[z] = (u64 *)c0[z0 + z]; B.p[z] = (u64 *)c1[z0 + z]; }
+        HC_TRY(hc_launch(c, "dec_combine_lv", hc_k_dec_combine_lv, dim3(64, (unsigned)nl, (unsigned)n), A, B, (const u64 *)sk_ntt, t, (const HcMod *)c->d_mods, nl));
+        HcInttCall m; m.rows = m.nl = nl; m.nz = n; m.in = {t, (size_t)nl * HC_N, 0, HC_ROWS_RAW}; m.out = {t, (size_t)nl * HC_N, 0, HC_ROWS_LIB8};
+        HC_TRY(hc_intt_mm(c, m));
+        HC_TRY(hc_dec_decode_any(c, (const u64 *)t, n, nl, 0, scale, coeffs + (size_t)z0 * HC_N));
+    }
+    if (log_slots >= 0) return hc_decode_slots_impl(c, coeffs, count, log_slots, out);
+    return HC_OK;
 }
 // out[2][level+1][N] = sum over t < ntaps of cts[t] (ciphertext [2][level+1][N]) x pts[t] (plaintext [level+1][N], NTT domain): the
 // MulNew / Add chain of conv.go:167-172 in one launch. cts: HOST array of ntaps device pointers; pts: device, [ntaps][level+1][N]

@@ -376,10 +376,10 @@ struct Boot {
         return r;
     }
     // debugging aid (HCONV_DEBUG_BOOT): decrypt on the limbs 0, 1 (needs |message| * scale < Q0 Q1 / 2) and decode to slots
-    std::vector<cplx> debug_slots(const DCt &a) {
-        Single one(this);                                          // image 0 of a batch
+    std::vector<double> debug_coeffs(const DCt &a, int z = 0) {       // image z of a batch: the coefficient doubles
+        Single one(this);
         const int L = std::min(a.level, 1); auto t = block();
-        HCR(hc_lv_mul_plain(hc, L, a.p[1].get(), d_sk, t.get())); HCR(hc_lv_add(hc, L, a.p[0].get(), t.get(), t.get())); HCR(hc_lv_intt(hc, L, t.get(), t.get()));
+        HCR(hc_lv_mul_plain(hc, L, a.p[1].get() + (size_t)z * poly_stride(), d_sk, t.get())); HCR(hc_lv_add(hc, L, a.p[0].get() + (size_t)z * poly_stride(), t.get(), t.get())); HCR(hc_lv_intt(hc, L, t.get(), t.get()));
         std::vector<uint64_t> m((size_t)(L + 1) * N); HCR(hc_download(hc, m.data(), t.get(), m.size() * 8));
         std::vector<double> cf((size_t)N);
         if (L == 0) { const uint64_t q0 = Q[0]; for (int j = 0; j < N; j++) cf[(size_t)j] = (m[(size_t)j] > q0 / 2 ? -(double)(q0 - m[(size_t)j]) : (double)m[(size_t)j]) / a.scale; }
@@ -389,8 +389,15 @@ struct Boot {
             for (int j = 0; j < N; j++) { const uint64_t a0 = m[(size_t)j], a1 = m[(size_t)N + j], d = (a1 % q1 + q1 - a0 % q1) % q1; const u128 x = (u128)a0 + (u128)q0 * mulmod(d, inv, q1);
                 cf[(size_t)j] = x > QQ / 2 ? -(double)(QQ - x) / a.scale : (double)x / a.scale; }
         }
-        std::vector<cplx> v((size_t)N / 2); for (int i = 0; i < N / 2; i++) v[(size_t)i] = cplx(cf[(size_t)i], cf[(size_t)(i + N / 2)]);
-        enc.fft(v);
+        return cf;
+    }
+    // encoder.Decode's float half on the host: 2^log_slots values from the coefficients on the gap grid, the forward special FFT of the ring with that many slots
+    std::vector<cplx> debug_slots(const DCt &a, int z = 0, int log_slots = LOGN - 1) {
+        const std::vector<double> cf = debug_coeffs(a, z);
+        const int ns_ = 1 << log_slots, gap = (N / 2) / ns_;
+        std::vector<cplx> v((size_t)ns_); for (int i = 0; i < ns_; i++) v[(size_t)i] = cplx(cf[(size_t)(i * gap)], cf[(size_t)(N / 2 + i * gap)]);
+        if (log_slots == LOGN - 1) enc.fft(v);
+        else { auto it = sub_enc.find(log_slots + 1); if (it == sub_enc.end()) it = sub_enc.emplace(log_slots + 1, Encoder(log_slots + 1)).first; it->second.fft(v); }
         return v;
     }
     static void debug_compare(const char *what, const std::vector<cplx> &want, const std::vector<cplx> &got) {
@@ -1319,6 +1326,139 @@ static void replay_digest_line(Boot *B, const char *what, const DCt &c, int firs
         printf("%s\n", line.c_str());
     }
 }
+// ---------------------------------------------------------------- HCONV_DEBUG_LAYERS=1: the per-stage report of a layer (eval.go:440-604 with debug = true)
+// The reference decrypts after the convolution, after BootstrappConv_CtoS, after evalReLU and after BootstrappConv_StoC and compares each stage with a plain shadow of it
+// computed from what the stage BEFORE decrypted to (debugCtoS, debugReLU, debugStoC: eval.go:610-722), so every block prices one stage alone. Here every stage is ONE
+// hc_decrypt_decode_lv call at the stage's own level over all images of the launch set and both halves (merged as images or not). An observer: it draws nothing from any
+// generator and changes no ciphertext, level or scale. Not reproduced: the prt_mat_* dumps and the drivers' own debug blocks. HCONV_DEBUG_LAYERS_CHECK=1 (test mode)
+// decodes every stage again on the host (Boot::debug_slots: limbs 0 and 1, host FFT) and panics unless the doubles are bit-identical.
+static bool debugLayers() { static const bool on = getenv("HCONV_DEBUG_LAYERS") && atoi(getenv("HCONV_DEBUG_LAYERS")); return on; }
+static std::string precLog2(double err) { if (err == 0) return "+Inf"; char b[32]; snprintf(b, sizeof b, "%.2f", log2(1.0 / err)); return b; }
+// ckks.PrecisionStats.String() in the shape printDebugCfsPlain prints it, for complex values: (real, imaginary) per line
+static void printPrecisionStats(const std::vector<cplx> &want, const std::vector<cplx> &test, const char *tail) {
+    std::string col[4][2];
+    for (int k = 0; k < 2; k++) {
+        std::vector<double> d(want.size());
+        for (size_t i = 0; i < d.size(); i++) d[i] = k ? fabs(want[i].imag() - test[i].imag()) : fabs(want[i].real() - test[i].real());
+        const double mn = *std::min_element(d.begin(), d.end()), mx = *std::max_element(d.begin(), d.end()); double mean = 0;
+        for (double x : d) mean += x;
+        mean /= (double)d.size();
+        std::sort(d.begin(), d.end());
+        col[0][k] = precLog2(mx); col[1][k] = precLog2(mn); col[2][k] = precLog2(mean); col[3][k] = precLog2(d[d.size() / 2]);
+    }
+    static const char *names[4] = {"MIN", "MAX", "AVG", "MED"};
+    for (int r = 0; r < 4; r++) printf("%s Prec : (%s, %s) Log2 \n", names[r], col[r][0].c_str(), col[r][1].c_str());
+    printf("Err stdF :  -Inf Log2 \nErr stdT :  -Inf Log2 \n%s", tail);
+}
+struct LayerDebug {
+    Boot *B; std::string kind; int log_sparse, nimg, in_wid, kp_wid; double alpha, pow_; const std::vector<std::vector<int>> *keep_idx; bool check;
+    std::vector<std::vector<double>> cfs_preB;                 // per image: the decoded convolution result
+    std::vector<std::vector<cplx>> seen[2];                    // per half, per image: what the stage before decrypted to
+    static int brev15(int i) { int r = 0; for (int b = 0; b < LOGN - 1; b++) r |= ((i >> b) & 1) << (LOGN - 2 - b); return r; }
+    int log_slots() const { return log_sparse ? LOGN - log_sparse : LOGN - 1; }      // printDebug: LogSlots - (log_sparse - 1) for a packed ciphertext
+    // ONE hc_decrypt_decode_lv call over every image of every ciphertext given, in that order (the halves, each with the B->nb images it holds): log_slots = -1: [count][N]
+    // doubles, else [count][2^log_slots] (re, im) pairs
+    std::vector<double> decode(const std::vector<const DCt *> &cts, int ls) {
+        hc_ctx *hc = B->hc; const DCt &f = *cts[0]; std::vector<const uint64_t *> c0, c1;
+        for (const DCt *c : cts) {
+            if (c->deg != 1 || c->level != f.level || c->scale != f.scale) panic("HCONV_DEBUG_LAYERS: the ciphertexts of a stage differ in degree, level or scale");
+            for (int z = 0; z < B->nb; z++) { c0.push_back(c->p[0].get() + (size_t)z * B->poly_stride()); c1.push_back(c->p[1].get() + (size_t)z * B->poly_stride()); }
+        }
+        const int count = (int)c0.size(); const size_t per = ls < 0 ? (size_t)N : (size_t)2 << ls;
+        void *v = nullptr; HCR(hc_malloc(hc, (size_t)count * per * 8, &v));
+        HCR(hc_decrypt_decode_lv(hc, count, f.level, c0.data(), c1.data(), B->d_sk, f.scale, ls, (double *)v));
+        std::vector<double> out((size_t)count * per); HCR(hc_download(hc, out.data(), v, out.size() * 8)); HCR(hc_free(hc, v));
+        if (check) {
+            const int nb = B->nb; size_t k = 0;
+            for (const DCt *c : cts) for (int z = 0; z < nb; z++, k++) {
+                bool same;
+                if (ls < 0) { const std::vector<double> h = B->debug_coeffs(*c, z); same = !memcmp(h.data(), &out[k * per], per * 8); }
+                else { const std::vector<cplx> h = B->debug_slots(*c, z, ls); same = !memcmp(h.data(), &out[k * per], per * 8); }
+                if (!same) panic("HCONV_DEBUG_LAYERS_CHECK: the device's decode differs from the host's (ciphertext " + std::to_string(k) + " of the stage)");
+            }
+            printf("stage decode: device == host (%zu values)\n", ls < 0 ? out.size() : out.size() / 2);
+        }
+        return out;
+    }
+    void image_line(int z) const { if (nimg > 1) printf("image %d\n", z); }
+    // main.go:722-756 without the decryption
+    static void printDebug(const std::vector<cplx> &test, const std::vector<cplx> &want) {
+        printf("\nValuesTest:"); for (int i = 0; i < 15; i++) printf("%6.5f, ", test[(size_t)i].real()); printf("... \n");
+        printf("ValuesWant:"); for (int i = 0; i < 15; i++) printf("%6.5f, ", want[(size_t)i].real()); printf("... \n");
+        printPrecisionStats(want, test, "\n\n");
+    }
+    void after_conv(const DCt &ct) {                                                                      // eval.go:443: cfs_preB
+        printf("layer debug: kind %s log_sparse %d images %d\n", kind.c_str(), log_sparse, nimg);
+        const std::vector<double> cf = decode({&ct}, -1);
+        for (int z = 0; z < nimg; z++) cfs_preB.emplace_back(cf.begin() + (size_t)z * N, cf.begin() + (size_t)(z + 1) * N);
+    }
+    // one slot stage: decode halves x images, print every block against want(z, half), remember what was seen
+    template <class Want> void slot_stage(const std::vector<const DCt *> &cts, int iter, Want want) {
+        const int ls = log_slots(); const size_t ns_ = (size_t)1 << ls;
+        const std::vector<double> v = decode(cts, ls);
+        if (v.size() != (size_t)iter * nimg * 2 * ns_) panic("HCONV_DEBUG_LAYERS: a stage holds other ciphertexts than halves x images");
+        std::vector<std::vector<cplx>> now[2];
+        for (int h = 0; h < iter; h++) for (int z = 0; z < nimg; z++) { const double *p = &v[((size_t)h * nimg + z) * 2 * ns_]; std::vector<cplx> t(ns_); for (size_t i = 0; i < ns_; i++) t[i] = cplx(p[2 * i], p[2 * i + 1]); now[h].push_back(t); }
+        for (int z = 0; z < nimg; z++) { image_line(z); for (int h = 0; h < iter; h++) printDebug(now[h][(size_t)z], want(z, h)); }
+        for (int h = 0; h < 2; h++) seen[h] = now[h];
+    }
+    void after_ctos(const std::vector<const DCt *> &cts, int iter) {                                       // debugCtoS (eval.go:610-633)
+        slot_stage(cts, iter, [&](int z, int h) {
+            const std::vector<double> &cf = cfs_preB[(size_t)z]; const int part = (N / 2) >> log_sparse;
+            std::vector<cplx> s((size_t)(log_sparse ? 2 * part : part));
+            for (int i = 0; i < part; i++) { if (log_sparse) { s[(size_t)i] = cplx(cf[(size_t)brev15(i)], 0); s[(size_t)(part + i)] = cplx(cf[(size_t)(brev15(i) + N / 2)], 0); } else s[(size_t)i] = cplx(cf[(size_t)(brev15(i) + h * (N / 2))], 0); }
+            return s; });
+    }
+    void after_relu(const DCt boots[2], int iter) {                                                      // debugReLU (eval.go:635-651)
+        printf("after Relu:  %.15g lv:  %d\n", log2(boots[0].scale), boots[0].level);
+        std::vector<const DCt *> cts; for (int h = 0; h < iter; h++) cts.push_back(&boots[h]);
+        const std::vector<std::vector<cplx>> before[2] = {seen[0], seen[1]};
+        slot_stage(cts, iter, [&](int z, int h) {
+            const std::vector<cplx> &s = before[h][(size_t)z]; std::vector<cplx> r(s.size());
+            for (size_t i = 0; i < s.size(); i++) r[i] = cplx((std::max(0.0, s[i].real()) + std::min(0.0, s[i].real() * alpha)) * pow(2.0, pow_), 0);
+            return r; });
+    }
+    // debugStoC (eval.go:653-722) for the kinds the tail runs, over the index generators the layer itself masks with
+    std::vector<double> shadow_stoc(int z, int iter) const {
+        const int n = N / 2; std::vector<double> fl[2] = {std::vector<double>((size_t)n, 0.0), std::vector<double>((size_t)n, 0.0)}, tmp[2];
+        for (int h = 0; h < iter; h++) for (size_t i = 0; i < seen[h][(size_t)z].size(); i++) fl[h][i] = seen[h][(size_t)z][i].real();
+        auto masked = [&](const std::vector<double> &in, const std::vector<int> &m) { std::vector<double> o((size_t)n); for (int i = 0; i < n; i++) o[(size_t)i] = in[(size_t)i] * (double)m[(size_t)i]; return o; };
+        auto halves_of = [&](const std::vector<double> &t) { const size_t half = seen[0][(size_t)z].size() / 2; tmp[0].assign((size_t)n, 0.0); tmp[1].assign((size_t)n, 0.0); for (size_t i = 0; i < half; i++) { tmp[0][i] = t[i]; tmp[1][i] = t[i + half]; } };
+        if (kind == "StrConv_sparse") {                                                                   // comprs_vec_sparse (rot_util.go:101-136)
+            if (iter != 1) panic("HCONV_DEBUG_LAYERS: StrConv_sparse on full packing is a wide network's layer (out of scope)");
+            IdxMap m_idx, r_idx; gen_comprs_sparse(n, in_wid, kp_wid, log_sparse, 0, m_idx, r_idx);
+            auto pass = [&](const std::vector<double> &in, const IdxMap &idx) {
+                std::vector<double> o((size_t)n, 0.0);
+                for (auto &e : idx) { const int rot = ((e.first % n) + n) % n; for (int j = 0; j < n; j++) { const int src = (j + rot) % n; o[(size_t)j] += in[(size_t)src] * (double)e.second[(size_t)src]; } }
+                return o; };
+            halves_of(pass(pass(fl[0], m_idx), r_idx));
+        } else if (iter == 1) halves_of(masked(fl[0], gen_keep_vec_sparse(n, in_wid, kp_wid, log_sparse)));         // keep_vec_sparse
+        else if (keep_idx) for (int h = 0; h < 2; h++) tmp[h] = masked(fl[h], (*keep_idx)[(size_t)h]);              // keep_vec_stride: the context's ext_idx[step]
+        else for (int h = 0; h < 2; h++) tmp[h] = masked(fl[h], gen_keep_vec(n, in_wid, kp_wid, h));                // keep_vec
+        std::vector<double> cfs((size_t)N);
+        for (int i = 0; i < n; i++) { cfs[(size_t)i] = tmp[0][(size_t)brev15(i)]; cfs[(size_t)(n + i)] = tmp[1][(size_t)brev15(i)]; }
+        return cfs;
+    }
+    void after_stoc(const DCt &res, int iter) {                                                          // printDebugCfs (main.go:647-692) with the sparse bootstrapper's slot count
+        printf("Boot out: \n");
+        const std::vector<double> cf = decode({&res}, -1);
+        std::vector<uint64_t> Qw(1, 1); for (int l = 0; l <= res.level; l++) { uint64_t carry = 0; for (auto &w : Qw) { const u128 p = (u128)w * B->Q[(size_t)l] + carry; w = (uint64_t)p; carry = (uint64_t)(p >> 64); } if (carry) Qw.push_back(carry); }
+        const int logQ = 64 * (int)(Qw.size() - 1) + (64 - __builtin_clzll(Qw.back()));
+        const int slots = (N / 2) >> log_sparse, step = 1 << log_sparse;
+        for (int z = 0; z < nimg; z++) {
+            image_line(z);
+            const std::vector<double> want = shadow_stoc(z, iter);
+            std::vector<cplx> t((size_t)2 * slots), w((size_t)2 * slots);
+            for (int i = 0; i < 2 * slots; i++) { t[(size_t)i] = cplx(cf[(size_t)z * N + (size_t)i * step], 0); w[(size_t)i] = cplx(want[(size_t)i * step], 0); }
+            printf("len val Want: %d\nlen val Test: %d\n\n", N, 2 * slots);
+            printf("Level: %d (logQ = %d)\nScale: 2^%f\n", res.level, logQ, log2(res.scale));
+            printf("ValuesTest:"); for (int i = 0; i < 15; i++) printf("%6.10f, ", t[(size_t)i].real()); printf("... \n");
+            printf("ValuesWant:"); for (int i = 0; i < 15; i++) printf("%6.10f, ", w[(size_t)i].real()); printf("... \n");
+            printPrecisionStats(std::vector<cplx>(w.begin(), w.begin() + slots), std::vector<cplx>(t.begin(), t.begin() + slots), "\n");
+            printPrecisionStats(std::vector<cplx>(w.begin() + slots, w.end()), std::vector<cplx>(t.begin() + slots, t.end()), "\n\n");
+        }
+    }
+};
 // eval.go:437-565: everything after the convolution(s). ct_conv = the level-0 convolution result at out_scale
 // 2^(round(log2 Q0) - (pow+8)). kind "Conv" (log_sparse 0, two ciphertexts through sine/ReLU, keep_ctxt masks of gen_keep_vec),
 // "Conv_sparse" (one packed ciphertext, gen_keep_vec_sparse), "StrConv_sparse" (one packed ciphertext, ext_double_ctxt with
@@ -1355,6 +1495,12 @@ std::vector<BootCiphertext> evalConv_BNRelu_tail_batch(Boot *B, const std::strin
         }
     }
     const bool prof = getenv("HCONV_PROFILE") && atoi(getenv("HCONV_PROFILE"));
+    std::unique_ptr<LayerDebug> dbg;
+    if (debugLayers()) {
+        const char *ck = testOnlyEnv("HCONV_DEBUG_LAYERS_CHECK");                                       // fatal outside test mode
+        dbg.reset(new LayerDebug{B, kind, log_sparse, nimg, in_wid, kp_wid, alpha, pow_, inside ? keep_idx : nullptr, ck && atoi(ck) != 0, {}, {}});
+        dbg->after_conv(ct);
+    }
     if (prof) { HCR(hc_set_option(hc, "profile", 1)); hc_profile_get(hc, nullptr, nullptr, nullptr); }
     printf("Bootstrapping... Ours (until CtoS):\n");
     auto start = now();
@@ -1372,6 +1518,7 @@ std::vector<BootCiphertext> evalConv_BNRelu_tail_batch(Boot *B, const std::strin
         for (int ul = 0; ul < iter; ul++) replay_digest(ul ? "ctos1" : "ctos0", boots[ul]);
     }
     if (rls) { printf("replay of the sparse-slot BootstrappConv_CtoS done (log_sparse %d)\n", ls_run); fflush(stdout); exit(0); }
+    if (dbg) { std::vector<const DCt *> cts; for (int ul = 0; ul < (B->parts_merged ? 1 : iter); ul++) cts.push_back(&boots[ul]); dbg->after_ctos(cts, iter); }       // merged: ONE ciphertext of 2 nimg images, half-major
     start = now();
     for (int ul = 0; ul < (B->parts_merged ? 1 : iter); ul++) {
         if (B->parts_merged) printf("Eval: ");                                                        // the reference's loop (eval.go:462-477) prints once per half: same line shape
@@ -1382,6 +1529,7 @@ std::vector<BootCiphertext> evalConv_BNRelu_tail_batch(Boot *B, const std::strin
     HCR(hc_sync(hc));
     printf("ReLU Done in %s \n", dur(start).c_str());
     if (prof) profile_dump(B, "ReLU");
+    if (dbg) dbg->after_relu(boots, iter);
     start = now();
     DCt keep[2];
     const std::string mk = std::to_string(in_wid) + "/" + std::to_string(kp_wid) + "/" + std::to_string(log_sparse);
@@ -1395,6 +1543,7 @@ std::vector<BootCiphertext> evalConv_BNRelu_tail_batch(Boot *B, const std::strin
     HCR(hc_sync(hc));
     printf("Boot (StoC) Done in %s \n", dur(start).c_str());
     if (B->replay_seed) replay_digest("final", res);
+    if (dbg) dbg->after_stoc(res, iter);
     if (prof) { profile_dump(B, ("mask + SlotsToCoeffs; the layer was " + kind + " log_sparse " + std::to_string(log_sparse)).c_str()); HCR(hc_set_option(hc, "profile", 0)); }
     if (getenv("HCONV_ALG_BYTES")) printf("algorithmic traffic of the layer's tail: %.6g GB per ciphertext + %.6g GB shared by the %d image%s of the launch set\n", B->alg_ct * N * 8 / 1e9, B->alg_shared * N * 8 / 1e9, nimg, nimg > 1 ? "s" : "");
     B->alg_ct = B->alg_shared = 0;
@@ -1482,6 +1631,13 @@ void blBootReLU(Boot *B, const uint64_t *ct_res0, const uint64_t *ct_res1, doubl
 std::vector<double> bootDecryptDecodeCoeffs(Boot *B, const BootCiphertext &ct) {
     hc_ctx *hc = B->hc;
     if (ct.level != 1) panic("bootDecryptDecodeCoeffs expects the level-1 result of the chain");
+    if (deviceEncrypt()) {            // HCONV_DEVICE_ENCRYPT=1 and no replay: the device's decoder (level 1: the same kernel and bits as the host loop below)
+        void *o = nullptr; HCR(hc_malloc(hc, (size_t)N * 8, &o));
+        const uint64_t *c0 = ct.d, *c1 = ct.d + (size_t)2 * N;
+        HCR(hc_decrypt_decode_lv(hc, 1, 1, &c0, &c1, B->d_sk, ct.Scale, -1, (double *)o));
+        std::vector<double> cf((size_t)N); HCR(hc_download(hc, cf.data(), o, cf.size() * 8)); HCR(hc_free(hc, o));
+        return cf;
+    }
     void *v = nullptr; HCR(hc_malloc(hc, (size_t)2 * N * 8, &v)); uint64_t *t = (uint64_t *)v;
     HCR(hc_lv_mul_plain(hc, 1, ct.d + (size_t)2 * N, B->d_sk, t)); HCR(hc_lv_add(hc, 1, ct.d, t, t)); HCR(hc_lv_intt(hc, 1, t, t));
     std::vector<uint64_t> m((size_t)2 * N); HCR(hc_download(hc, m.data(), t, m.size() * 8)); HCR(hc_free(hc, t));
