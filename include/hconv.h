@@ -102,6 +102,10 @@ int hc_set_batch(hc_ctx *ctx, int n, size_t poly_stride_words, size_t qp_stride_
 /* ---- L0, leveled: a polynomial at `level` is (level+1) consecutive rows, row l modulo q_l (Lattigo's ring.Poly / ckks.Element
  * at that level). One call covers all limbs. These are what a general-level ckks.Evaluator binds for the convReLU chain
  * (eval.go:272-607): MulNew/MulRelin's tensor products, Add/Sub, MultByConst / MulByPow2, AddConst, and the bootstrapper's modUp. */
+/* Aliasing of the pointwise and transform calls below: out may be a, and out may be b (every coefficient is read before it is written, by the same thread):
+ * hc_lv_mul / hc_lv_mul_plain / hc_lv_add / hc_lv_sub with out == a or out == b (hc_lv_add(a, t, t): a running sum), hc_lv_mul_const / hc_lv_add_const with out == a,
+ * hc_lv_op2 with out_k == a_k (and out_k == b_k where b is per image: HC_LV_MUL, HC_LV_ADD, HC_LV_SUB), hc_lv_mul_acc with a == b (a square); hc_lv_ntt / hc_lv_intt with out == in (the transform goes
+ * through the context's seam). An operand that only PARTLY overlaps an output is never allowed. */
 int hc_lv_ntt(hc_ctx *ctx, int level, const uint64_t *in, uint64_t *out);
 int hc_lv_intt(hc_ctx *ctx, int level, const uint64_t *in, uint64_t *out);
 int hc_lv_mul(hc_ctx *ctx, int level, const uint64_t *a, const uint64_t *b, uint64_t *out);
@@ -164,10 +168,11 @@ int hc_rotate_gal_l0(hc_ctx *ctx, uint64_t galEl, const uint64_t *c0, const uint
 int hc_swk_load(hc_ctx *ctx, uint64_t key_id, int level, const uint64_t *rows_host);
 int hc_keyswitch(hc_ctx *ctx, uint64_t key_id, int level, const uint64_t *cx, uint64_t *d0, uint64_t *d1);
 /* evaluator.Relinearize / MulRelin's tail as one call: out_k = a_k + (hc_keyswitch of cx)_k, k = 0, 1 (a = the degree-0 and degree-1 parts of the tensor product, cx = its
- * degree-2 part); the addition rides in ModDown's last pass. The same residues as hc_keyswitch + hc_lv_op2(HC_LV_ADD). out_k may be a_k. */
+ * degree-2 part); the addition rides in ModDown's last pass. The same residues as hc_keyswitch + hc_lv_op2(HC_LV_ADD). out_k may be a_k, for both k or for one of them only (mulRelin: out0 == a0, out1 a block of its own). */
 int hc_keyswitch_add(hc_ctx *ctx, uint64_t key_id, int level, const uint64_t *cx, const uint64_t *a0, const uint64_t *a1, uint64_t *out0, uint64_t *out1);
 /* hc_keyswitch_add followed by ONE hc_div_round_last2 (evaluator.MulRelin + Rescale's first drop), as one call: out_k = Rescale(a_k + (key switch of cx)_k), level >= 2,
- * out at level - 1. Same residues as the two calls; ModDown and the rescale share one forward transform per limb. */
+ * out at level - 1. Same residues as the two calls; ModDown and the rescale share one forward transform per limb. out_k may be a_k (rows 0..level-1 are written; row
+ * `level` of a_k is then left as it was). */
 int hc_keyswitch_add_rescale(hc_ctx *ctx, uint64_t key_id, int level, const uint64_t *cx, const uint64_t *a0, const uint64_t *a1, uint64_t *out0, uint64_t *out1);
 /* HARNESS ONLY - not part of what a Lattigo host binds (it owns its keys and hands them over with hc_swk_load): rlwe.KeyGenerator.GenSwitchingKey on the device for
  * the C++ test harness, restricted to the rows a level-`level` key switch reads. galEl odd: the rotation / conjugation key of galEl (s_out = sigma_{galEl^-1}(s));
@@ -177,8 +182,24 @@ int hc_keyswitch_add_rescale(hc_ctx *ctx, uint64_t key_id, int level, const uint
 int hc_swk_generate(hc_ctx *ctx, uint64_t key_id, int level, uint64_t galEl, const uint64_t *sk_ntt, const uint32_t *seed8);
 /* Hoisted form (evaluator.RotateHoisted, conv.go:131; Lattigo's linear transforms): hc_keyswitch_decompose computes the digit
  * decomposition of cx once and keeps it in the context; each hc_keyswitch_hoisted(key, level, cx, ...) then only does the inner
- * product with its key and the ModDown. Bit-identical to hc_keyswitch. The decomposition is valid until the next hc_keyswitch /
- * hc_keyswitch_decompose / hc_div_round_last on this context. */
+ * product with its key and the ModDown. Bit-identical to hc_keyswitch. A consumer - hc_keyswitch_hoisted, and hc_keyswitch_rotate / hc_keyswitch_qp /
+ * hc_keyswitch_qp_rotate with hoisted != 0, hc_keyswitch_qp_rotate_many - names the polynomial by its pointer and level; when the context no longer holds the
+ * decomposition of exactly that pointer at that level it returns HC_ERR_STATE before anything is launched (another pointer with the same contents is another polynomial).
+ * What ENDS a held decomposition (tests/abi_contract_cases.py runs every entry point between a decomposition and each consumer):
+ *  - every call that decomposes by itself: hc_keyswitch, hc_keyswitch_add, hc_keyswitch_add_rescale, hc_keyswitch_decompose (of any polynomial: the new one is
+ *    held instead), hc_keyswitch_rotate / hc_keyswitch_qp / hc_keyswitch_qp_rotate with hoisted = 0;
+ *  - the calls that share its scratch: hc_div_round_last / hc_div_round_last2 at level 2 and above, hc_lv_mod_raise, hc_mod_down2 / hc_mod_down2_add_rescale at
+ *    ANOTHER level, and any leveled call at a level (or batch) high enough to make that scratch grow;
+ *  - hc_swk_generate (and the test hook hc_swk_generate_splitmix), hc_encode_slots / hc_encode_slots_ex / hc_encode_coeffs with to_ntt != 0, hc_encrypt_sk,
+ *    hc_decrypt_decode_coeffs, hc_decrypt_decode_slots: dropped out of caution, a caller must not count on either outcome;
+ *  - hc_set_batch to another setting (one image has no strides: hc_set_batch(1, s, t) is hc_set_batch(1, 0, 0)), option pack32 (any value);
+ *  - hc_free of the block that cx lies in (the next block of that size may have the same address), and the caller overwriting cx - which the library cannot see.
+ * What does NOT: the consumers themselves, in any order and number; hc_mod_down2 / hc_mod_down2_add_rescale at the SAME level; the pointwise and transform calls
+ * (hc_lv_ntt .. hc_lv_add_const, hc_lv_op2, hc_lv_lincomb2, hc_lv_mul_tensor, hc_rotate_finish, hc_lv_permute, hc_qp_permute2, hc_qp_op2, hc_qp_mul_sum*, hc_lv_mul_sum);
+ * hc_div_round_last / hc_div_round_last2 at level 1; the encoders with to_ntt = 0; the one-row primitives (hc_ntt .. hc_permute); hc_malloc, hc_free of other blocks, hc_copy, hc_upload, hc_download, hc_sync;
+ * hc_swk_load; hc_decode_slots, hc_decode_coeffs, hc_decrypt_decode_lv; hc_set_batch to the setting in force; every other option; the level-0 / 1 convolution
+ * entry points (kernel loading and preparation, hc_idx_load, hc_conv_mult_phase). Between a decomposition and its last consumer the product host calls hc_malloc,
+ * hc_free, hc_copy, hc_lv_add, hc_qp_permute2, hc_add and hc_permute, and re-decomposes nothing. */
 int hc_keyswitch_decompose(hc_ctx *ctx, int level, const uint64_t *cx);
 /* The key switch in two halves, and arithmetic in the extended basis QP (rows Q_0..Q_level, then P_0..P_(np-1)) between them: what Lattigo's
  * MultiplyByDiagMatrixBSGS (the linear transforms of CoeffsToSlots / SlotsToCoeffs; test_run @52a580) is made of.

@@ -128,6 +128,7 @@ struct hc_ctx {
     long small_mm_wgs = 1024;                               // option small_mm_wgs: a batched inverse pass / second forward pass of at most this many 16-row workgroups runs on quarter tiles (0: never); measured 512 .. 32 768: profiles/round6_chain_probes.txt
 #endif
     long allocs_live = 0;                                   // hc_malloc blocks not yet freed (the allocation mode may only change while there are none)
+    std::map<const char *, size_t> user_blk;                // hc_malloc blocks and their sizes: hc_free of the block that holds hoist_cx ends the held decomposition
     HcRowMod *d_rowmods = nullptr;                          // per modulus: both twiddle tables + q, mu (multi-modulus batched transforms)
     u64 *ws_mm = nullptr; size_t ws_mm_rows = 0;            // scratch of the batched key switch / rescale
     u64 *ws_accm = nullptr; size_t ws_accm_rows = 0;        // inner products of several hoisted rotations (hc_keyswitch_qp_rotate_many)
@@ -417,7 +418,7 @@ extern "C" void hc_ctx_destroy(hc_ctx *c) {
 }
 
 // ------------------------------------------------------------------ memory
-extern "C" int hc_malloc(hc_ctx *c, size_t bytes, void **dptr) { HC_ENTER(c); if (!dptr) return hc_fail(c, HC_ERR_ARG, "hc_malloc: null"); HC_HIP(c, hcx_malloc(c, dptr, bytes)); c->allocs_live++; return HC_OK; }
+extern "C" int hc_malloc(hc_ctx *c, size_t bytes, void **dptr) { HC_ENTER(c); if (!dptr) return hc_fail(c, HC_ERR_ARG, "hc_malloc: null"); HC_HIP(c, hcx_malloc(c, dptr, bytes)); c->allocs_live++; c->user_blk[(const char *)*dptr] = bytes; return HC_OK; }
 // hipFree drains the device by itself. With cached allocations (option async_alloc = 1) the block is parked for reuse by THIS context, and
 // hc_free does not wait for the stream. Plain mode: hipFree drains the device itself. Cached mode (option async_alloc = 1): the block is parked behind an event
 // and handed out again only to work queued on this same stream (hcx_free / hcx_h2d_async). What the caller owes: a block is freed into the context that
@@ -429,7 +430,15 @@ extern "C" int hc_free(hc_ctx *c, void *dptr) {
     hipError_t e = hcx_free(c, dptr);
     if (e == hipErrorInvalidDevicePointer) return hc_fail(c, HC_ERR_ARG, "hc_free: %p was not allocated by this context (with cached allocations a block goes back to the context it came from)", dptr);
     HC_HIP(c, e);
-    if (dptr) c->allocs_live--;
+    if (dptr) {
+        c->allocs_live--;
+        // the polynomial of a held decomposition went with its block: the next block of this size may get the same address (always, with cached allocations), and
+        // the pointer comparison of the hoisted consumers would then take the digits of the old contents for those of the new
+        auto ub = c->user_blk.find((const char *)dptr);
+        const size_t n = ub == c->user_blk.end() ? 1 : (ub->second ? ub->second : 1);
+        if (c->hoist_cx && (const char *)c->hoist_cx >= (const char *)dptr && (const char *)c->hoist_cx < (const char *)dptr + n) c->hoist_cx = nullptr;
+        if (ub != c->user_blk.end()) c->user_blk.erase(ub);
+    }
     return HC_OK;
 }
 extern "C" int hc_upload(hc_ctx *c, void *dst, const void *src, size_t bytes) {
@@ -565,8 +574,9 @@ extern "C" int hc_set_batch(hc_ctx *c, int n, size_t poly_stride_words, size_t q
     if (!c) return HC_ERR_ARG;
     if (n < 1 || n > HC_MAXIMG) return hc_fail(c, HC_ERR_ARG, "hc_set_batch: n=%d outside 1..%d", n, HC_MAXIMG);
     if (n > 1 && (poly_stride_words < (size_t)HC_N || (c->np > 0 && qp_stride_words < (size_t)HC_N))) return hc_fail(c, HC_ERR_ARG, "hc_set_batch: strides must cover at least one row");
-    if (n != c->nb || poly_stride_words != c->bs_poly || qp_stride_words != c->bs_qp) c->hoist_cx = nullptr;       // a held decomposition belongs to the batch it was taken under
-    c->nb = n; c->bs_poly = n > 1 ? poly_stride_words : 0; c->bs_qp = n > 1 ? qp_stride_words : 0;
+    const size_t ps = n > 1 ? poly_stride_words : 0, qs = n > 1 ? qp_stride_words : 0;                           // one image has no strides, whatever was passed
+    if (n != c->nb || ps != c->bs_poly || qs != c->bs_qp) c->hoist_cx = nullptr;                                 // a held decomposition belongs to the batch it was taken under
+    c->nb = n; c->bs_poly = ps; c->bs_qp = qs;
     return HC_OK;
 }
 
@@ -1511,8 +1521,19 @@ extern "C" int hc_keyswitch_add_rescale(hc_ctx *c, uint64_t key_id, int level, c
 }
 // Hoisted key switching (evaluator.RotateHoisted, conv.go:131; the baby steps of a linear transform): the decomposition of cx is
 // computed once and kept in the context; every hc_keyswitch_hoisted with the same (cx, level) then only does the inner product with
-// ITS key and the ModDown. Results are bit-identical to hc_keyswitch. The decomposition stays valid until the next hc_keyswitch /
-// hc_keyswitch_decompose on this context or until cx is overwritten by the caller.
+// ITS key and the ModDown. Results are bit-identical to hc_keyswitch. hoist_cx / hoist_level name what ws_mm holds: a consumer given another pointer or another level
+// is refused with HC_ERR_STATE before anything is launched. What ends a held decomposition, i.e. clears hoist_cx (include/hconv.h above hc_keyswitch_decompose has the
+// same list; tests/abi_contract_cases.py runs every entry point between a decomposition and each consumer - MUST_REFUSE / MUST_SURVIVE - so a new user of ws_mm that
+// forgets the clear, or a new entry point nobody placed, fails there):
+//   - the calls that decompose by themselves: hc_keyswitch, hc_keyswitch_add, hc_keyswitch_add_rescale, hc_keyswitch_decompose (any polynomial: it is held instead),
+//     hc_keyswitch_rotate / hc_keyswitch_qp / hc_keyswitch_qp_rotate with hoisted = 0;
+//   - the other users of ws_mm: Rescale at level 2 and above (hc_div_round_last_n), hc_lv_mod_raise, hc_mod_down2 / hc_mod_down2_add_rescale at ANOTHER level (pc / ext of
+//     another level overlap the digits), and whatever makes ws_mm grow (hc_ensure_mm: the block the digits lay in is gone);
+//   - out of caution, though they do not touch ws_mm: hc_swk_generate(_splitmix), the encoders with to_ntt != 0, hc_encrypt_sk, hc_decrypt_decode_coeffs / _slots;
+//   - hc_set_batch to another setting (the scratch is laid out per image), option pack32, hc_free of the block cx lies in (its address may come back with other contents).
+// What does not: the consumers in any order and number, ModDown at the held level, Rescale at level 1 (loop A's path), every call whose only scratch is the transforms'
+// seam ws_tmp (hc_lv_ntt / hc_lv_intt, hc_decode_coeffs, hc_decrypt_decode_lv) or none at all (pointwise, permutations, extended-basis arithmetic, one-row primitives, copies,
+// other blocks' hc_malloc / hc_free, hc_swk_load, the other options, the level-0 / 1 convolution path). The caller overwriting cx is the one thing the library cannot see.
 extern "C" int hc_keyswitch_decompose(hc_ctx *c, int level, const uint64_t *cx) {
     HC_ENTER(c);
     if (!cx || level < 0 || level >= c->nq || c->np < 1) return hc_fail(c, HC_ERR_ARG, "hc_keyswitch_decompose: bad arguments");
