@@ -185,6 +185,9 @@ int hc_swk_generate(hc_ctx *ctx, uint64_t key_id, int level, uint64_t galEl, con
  * product with its key and the ModDown. Bit-identical to hc_keyswitch. A consumer - hc_keyswitch_hoisted, and hc_keyswitch_rotate / hc_keyswitch_qp /
  * hc_keyswitch_qp_rotate with hoisted != 0, hc_keyswitch_qp_rotate_many - names the polynomial by its pointer and level; when the context no longer holds the
  * decomposition of exactly that pointer at that level it returns HC_ERR_STATE before anything is launched (another pointer with the same contents is another polynomial).
+ * The digits lie in a scratch block that other calls use. Inside the library that block is reached only through a claim that says what the call does with it - rewrite the
+ * digits, read them, or use the ModDown's part behind them - and the claim ends, requires or keeps the hold BEFORE the call writes a word: a call of the first two groups
+ * below that fails half way (HC_ERR_HIP) has ended the hold all the same, and a hc_keyswitch_decompose that fails holds nothing.
  * What ENDS a held decomposition (tests/abi_contract_cases.py runs every entry point between a decomposition and each consumer):
  *  - every call that decomposes by itself: hc_keyswitch, hc_keyswitch_add, hc_keyswitch_add_rescale, hc_keyswitch_decompose (of any polynomial: the new one is
  *    held instead), hc_keyswitch_rotate / hc_keyswitch_qp / hc_keyswitch_qp_rotate with hoisted = 0;

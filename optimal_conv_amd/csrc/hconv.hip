@@ -169,6 +169,13 @@ static int hc_fail(hc_ctx *c, int code, const char *fmt, ...) {
 }
 #define HC_HIP(c, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return hc_fail(c, HC_ERR_HIP, "%s: %s", #call, hipGetErrorString(e_)); } while (0)
 #define HC_ENTER(c) do { if (!(c)) return HC_ERR_ARG; HC_HIP(c, hipSetDevice((c)->device)); } while (0)
+// The decomposition hc_keyswitch_decompose left in ws_mm for later calls (the rule: above hc_keyswitch_decompose). Nothing else assigns hoist_cx / hoist_level.
+static void hc_hoist_drop(hc_ctx *c) { c->hoist_cx = nullptr; }
+static void hc_hoist_hold(hc_ctx *c, const void *cx, int level) { c->hoist_cx = cx; c->hoist_level = level; }
+static int hc_hoist_need(hc_ctx *c, const char *fn, const void *cx, int level) {
+    if (c->hoist_cx == cx && c->hoist_level == level) return HC_OK;
+    return hc_fail(c, HC_ERR_STATE, "%s: no decomposition of this polynomial at level %d is held (call hc_keyswitch_decompose first)", fn, level);
+}
 
 // forward lazy-reduction mode by modulus size (see HC_FM_* in hc_kernels.h): FREE needs 74q < 2^64 <=> q < 2^57 (hc_fm_free); ALT needs 8q < 2^64
 // Allocation: plain hipMalloc / hipFree by default. hipFree synchronises the whole device, which is harmless with one context but
@@ -436,7 +443,7 @@ extern "C" int hc_free(hc_ctx *c, void *dptr) {
         // the pointer comparison of the hoisted consumers would then take the digits of the old contents for those of the new
         auto ub = c->user_blk.find((const char *)dptr);
         const size_t n = ub == c->user_blk.end() ? 1 : (ub->second ? ub->second : 1);
-        if (c->hoist_cx && (const char *)c->hoist_cx >= (const char *)dptr && (const char *)c->hoist_cx < (const char *)dptr + n) c->hoist_cx = nullptr;
+        if (c->hoist_cx && (const char *)c->hoist_cx >= (const char *)dptr && (const char *)c->hoist_cx < (const char *)dptr + n) hc_hoist_drop(c);
         if (ub != c->user_blk.end()) c->user_blk.erase(ub);
     }
     return HC_OK;
@@ -493,11 +500,13 @@ static int hc_ensure(hc_ctx *c, T *&ws, size_t &cap, size_t units, size_t unit_b
 static int hc_ensure_tmp(hc_ctx *c, size_t rows) { return hc_ensure(c, c->ws_tmp, c->ws_tmp_rows, rows, HC_N * sizeof(u64)); }
 static int hc_ensure_cts(hc_ctx *c, size_t rows) { return hc_ensure(c, c->ws_cts, c->ws_cts_rows, rows, HC_N * sizeof(u64)); }
 static int hc_ensure_ctc(hc_ctx *c, size_t nct) { return hc_ensure(c, c->ws_ctc, c->ws_ctc_cts, nct, 4 * HC_N * sizeof(HcTw)); }
-static int hc_ensure_mm(hc_ctx *c, size_t rows) {
-    const size_t had = c->ws_mm_rows;
-    const int rc = hc_ensure(c, c->ws_mm, c->ws_mm_rows, rows, HC_N * sizeof(u64));
-    if (c->ws_mm_rows != had) c->hoist_cx = nullptr;        // the old block is gone, and the decomposition it held with it
-    return rc;
+// ws_mm is handed out by two claims and by nothing else: this one (Rescale at level 2 and above, hc_lv_mod_raise) and the key switch's (hc_ks_claim). Its first words are where a
+// held decomposition's digits lie, so the hold ends before the caller has the pointer.
+static int hc_mm_claim(hc_ctx *c, size_t rows, u64 **t) {
+    hc_hoist_drop(c);
+    HC_TRY(hc_ensure(c, c->ws_mm, c->ws_mm_rows, rows, HC_N * sizeof(u64)));
+    *t = c->ws_mm;
+    return HC_OK;
 }
 
 extern "C" int hc_ntt(hc_ctx *c, int mod, const uint64_t *in, uint64_t *out, int count) {
@@ -575,7 +584,7 @@ extern "C" int hc_set_batch(hc_ctx *c, int n, size_t poly_stride_words, size_t q
     if (n < 1 || n > HC_MAXIMG) return hc_fail(c, HC_ERR_ARG, "hc_set_batch: n=%d outside 1..%d", n, HC_MAXIMG);
     if (n > 1 && (poly_stride_words < (size_t)HC_N || (c->np > 0 && qp_stride_words < (size_t)HC_N))) return hc_fail(c, HC_ERR_ARG, "hc_set_batch: strides must cover at least one row");
     const size_t ps = n > 1 ? poly_stride_words : 0, qs = n > 1 ? qp_stride_words : 0;                           // one image has no strides, whatever was passed
-    if (n != c->nb || ps != c->bs_poly || qs != c->bs_qp) c->hoist_cx = nullptr;                                 // a held decomposition belongs to the batch it was taken under
+    if (n != c->nb || ps != c->bs_poly || qs != c->bs_qp) hc_hoist_drop(c);                                 // a held decomposition belongs to the batch it was taken under
     c->nb = n; c->bs_poly = ps; c->bs_qp = qs;
     return HC_OK;
 }
@@ -774,8 +783,7 @@ extern "C" int hc_lv_lincomb2(hc_ctx *c, int level, int nterms, const uint64_t *
 extern "C" int hc_lv_mod_raise(hc_ctx *c, int level, const uint64_t *in_q0, uint64_t *out) {
     HC_ENTER(c); HC_TRY(hc_lv_check(c, "hc_lv_mod_raise", level, in_q0, out));
     if ((const void *)in_q0 == (const void *)out) return hc_fail(c, HC_ERR_ARG, "hc_lv_mod_raise: in and out must differ");
-    HC_TRY(hc_ensure_mm(c, (size_t)c->nb)); c->hoist_cx = nullptr;
-    u64 *t = c->ws_mm;                                                                  // one coefficient row per image
+    u64 *t; HC_TRY(hc_mm_claim(c, (size_t)c->nb, &t));                                    // one coefficient row per image
     HcInttCall mi; mi.rows = mi.nl = 1; mi.images = c->nb; mi.in = {in_q0, 0, c->bs_poly, HC_ROWS_USER}; mi.out = {t, 0, (size_t)HC_N, HC_ROWS_LIB8}; HC_TRY(hc_intt_mm(c, mi));
     HC_TRY(hc_launch(c, "mod_raise", hc_k_mod_raise, dim3(HC_GX_LV, (unsigned)(level + 1), (unsigned)c->nb), (const u64 *)t, (u64 *)out, (const HcMod *)c->d_mods, c->bs_poly));
     HcNttCall m; m.rows = m.nl = level + 1; m.images = c->nb; m.in = {out, 0, c->bs_poly, HC_ROWS_USER}; m.out = {out, 0, c->bs_poly, HC_ROWS_USER}; return hc_ntt_mm(c, m);
@@ -879,9 +887,7 @@ static int hc_div_round_last_n(hc_ctx *c, int level, const u64 *x, size_t xs, u6
         const HcTw *qlinv; HC_TRY(hc_rescale_plan(c, level, &qlinv));
         // np polynomials of each of the nb images per launch (blockIdx.z): x, x + xs and out, out + os (distances in words, modulo 2^64); images bs_poly apart
         const int nb = c->nb, nz = np * nb;
-        HC_TRY(hc_ensure_mm(c, (size_t)nz * (level + 1)));
-        c->hoist_cx = nullptr;                                   // the scratch is shared with the key switch's decomposition
-        u64 *t = c->ws_mm;                                         // t[z][N], z = polynomial + np * image
+        u64 *t; HC_TRY(hc_mm_claim(c, (size_t)nz * (level + 1), &t));     // t[z][N], z = polynomial + np * image
         // InvNTT of the last limb of every polynomial: the multi-modulus kernels over rows 0..level with rows below `level` skipped
         HcInttCall mi; mi.rows = mi.nl = level + 1; mi.skip_hi = mi.out_first_row = level; mi.nz = np; mi.images = nb; mi.in = {x, xs, c->bs_poly, HC_ROWS_USER}; mi.out = {t, (size_t)HC_N, (size_t)np * HC_N, HC_ROWS_LIB8}; mi.tag = "rescale"; HC_TRY(hc_intt_mm(c, mi));
         // the lift of t into every lower modulus happens where the forward transform reads its input, (x - NTT(lift)) / q_L where it writes its output: two launches,
@@ -1330,7 +1336,7 @@ static int hc_swk_generate_impl(hc_ctx *c, uint64_t key_id, int level, uint64_t 
     }
     const dim3 grid(64, (unsigned)nt, (unsigned)beta);
     HC_TRY(hc_launch(c, "swk_sample", hc_k_swk_sample, grid, k.rows, (const HcMod *)c->d_mods, G));
-    c->hoist_cx = nullptr;
+    hc_hoist_drop(c);
     // the e rows (component 0 of every digit), all limbs, in place; key rows are 8-byte words until hc_k_pack32_rows below
     HcNttCall m; m.rows = nt; m.nl = nl; m.nz = beta; m.in = {k.rows, (size_t)2 * nt * HC_N, 0, HC_ROWS_RAW}; m.out = {k.rows, (size_t)2 * nt * HC_N, 0, HC_ROWS_RAW}; HC_TRY(hc_ntt_mm(c, m));
     HC_TRY(hc_launch(c, "swk_finish", hc_k_swk_finish, grid, k.rows, (const u64 *)sk_ntt, (const HcMod *)c->d_mods, (const HcTw *)pm, G));
@@ -1395,11 +1401,24 @@ static int hc_ks_plan(hc_ctx *c, int level, const hc_ctx::KsPlan **out) {
 #define HC_MAC_NB 4                  // images per thread of the key switch's inner product at batches above 2 (hc_k_ks_mac_all)
 #endif
 struct HcKsScratch { u64 *digits, *acc, *pc, *ext, *yv; size_t digits_is, acc_is, pc_is, ext_is; };
-static int hc_ks_scratch(hc_ctx *c, int level, HcKsScratch *S) {
+// What a caller of the key switch's claim does with the digits section, which decides what becomes of a held decomposition BEFORE the caller can write a word:
+enum HcKsUse {
+    HC_KS_DECOMPOSE,     // rewrites the digits: the hold ends
+    HC_KS_HELD,          // only reads the held digits of (cx, level): refused without them, before the block is sized (hc_keyswitch_hoisted, hc_keyswitch_qp_rotate_many)
+    HC_KS_HELD_SIZED,    // the same, refused after the block is sized (hoisted != 0 of hc_keyswitch_rotate / _qp / _qp_rotate): a refused call at a level that makes the block grow ends a hold
+    HC_KS_TAIL           // uses acc / pc / ext / yv only (ModDown): the hold survives at the held level; the sections of another level overlap the held digits, and it ends
+};
+static int hc_ks_claim(hc_ctx *c, const char *fn, int level, const void *cx, HcKsUse use, HcKsScratch *S) {
+    if (use == HC_KS_DECOMPOSE || (use == HC_KS_TAIL && level != c->hoist_level)) hc_hoist_drop(c);
+    if (use == HC_KS_HELD) HC_TRY(hc_hoist_need(c, fn, cx, level));
     const int alpha = c->np, nl = level + 1, nt = nl + alpha, beta = (nl + alpha - 1) / alpha; const size_t nb = (size_t)c->nb;
     S->digits_is = (size_t)beta * nt * HC_N; S->acc_is = (size_t)2 * nt * HC_N; S->pc_is = (size_t)2 * (alpha + 2) * HC_N; S->ext_is = (size_t)2 * nl * HC_N;
     const size_t yv_rows = (size_t)(beta > 2 ? beta : 2) * (alpha + 1);                // y_i / v rows of the decomposition's digits, later of ModDown's two polynomials
-    HC_TRY(hc_ensure_mm(c, nb * ((size_t)beta * nt + 2 * nt + 2 * (alpha + 2) + 2 * nl + yv_rows)));
+    const size_t had = c->ws_mm_rows;
+    const int rc = hc_ensure(c, c->ws_mm, c->ws_mm_rows, nb * ((size_t)beta * nt + 2 * nt + 2 * (alpha + 2) + 2 * nl + yv_rows), HC_N * sizeof(u64));
+    if (c->ws_mm_rows != had) hc_hoist_drop(c);              // the old block is gone, and the decomposition it held with it
+    HC_TRY(rc);
+    if (use == HC_KS_HELD_SIZED) HC_TRY(hc_hoist_need(c, fn, cx, level));
     S->digits = c->ws_mm; S->acc = S->digits + nb * S->digits_is; S->pc = S->acc + nb * S->acc_is; S->ext = S->pc + nb * S->pc_is; S->yv = S->ext + nb * S->ext_is;
     return HC_OK;
 }
@@ -1485,35 +1504,32 @@ static int hc_ks_find(hc_ctx *c, const char *fn, uint64_t key_id, int level, con
     *key = &it->second;
     return HC_OK;
 }
+// How every key-switch entry point opens, in the order of its refusals: the key; the entry point's own verdict on its arguments (bad: what is wrong with them, null when
+// nothing is); the scratch; the digits of cx in it - held since hc_keyswitch_decompose, or decomposed now, the hold given up before the first of them is written
+static int hc_ks_begin(hc_ctx *c, const char *fn, uint64_t key_id, bool qp_operands, int level, const char *bad, const u64 *cx, HcKsUse use, const HcSwk **key, HcKsScratch *S) {
+    HC_TRY(hc_ks_find(c, fn, key_id, level, key, qp_operands));
+    if (bad) return hc_fail(c, HC_ERR_ARG, "%s: %s", fn, bad);
+    HC_TRY(hc_ks_claim(c, fn, level, cx, use, S));
+    return use == HC_KS_DECOMPOSE ? hc_ks_decompose_into(c, level, cx, *S) : HC_OK;
+}
 extern "C" int hc_keyswitch(hc_ctx *c, uint64_t key_id, int level, const uint64_t *cx, uint64_t *d0, uint64_t *d1) {
     HC_ENTER(c);
-    const HcSwk *key; HC_TRY(hc_ks_find(c, "hc_keyswitch", key_id, level, &key));
-    if (!cx || !d0 || !d1) return hc_fail(c, HC_ERR_ARG, "hc_keyswitch: null");
-    HcKsScratch S; HC_TRY(hc_ks_scratch(c, level, &S));
-    HC_TRY(hc_ks_decompose_into(c, level, cx, S));
-    c->hoist_cx = nullptr;                                   // the scratch no longer holds a hoisted decomposition
+    const HcSwk *key; HcKsScratch S; HC_TRY(hc_ks_begin(c, "hc_keyswitch", key_id, false, level, !cx || !d0 || !d1 ? "null" : nullptr, cx, HC_KS_DECOMPOSE, &key, &S));
     return hc_ks_apply_from(c, *key, level, cx, S, d0, d1);
 }
 // evaluator.Relinearize's tail in the key switch: out_k = a_k + (key switch of cx)_k, the addition inside ModDown's last pass. out may be a (element-wise in place).
 extern "C" int hc_keyswitch_add(hc_ctx *c, uint64_t key_id, int level, const uint64_t *cx, const uint64_t *a0, const uint64_t *a1, uint64_t *out0, uint64_t *out1) {
     HC_ENTER(c);
-    const HcSwk *key; HC_TRY(hc_ks_find(c, "hc_keyswitch_add", key_id, level, &key));
-    if (!cx || !a0 || !a1 || !out0 || !out1) return hc_fail(c, HC_ERR_ARG, "hc_keyswitch_add: null");
-    HcKsScratch S; HC_TRY(hc_ks_scratch(c, level, &S));
-    HC_TRY(hc_ks_decompose_into(c, level, cx, S));
-    c->hoist_cx = nullptr;
+    const HcSwk *key; HcKsScratch S; HC_TRY(hc_ks_begin(c, "hc_keyswitch_add", key_id, false, level, !cx || !a0 || !a1 || !out0 || !out1 ? "null" : nullptr, cx, HC_KS_DECOMPOSE, &key, &S));
     return hc_ks_apply_from(c, *key, level, cx, S, (u64 *)out0, (u64 *)out1, 0, nullptr, (const u64 *)a0, (const u64 *)a1);
 }
 // hc_keyswitch_add followed by one hc_div_round_last2, as one call: out_k = Rescale(a_k + (key switch of cx)_k) at level - 1 (level >= 2). ModDown and the rescale share
 // one forward transform per limb (hc_ks_moddown_rescale); the residues are those of the two calls. out may be a.
 extern "C" int hc_keyswitch_add_rescale(hc_ctx *c, uint64_t key_id, int level, const uint64_t *cx, const uint64_t *a0, const uint64_t *a1, uint64_t *out0, uint64_t *out1) {
     HC_ENTER(c);
-    const HcSwk *key; HC_TRY(hc_ks_find(c, "hc_keyswitch_add_rescale", key_id, level, &key));
-    if (!cx || !a0 || !a1 || !out0 || !out1) return hc_fail(c, HC_ERR_ARG, "hc_keyswitch_add_rescale: null");
-    if (level < 2) return hc_fail(c, HC_ERR_ARG, "hc_keyswitch_add_rescale: level %d: the fused rescale needs level >= 2 (use hc_keyswitch_add and hc_div_round_last2)", level);
-    HcKsScratch S; HC_TRY(hc_ks_scratch(c, level, &S));
-    HC_TRY(hc_ks_decompose_into(c, level, cx, S));
-    c->hoist_cx = nullptr;
+    char low[128]; const char *bad = !cx || !a0 || !a1 || !out0 || !out1 ? "null" : nullptr;
+    if (!bad && level < 2) { snprintf(low, sizeof low, "level %d: the fused rescale needs level >= 2 (use hc_keyswitch_add and hc_div_round_last2)", level); bad = low; }
+    const HcSwk *key; HcKsScratch S; HC_TRY(hc_ks_begin(c, "hc_keyswitch_add_rescale", key_id, false, level, bad, cx, HC_KS_DECOMPOSE, &key, &S));
     const hc_ctx::KsPlan *P; HC_TRY(hc_ks_plan(c, level, &P));
     HcMacPrep PR; PR.pinv = P->pinv; PR.add = (const u64 *)a0; PR.add_zs = (size_t)((const u64 *)a1 - (const u64 *)a0); PR.add_is = c->bs_poly;      // acc_L / P + add_L leaves the inner product (hc_ks_moddown_rescale's first step)
     HC_TRY(hc_ks_mac(c, *key, level, cx, S, S.acc, S.acc_is, &PR));
@@ -1521,34 +1537,28 @@ extern "C" int hc_keyswitch_add_rescale(hc_ctx *c, uint64_t key_id, int level, c
 }
 // Hoisted key switching (evaluator.RotateHoisted, conv.go:131; the baby steps of a linear transform): the decomposition of cx is
 // computed once and kept in the context; every hc_keyswitch_hoisted with the same (cx, level) then only does the inner product with
-// ITS key and the ModDown. Results are bit-identical to hc_keyswitch. hoist_cx / hoist_level name what ws_mm holds: a consumer given another pointer or another level
-// is refused with HC_ERR_STATE before anything is launched. What ends a held decomposition, i.e. clears hoist_cx (include/hconv.h above hc_keyswitch_decompose has the
-// same list; tests/abi_contract_cases.py runs every entry point between a decomposition and each consumer - MUST_REFUSE / MUST_SURVIVE - so a new user of ws_mm that
-// forgets the clear, or a new entry point nobody placed, fails there):
-//   - the calls that decompose by themselves: hc_keyswitch, hc_keyswitch_add, hc_keyswitch_add_rescale, hc_keyswitch_decompose (any polynomial: it is held instead),
-//     hc_keyswitch_rotate / hc_keyswitch_qp / hc_keyswitch_qp_rotate with hoisted = 0;
-//   - the other users of ws_mm: Rescale at level 2 and above (hc_div_round_last_n), hc_lv_mod_raise, hc_mod_down2 / hc_mod_down2_add_rescale at ANOTHER level (pc / ext of
-//     another level overlap the digits), and whatever makes ws_mm grow (hc_ensure_mm: the block the digits lay in is gone);
-//   - out of caution, though they do not touch ws_mm: hc_swk_generate(_splitmix), the encoders with to_ntt != 0, hc_encrypt_sk, hc_decrypt_decode_coeffs / _slots;
-//   - hc_set_batch to another setting (the scratch is laid out per image), option pack32, hc_free of the block cx lies in (its address may come back with other contents).
-// What does not: the consumers in any order and number, ModDown at the held level, Rescale at level 1 (loop A's path), every call whose only scratch is the transforms'
-// seam ws_tmp (hc_lv_ntt / hc_lv_intt, hc_decode_coeffs, hc_decrypt_decode_lv) or none at all (pointwise, permutations, extended-basis arithmetic, one-row primitives, copies,
-// other blocks' hc_malloc / hc_free, hc_swk_load, the other options, the level-0 / 1 convolution path). The caller overwriting cx is the one thing the library cannot see.
+// ITS key and the ModDown. Results are bit-identical to hc_keyswitch. The digits lie at the start of ws_mm and the context names their polynomial and level (hc_hoist_hold);
+// a consumer given another pointer or another level is refused with HC_ERR_STATE before anything is launched (hc_hoist_need). The rule that keeps the name true: ws_mm is
+// reached through a claim only, and the claim settles the hold before its caller has the pointer -
+//   - hc_mm_claim (Rescale at level 2 and above, hc_lv_mod_raise): the hold ends;
+//   - hc_ks_claim by what the caller says it will do (HcKsUse): rewrite the digits - every call that decomposes by itself, this one included - ends it; read them needs
+//     it; ModDown's sections alone (hc_mod_down2 / hc_mod_down2_add_rescale) leave it at the held level and end it at another; a block that had to grow ends it.
+// A hold also ends (hc_hoist_drop at the site of the reason) with hc_set_batch to another setting (the scratch is laid out per image), option pack32, hc_free of the block cx
+// lies in (its address may come back with other contents) and, out of caution though they do not touch ws_mm, with hc_swk_generate(_splitmix), the encoders with to_ntt != 0,
+// hc_encrypt_sk and hc_decrypt_decode_coeffs / _slots. Nothing else ends one: include/hconv.h above hc_keyswitch_decompose lists both sides by entry point for the caller,
+// and tests/abi_contract_cases.py runs every entry point between a decomposition and each consumer. The caller overwriting cx is the one thing the library cannot see.
 extern "C" int hc_keyswitch_decompose(hc_ctx *c, int level, const uint64_t *cx) {
     HC_ENTER(c);
     if (!cx || level < 0 || level >= c->nq || c->np < 1) return hc_fail(c, HC_ERR_ARG, "hc_keyswitch_decompose: bad arguments");
     HC_TRY(hc_batch_fits(c, "hc_keyswitch_decompose", level, false));
-    HcKsScratch S; HC_TRY(hc_ks_scratch(c, level, &S));
+    HcKsScratch S; HC_TRY(hc_ks_claim(c, "hc_keyswitch_decompose", level, cx, HC_KS_DECOMPOSE, &S));
     HC_TRY(hc_ks_decompose_into(c, level, cx, S));
-    c->hoist_cx = cx; c->hoist_level = level;
+    hc_hoist_hold(c, cx, level);                             // only now: a decomposition that failed half way leaves nothing held
     return HC_OK;
 }
 extern "C" int hc_keyswitch_hoisted(hc_ctx *c, uint64_t key_id, int level, const uint64_t *cx, uint64_t *d0, uint64_t *d1) {
     HC_ENTER(c);
-    const HcSwk *key; HC_TRY(hc_ks_find(c, "hc_keyswitch_hoisted", key_id, level, &key));
-    if (!cx || !d0 || !d1) return hc_fail(c, HC_ERR_ARG, "hc_keyswitch_hoisted: null");
-    if (c->hoist_cx != cx || c->hoist_level != level) return hc_fail(c, HC_ERR_STATE, "hc_keyswitch_hoisted: no decomposition of this polynomial at level %d is held (call hc_keyswitch_decompose first)", level);
-    HcKsScratch S; HC_TRY(hc_ks_scratch(c, level, &S));
+    const HcSwk *key; HcKsScratch S; HC_TRY(hc_ks_begin(c, "hc_keyswitch_hoisted", key_id, false, level, !cx || !d0 || !d1 ? "null" : nullptr, cx, HC_KS_HELD, &key, &S));
     return hc_ks_apply_from(c, *key, level, cx, S, d0, d1);
 }
 
@@ -1557,15 +1567,8 @@ extern "C" int hc_keyswitch_hoisted(hc_ctx *c, uint64_t key_id, int level, const
 // context (evaluator.RotateHoisted). Outputs must not alias the inputs.
 extern "C" int hc_keyswitch_rotate(hc_ctx *c, uint64_t key_id, uint64_t galEl, int level, const uint64_t *c0, const uint64_t *c1, uint64_t *out0, uint64_t *out1, int hoisted) {
     HC_ENTER(c);
-    const HcSwk *key; HC_TRY(hc_ks_find(c, "hc_keyswitch_rotate", key_id, level, &key));
-    if (!c0 || !c1 || !out0 || !out1 || out0 == c0 || out0 == c1 || out1 == c1 || out1 == c0 || !(galEl & 1)) return hc_fail(c, HC_ERR_ARG, "hc_keyswitch_rotate: bad arguments (outputs must differ from inputs, galEl odd)");
-    HcKsScratch S; HC_TRY(hc_ks_scratch(c, level, &S));
-    if (hoisted) {
-        if (c->hoist_cx != c1 || c->hoist_level != level) return hc_fail(c, HC_ERR_STATE, "hc_keyswitch_rotate: no decomposition of this polynomial at level %d is held (call hc_keyswitch_decompose first)", level);
-    } else {
-        HC_TRY(hc_ks_decompose_into(c, level, c1, S));
-        c->hoist_cx = nullptr;
-    }
+    const char *bad = !c0 || !c1 || !out0 || !out1 || out0 == c0 || out0 == c1 || out1 == c1 || out1 == c0 || !(galEl & 1) ? "bad arguments (outputs must differ from inputs, galEl odd)" : nullptr;
+    const HcSwk *key; HcKsScratch S; HC_TRY(hc_ks_begin(c, "hc_keyswitch_rotate", key_id, false, level, bad, c1, hoisted ? HC_KS_HELD_SIZED : HC_KS_DECOMPOSE, &key, &S));
     return hc_ks_apply_from(c, *key, level, c1, S, out0, out1, galEl, c0);
 }
 
@@ -1575,15 +1578,7 @@ extern "C" int hc_keyswitch_rotate(hc_ctx *c, uint64_t key_id, uint64_t galEl, i
 // hc_keyswitch_decompose(level, cx) left in the context): acc[2][level+1+np][N], rows Q_0..Q_level then P_0..P_(np-1), canonical, NTT.
 extern "C" int hc_keyswitch_qp(hc_ctx *c, uint64_t key_id, int level, const uint64_t *cx, uint64_t *acc, int hoisted) {
     HC_ENTER(c);
-    const HcSwk *key; HC_TRY(hc_ks_find(c, "hc_keyswitch_qp", key_id, level, &key, true));
-    if (!cx || !acc) return hc_fail(c, HC_ERR_ARG, "hc_keyswitch_qp: null");
-    HcKsScratch S; HC_TRY(hc_ks_scratch(c, level, &S));
-    if (hoisted) {
-        if (c->hoist_cx != cx || c->hoist_level != level) return hc_fail(c, HC_ERR_STATE, "hc_keyswitch_qp: no decomposition of this polynomial at level %d is held (call hc_keyswitch_decompose first)", level);
-    } else {
-        HC_TRY(hc_ks_decompose_into(c, level, cx, S));
-        c->hoist_cx = nullptr;
-    }
+    const HcSwk *key; HcKsScratch S; HC_TRY(hc_ks_begin(c, "hc_keyswitch_qp", key_id, true, level, !cx || !acc ? "null" : nullptr, cx, hoisted ? HC_KS_HELD_SIZED : HC_KS_DECOMPOSE, &key, &S));
     return hc_ks_mac(c, *key, level, cx, S, (u64 *)acc, c->bs_qp);
 }
 // One rotation of MultiplyByDiagMatrixBSGS kept in the extended basis: hc_keyswitch_qp of cx with the key of galEl, + pc0 (P * c0; may be null) on the Q rows of the first
@@ -1591,15 +1586,7 @@ extern "C" int hc_keyswitch_qp(hc_ctx *c, uint64_t key_id, int level, const uint
 // one pass applies the rest. The same residues as hc_keyswitch_qp + hc_lv_add + hc_qp_permute2 (+ hc_qp_op2 ADD).
 extern "C" int hc_keyswitch_qp_rotate(hc_ctx *c, uint64_t key_id, uint64_t galEl, int level, const uint64_t *pc0, const uint64_t *cx, uint64_t *out, int hoisted, int accumulate) {
     HC_ENTER(c);
-    const HcSwk *key; HC_TRY(hc_ks_find(c, "hc_keyswitch_qp_rotate", key_id, level, &key, true));
-    if (!cx || !out || !(galEl & 1)) return hc_fail(c, HC_ERR_ARG, "hc_keyswitch_qp_rotate: bad arguments (galEl odd)");
-    HcKsScratch S; HC_TRY(hc_ks_scratch(c, level, &S));
-    if (hoisted) {
-        if (c->hoist_cx != cx || c->hoist_level != level) return hc_fail(c, HC_ERR_STATE, "hc_keyswitch_qp_rotate: no decomposition of this polynomial at level %d is held (call hc_keyswitch_decompose first)", level);
-    } else {
-        HC_TRY(hc_ks_decompose_into(c, level, cx, S));
-        c->hoist_cx = nullptr;
-    }
+    const HcSwk *key; HcKsScratch S; HC_TRY(hc_ks_begin(c, "hc_keyswitch_qp_rotate", key_id, true, level, !cx || !out || !(galEl & 1) ? "bad arguments (galEl odd)" : nullptr, cx, hoisted ? HC_KS_HELD_SIZED : HC_KS_DECOMPOSE, &key, &S));
     HC_TRY(hc_ks_mac(c, *key, level, cx, S, S.acc, S.acc_is));
     const int nl = level + 1, nt = nl + c->np;
     return hc_launch(c, "qp_rotate_finish", hc_k_qp_rotate_finish, dim3(HC_GX_ROT, (unsigned)nt, 2u * (unsigned)c->nb), (const u64 *)S.acc, S.acc_is, (const u64 *)pc0, c->bs_poly, (u64 *)out, c->bs_qp, (const HcMod *)c->d_mods, nl, c->nq, nt, (u32)(galEl & 0x1FFFF), accumulate ? 1 : 0);
@@ -1610,18 +1597,11 @@ extern "C" int hc_keyswitch_qp_rotate(hc_ctx *c, uint64_t key_id, uint64_t galEl
 extern "C" int hc_keyswitch_qp_rotate_many(hc_ctx *c, int nrot, const uint64_t *key_ids, const uint64_t *galEls, int level, const uint64_t *pc0, const uint64_t *cx, uint64_t *const *outs) {
     HC_ENTER(c);
     if (nrot < 1 || !key_ids || !galEls || !cx || !outs) return hc_fail(c, HC_ERR_ARG, "hc_keyswitch_qp_rotate_many: bad arguments");
-    if (c->hoist_cx != cx || c->hoist_level != level) return hc_fail(c, HC_ERR_STATE, "hc_keyswitch_qp_rotate_many: no decomposition of this polynomial at level %d is held (call hc_keyswitch_decompose first)", level);
-    HcKsScratch S; HC_TRY(hc_ks_scratch(c, level, &S));
+    HcKsScratch S; HC_TRY(hc_ks_claim(c, "hc_keyswitch_qp_rotate_many", level, cx, HC_KS_HELD, &S));            // the keys are looked up below, one per rotation: the prologue without its first two steps
     const int alpha = c->np, nl = level + 1, nt = nl + alpha, nb = c->nb;
     const int NB = nb <= 1 ? 1 : nb <= 2 ? 2 : nb <= 4 ? 4 : 8, R = NB == 8 ? 2 : NB == 4 ? 4 : 8;
     const size_t acc_is = (size_t)2 * nt * HC_N, acc_rs = acc_is * (size_t)nb;
-    if (c->ws_accm_rows < (size_t)R * nb * 2 * nt) {
-        HC_HIP(c, hipStreamSynchronize(c->stream));
-        if (c->ws_accm) HC_HIP(c, hcx_free(c, c->ws_accm));
-        c->ws_accm = nullptr; c->ws_accm_rows = 0;
-        HC_HIP(c, hcx_malloc(c, (void **)&c->ws_accm, (size_t)R * nb * 2 * nt * HC_N * sizeof(u64)));
-        c->ws_accm_rows = (size_t)R * nb * 2 * nt;
-    }
+    HC_TRY(hc_ensure(c, c->ws_accm, c->ws_accm_rows, (size_t)R * nb * 2 * nt, HC_N * sizeof(u64)));
     std::vector<const HcSwk *> keys((size_t)nrot);                           // every rotation is checked before the first launch: an error leaves nothing half done
     for (int r = 0; r < nrot; r++) {
         HC_TRY(hc_ks_find(c, "hc_keyswitch_qp_rotate_many", key_ids[r], level, &keys[(size_t)r], true));
@@ -1651,15 +1631,19 @@ extern "C" int hc_keyswitch_qp_rotate_many(hc_ctx *c, int nrot, const uint64_t *
     }
     return HC_OK;
 }
+// the level of an extended-basis operand: min_level..nq-1, and special primes to extend by
+static int hc_qp_check(hc_ctx *c, const char *fn, int level, int min_level) {
+    if (level < min_level || level >= c->nq || c->np < 1) return hc_fail(c, HC_ERR_ARG, "%s: level %d outside %d..%d or no special primes", fn, level, min_level, c->nq - 1);
+    return HC_OK;
+}
 // hc_mod_down2 = ring.(*FastBasisExtender).ModDownSplitNTTPQ on the two polynomials x[2][level+1+np][N] -> out0, out1 [level+1][N]. A hoisted
 // decomposition held by the context survives it when it was taken at this same level (any other level drops it).
 extern "C" int hc_mod_down2(hc_ctx *c, int level, const uint64_t *x, uint64_t *out0, uint64_t *out1) {
     HC_ENTER(c);
-    if (level < 0 || level >= c->nq || c->np < 1) return hc_fail(c, HC_ERR_ARG, "hc_mod_down2: level %d outside 0..%d or no special primes", level, c->nq - 1);
+    HC_TRY(hc_qp_check(c, "hc_mod_down2", level, 0));
     if (!x || !out0 || !out1) return hc_fail(c, HC_ERR_ARG, "hc_mod_down2: null");
     HC_TRY(hc_batch_fits(c, "hc_mod_down2", level, true));
-    HcKsScratch S; HC_TRY(hc_ks_scratch(c, level, &S));
-    if (level != c->hoist_level) c->hoist_cx = nullptr;      // the scratch layout depends on the level: pc / ext of another level overlap the held digits
+    HcKsScratch S; HC_TRY(hc_ks_claim(c, "hc_mod_down2", level, nullptr, HC_KS_TAIL, &S));
     return hc_ks_moddown(c, level, (const u64 *)x, c->bs_qp, S, (u64 *)out0, (u64 *)out1, 0, nullptr);
 }
 // hc_mod_down2 followed by + a_k and ONE hc_div_round_last2, as one call (the end of a linear transform: ModDown of the accumulators, the other terms, Rescale's first drop):
@@ -1667,18 +1651,17 @@ extern "C" int hc_mod_down2(hc_ctx *c, int level, const uint64_t *x, uint64_t *o
 // residues of the three calls. Row `level` of both components of x is overwritten.
 extern "C" int hc_mod_down2_add_rescale(hc_ctx *c, int level, uint64_t *x, const uint64_t *a0, const uint64_t *a1, uint64_t *out0, uint64_t *out1) {
     HC_ENTER(c);
-    if (level < 2 || level >= c->nq || c->np < 1) return hc_fail(c, HC_ERR_ARG, "hc_mod_down2_add_rescale: level %d outside 2..%d or no special primes", level, c->nq - 1);
+    HC_TRY(hc_qp_check(c, "hc_mod_down2_add_rescale", level, 2));
     if (!x || !out0 || !out1 || (a0 == nullptr) != (a1 == nullptr)) return hc_fail(c, HC_ERR_ARG, "hc_mod_down2_add_rescale: null (the addends come as a pair)");
     HC_TRY(hc_batch_fits(c, "hc_mod_down2_add_rescale", level, true));
-    HcKsScratch S; HC_TRY(hc_ks_scratch(c, level, &S));
-    if (level != c->hoist_level) c->hoist_cx = nullptr;
+    HcKsScratch S; HC_TRY(hc_ks_claim(c, "hc_mod_down2_add_rescale", level, nullptr, HC_KS_TAIL, &S));
     return hc_ks_moddown_rescale(c, level, (u64 *)x, c->bs_qp, S, (u64 *)out0, (u64 *)out1, (const u64 *)a0, (const u64 *)a1);
 }
 // hc_qp_op2: out_k = a_k (op) b_k, k = 0, 1, over the level+1+np rows of the extended basis (op: HC_LV_MUL, HC_LV_ADD, HC_LV_MUL_ACC; b1 == b0
 // for a plaintext operand; products of two NTT residues as hc_lv_mul)
 extern "C" int hc_qp_op2(hc_ctx *c, int op, int level, const uint64_t *a0, const uint64_t *a1, const uint64_t *b0, const uint64_t *b1, uint64_t *out0, uint64_t *out1) {
     HC_ENTER(c);
-    if (level < 0 || level >= c->nq || c->np < 1) return hc_fail(c, HC_ERR_ARG, "hc_qp_op2: level %d outside 0..%d or no special primes", level, c->nq - 1);
+    HC_TRY(hc_qp_check(c, "hc_qp_op2", level, 0));
     const bool plain = op == HC_LV_MUL_PLAIN || op == HC_LV_MUL_ACC_PLAIN;
     if (plain) { if (b1 && b1 != b0) return hc_fail(c, HC_ERR_ARG, "hc_qp_op2: a plaintext operand is ONE polynomial over the extended basis (b1 must be null or b0)"); b1 = b0; op = op == HC_LV_MUL_PLAIN ? HC_LV_MUL : HC_LV_MUL_ACC; }
     else if ((op == HC_LV_MUL || op == HC_LV_MUL_ACC) && c->nb > 1 && b0 && b0 == b1)      // the legacy form of a shared plaintext (hc_lv_pw2)
@@ -1701,7 +1684,7 @@ extern "C" int hc_qp_op2(hc_ctx *c, int op, int level, const uint64_t *a0, const
 // hc_qp_mul_sum: out (+)= sum_t a_t (*) pt_t over the extended basis - the diagonal sum of a giant step in one launch (hc_k_qp_mul_sum)
 extern "C" int hc_qp_mul_sum(hc_ctx *c, int level, int nterms, const uint64_t *const *a, const uint64_t *const *pt, uint64_t *out, int accumulate) {
     HC_ENTER(c);
-    if (level < 0 || level >= c->nq || c->np < 1) return hc_fail(c, HC_ERR_ARG, "hc_qp_mul_sum: level %d outside 0..%d or no special primes", level, c->nq - 1);
+    HC_TRY(hc_qp_check(c, "hc_qp_mul_sum", level, 0));
     if (!a || !pt || !out || nterms < 1 || nterms > HC_MAXTERMS) return hc_fail(c, HC_ERR_ARG, "hc_qp_mul_sum: bad arguments (1 <= nterms <= %d)", HC_MAXTERMS);
     HC_TRY(hc_batch_fits(c, "hc_qp_mul_sum", level, true));
     HcTermPtrs P; memset(&P, 0, sizeof P);
@@ -1713,7 +1696,7 @@ extern "C" int hc_qp_mul_sum(hc_ctx *c, int level, int nterms, const uint64_t *c
 // several giant steps' sums from one pass over the rotations: out[h] (+)= sum_t a[t] (*) pt[h * nterms + t], h < ngiant <= 4; a diagonal pointer may be NULL (giant step h has
 // no diagonal for baby step t; every t has at least one). The residues of ngiant hc_qp_mul_sum calls.
 static int hc_qp_mul_sum_g(hc_ctx *c, const char *fn, int level, int nterms, int ngiant, const uint64_t *const *a, const uint64_t *const *pt, uint64_t *const *out, const int *accumulate) {
-    if (level < 0 || level >= c->nq || c->np < 1) return hc_fail(c, HC_ERR_ARG, "%s: level %d outside 0..%d or no special primes", fn, level, c->nq - 1);
+    HC_TRY(hc_qp_check(c, fn, level, 0));
     if (!a || !pt || !out || !accumulate || ngiant < 1 || ngiant > HC_MAXGIANT || nterms < 1 || nterms > HC_MAXTERMS) return hc_fail(c, HC_ERR_ARG, "%s: bad arguments (1 <= nterms <= %d, 1 <= giant steps <= %d)", fn, HC_MAXTERMS, HC_MAXGIANT);
     HC_TRY(hc_batch_fits(c, fn, level, true));
     HcTermPtrsG P; memset(&P, 0, sizeof P);
@@ -1920,7 +1903,7 @@ static int hc_encode_slots_impl(hc_ctx *c, const char *fn, double *values, int c
     if (log_slots > 0) HC_TRY(hc_launch(c, "sfft_inv_b", hc_k_sfft_inv_b, dim3((unsigned)((total + 2047) / 2048)), (const HcCplx *)v, v, E, total, log_slots > 11 ? 8 : log_slots));
     HC_TRY(hc_launch(c, "slots_round", hc_k_slots_round, dim3(64, (unsigned)count), (const HcCplx *)v, (u64 *)out, (const HcMod *)c->d_mods, nl, np, c->nq, log_slots, scale));
     if (!to_ntt) return HC_OK;
-    c->hoist_cx = nullptr;
+    hc_hoist_drop(c);
     HcNttCall m; m.rows = nt; m.nl = nl; m.nz = count; m.in = {out, (size_t)nt * HC_N, 0, HC_ROWS_USER}; m.out = {out, (size_t)nt * HC_N, 0, HC_ROWS_USER};       // row nl + j: special prime j
     HC_TRY(hc_ntt_mm(c, m));
     return HC_OK;
@@ -1948,7 +1931,7 @@ extern "C" int hc_encode_coeffs(hc_ctx *c, const double *values, int count, int 
     HC_HIP(c, hipStreamSynchronize(c->stream));
     if (flag) return hc_fail(c, HC_ERR_UNSUPPORTED, "hc_encode_coeffs: a value times the scale exceeds 2^64 or is not finite (scaleUpVecExact's big-float branch is not built)");
     HcNttCall m; m.rows = m.nl = level + 1; m.nz = count; m.in = {out, (size_t)(level + 1) * HC_N, 0, HC_ROWS_USER}; m.out = {out, (size_t)(level + 1) * HC_N, 0, HC_ROWS_USER};
-    if (to_ntt) { c->hoist_cx = nullptr; HC_TRY(hc_ntt_mm(c, m)); }
+    if (to_ntt) { hc_hoist_drop(c); HC_TRY(hc_ntt_mm(c, m)); }
     return HC_OK;
 }
 // Harness-side sk-encryption (include/hconv.h): per chunk of at most HC_MAXCTS images one launch forms e + m for all limbs, one batched transform takes it to the NTT
@@ -1964,7 +1947,7 @@ extern "C" int hc_encrypt_sk(hc_ctx *c, int count, int level, const uint64_t *pt
     HcScratch S(c);
     const int chunk = count < HC_MAXCTS ? count : HC_MAXCTS;
     u64 *t = nullptr; HC_HIP(c, S.alloc(&t, (size_t)chunk * nl * HC_N * sizeof(u64)));
-    c->hoist_cx = nullptr;
+    hc_hoist_drop(c);
     for (int z0 = 0; z0 < count; z0 += chunk) {
         const int n = count - z0 < chunk ? count - z0 : chunk;
         HcCtPtrs O; memset(&O, 0, sizeof O); for (int z = 0; z < n; z++) O.p[z] = (u64 *)ct_out[z0 + z];
@@ -1991,7 +1974,7 @@ static int hc_decrypt_decode_coeffs_impl(hc_ctx *c, int count, int level, const 
     HcScratch S(c);
     const int chunk = count < HC_MAXCTS ? count : HC_MAXCTS;
     u64 *t = nullptr; HC_HIP(c, S.alloc(&t, (size_t)chunk * nl * HC_N * sizeof(u64)));
-    c->hoist_cx = nullptr;
+    hc_hoist_drop(c);
     for (int z0 = 0; z0 < count; z0 += chunk) {
         const int n = count - z0 < chunk ? count - z0 : chunk;
         HcCtPtrs I; memset(&I, 0, sizeof I); for (int z = 0; z < n; z++) I.p[z] = (u64 *)ct[z0 + z];
@@ -2177,7 +2160,7 @@ extern "C" int hc_set_option(hc_ctx *c, const char *name, long value) {
         if (value < 0 || value > 2) return hc_fail(c, HC_ERR_ARG, "pack32 must be 0, 1 or 2");
         if (((value == 0) != (c->pack32 == 0)) && !c->swk.empty()) return hc_fail(c, HC_ERR_STATE, "pack32: switching keys are already stored in the other form");
         HC_ENTER(c); HC_HIP(c, hipStreamSynchronize(c->stream));
-        c->pack32 = (int)value; c->hoist_cx = nullptr;
+        c->pack32 = (int)value; hc_hoist_drop(c);
         std::vector<HcMod> hm; for (auto &mh : c->mods) { mh.m.row32 = hc_row32(c->pack32, mh.m.q, hm.size(), c->mods.size()); hm.push_back(mh.m); }
         HC_HIP(c, hcx_h2d(c, c->d_mods, hm.data(), hm.size() * sizeof(HcMod)));
         return hc_upload_rowmods(c);
