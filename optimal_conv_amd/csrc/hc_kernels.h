@@ -366,6 +366,22 @@ __device__ __forceinline__ T hc_const_copy(const T *p) {
 // the twiddle of a slot: A = the round on the high bits (16 consecutive entries), B = the round on the low bits (per thread: entries 16 apart)
 template <bool KC, class TW> struct HcTwA { const TW *p; __device__ __forceinline__ TW operator()(int slot) const { if (KC) return HC_TW_LOADK(TW, p, slot); else return HC_TW_LOAD(TW, p, slot); } };
 template <bool KC, class TW> struct HcTwB { const TW *p; __device__ __forceinline__ TW operator()(int slot) const { if (KC) return HC_TW_LOADK(TW, p, slot * 16); else return HC_TW_LOAD(TW, p, slot * 16); } };
+// ---- the A group of a rows pass staged through LDS. The 16 lanes of a row all want the same 16 rowsA entries: as global loads that is 15 vector-memory instructions per thread
+// for bytes ONE coalesced load per thread brings - thread t = (rloc, tid) loads entry HC_TILE * 256 + t = slot tid of its own row (hc_twl_load), writes it into the row's image
+// in LDS (hc_twl_put) and the round reads its twiddles back as ds_read_b128 broadcasts (HcTwL): no vector-memory instruction, no 64-bit address arithmetic, no place in the vmcnt
+// queue of the operand loads. The image lives in the row's own 2 KiB slice of the rows tile while the exchanges do not use it - in front of the first exchange of a forward pass,
+// behind the last read-back of an inverse pass (the entry waits in 4 VGPRs until then) - so the kernels keep their 32 KiB and their workgroups per CU. Only the 16 lanes of the row
+// write and read a row's image: row-local syncs on both sides of the write (hc_twl_put) and one more by the caller between the round that reads the image and the next write to the
+// tile. Odd rows sit 64 bytes further on: the two rows a ds_read_b128 lane group spans then read different banks. Same tables, same values: results are bit-identical.
+struct HcTwL { const HcTw *p; __device__ __forceinline__ HcTw operator()(int slot) const { return p[slot]; } };
+__device__ __forceinline__ HcTw hc_twl_load(const HcTwTab &T, int tile, int t) { return HC_TW_LOAD(HcTw, T.rowsA, tile * 256 + t); }
+__device__ __forceinline__ HcTwL hc_twl_put(u64 *lds, const HcTw &w, int rloc, int tid) {
+    HcTw *img = reinterpret_cast<HcTw *>(lds + rloc * 256 + (rloc & 1) * 8);
+    HC_ROW_SYNC();        // row-local: whatever the row's lanes read from the slice before
+    img[tid] = w;
+    HC_ROW_SYNC();
+    return HcTwL{img};
+}
 
 // ---------------------------------------------------------------- the exchange through LDS
 // Every tile element goes to word wa(i) and comes back from word ra(i); sync() between the two (HC_ROW_SYNC for the row-local exchanges, __syncthreads for the others).
@@ -467,15 +483,18 @@ __device__ __forceinline__ void hc_rows_fwd(const P &pol, u64 *lds, const HcTwTa
     for (int lo = 0; lo < 16; lo++) e[lo] = lds[hc_rows_lds(rloc, tid * 16 + lo)];
     hc_ct_round(pol, HcTwB<false, HcTw>{T.rowsB + row * 256 + tid}, e);
 }
+// wA: the thread's entry of a staged A group (HcTwL above; hc_k_b1), null: global loads (hc_k_rows_inv). ONE function for both on purpose: as hc_k_rows_inv's own helper, with hc_k_b1 on a
+// staged sibling, the compiler schedules hc_k_rows_inv differently (a function inlined into its only caller is not treated as one inlined into two).
 template <class P>
-__device__ __forceinline__ void hc_rows_inv(const P &pol, u64 *lds, const HcTwTab &T, int row, int rloc, int tid, u64 (&e)[16]) {
+__device__ __forceinline__ void hc_rows_inv(const P &pol, u64 *lds, const HcTwTab &T, int row, int rloc, int tid, u64 (&e)[16], const HcTw *wA = nullptr) {
     hc_gs_round(pol, HcTwB<false, HcTw>{T.rowsB + row * 256 + tid}, e);
 #pragma unroll
     for (int lo = 0; lo < 16; lo++) lds[hc_rows_lds(rloc, tid * 16 + lo)] = e[lo];
     HC_ROW_SYNC();
 #pragma unroll
     for (int hi = 0; hi < 16; hi++) e[hi] = lds[hc_rows_lds(rloc, hi * 16 + tid)];
-    hc_gs_round(pol, HcTwA<false, HcTw>{T.rowsA + row * 16}, e);
+    if (wA != nullptr) hc_gs_round(pol, hc_twl_put(lds, *wA, rloc, tid), e);
+    else hc_gs_round(pol, HcTwA<false, HcTw>{T.rowsA + row * 16}, e);
 }
 template <class P>
 __device__ __forceinline__ void hc_cols_fwd(const P &pol, u64 *lds, const HcTwTab &T, int c, int tid, u64 (&e)[16]) {
@@ -512,13 +531,41 @@ __device__ __forceinline__ void hc_rows_lo_to_lin(u64 *lds, int t, int rloc, int
 #pragma unroll
     for (int k = 0; k < 16; k++) e[k] = lds[hc_rows_lds(k, t)];
 }
+// The rows passes with the A group staged (HcTwL above), for the convolution's rows kernels: forward on one tile (exchange written out, as above; hc_k_b3p - through an optional
+// entry of hc_rows_fwd, as hc_rows_inv has one, hc_k_b3p spills 28 bytes) and forward and inverse on two (hc_xchg). wA: the thread's entry
+// of the image, loaded by the kernel in front of its operand loads (hc_twl_load). Forward: the image goes in first, the tile being idle until the exchange.
+template <class P>
+__device__ __forceinline__ void hc_rows_fwd_twl(const P &pol, u64 *lds, const HcTwTab &T, const HcTw &wA, int row, int rloc, int tid, u64 (&e)[16]) {
+    hc_ct_round(pol, hc_twl_put(lds, wA, rloc, tid), e);
+    HC_ROW_SYNC();        // the image has been read before the exchange lands on it
+#pragma unroll
+    for (int hi = 0; hi < 16; hi++) lds[hc_rows_lds(rloc, hi * 16 + tid)] = e[hi];
+    HC_ROW_SYNC();
+#pragma unroll
+    for (int lo = 0; lo < 16; lo++) e[lo] = lds[hc_rows_lds(rloc, tid * 16 + lo)];
+    hc_ct_round(pol, HcTwB<false, HcTw>{T.rowsB + row * 256 + tid}, e);
+}
+template <class P>
+__device__ __forceinline__ void hc_rows_fwd_twl(const P &pol, u64 *lds, const HcTwTab &T, const HcTw &wA, int row, int rloc, int tid, u64 (&e0)[16], u64 (&e1)[16]) {
+    hc_ct_round(pol, hc_twl_put(lds, wA, rloc, tid), e0, e1);
+    HC_ROW_SYNC();        // the image has been read before the exchange lands on it
+    hc_xchg(lds, [&](int hi) { return hc_rows_lds(rloc, hi * 16 + tid); }, [&](int lo) { return hc_rows_lds(rloc, tid * 16 + lo); }, [] { HC_ROW_SYNC(); }, e0, e1);
+    hc_ct_round(pol, HcTwB<false, HcTw>{T.rowsB + row * 256 + tid}, e0, e1);
+}
+// Inverse: the image goes in behind the exchange's read-back; nothing but the A round uses the tile after it.
+template <class P>
+__device__ __forceinline__ void hc_rows_inv_twl(const P &pol, u64 *lds, const HcTwTab &T, const HcTw &wA, int row, int rloc, int tid, u64 (&e0)[16], u64 (&e1)[16]) {
+    hc_gs_round(pol, HcTwB<false, HcTw>{T.rowsB + row * 256 + tid}, e0, e1);
+    hc_xchg(lds, [&](int lo) { return hc_rows_lds(rloc, tid * 16 + lo); }, [&](int hi) { return hc_rows_lds(rloc, hi * 16 + tid); }, [] { HC_ROW_SYNC(); }, e0, e1);
+    hc_gs_round(pol, hc_twl_put(lds, wA, rloc, tid), e0, e1);
+}
 // fp64 forms of the inverse cols pass (4-byte words) and of the inverse rows pass on two tiles (8-byte words)
 __device__ __forceinline__ void hc_cols_inv_f64(double (&e)[16], u32 *lds, const HcTwTab &T, int c, int tid, HcF64Mod m) {
     hc_gs_round_f64<false>(e, HcTwB<false, HcTw>{T.colsB + tid}, m, T.ninv, T.ninv);
     hc_xchg(lds, [&](int lo) { return hc_cols_lds<u32>(tid * 16 + lo, c); }, [&](int hi) { return hc_cols_lds<u32>(hi * 16 + tid, c); }, [] { __syncthreads(); }, e);
     hc_gs_round_f64<true>(e, HcTwA<false, HcTw>{T.colsA}, m, T.ninv, T.w_last_ninv);
 }
-__device__ __forceinline__ void hc_rows_inv2_f64(double (&f0)[16], double (&f1)[16], u64 *lds, const HcTwTab &T, int row, int rloc, int tid, HcF64Mod m) {
+__device__ __forceinline__ void hc_rows_inv2_f64(double (&f0)[16], double (&f1)[16], u64 *lds, const HcTwTab &T, const HcTw &wA, int row, int rloc, int tid, HcF64Mod m) {
     hc_gs_round2_f64(f0, f1, HcTwB<false, HcTw>{T.rowsB + row * 256 + tid}, m);
     u64 b0[16], b1[16];
 #pragma unroll
@@ -526,7 +573,7 @@ __device__ __forceinline__ void hc_rows_inv2_f64(double (&f0)[16], double (&f1)[
     hc_xchg(lds, [&](int lo) { return hc_rows_lds(rloc, tid * 16 + lo); }, [&](int hi) { return hc_rows_lds(rloc, hi * 16 + tid); }, [] { HC_ROW_SYNC(); }, b0, b1);
 #pragma unroll
     for (int i = 0; i < 16; i++) { f0[i] = hc_u2d(b0[i]); f1[i] = hc_u2d(b1[i]); }
-    hc_gs_round2_f64(f0, f1, HcTwA<false, HcTw>{T.rowsA + row * 16}, m);
+    hc_gs_round2_f64(f0, f1, hc_twl_put(lds, wA, rloc, tid), m);        // the A group through LDS (HcTwL), behind the last read-back
 }
 
 // x mod q for x < 2^64 with mu = floor(2^64/q): result canonical
@@ -912,15 +959,17 @@ struct HcLoopA {
 };
 // KA1: a_1 = c'_p[1] (*) k_i[1] and its rows-inverse (mod Q1) for BOTH polynomials of a channel (jobs 2c and 2c + 1 of tmp): grid = (jobs / 2, 16, batch). F64 = 1: Q1 < 2^49, the transform
 // runs in fp64 (T1inv = the fp64 table) and tmp carries doubles (bit patterns) to KA2. The kernel-plaintext tile
-// k_i[1] is loaded once and every T1inv twiddle once for the two transforms (hc_rows_inv on two tiles / hc_rows_inv2_f64); one LDS tile, used by the two polynomials in turn.
+// k_i[1] is loaded once and every T1inv twiddle once for the two transforms (hc_rows_inv_twl on two tiles / hc_rows_inv2_f64); one LDS tile, used by the two polynomials in turn.
+// The row's 16 rowsA twiddles come through LDS (HcTwL): one load per thread at kernel entry, the image in the tile behind the last read-back.
 template <int F64>
 __global__ __launch_bounds__(HC_TPB, HC_W_A1) void hc_k_a1p(HcLoopA A, HcTwTab T1inv) {
-    __shared__ u64 lds[HC_ROWS_LDS];
+    __shared__ __attribute__((aligned(16))) u64 lds[HC_ROWS_LDS];
     const int t = threadIdx.x, tid = t & 15, rloc = t >> 4, row = HC_TILE * 16 + rloc;
     const int ch = HC_JOB, i = A.i0 + ch * A.norm, z = blockIdx.z;
     const HcTw *__restrict__ c0 = A.ctc + ((size_t)z * 4 + 1) * 65536 + (size_t)HC_TILE * 4096 + t;          // c'_0[1] ; c'_1[1] is 2 * 65536 pairs on
     const u64 *__restrict__ k = A.ker.p[z] + ((size_t)i * 2 + 1) * 65536 + (size_t)HC_TILE * 4096 + t;
     const HcQ Q = hc_q(A.m1.q);
+    const HcTw wA = hc_twl_load(T1inv, HC_TILE, t);
     u64 e0[16], e1[16];
 #pragma unroll
     for (int kk = 0; kk < 16; kk++) {
@@ -937,11 +986,11 @@ __global__ __launch_bounds__(HC_TPB, HC_W_A1) void hc_k_a1p(HcLoopA A, HcTwTab T
         double f0[16], f1[16];
 #pragma unroll
         for (int kk = 0; kk < 16; kk++) { f0[kk] = hc_f64_reduce(hc_f64_from_u(e0[kk]), m.q, m.qinv); f1[kk] = hc_f64_reduce(hc_f64_from_u(e1[kk]), m.q, m.qinv); }   // 4*Q1 < 2^51: exact; |f| <= Q1/2
-        hc_rows_inv2_f64(f0, f1, lds, T1inv, row, rloc, tid, m);
+        hc_rows_inv2_f64(f0, f1, lds, T1inv, wA, row, rloc, tid, m);
 #pragma unroll
         for (int hi = 0; hi < 16; hi++) { o[hi * 16 + tid] = hc_d2u(f0[hi]); o[65536 + hi * 16 + tid] = hc_d2u(f1[hi]); }
     } else {
-        hc_rows_inv(HcLazy<>{Q}, lds, T1inv, row, rloc, tid, e0, e1);
+        hc_rows_inv_twl(HcLazy<>{Q}, lds, T1inv, wA, row, rloc, tid, e0, e1);
 #pragma unroll
         for (int hi = 0; hi < 16; hi++) { o[hi * 16 + tid] = e0[hi]; o[65536 + hi * 16 + tid] = e1[hi]; }
     }
@@ -985,10 +1034,11 @@ __global__ __launch_bounds__(HC_TPB, HC_W_A2) void hc_k_a2(HcLoopA A, HcTwTab T1
 }
 // KA3: rows-forward mod Q0, then out = (a_0 - u) * Q1^-1 with a_0 = c'_p[0] (*) k_i[0], for both polynomials of a channel per workgroup, grid = (jobs / 2, 16, batch): k_i[0] loaded once (held across the transform: 32 VGPRs), every T0fwd twiddle once
 // (hc_rows_fwd on two tiles). The two c'_p[0] tiles are loaded behind the transform in row batches, as hc_k_b5m's epilogue loads its operands: two a_0 tiles formed before the transform
-// (all loads up front, as the one-polynomial form of this kernel had them) would be 64 more registers across it.
+// (all loads up front, as the one-polynomial form of this kernel had them) would be 64 more registers across it. The row's 16 rowsA twiddles come through LDS (HcTwL): one load per
+// thread at kernel entry, the image in the tile ahead of the first exchange (hc_rows_fwd_twl).
 template <int FM>
 __global__ __launch_bounds__(HC_TPB, HC_W_A3) void hc_k_a3p(HcLoopA A, HcTwTab T0fwd) {
-    __shared__ u64 lds[HC_ROWS_LDS];
+    __shared__ __attribute__((aligned(16))) u64 lds[HC_ROWS_LDS];
     const int t = threadIdx.x, tid = t & 15, rloc = t >> 4, row = HC_TILE * 16 + rloc;
     const int ch = HC_JOB, i = A.i0 + ch * A.norm, z = blockIdx.z;
     const u64 *__restrict__ in = A.tmp + ((size_t)z * A.njobs + 2 * ch) * 65536 + (size_t)row * 256;
@@ -996,12 +1046,13 @@ __global__ __launch_bounds__(HC_TPB, HC_W_A3) void hc_k_a3p(HcLoopA A, HcTwTab T
     const u64 *__restrict__ k = A.ker.p[z] + ((size_t)i * 2) * 65536 + (size_t)HC_TILE * 4096 + t;
     u64 *__restrict__ o = A.cts + (size_t)z * A.cts_stride + (size_t)(A.slot0 + ch * A.slot_step) * 2 * 65536 + (size_t)HC_TILE * 4096 + t;
     const HcQ Q = hc_q(A.m0.q);
+    const HcTw wA = hc_twl_load(T0fwd, HC_TILE, t);
     u64 e0[16], e1[16], kv[16];
 #pragma unroll
     for (int hi = 0; hi < 16; hi++) { e0[hi] = in[hi * 16 + tid]; e1[hi] = in[65536 + hi * 16 + tid]; }
 #pragma unroll
     for (int kk = 0; kk < 16; kk++) kv[kk] = k[kk * 256];
-    hc_rows_fwd(HcLazy<FM>{Q}, lds, T0fwd, row, rloc, tid, e0, e1);
+    hc_rows_fwd_twl(HcLazy<FM>{Q}, lds, T0fwd, wA, row, rloc, tid, e0, e1);
     HC_ROW_SYNC();        // row-local: the reads before and the writes after stay inside the 16 lanes of a row
     hc_xchg(lds, [&](int lo) { return hc_rows_lds(rloc, tid * 16 + lo); }, [&](int kk) { return hc_rows_lds(kk, t); }, [] { __syncthreads(); }, e0, e1);
 #pragma unroll
@@ -1048,9 +1099,10 @@ struct HcLoopB {
     u32 gal;             // Galois element of this level
 };
 // KB1: t2.c1 = y1 - I*x1 (kept in tmpT for KB5) and its rows-inverse (mod Q0). grid = (batch*nodes, 16). Everything else a node needs
-// from x and y (t1, t2.c0, the Q-part of the key switch) is formed in KB5 from src and tmpT.
+// from x and y (t1, t2.c0, the Q-part of the key switch) is formed in KB5 from src and tmpT. The row's 16 rowsA twiddles come through LDS (HcTwL), the image in the tile behind the
+// last read-back (hc_rows_inv with a staged entry).
 __global__ __launch_bounds__(HC_TPB, HC_W_B1) void hc_k_b1(HcLoopB B, HcTwTab T0inv) {
-    __shared__ u64 lds[HC_ROWS_LDS];
+    __shared__ __attribute__((aligned(16))) u64 lds[HC_ROWS_LDS];
     const int t = threadIdx.x, tid = t & 15, rloc = t >> 4, row = HC_TILE * 16 + rloc;
     const int job = HC_JOB, z = job / B.nodes, node = job - z * B.nodes, i = (B.n0 + node) * B.norm;
     const size_t tile = (size_t)HC_TILE * 4096 + t;
@@ -1072,8 +1124,9 @@ __global__ __launch_bounds__(HC_TPB, HC_W_B1) void hc_k_b1(HcLoopB B, HcTwTab T0
         for (int kk = 0; kk < 16; kk++) tt[kk * 256] = e[kk];
     }
     hc_rows_lin_to_lo(lds, t, rloc, tid, e);
+    const HcTw wA = hc_twl_load(T0inv, HC_TILE, t);        // behind the first exchange: at kernel entry the entry's 4 VGPRs across the operand loads cost the fifth workgroup per CU
     HC_ROW_SYNC();        // row-local: the reads before and the writes after stay inside the 16 lanes of a row
-    hc_rows_inv(HcLazy<>{Q}, lds, T0inv, row, rloc, tid, e);
+    hc_rows_inv(HcLazy<>{Q}, lds, T0inv, row, rloc, tid, e, &wA);
     u64 *__restrict__ o = B.tmpC + (size_t)job * 65536 + (size_t)row * 256;
 #pragma unroll
     for (int hi = 0; hi < 16; hi++) o[hi * 16 + tid] = e[hi];
@@ -1096,20 +1149,24 @@ __global__ __launch_bounds__(HC_TPB, HC_W_B2) void hc_k_b2(HcLoopB B, HcTwTab T0
 #pragma unroll
     for (int lo = 0; lo < 16; lo++) base[(size_t)(tid * 16 + lo) * 256] = e[lo];
 }
-// KB3: rows-forward mod P, multiply by b_P and a_P, rows-inverse mod P of both in lock step, every TPinv twiddle loaded once (hc_rows_inv on two tiles). grid = (batch*nodes, 16)
+// KB3: rows-forward mod P, multiply by b_P and a_P, rows-inverse mod P of both in lock step, every TPinv twiddle loaded once (hc_rows_inv_twl on two tiles). grid = (batch*nodes, 16)
+// The rowsA twiddles of both transforms come through LDS (HcTwL): TPfwd's image in the tile ahead of the first exchange, TPinv's (its entry loaded behind the forward pass) behind the last read-back.
 template <int FMP>
 __global__ __launch_bounds__(HC_TPB, HC_W_B3) void hc_k_b3p(HcLoopB B, HcTwTab TPfwd, HcTwTab TPinv) {
-    __shared__ u64 lds[HC_ROWS_LDS];
+    __shared__ __attribute__((aligned(16))) u64 lds[HC_ROWS_LDS];
     const int t = threadIdx.x, tid = t & 15, rloc = t >> 4, row = HC_TILE * 16 + rloc;
     const int node = HC_JOB;
     const u64 *in = B.tmpC + (size_t)node * 65536 + (size_t)row * 256;
     const HcQ Q = hc_q(B.mp.q);
     u64 e0[16], e1[16];
+    HcTw wI;
     {
+        const HcTw wA = hc_twl_load(TPfwd, HC_TILE, t);
         u64 cp[16];
 #pragma unroll
         for (int hi = 0; hi < 16; hi++) cp[hi] = in[hi * 16 + tid];
-        hc_rows_fwd(HcLazy<FMP>{Q}, lds, TPfwd, row, rloc, tid, cp);
+        hc_rows_fwd_twl(HcLazy<FMP>{Q}, lds, TPfwd, wA, row, rloc, tid, cp);
+        wI = hc_twl_load(TPinv, HC_TILE, t);           // the second image's entry: behind the forward pass, so that it is not live across it
         const HcTw *__restrict__ ev = B.evkP + (size_t)HC_TILE * 4096 + t;                 // b_P rows ; a_P is 65536 pairs on
 #pragma unroll
         for (int lo = 0; lo < 16; lo++) {
@@ -1119,7 +1176,7 @@ __global__ __launch_bounds__(HC_TPB, HC_W_B3) void hc_k_b3p(HcLoopB B, HcTwTab T
         }
     }
     HC_ROW_SYNC();             // row-local (the forward pass's reads of this row, then the inverse pass's writes): hc_k_b3 has no workgroup barrier
-    hc_rows_inv(HcLazy<>{Q}, lds, TPinv, row, rloc, tid, e0, e1);
+    hc_rows_inv_twl(HcLazy<>{Q}, lds, TPinv, wI, row, rloc, tid, e0, e1);
     u64 *o = B.tmpE + (size_t)node * 2 * 65536 + (size_t)row * 256;
 #pragma unroll
     for (int hi = 0; hi < 16; hi++) { o[hi * 16 + tid] = e0[hi]; o[65536 + hi * 16 + tid] = e1[hi]; }
@@ -1242,6 +1299,7 @@ __global__ __launch_bounds__(HC_TPB, 3) void hc_k_b5(HcLoopB B, HcTwTab T0fwd, H
 // its shape follows the bytes a workgroup sends through the CU's address unit (profiles/b5m_request_stream_*.txt: 576 -> 352 KiB per workgroup, -37 % requests, -15 % time):
 //  * both rows-forward transforms run together on two register tiles and two LDS tiles (hc_rows_fwd2_lin): same 16 rows, same modulus, so every twiddle is loaded ONCE
 //    for both (64 KiB of per-thread twiddles instead of 128); 64 KiB of LDS, two workgroups per CU (the kernel measured the same at 2, 3 and 4), 126-159 VGPRs, no scratch;
+//    the row's 16 rowsA twiddles come through LDS (HcTwL): one load per thread at kernel entry, the image in tile l0 ahead of the first exchange;
 //  * the two fixed multiplicands (idx, the key's Q rows) are read as ONE 8-byte Montgomery word each (B.idxM, B.evkQM; hc_mont_lazy) instead of 16-byte Shoup pairs,
 //    ~12 more VALU instructions per product, and idx is read once for both polynomials;
 //  * one epilogue over the row batches does both polynomials, so t2.c1 lives for one batch and not across a transform.
@@ -1258,8 +1316,9 @@ __global__ __launch_bounds__(HC_TPB, 3) void hc_k_b5(HcLoopB B, HcTwTab T0fwd, H
 #endif
 // hc_rows_fwd on two polynomials (tiles l0, l1 of LDS), then hc_rows_lo_to_lin on both: out e_k[kk] = n_k at (row kk, column t)
 template <int FM>
-__device__ __forceinline__ void hc_rows_fwd2_lin(u64 (&e0)[16], u64 (&e1)[16], u64 *l0, u64 *l1, const HcTwTab &T, int row, int rloc, int tid, int t, const HcQ &Q) {
-    hc_ct_round(HcLazy<FM>{Q}, HcTwA<false, HcTw>{T.rowsA + row * 16}, e0, e1);
+__device__ __forceinline__ void hc_rows_fwd2_lin(u64 (&e0)[16], u64 (&e1)[16], u64 *l0, u64 *l1, const HcTwTab &T, const HcTw &wA, int row, int rloc, int tid, int t, const HcQ &Q) {
+    hc_ct_round(HcLazy<FM>{Q}, hc_twl_put(l0, wA, rloc, tid), e0, e1);       // the A group through LDS (HcTwL), its image in tile l0 ahead of the exchange
+    HC_ROW_SYNC();        // the image has been read before the exchange lands on it
 #pragma unroll
     for (int hi = 0; hi < 16; hi++) { const int a = hc_rows_lds(rloc, hi * 16 + tid); l0[a] = e0[hi]; l1[a] = e1[hi]; }
     HC_ROW_SYNC();
@@ -1275,7 +1334,7 @@ __device__ __forceinline__ void hc_rows_fwd2_lin(u64 (&e0)[16], u64 (&e1)[16], u
 }
 template <int FM>
 __global__ __launch_bounds__(HC_TPB, HC_B5M_WAVES) void hc_k_b5m(HcLoopB B, HcTwTab T0fwd, HcPtrs biases, HcPtrs outs) {
-    __shared__ u64 lds[2 * HC_ROWS_LDS];
+    __shared__ __attribute__((aligned(16))) u64 lds[2 * HC_ROWS_LDS];
     u64 *l0 = lds, *l1 = lds + HC_ROWS_LDS;
     const int t = threadIdx.x, tid = t & 15, rloc = t >> 4, row = HC_TILE * 16 + rloc;
     const int zn = HC_JOB, z = zn / B.nodes, node = zn - z * B.nodes, i = (B.n0 + node) * B.norm;
@@ -1288,13 +1347,14 @@ __global__ __launch_bounds__(HC_TPB, HC_B5M_WAVES) void hc_k_b5m(HcLoopB B, HcTw
     const u64 *__restrict__ evk = B.evkQM + tile;                                                                  // b_Q/P, then a_Q/P 65536 words on
     u64 *__restrict__ o = (outs.p[z] != nullptr ? const_cast<u64 *>(outs.p[z]) : B.dst + (size_t)z * B.dst_stride + (size_t)i * 2 * 65536) + tile;
     const u64 *__restrict__ bias = biases.p[z] != nullptr ? biases.p[z] + tile : nullptr;        // null except on the last node of the tree (eval.go:258)
+    const HcTw wA = hc_twl_load(T0fwd, HC_TILE, t);
     u64 e0[16], e1[16];
     {
         const u64 *__restrict__ in = B.tmpE + (size_t)zn * 2 * 65536 + (size_t)row * 256;
 #pragma unroll
         for (int hi = 0; hi < 16; hi++) { e0[hi] = in[hi * 16 + tid]; e1[hi] = in[65536 + hi * 16 + tid]; }
     }
-    hc_rows_fwd2_lin<FM>(e0, e1, l0, l1, T0fwd, row, rloc, tid, t, Q);
+    hc_rows_fwd2_lin<FM>(e0, e1, l0, l1, T0fwd, wA, row, rloc, tid, t, Q);
     __syncthreads();
 #pragma unroll
     for (int b = 0; b < 16; b += HC_B5_ROWS) {
