@@ -104,7 +104,7 @@ int hc_set_batch(hc_ctx *ctx, int n, size_t poly_stride_words, size_t qp_stride_
  * (eval.go:272-607): MulNew/MulRelin's tensor products, Add/Sub, MultByConst / MulByPow2, AddConst, and the bootstrapper's modUp. */
 /* Aliasing of the pointwise and transform calls below: out may be a, and out may be b (every coefficient is read before it is written, by the same thread):
  * hc_lv_mul / hc_lv_mul_plain / hc_lv_add / hc_lv_sub with out == a or out == b (hc_lv_add(a, t, t): a running sum), hc_lv_mul_const / hc_lv_add_const with out == a,
- * hc_lv_op2 with out_k == a_k (and out_k == b_k where b is per image: HC_LV_MUL, HC_LV_ADD, HC_LV_SUB), hc_lv_mul_acc with a == b (a square); hc_lv_ntt / hc_lv_intt with out == in (the transform goes
+ * hc_lv_op2 with out_k == a_k (and out_k == b_k where b is per image: HC_LV_MUL, HC_LV_ADD, HC_LV_SUB, HC_LV_MONOMIAL), hc_lv_mul_acc with a == b (a square); hc_lv_ntt / hc_lv_intt with out == in (the transform goes
  * through the context's seam). An operand that only PARTLY overlaps an output is never allowed. */
 int hc_lv_ntt(hc_ctx *ctx, int level, const uint64_t *in, uint64_t *out);
 int hc_lv_intt(hc_ctx *ctx, int level, const uint64_t *in, uint64_t *out);
@@ -120,7 +120,15 @@ int hc_lv_sub(hc_ctx *ctx, int level, const uint64_t *a, const uint64_t *b, uint
 /* the pointwise operations above on BOTH polynomials of a ciphertext in one launch (out_k = a_k op b_k, k = 0, 1; the polynomials may live
  * in separate allocations; HC_LV_MUL_CONST takes `consts` and ignores b; HC_LV_MUL_ACC accumulates into out; HC_LV_MUL_PLAIN / HC_LV_MUL_ACC_PLAIN: b0 is ONE plaintext that
  * multiplies both polynomials of every image, b1 must be NULL or b0) */
-enum { HC_LV_MUL = 0, HC_LV_ADD = 1, HC_LV_SUB = 2, HC_LV_MUL_CONST = 3, HC_LV_MUL_ACC = 7, HC_LV_MUL_PLAIN = 8, HC_LV_MUL_ACC_PLAIN = 9 };
+/* HC_LV_MONOMIAL (MultByi, DivByi, a monomial shift - with the neighbouring addition in the same pass, and without a plaintext):
+ *     out_k[l][j] = M_e1[l][j] * (a_k[l][j] + M_e0[l][j] * b_k[l][j]) mod q_l,  k = 0, 1, l = 0..level,  M_e = NTT_l(X^e), 0 <= e < 2N (X^N = -1: e = N + s is -X^s).
+ * consts is a HOST array of exactly two words {e0, e1}, whatever the level. b0 == b1 == NULL: out_k = M_e1 * a_k and e0 is ignored. b is per image (there is no shared form).
+ * The factors are formed inside the kernel from a table of psi powers that the context keeps per modulus; exponents 0 and N (+1 and -1) cost no product. Results are
+ * canonical and bit-identical to hc_lv_ntt of the one-hot polynomial + HC_LV_MUL_PLAIN + HC_LV_ADD. out_k may be a_k or b_k (no partial overlap). The operation claims no
+ * scratch and leaves a held decomposition alone. HC_ERR_ARG: an exponent >= 2N, consts NULL, exactly one of b0 / b1 NULL, a level outside the context, batch strides
+ * below the operands. It came without a new hc_version(): a caller detects it by calling it - a library without it answers HC_ERR_ARG, "unknown operation 10". hc_qp_op2
+ * does not take it. */
+enum { HC_LV_MUL = 0, HC_LV_ADD = 1, HC_LV_SUB = 2, HC_LV_MUL_CONST = 3, HC_LV_MUL_ACC = 7, HC_LV_MUL_PLAIN = 8, HC_LV_MUL_ACC_PLAIN = 9, HC_LV_MONOMIAL = 10 };
 int hc_lv_op2(hc_ctx *ctx, int op, int level, const uint64_t *a0, const uint64_t *a1, const uint64_t *b0, const uint64_t *b1, uint64_t *out0, uint64_t *out1, const uint64_t *consts);
 /* evaluator.permuteNTT's tail after the key switch (RotateNew, RotateHoisted, ConjugateNew): out0 = Permute_galEl(d0 + c0),
  * out1 = Permute_galEl(d1) over limbs 0..level in one launch; same residues as hc_lv_add + two hc_permute calls */

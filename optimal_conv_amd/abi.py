@@ -13,6 +13,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 DEFAULT_LIB = os.path.join(HERE, "libhconv.so")
 
 u64p = C.POINTER(C.c_uint64)
+HC_LV_MONOMIAL = 10      # hc_lv_op2: out_k = M_e1 (a_k + M_e0 b_k), M_e = NTT(X^e); consts = {e0, e1} (include/hconv.h)
 
 # every symbol include/hconv.h declares: name -> (restype, argtypes)
 SYMBOLS = {
@@ -235,9 +236,11 @@ class Context:
         binding should hold it: the context is back at ONE image per call on every way out of the block, exceptions included, so that a later call can never stride into
         images it was not given (the Go shim of INTEGRATION.md 3d does the same with `defer`)."""
         self.set_batch(n, poly_stride, qp_stride)
+        self._batch = (int(n), int(poly_stride) if n > 1 else 0)      # what lv_monomial lays its images out by
         try:
             yield self
         finally:
+            self._batch = (1, 0)
             self.L.hc_set_batch(self.h, 1, 0, 0)
 
     def set_option(self, name, value):
@@ -433,6 +436,32 @@ class Context:
         for x in A + O + (Bs[:1] if shared_b else Bs):
             x.free()
         return res
+
+    def lv_monomial(self, level, a, e1, b=None, e0=0, out=None):
+        """hc_lv_op2(HC_LV_MONOMIAL): X^e1 (a + X^e0 b) on both polynomials, exponents below 2N (X^N = -1); b = None: X^e1 a. a, b = (2, level+1, N), separate allocations per
+        polynomial. out = "a" / "b": the result is written over that operand (the permitted aliasing). Under Context.batch(n, stride) a and b are (n, 2, level+1, N) and image z
+        of a polynomial lies z * stride words into its allocation."""
+        nl, (n, stride) = level + 1, getattr(self, "_batch", (1, 0))
+        shape = (n, 2, nl, self.N)
+        def up(x):
+            x = np.ascontiguousarray(x, dtype=np.uint64).reshape(shape)
+            bufs = []
+            for k in range(2):
+                d = self.buf(nwords=(n - 1) * stride + nl * self.N)
+                for z in range(n):
+                    d.upload(self.pack_rows(x[z, k], nl), z * stride)
+                bufs.append(d)
+            return bufs
+        A, B_ = up(a), (up(b) if b is not None else None)
+        O = {None: None, "a": A, "b": B_}[out] or [self.buf(nwords=(n - 1) * stride + nl * self.N) for _ in range(2)]
+        cs = (C.c_uint64 * 2)(int(e0), int(e1))
+        try:
+            self._ck(self.L.hc_lv_op2(self.h, HC_LV_MONOMIAL, level, A[0].ptr, A[1].ptr, B_[0].ptr if B_ else None, B_[1].ptr if B_ else None, O[0].ptr, O[1].ptr, cs))
+            res = np.stack([np.stack([self.unpack_rows(O[k].download((nl, self.N), z * stride, nl * self.N), nl) for k in range(2)]) for z in range(n)])
+        finally:
+            for x in {id(x): x for x in A + (B_ or []) + O}.values():
+                x.free()
+        return res if n > 1 else res[0]
 
     def lv_sub(self, level, a, b): return self._lv(self.L.hc_lv_sub, level, a, b)
     def lv_mul_const(self, level, a, consts): return self._lv(self.L.hc_lv_mul_const, level, a, consts=consts)

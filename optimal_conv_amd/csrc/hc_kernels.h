@@ -699,6 +699,47 @@ __global__ __launch_bounds__(HC_TPB) void hc_k_lv_pointwise(const u64 *a, const 
     };
     HC_ROW_DISPATCH(m.row32, body);
 }
+// HC_LV_MONOMIAL: out_k = M_e1 * (a_k + M_e0 * b_k), M_e = NTT(X^e), 0 <= e < 2N (X^N = -1): MultByi / DivByi / a monomial shift with the neighbouring addition in the same pass,
+// and no plaintext. Position j of a transformed row holds the value at psi^(2 brv16(j) + 1), so M_e[j] = psi^(e (2 brv16(j) + 1) mod 2N): formed from a two-level table of
+// psi powers per modulus, in Montgomery form: lo[k] = psi^k (k < 256), hi[k] = psi^(256 k) (k < 512) - 6 KB, staged into LDS by each workgroup (a workgroup works on one limb).
+// A factor is two LDS reads and one product (Montgomery times Montgomery stays Montgomery), applying it one more: canonical in, canonical out, the residues of a product by the
+// transformed one-hot plaintext. The factors +1 (e = 0) and -1 (e = N) need no product and no table: F0 / F1 say per LAUNCH which form each factor takes (the chain's
+// re + i im = re + X^(N/2) im and i (cc - ct) = X^(N/2) (cc + X^N ct) are ONE / GEN and NEG / GEN with a single product-bearing factor each). grid = (x, level + 1, 2 * images).
+#define HC_MONO_LO 256
+#define HC_MONO_HI 512
+#define HC_MONO_WORDS (HC_MONO_LO + HC_MONO_HI)
+enum { HC_MONO_ONE = 0, HC_MONO_NEG = 1, HC_MONO_GEN = 2, HC_MONO_NONE = 3 };      // the factor is +1, -1, psi powers from the table; NONE (F0 only): there is no b
+template <int F0, int F1>
+__global__ __launch_bounds__(HC_TPB) void hc_k_lv_monomial(const u64 *a, const u64 *b, u64 *out, const HcMod *mods, const u64 *mono, u32 e0, u32 e1, size_t as, size_t bs, size_t os, size_t is) {
+    __shared__ u64 tab[HC_MONO_WORDS];
+    const int l = blockIdx.y; const HcMod m = mods[l];
+    if (F0 == HC_MONO_GEN || F1 == HC_MONO_GEN) {
+        for (int k = threadIdx.x; k < HC_MONO_WORDS; k += HC_TPB) tab[k] = mono[(size_t)l * HC_MONO_WORDS + k];
+        __syncthreads();
+    }
+    const size_t base = (size_t)l * 65536, zp = blockIdx.z & 1, img = blockIdx.z >> 1;
+    const u64 *ar = a + zp * as + img * is + base, *br = b + zp * bs + img * is + base; u64 *outr = out + zp * os + img * is + base;      // distances in words, modulo 2^64
+    auto factor = [&](u32 e, u32 j) {                                               // M_e[j] * 2^64 mod q
+        const u32 t = (e * (2u * (__brev(j) >> 16) + 1u)) & 0x1FFFFu;               // e (2 brv16(j) + 1) mod 2N (the product wraps modulo 2^32, a multiple of 2N)
+        return hc_mont(tab[t & (HC_MONO_LO - 1)], tab[HC_MONO_LO + (t >> 8)], m.q, m.qinv);
+    };
+    auto body = [&](auto s32c) {
+    constexpr bool S32 = decltype(s32c)::value;
+    for (u32 i = blockIdx.x * HC_TPB + threadIdx.x; i < 65536; i += gridDim.x * HC_TPB) {
+        u64 s = HC_LD(S32, ar, i);
+        if (F0 != HC_MONO_NONE) {
+            const u64 y = HC_LD(S32, br, i);
+            if (F0 == HC_MONO_ONE) s = hc_addmod(s, y, m.q);
+            else if (F0 == HC_MONO_NEG) s = hc_submod(s, y, m.q);
+            else s = hc_addmod(s, hc_mont(y, factor(e0, i), m.q, m.qinv), m.q);
+        }
+        if (F1 == HC_MONO_NEG) s = s ? m.q - s : 0;
+        else if (F1 == HC_MONO_GEN) s = hc_mont(s, factor(e1, i), m.q, m.qinv);
+        HC_ST(S32, outr, i, s);
+    }
+    };
+    HC_ROW_DISPATCH(m.row32, body);
+}
 // A linear combination with integer coefficients of up to 8 ciphertexts, both polynomials, all limbs, every image of a batch in one launch: evaluatePolyFromPowerBasis'
 // leaf (a MultByConst per power of the basis and an Add chain, plus AddConst): out_k[l] = sum_t c[t][l] * a_t,k[l] (+ addc[l] on k = 0). The constants come in Montgomery
 // form (c * 2^64 mod q_l), the products are summed as 128-bit integers and reduced once (8 q^2 < q 2^64 needs q < 2^61: every accepted modulus): the residue of the

@@ -118,6 +118,7 @@ struct hc_ctx {
     HcTw *ws_ctc = nullptr; size_t ws_ctc_cts = 0;     // [batch][2 polys][2 limbs][N] ct_in times the MultByConst constants, Shoup pairs
     u64 *ws_tmp = nullptr; size_t ws_tmp_rows = 0;
     HcMod *d_mods = nullptr; HcTw *d_csts = nullptr;      // device copies: all moduli (Q then P); per-call constants of the leveled ops
+    u64 *d_mono = nullptr;                                // per modulus (Q then P): HC_MONO_WORDS powers of psi in Montgomery form (hc_k_lv_monomial)
     struct CacheBlk { size_t n = 0; hipEvent_t ev = nullptr; bool pending = false; };
     std::map<char *, CacheBlk> cache_blk; std::map<size_t, std::vector<void *>> cache_free;      // HCONV_ASYNC_ALLOC=1: sizes of the blocks this context allocated; parked blocks by size
     int async_alloc = 0;                                    // option async_alloc = 1: non-blocking stream + cached allocations (see hcx_malloc)
@@ -389,6 +390,18 @@ extern "C" int hc_ctx_create(hc_ctx **out, int logN, const uint64_t *q, int nq, 
         if (hcx_malloc(c, (void **)&c->d_mods, hm.size() * sizeof(HcMod)) != hipSuccess || hcx_malloc(c, (void **)&c->d_csts, hm.size() * sizeof(HcTw)) != hipSuccess ||
             hcx_h2d(c, c->d_mods, hm.data(), hm.size() * sizeof(HcMod)) != hipSuccess) { g_create_err = "hc_ctx_create: device modulus table"; hc_ctx_destroy(c); return HC_ERR_HIP; }
     }
+    {   // powers of psi for the monomial factors (HC_LV_MONOMIAL): lo[k] = psi^k, hi[k] = psi^(256 k), times 2^64, per modulus
+        std::vector<u64> mono(c->mods.size() * HC_MONO_WORDS);
+        for (size_t i = 0; i < c->mods.size(); i++) {
+            const u64 qi = c->mods[i].m.q, r = (u64)((((u128)1) << 64) % qi), psi256 = h_powmod(c->mods[i].psi, HC_MONO_LO, qi);
+            u64 *t = &mono[i * HC_MONO_WORDS], w = r;
+            for (int k = 0; k < HC_MONO_LO; k++) { t[k] = w; w = h_mulmod(w, c->mods[i].psi, qi); }
+            w = r;
+            for (int k = 0; k < HC_MONO_HI; k++) { t[HC_MONO_LO + k] = w; w = h_mulmod(w, psi256, qi); }
+        }
+        if (hcx_malloc(c, (void **)&c->d_mono, mono.size() * sizeof(u64)) != hipSuccess || hcx_h2d(c, c->d_mono, mono.data(), mono.size() * sizeof(u64)) != hipSuccess) {
+            g_create_err = "hc_ctx_create: device table of psi powers"; hc_ctx_destroy(c); return HC_ERR_HIP; }
+    }
     if (hcx_malloc(c, (void **)&c->d_rowmods, c->mods.size() * sizeof(HcRowMod)) != hipSuccess || hc_upload_rowmods(c) != HC_OK) { g_create_err = "hc_ctx_create: device table of transforms"; hc_ctx_destroy(c); return HC_ERR_HIP; }
     *out = c;
     return HC_OK;
@@ -413,7 +426,7 @@ extern "C" void hc_ctx_destroy(hc_ctx *c) {
     if (c->ev_fork) D(hipEventDestroy(c->ev_fork), "hipEventDestroy");
     if (c->ev_shard) D(hipEventDestroy(c->ev_shard), "hipEventDestroy");
     F(c->enc_roots); F(c->enc_rot_group); F(c->d_flag); F(c->crt_tab);
-    F(c->ws_ctc); F(c->ws_tmp); F(c->d_mods); F(c->d_rowmods); F(c->ws_mm); F(c->ws_accm);
+    F(c->ws_ctc); F(c->ws_tmp); F(c->d_mods); F(c->d_mono); F(c->d_rowmods); F(c->ws_mm); F(c->ws_accm);
     for (auto &kv : c->ks_plan) { F(kv.second.bx); F(kv.second.bxdown); F(kv.second.pinv); F(kv.second.pmod); F(kv.second.pinv_qlinv); }
     for (auto &kv : c->rescale_plan) F(kv.second);
     F(c->d_csts);
@@ -631,6 +644,27 @@ static int hc_lv_pw2(hc_ctx *c, const char *fn, int level, const u64 *a0, const 
     return hc_launch(c, fn, hc_k_lv_pointwise<OP>, dim3(HC_GX_PW, (unsigned)(level + 1), inthread ? 2u : 2u * (unsigned)c->nb), a0, bb0, o0, (const HcMod *)c->d_mods, K, (size_t)(a1 - a0), (size_t)(bb1 - bb0), (size_t)(o1 - o0), HC_ROW_IS_MOD, 0,
                      2, inthread ? c->nb : 1, c->bs_poly, b_shared ? (size_t)0 : c->bs_poly, c->bs_poly);
 }
+// HC_LV_MONOMIAL: out_k = M_e1 (a_k + M_e0 b_k), consts = {e0, e1} on the host; b0 == b1 == null: out_k = M_e1 a_k. The factors +1 and -1 (exponents 0 and N) are chosen here,
+// per launch. No scratch, no effect on a held decomposition.
+static int hc_lv_monomial(hc_ctx *c, int level, const u64 *a0, const u64 *a1, const u64 *b0, const u64 *b1, u64 *o0, u64 *o1, const uint64_t *consts) {
+    const char *fn = "hc_lv_op2(monomial)";
+    HC_TRY(hc_lv_check(c, fn, level, a0, o0));
+    if (!a1 || !o1) return hc_fail(c, HC_ERR_ARG, "%s: null", fn);
+    if (!consts) return hc_fail(c, HC_ERR_ARG, "%s: null exponents (consts = {e0, e1})", fn);
+    if (!b0 != !b1) return hc_fail(c, HC_ERR_ARG, "%s: b0 and b1 must both be given or both be null", fn);
+    const u64 e0 = b0 ? consts[0] : 0, e1 = consts[1];
+    if (e0 >= 2ull * HC_N || e1 >= 2ull * HC_N) return hc_fail(c, HC_ERR_ARG, "%s: exponents (%llu, %llu) outside 0..%d", fn, (unsigned long long)e0, (unsigned long long)e1, 2 * HC_N - 1);
+    auto form = [](u64 e) { return e == 0 ? HC_MONO_ONE : e == (u64)HC_N ? HC_MONO_NEG : HC_MONO_GEN; };
+    const int f0 = b0 ? form(e0) : HC_MONO_NONE, f1 = form(e1);
+    const u64 *bb0 = b0 ? b0 : a0, *bb1 = b1 ? b1 : a1;
+    const dim3 grid(HC_GX_PW, (unsigned)(level + 1), 2u * (unsigned)c->nb);
+#define HC_MONO_GO(F0, F1) case F0 * 4 + F1: return hc_launch(c, "lv_monomial", hc_k_lv_monomial<F0, F1>, grid, a0, bb0, o0, (const HcMod *)c->d_mods, (const u64 *)c->d_mono, (u32)e0, (u32)e1, (size_t)(a1 - a0), (size_t)(bb1 - bb0), (size_t)(o1 - o0), c->bs_poly)
+#define HC_MONO_GO3(F0) HC_MONO_GO(F0, HC_MONO_ONE); HC_MONO_GO(F0, HC_MONO_NEG); HC_MONO_GO(F0, HC_MONO_GEN)
+    switch (f0 * 4 + f1) { HC_MONO_GO3(HC_MONO_ONE); HC_MONO_GO3(HC_MONO_NEG); HC_MONO_GO3(HC_MONO_GEN); HC_MONO_GO3(HC_MONO_NONE); }
+#undef HC_MONO_GO3
+#undef HC_MONO_GO
+    return hc_fail(c, HC_ERR_ARG, "%s: unreachable", fn);
+}
 extern "C" int hc_lv_op2(hc_ctx *c, int op, int level, const uint64_t *a0, const uint64_t *a1, const uint64_t *b0, const uint64_t *b1, uint64_t *out0, uint64_t *out1, const uint64_t *consts) {
     HC_ENTER(c);
     switch (op) {
@@ -641,6 +675,7 @@ extern "C" int hc_lv_op2(hc_ctx *c, int op, int level, const uint64_t *a0, const
         case HC_LV_MUL_ACC: return hc_lv_pw2<HC_PW_MAC>(c, "hc_lv_op2(mul_acc)", level, a0, a1, b0, b1, out0, out1, nullptr);
         case HC_LV_MUL_PLAIN: return hc_lv_pw2<HC_PW_MUL>(c, "hc_lv_op2(mul)", level, a0, a1, b0, b1, out0, out1, nullptr, true);
         case HC_LV_MUL_ACC_PLAIN: return hc_lv_pw2<HC_PW_MAC>(c, "hc_lv_op2(mul_acc)", level, a0, a1, b0, b1, out0, out1, nullptr, true);
+        case HC_LV_MONOMIAL: return hc_lv_monomial(c, level, a0, a1, b0, b1, out0, out1, consts);
     }
     return hc_fail(c, HC_ERR_ARG, "hc_lv_op2: unknown operation %d", op);
 }

@@ -83,7 +83,7 @@ struct Boot {
     std::vector<uint64_t *> pool;
     ChaChaRng rng;                    // the bootstrapper's own key stream (switching keys, encryption masks)
     Encoder enc;
-    std::shared_ptr<uint64_t> mono_i;                        // NTT(X^(N/2)) for every limb
+    std::shared_ptr<uint64_t> mono_i;                        // NTT(X^(N/2)) for every limb: only for a degree-2 operand of mul_by_i (need_mono_i)
     struct LT { int n1 = 1; std::map<int, std::map<int, DPt>> giant; double pt_scale = 0; int level = 0; bool qp = false; };   // the diagonals are encoded mod Q_0..Q_level AND mod every P (rows [level+1+np][N]) for linear_transform_qp
     struct Set { int ls = 0, ns = 0; std::vector<LT> cts, stc; };      // one bootstrapper of the reference (btp, btp2..btp5: main.go:480-500)
     std::map<int, Set> sets;                                           // by log_sparse
@@ -317,10 +317,37 @@ struct Boot {
         else for (int d = 0; d <= a.deg; d++) HCR(hc_lv_mul_plain(hc, a.level, a.p[d].get(), pt.p.get(), r.p[d].get()));
         return r;
     }
+    // MultByi = the product by X^(N/2): one HC_LV_MONOMIAL launch, the factor formed in the kernel (no plaintext). A degree-2 operand (none in the chains as they stand) takes
+    // the former product by the transformed one-hot plaintext, built when first asked for.
     DCt mul_by_i(const DCt &a) {
         DCt r = new_ct(a.level, a.deg, a.scale); alg_ct += 2.0 * (a.deg + 1) * (a.level + 1); alg_shared += a.level + 1;
-        if (a.deg == 1) HCR(hc_lv_op2(hc, HC_LV_MUL_PLAIN, a.level, a.p[0].get(), a.p[1].get(), mono_i.get(), nullptr, r.p[0].get(), r.p[1].get(), nullptr));
-        else for (int d = 0; d <= a.deg; d++) HCR(hc_lv_mul_plain(hc, a.level, a.p[d].get(), mono_i.get(), r.p[d].get()));
+        const uint64_t e[2] = {0, (uint64_t)N / 2};
+        if (a.deg == 1) HCR(hc_lv_op2(hc, HC_LV_MONOMIAL, a.level, a.p[0].get(), a.p[1].get(), nullptr, nullptr, r.p[0].get(), r.p[1].get(), e));
+        else { need_mono_i(); for (int d = 0; d <= a.deg; d++) HCR(hc_lv_mul_plain(hc, a.level, a.p[d].get(), mono_i.get(), r.p[d].get())); }
+        return r;
+    }
+    void need_mono_i() {
+        if (mono_i) return;
+        Single one(this);
+        mono_i = block1();
+        std::vector<uint64_t> m((size_t)NQ * N, 0); for (int l = 0; l < NQ; l++) m[(size_t)l * N + N / 2] = 1;
+        pack_rows(m, NQ); HCR(hc_upload(hc, mono_i.get(), m.data(), m.size() * 8)); HCR(hc_lv_ntt(hc, NQ - 1, mono_i.get(), mono_i.get()));
+    }
+    // X^e1 (a + X^e0 b) in one pass over the operands (HC_LV_MONOMIAL; exponents below 2N, X^N = -1): re + i im is (N/2, 0), i (a - b) is (N, N/2). Counted as the evaluator
+    // operations it stands for: a monomial product of b unless e0 is 0 or N, the addition or subtraction, a monomial product of the sum unless e1 is 0.
+    DCt monomial_fma(const DCt &a, const DCt &b, int e0, int e1) {
+        if (a.deg != 1 || b.deg != 1) {
+            if (e0 == N / 2 && e1 == 0) return add(a, mul_by_i(b));
+            if (e0 == N && e1 == N / 2) return mul_by_i(sub(a, b));
+            panic("monomial_fma: degree-1 operands");
+        }
+        const int L = std::min(a.level, b.level); same_scale(a.scale, b.scale);
+        DCt r = new_ct(L, 1, a.scale);
+        if (e0 != 0 && e0 != N) { alg_ct += 4.0 * (b.level + 1); alg_shared += b.level + 1; }
+        alg_ct += 6.0 * (L + 1);
+        if (e1 != 0) { alg_ct += 4.0 * (L + 1); alg_shared += L + 1; }
+        const uint64_t e[2] = {(uint64_t)e0, (uint64_t)e1};
+        HCR(hc_lv_op2(hc, HC_LV_MONOMIAL, L, a.p[0].get(), a.p[1].get(), b.p[0].get(), b.p[1].get(), r.p[0].get(), r.p[1].get(), e));
         return r;
     }
     DCt mul_relin(const DCt &a, const DCt &b) {                   // evaluator.MulRelin: tensor, key switch of c2 with the rlk
@@ -1001,8 +1028,6 @@ struct Boot {
             for (int j = 0; j < N; j++) h[(size_t)j] = sk[(size_t)j] >= 0 ? (uint64_t)sk[(size_t)j] : q - (uint64_t)(-sk[(size_t)j]);
             HCR(hc_upload(hc, d_sk + (size_t)m * N, h.data(), (size_t)N * 8)); HCR(hc_ntt(hc, m, d_sk + (size_t)m * N, d_sk + (size_t)m * N, 1));
         }
-        mono_i = block1();
-        { std::vector<uint64_t> m((size_t)NQ * N, 0); for (int l = 0; l < NQ; l++) m[(size_t)l * N + N / 2] = 1; pack_rows(m, NQ); HCR(hc_upload(hc, mono_i.get(), m.data(), m.size() * 8)); HCR(hc_lv_ntt(hc, NQ - 1, mono_i.get(), mono_i.get())); }
         // Chebyshev interpolant of cos(2 pi (K u - 1/4) / 2^r) on [-1,1]
         const int m = SIN_DEG + 1; sine.assign((size_t)m, 0.0);
         for (int j = 0; j < m; j++) {
@@ -1097,7 +1122,7 @@ struct Boot {
         if (ct.level != LV_SINE_TOP) panic("CoeffsToSlots ended at the wrong level");
         if (profiling()) profile_dump(this, "modUp + CoeffsToSlots");
         DCt cc = conjugate(ct);
-        DCt parts[2] = {add(ct, cc), mul_by_i(sub(cc, ct))};           // DivByi(ct - conj) = -i (ct - conj) = i (conj - ct): the same residues
+        DCt parts[2] = {add(ct, cc), monomial_fma(cc, ct, N, N / 2)};           // DivByi(ct - conj) = -i (ct - conj) = i (conj - ct): the same residues
         const int nparts = ls ? 1 : 2;
         if (ls) parts[0] = add(parts[0], rotate(parts[1], S.ns));      // repacking: the imaginary half next to the real one
         double target = sinescale;
@@ -1129,7 +1154,7 @@ struct Boot {
         for (auto &lt : S.cts) ct = rescale(linear_transform(ct, lt));
         if (ct.level != LV_SINE_TOP) panic("CoeffsToSlots ended at the wrong level");
         DCt cc = conjugate(ct);
-        DCt parts[2] = {add(ct, cc), mul_by_i(sub(cc, ct))};           // (w + conj w), -i (w - conj w); the 1/2 is in the matrices
+        DCt parts[2] = {add(ct, cc), monomial_fma(cc, ct, N, N / 2)};           // (w + conj w), -i (w - conj w); the 1/2 is in the matrices
         int np = 2;
         if (ls) { parts[0] = add(parts[0], rotate(parts[1], S.ns)); np = 1; }
         const double c_m = q0 / (2.0 * M_PI * msg_scale);
@@ -1148,7 +1173,7 @@ struct Boot {
         Set &S = set(ls);
         if (ls && im) panic("sparse SlotsToCoeffs takes one packed ciphertext");
         if (chain == 7 && ls == 0) {      // ckks.SlotsToCoeffs inside the stock Bootstrapp (ref_flow_bl_5_1.json): MultByi + Add, LinearTransform on the matrices' own levels 15, 15, 14, each followed by a Rescale(min = the scale before) that finds nothing to drop: level 14, scale ~2^120
-            DCt ct = add(re, mul_by_i(*im));
+            DCt ct = monomial_fma(re, *im, N / 2, 0);
             std::shared_ptr<uint64_t> prev_c1;                                       // the second polynomial of the previous LinearTransform's input (see linear_transform_qp)
             for (auto &lt : S.stc) {
                 const double s_in = ct.scale;
@@ -1163,7 +1188,7 @@ struct Boot {
             }
             return ct;
         }
-        DCt ct = drop_to(ls ? re : add(re, mul_by_i(*im)), LV_STC_TOP);
+        DCt ct = drop_to(ls ? re : monomial_fma(re, *im, N / 2, 0), LV_STC_TOP);
         if (chain == 6) {        // ckks.SlotsToCoeffs as the fork runs it (sparse slots: one packed ciphertext, no MultByi + Add) (ref_flow_5_1.json): MultByi + Add, three LinearTransforms each followed by Rescale(min = the scale before), then eval.go:564's Rescale(2^30): level 3 -> 1
             for (auto &lt : S.stc) { const double s_in = ct.scale; ct = lt_rescale(linear_transform(ct, lt, s_in), s_in); }
             return lt_rescale(ct, 1073741824.0);
@@ -1608,7 +1633,7 @@ void blBootReLU(Boot *B, const uint64_t *ct_res0, const uint64_t *ct_res1, doubl
       if (ct_boot.level != 12) panic("the baseline's rescale after Bootstrapp ended at an unexpected level"); }
     if (dbg) Boot::debug_compare("Bootstrapp + scale plaintext", z_in, B->debug_slots(ct_boot));
     DCt ct_iboot = B->conjugate(ct_boot);                                                                // test_BL.go:155
-    DCt res[2] = {B->add(ct_boot, ct_iboot), B->mul_by_i(B->sub(ct_iboot, ct_boot))};                    // DivByi(a - b) = i (b - a)
+    DCt res[2] = {B->add(ct_boot, ct_iboot), B->monomial_fma(ct_iboot, ct_boot, N, N / 2)};                    // DivByi(a - b) = i (b - a)
     HCR(hc_sync(hc));
     { double ns = (img_part + std::chrono::duration<double>(now() - img_eval).count()) * 1e9; char b[64];
       if (ns < 1e6) snprintf(b, sizeof b, "%.6gµs", ns / 1e3); else if (ns < 1e9) snprintf(b, sizeof b, "%.9gms", ns / 1e6); else snprintf(b, sizeof b, "%.9gs", ns / 1e9);

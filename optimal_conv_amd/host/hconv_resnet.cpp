@@ -43,15 +43,6 @@ static std::string dur(std::chrono::steady_clock::time_point t0) {
 static std::chrono::steady_clock::time_point now() { return std::chrono::steady_clock::now(); }
 static double secs(std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); }
 
-// MulNew(ct, EncodeCoeffs(+-X^idx at scale 1)) on a level-0 ciphertext (eval.go:361-367, 374-387), in place
-static void mul_monomial_l0(Context *c, Ciphertext &ct, int idx, bool negative) {
-    std::vector<uint64_t> m((size_t)N, 0); m[(size_t)idx] = negative ? PARAMS6_Q[0] - 1 : 1;
-    void *v = nullptr; HCX(c->hc, hc_malloc(c->hc, (size_t)N * 8, &v)); uint64_t *pt = (uint64_t *)v;
-    HCX(c->hc, hc_upload(c->hc, pt, m.data(), (size_t)N * 8)); HCX(c->hc, hc_ntt(c->hc, 0, pt, pt, 1));
-    for (int d = 0; d < 2; d++) HCX(c->hc, hc_mul(c->hc, 0, ct.d + (size_t)d * N, pt, ct.d + (size_t)d * N, 1));
-    HCX(c->hc, hc_free(c->hc, pt));
-}
-
 // eval.go:272-607 for the kinds the conv / convReLU / resnet command lines reach, for the images of a batch (ct_inputs.size() <= HCONV_IMAGE_BATCH): every image
 // sees the operations of the reference's per-image flow, but a launch covers all of them (hc_conv_then_pack_batch; hc_set_batch inside the tail)
 std::vector<Ciphertext> evalConv_BNRelu_new_batch(Context *cont, const std::vector<Ciphertext> &ct_inputs, const std::vector<double> &ker_in, const std::vector<double> &bn_a,
@@ -74,11 +65,13 @@ std::vector<Ciphertext> evalConv_BNRelu_new_batch(Context *cont, const std::vect
         std::vector<Ciphertext> r1 = evalConv_BN_batch(cont, ct_inputs, k0, a0, b0, in_wid, ker_wid, real_ib, real_ob / 2, norm / 2, out_scale, false);
         std::vector<Ciphertext> r2 = evalConv_BN_batch(cont, ct_inputs, k1, a1, b1, in_wid, ker_wid, real_ib, real_ob / 2, norm / 2, out_scale, false);
         const int max_batch = N / (in_wid * in_wid);
+        // MulNew(r2, EncodeCoeffs(X^(norm/4))) (eval.go:361-367), AddNew (369) and, for these widths, MulNew by -X^(N - max_batch (in_wid + 1)) (eval.go:377-387; -X^s is
+        // X^(N + s)) as ONE pass per image at level 0: HC_LV_MONOMIAL forms the transformed monomials in the kernel
+        const uint64_t e[2] = {(uint64_t)(norm / 4), (in_wid - ker_wid / 2) % 2 == 0 ? (uint64_t)(2 * N - max_batch * (in_wid + 1)) : 0};
         for (int z = 0; z < nimg; z++) {
-            mul_monomial_l0(cont, r2[(size_t)z], norm / 4, false);                                        // eval.go:361-367
-            for (int d = 0; d < 2; d++) HCX(cont->hc, hc_add(cont->hc, 0, r1[(size_t)z].d + (size_t)d * N, r2[(size_t)z].d + (size_t)d * N, r1[(size_t)z].d + (size_t)d * N, 1));   // AddNew (369)
+            uint64_t *a = r1[(size_t)z].d, *b = r2[(size_t)z].d;
+            HCX(cont->hc, hc_lv_op2(cont->hc, HC_LV_MONOMIAL, 0, a, a + N, b, b + N, a, a + N, e));
             freeCt(cont, r2[(size_t)z]);
-            if ((in_wid - ker_wid / 2) % 2 == 0) mul_monomial_l0(cont, r1[(size_t)z], N - max_batch * (in_wid + 1), true);                        // eval.go:377-387
         }
         ct_conv = r1;
     } else if (kind == "Conv_sparse" || kind == "Conv") {
