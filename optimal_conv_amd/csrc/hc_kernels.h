@@ -559,9 +559,38 @@ __device__ __forceinline__ void hc_rows_inv_twl(const P &pol, u64 *lds, const Hc
     hc_xchg(lds, [&](int lo) { return hc_rows_lds(rloc, tid * 16 + lo); }, [&](int hi) { return hc_rows_lds(rloc, hi * 16 + tid); }, [] { HC_ROW_SYNC(); }, e0, e1);
     hc_gs_round(pol, hc_twl_put(lds, wA, rloc, tid), e0, e1);
 }
-// fp64 forms of the inverse cols pass (4-byte words) and of the inverse rows pass on two tiles (8-byte words)
-__device__ __forceinline__ void hc_cols_inv_f64(double (&e)[16], u32 *lds, const HcTwTab &T, int c, int tid, HcF64Mod m) {
-    hc_gs_round_f64<false>(e, HcTwB<false, HcTw>{T.colsB + tid}, m, T.ninv, T.ninv);
+// ---- the B group of a cols pass staged through LDS, for the convolution's cols kernels (hc_k_a2, hc_k_b2, hc_k_b4). In a cols pass thread t = (c = t & 15, tid = t >> 4): the 16
+// lanes of a column group want the same 15 colsB entries (slot * 16 + tid), and a wavefront (tids 4w .. 4w + 3) only ever wants 60 of the table's 256: as global loads that is 15
+// vector-memory instructions per thread and transform for bytes ONE coalesced load per thread brings. Lane L of wavefront w loads entry (L >> 2) * 16 + 4w + (L & 3) - slot L >> 2 of
+// tid 4w + (L & 3) - and writes it to word (L >> 2) * 4 + (L & 3) of the wavefront's own 1 KiB image (hc_twc_load, hc_twc_put); slot s of the round is then img[s * 4 + (tid & 3)]
+// (HcTwC): a ds_read_b128 over four adjacent 16-byte entries, each broadcast to 16 lanes. Only the wavefront's own lanes write and read its image, so its syncs are wave-local
+// (HC_ROW_SYNC) and the kernel gains no workgroup barrier. The images of a kernel's two tables (inverse, forward) are loaded at kernel entry, in front of the data loads - the
+// inverse pass uses colsB in its FIRST round - into their own 8 KiB beside the 16 KiB exchange tile (HC_COLS_TWL words of HcTw). The colsA round stays scalar. Same tables, same
+// values: results are bit-identical. The standalone transforms, the S kernels and the multi-modulus kernels keep hc_cols_fwd / hc_cols_inv.
+#define HC_COLS_TWL (2 * 4 * 64)        // HcTw entries: 2 tables x 4 wavefronts x 64
+struct HcTwC { const HcTw *p; __device__ __forceinline__ HcTw operator()(int slot) const { return p[slot * 4]; } };
+__device__ __forceinline__ HcTw hc_twc_load(const HcTwTab &T, int t) { return HC_TW_LOAD(HcTw, T.colsB, ((t & 63) >> 2) * 16 + (t >> 6) * 4 + (t & 3)); }
+// which = 0 / 1: the kernel's first / second table. Returns the thread's view of the image; the caller syncs (HC_ROW_SYNC) once after its puts.
+__device__ __forceinline__ HcTwC hc_twc_put(HcTw *twl, int which, const HcTw &w, int t) {
+    HcTw *img = twl + (which * 4 + (t >> 6)) * 64;
+    img[t & 63] = w;                                                        // (L >> 2) * 4 + (L & 3) = L
+    return HcTwC{img + ((t >> 4) & 3)};
+}
+template <class P, class L>
+__device__ __forceinline__ void hc_cols_fwd_twl(const P &pol, L *lds, const HcTwTab &T, const HcTwC &wB, int c, int tid, u64 (&e)[16]) {
+    hc_ct_round(pol, HcTwA<false, HcTw>{T.colsA}, e);
+    hc_xchg(lds, [&](int hi) { return hc_cols_lds<L>(hi * 16 + tid, c); }, [&](int lo) { return hc_cols_lds<L>(tid * 16 + lo, c); }, [] { __syncthreads(); }, e);
+    hc_ct_round(pol, wB, e);
+}
+template <bool SCALE = true, class P, class L>
+__device__ __forceinline__ void hc_cols_inv_twl(const P &pol, L *lds, const HcTwTab &T, const HcTwC &wB, int c, int tid, u64 (&e)[16], const HcTw &ninv, const HcTw &w_last) {
+    hc_gs_round(pol, wB, e);
+    hc_xchg(lds, [&](int lo) { return hc_cols_lds<L>(tid * 16 + lo, c); }, [&](int hi) { return hc_cols_lds<L>(hi * 16 + tid, c); }, [] { __syncthreads(); }, e);
+    hc_gs_round<SCALE>(pol, HcTwA<false, HcTw>{T.colsA}, e, ninv, w_last);
+}
+// fp64 forms of the inverse cols pass (4-byte words, the B group staged: hc_k_a2) and of the inverse rows pass on two tiles (8-byte words)
+__device__ __forceinline__ void hc_cols_inv_f64(double (&e)[16], u32 *lds, const HcTwTab &T, const HcTwC &wB, int c, int tid, HcF64Mod m) {
+    hc_gs_round_f64<false>(e, wB, m, T.ninv, T.ninv);
     hc_xchg(lds, [&](int lo) { return hc_cols_lds<u32>(tid * 16 + lo, c); }, [&](int hi) { return hc_cols_lds<u32>(hi * 16 + tid, c); }, [] { __syncthreads(); }, e);
     hc_gs_round_f64<true>(e, HcTwA<false, HcTw>{T.colsA}, m, T.ninv, T.w_last_ninv);
 }
@@ -1036,23 +1065,28 @@ __global__ __launch_bounds__(HC_TPB, HC_W_A1) void hc_k_a1p(HcLoopA A, HcTwTab T
         for (int hi = 0; hi < 16; hi++) { o[hi * 16 + tid] = e0[hi]; o[65536 + hi * 16 + tid] = e1[hi]; }
     }
 }
-// KA2: cols-inverse mod Q1, centred lift to Q0, cols-forward mod Q0, in place on tmp. grid = (jobs * batch, 16)
+// KA2: cols-inverse mod Q1, centred lift to Q0, cols-forward mod Q0, in place on tmp. grid = (jobs * batch, 16). The colsB twiddles of both transforms come through wave-local LDS images (HcTwC):
+// one load per thread and table at kernel entry, 8 KiB beside the 16 KiB exchange tile.
 template <int FM, int F64>
 __global__ __launch_bounds__(HC_TPB, HC_W_A2) void hc_k_a2(HcLoopA A, HcTwTab T1inv, HcTwTab T0fwd) {
     __shared__ u32 lds[HC_COLS_LDS];
+    __shared__ __attribute__((aligned(16))) HcTw twl[HC_COLS_TWL];
     const int t = threadIdx.x, c = t & 15, tid = t >> 4;
     u64 *base = A.tmp + (size_t)HC_JOB * 65536 + HC_TILE * 16 + c;
     const HcQ Q0 = hc_q(A.m0.q);
+    const HcTw wI = hc_twc_load(T1inv, t), wF = hc_twc_load(T0fwd, t);
     u64 e[16];
 #pragma unroll
     for (int lo = 0; lo < 16; lo++) e[lo] = base[(size_t)(tid * 16 + lo) * 256];
+    const HcTwC tI = hc_twc_put(twl, 0, wI, t), tF = hc_twc_put(twl, 1, wF, t);
+    HC_ROW_SYNC();        // wave-local: an image is written and read by the lanes of one wavefront
     if (F64) {
         const double q1 = (double)A.m1.q, hh = (double)A.h;
         const HcF64Mod m{q1, 1.0 / q1};
         double f[16];
 #pragma unroll
         for (int lo = 0; lo < 16; lo++) f[lo] = hc_u2d(e[lo]);
-        hc_cols_inv_f64(f, lds, T1inv, c, tid, m);
+        hc_cols_inv_f64(f, lds, T1inv, tI, c, tid, m);
 #pragma unroll
         for (int hi = 0; hi < 16; hi++) {
             double v = f[hi];                                         // exact, |v| < Q1, congruent to t
@@ -1061,7 +1095,7 @@ __global__ __launch_bounds__(HC_TPB, HC_W_A2) void hc_k_a2(HcLoopA A, HcTwTab T1
         }
     } else {
         const HcQ Q1 = hc_q(A.m1.q);
-        hc_cols_inv(HcLazy<>{Q1}, lds, T1inv, c, tid, e, T1inv.ninv, T1inv.w_last_ninv);
+        hc_cols_inv_twl(HcLazy<>{Q1}, lds, T1inv, tI, c, tid, e, T1inv.ninv, T1inv.w_last_ninv);
 #pragma unroll
         for (int hi = 0; hi < 16; hi++) {
             const u64 v = hc_csub(hc_canon4(e[hi], Q1) + A.h, A.m1.q);   // [t + h]_{Q1}
@@ -1069,7 +1103,7 @@ __global__ __launch_bounds__(HC_TPB, HC_W_A2) void hc_k_a2(HcLoopA A, HcTwTab T1
         }
     }
     __syncthreads();
-    hc_cols_fwd(HcLazy<FM>{Q0}, lds, T0fwd, c, tid, e);
+    hc_cols_fwd_twl(HcLazy<FM>{Q0}, lds, T0fwd, tF, c, tid, e);
 #pragma unroll
     for (int lo = 0; lo < 16; lo++) base[(size_t)(tid * 16 + lo) * 256] = e[lo];
 }
@@ -1172,21 +1206,25 @@ __global__ __launch_bounds__(HC_TPB, HC_W_B1) void hc_k_b1(HcLoopB B, HcTwTab T0
 #pragma unroll
     for (int hi = 0; hi < 16; hi++) o[hi * 16 + tid] = e[hi];
 }
-// KB2: cols-inverse mod Q0 (-> canonical c < Q0 < P), cols-forward mod P, in place on tmpC. grid = (batch*nodes, 16)
+// KB2: cols-inverse mod Q0 (-> canonical c < Q0 < P), cols-forward mod P, in place on tmpC. grid = (batch*nodes, 16). colsB twiddles of both transforms through LDS images (HcTwC), as in KA2.
 template <int FMP>
 __global__ __launch_bounds__(HC_TPB, HC_W_B2) void hc_k_b2(HcLoopB B, HcTwTab T0inv, HcTwTab TPfwd) {
     __shared__ u32 lds[HC_COLS_LDS];
+    __shared__ __attribute__((aligned(16))) HcTw twl[HC_COLS_TWL];
     const int t = threadIdx.x, c = t & 15, tid = t >> 4;
     u64 *base = B.tmpC + (size_t)HC_JOB * 65536 + HC_TILE * 16 + c;
     const HcQ Q0 = hc_q(B.m0.q), QP = hc_q(B.mp.q);
+    const HcTw wI = hc_twc_load(T0inv, t), wF = hc_twc_load(TPfwd, t);
     u64 e[16];
 #pragma unroll
     for (int lo = 0; lo < 16; lo++) e[lo] = base[(size_t)(tid * 16 + lo) * 256];
-    hc_cols_inv(HcLazy<>{Q0}, lds, T0inv, c, tid, e, T0inv.ninv, T0inv.w_last_ninv);
+    const HcTwC tI = hc_twc_put(twl, 0, wI, t), tF = hc_twc_put(twl, 1, wF, t);
+    HC_ROW_SYNC();        // wave-local: an image is written and read by the lanes of one wavefront
+    hc_cols_inv_twl(HcLazy<>{Q0}, lds, T0inv, tI, c, tid, e, T0inv.ninv, T0inv.w_last_ninv);
 #pragma unroll
     for (int hi = 0; hi < 16; hi++) e[hi] = hc_canon4(e[hi], Q0);          // the integer in [0, Q0) is what is read modulo P
     __syncthreads();
-    hc_cols_fwd(HcLazy<FMP>{QP}, lds, TPfwd, c, tid, e);
+    hc_cols_fwd_twl(HcLazy<FMP>{QP}, lds, TPfwd, tF, c, tid, e);
 #pragma unroll
     for (int lo = 0; lo < 16; lo++) base[(size_t)(tid * 16 + lo) * 256] = e[lo];
 }
@@ -1223,17 +1261,21 @@ __global__ __launch_bounds__(HC_TPB, HC_W_B3) void hc_k_b3p(HcLoopB B, HcTwTab T
     for (int hi = 0; hi < 16; hi++) { o[hi * 16 + tid] = e0[hi]; o[65536 + hi * 16 + tid] = e1[hi]; }
 }
 // KB4: cols-inverse mod P, exact basis extension P -> Q0 (ring.modUpExact, one P prime), cols-forward mod Q0.
-// grid = (2*batch*nodes, 16), in place on tmpE
+// grid = (2*batch*nodes, 16), in place on tmpE. colsB twiddles of both transforms through LDS images (HcTwC), as in KA2.
 template <int FM>
 __global__ __launch_bounds__(HC_TPB, HC_W_B4) void hc_k_b4(HcLoopB B, HcTwTab TPinv, HcTwTab T0fwd) {
     __shared__ u32 lds[HC_COLS_LDS];
+    __shared__ __attribute__((aligned(16))) HcTw twl[HC_COLS_TWL];
     const int t = threadIdx.x, c = t & 15, tid = t >> 4;
     u64 *base = B.tmpE + (size_t)HC_JOB * 65536 + HC_TILE * 16 + c;
     const HcQ QP = hc_q(B.mp.q), Q = hc_q(B.m0.q);
+    const HcTw wI = hc_twc_load(TPinv, t), wF = hc_twc_load(T0fwd, t);
     u64 e[16];
 #pragma unroll
     for (int lo = 0; lo < 16; lo++) e[lo] = base[(size_t)(tid * 16 + lo) * 256];
-    hc_cols_inv<false>(HcLazy<>{QP}, lds, TPinv, c, tid, e, TPinv.ninv, TPinv.w_last_ninv);                 // N^-1 mod P is inside the key rows (hc_evk_load)
+    const HcTwC tI = hc_twc_put(twl, 0, wI, t), tF = hc_twc_put(twl, 1, wF, t);
+    HC_ROW_SYNC();        // wave-local: an image is written and read by the lanes of one wavefront
+    hc_cols_inv_twl<false>(HcLazy<>{QP}, lds, TPinv, tI, c, tid, e, TPinv.ninv, TPinv.w_last_ninv);         // N^-1 mod P is inside the key rows (hc_evk_load)
 #pragma unroll
     for (int hi = 0; hi < 16; hi++) {
         const u64 yv = hc_canon4(e[hi], QP);                       // [d]_P in [0,P)
@@ -1246,7 +1288,7 @@ __global__ __launch_bounds__(HC_TPB, HC_W_B4) void hc_k_b4(HcLoopB B, HcTwTab TP
         e[hi] = r;
     }
     __syncthreads();
-    hc_cols_fwd(HcLazy<FM>{Q}, lds, T0fwd, c, tid, e);
+    hc_cols_fwd_twl(HcLazy<FM>{Q}, lds, T0fwd, tF, c, tid, e);
 #pragma unroll
     for (int lo = 0; lo < 16; lo++) base[(size_t)(tid * 16 + lo) * 256] = e[lo];
 }
