@@ -1380,45 +1380,46 @@ __global__ __launch_bounds__(HC_TPB, 3) void hc_k_b5(HcLoopB B, HcTwTab T0fwd, H
 // nobody reads it (round 3; round 4 measured re-deriving it a second time instead of carrying it: +6 % fabric traffic, not kept - profiles/round4_conv33_b5m_ab.txt).
 // The kernel waits on its loads, not on the VALU (VALU pipe 41 %, SQ_WAIT_ANY 58 %, 14.3 M L1->L2 read requests per launch, 62 % of them L2 hits on fixed tables), so
 // its shape follows the bytes a workgroup sends through the CU's address unit (profiles/b5m_request_stream_*.txt: 576 -> 352 KiB per workgroup, -37 % requests, -15 % time):
-//  * both rows-forward transforms run together on two register tiles and two LDS tiles (hc_rows_fwd2_lin): same 16 rows, same modulus, so every twiddle is loaded ONCE
-//    for both (64 KiB of per-thread twiddles instead of 128); 64 KiB of LDS, two workgroups per CU (the kernel measured the same at 2, 3 and 4), 126-159 VGPRs, no scratch;
-//    the row's 16 rowsA twiddles come through LDS (HcTwL): one load per thread at kernel entry, the image in tile l0 ahead of the first exchange;
+//  * both rows-forward transforms run together on two register tiles (hc_rows_fwd2_lin): same 16 rows, same modulus, so every twiddle is loaded ONCE for both (64 KiB of
+//    per-thread twiddles instead of 128); the row's 16 rowsA twiddles come through LDS (HcTwL): one load per thread at kernel entry, the image in the tile ahead of the
+//    first exchange;
 //  * the two fixed multiplicands (idx, the key's Q rows) are read as ONE 8-byte Montgomery word each (B.idxM, B.evkQM; hc_mont_lazy) instead of 16-byte Shoup pairs,
 //    ~12 more VALU instructions per product, and idx is read once for both polynomials;
 //  * one epilogue over the row batches does both polynomials, so t2.c1 lives for one batch and not across a transform.
+// ONE 32 KiB LDS tile serves all of it, so that LDS does not cap the kernel below what its registers allow (two tiles, 64 KiB, held it at two workgroups per CU; the
+// figures of every form are in profiles/LEDGER.md, tests/test_b5m_budget.py pins them). In the transform the two register tiles go through the tile in turn, as in hc_k_a3p.
+// In the epilogue a batch touches HC_B5_ROWS rows per polynomial: polynomial 0 of batch b goes through tile rows kk = b .. b + HC_B5_ROWS - 1, polynomial 1 through rows
+// kk ^ 8 (the Galois source stays inside the 256-coefficient row, so only the row label changes; the swizzle of hc_rows_lds uses row bit 0 alone). The one barrier per batch is
+// enough (b = a batch's first row): the two row sets of a batch are disjoint; the batches up to b + 4 touch rows disjoint from batch b's, so the writes of the batch that
+// follows b cannot reach a row that a slower wavefront still reads for batch b; batch b + 8 is the first to reuse batch b's rows, and the barrier of batch b + 4 lies between -
+// nobody passes it before everybody has finished reading batch b. This holds for HC_B5_ROWS <= 4 only (static_assert below): at 8 rows the very next batch would write the
+// rows being read, and a second barrier per batch would be needed.
 // Per row batch:
 //   m_k = I*x_k ; T = y1 - m1 ; t1_k = y_k + m_k (+ bias, k = 0) ; F_1 = (a_Q/P)*T ; F_0 = y0 - m0 + (b_Q/P)*T
-//   d_k = F_k - n_k (n_k = rows-forward of the k-th extension, divided by P by b4) ; through the LDS row of tile k ; dst_k = reduce(t1_k + perm(d_k))
+//   d_k = F_k - n_k (n_k = rows-forward of the k-th extension, divided by P by b4) ; through its row of the LDS tile ; dst_k = reduce(t1_k + perm(d_k))
 // Both kinds of product lie in (0, 2q), inside the [0, 4q) of hc_shoup4 that the lazy accounting was made for: FREE mode (Q0 < 2^57) t1 < 4q, T < 4q, d < 79q,
 // t1 + d < 83q < 2^64, one hc_reduce64 at the end; ALT mode works on canonical terms.
 #ifndef HC_B5_ROWS
-#define HC_B5_ROWS 4                  // rows per epilogue batch of hc_k_b5m, both polynomials: 4 x 7 operand loads in flight per thread and barrier (2 rows: 783 against 789 conv/s; 159 VGPRs at 4, 126 at 2)
+#define HC_B5_ROWS 2                  // rows per epilogue batch of hc_k_b5m, both polynomials: 2 x 7 operand loads in flight per thread and barrier; 127 / 124 VGPRs (4 rows: 161 / 158, three workgroups per CU, slower in every round)
 #endif
 #ifndef HC_B5M_WAVES
-#define HC_B5M_WAVES 2                // 64 KiB of LDS per workgroup: two workgroups per CU (the one-tile form measured the same at 2, 3 and 4)
+#define HC_B5M_WAVES 4                // one 32 KiB tile and at most 128 VGPRs: four workgroups per CU (128 KiB of its LDS)
 #endif
-// hc_rows_fwd on two polynomials (tiles l0, l1 of LDS), then hc_rows_lo_to_lin on both: out e_k[kk] = n_k at (row kk, column t)
+static_assert(HC_B5_ROWS <= 4 && 16 % HC_B5_ROWS == 0, "hc_k_b5m's epilogue shares one tile between the two polynomials: a batch of 8 rows needs a second barrier");
+// hc_rows_fwd_twl on two register tiles through ONE LDS tile, then lo-local -> linear on both in turn: out e_k[kk] = n_k at (row kk, column t). The text of hc_k_a3p's front end
+// under a name of its own: as a second caller of hc_rows_fwd_twl, hc_k_b5m makes the compiler schedule hc_k_a3p differently (profiles/LEDGER.md).
 template <int FM>
-__device__ __forceinline__ void hc_rows_fwd2_lin(u64 (&e0)[16], u64 (&e1)[16], u64 *l0, u64 *l1, const HcTwTab &T, const HcTw &wA, int row, int rloc, int tid, int t, const HcQ &Q) {
-    hc_ct_round(HcLazy<FM>{Q}, hc_twl_put(l0, wA, rloc, tid), e0, e1);       // the A group through LDS (HcTwL), its image in tile l0 ahead of the exchange
+__device__ __forceinline__ void hc_rows_fwd2_lin(u64 (&e0)[16], u64 (&e1)[16], u64 *lds, const HcTwTab &T, const HcTw &wA, int row, int rloc, int tid, int t, const HcQ &Q) {
+    hc_ct_round(HcLazy<FM>{Q}, hc_twl_put(lds, wA, rloc, tid), e0, e1);      // the A group through LDS (HcTwL), its image in the tile ahead of the first exchange
     HC_ROW_SYNC();        // the image has been read before the exchange lands on it
-#pragma unroll
-    for (int hi = 0; hi < 16; hi++) { const int a = hc_rows_lds(rloc, hi * 16 + tid); l0[a] = e0[hi]; l1[a] = e1[hi]; }
-    HC_ROW_SYNC();
-#pragma unroll
-    for (int lo = 0; lo < 16; lo++) { const int a = hc_rows_lds(rloc, tid * 16 + lo); e0[lo] = l0[a]; e1[lo] = l1[a]; }
+    hc_xchg(lds, [&](int hi) { return hc_rows_lds(rloc, hi * 16 + tid); }, [&](int lo) { return hc_rows_lds(rloc, tid * 16 + lo); }, [] { HC_ROW_SYNC(); }, e0, e1);
     hc_ct_round(HcLazy<FM>{Q}, HcTwB<false, HcTw>{T.rowsB + row * 256 + tid}, e0, e1);
     HC_ROW_SYNC();        // row-local: the reads before and the writes after stay inside the 16 lanes of a row
-#pragma unroll
-    for (int lo = 0; lo < 16; lo++) { const int a = hc_rows_lds(rloc, tid * 16 + lo); l0[a] = e0[lo]; l1[a] = e1[lo]; }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < 16; k++) { const int a = hc_rows_lds(k, t); e0[k] = l0[a]; e1[k] = l1[a]; }
+    hc_xchg(lds, [&](int lo) { return hc_rows_lds(rloc, tid * 16 + lo); }, [&](int kk) { return hc_rows_lds(kk, t); }, [] { __syncthreads(); }, e0, e1);
 }
 template <int FM>
 __global__ __launch_bounds__(HC_TPB, HC_B5M_WAVES) void hc_k_b5m(HcLoopB B, HcTwTab T0fwd, HcPtrs biases, HcPtrs outs) {
-    __shared__ __attribute__((aligned(16))) u64 lds[2 * HC_ROWS_LDS];
-    u64 *l0 = lds, *l1 = lds + HC_ROWS_LDS;
+    __shared__ __attribute__((aligned(16))) u64 lds[HC_ROWS_LDS];
     const int t = threadIdx.x, tid = t & 15, rloc = t >> 4, row = HC_TILE * 16 + rloc;
     const int zn = HC_JOB, z = zn / B.nodes, node = zn - z * B.nodes, i = (B.n0 + node) * B.norm;
     const HcQ Q = hc_q(B.m0.q);
@@ -1437,8 +1438,8 @@ __global__ __launch_bounds__(HC_TPB, HC_B5M_WAVES) void hc_k_b5m(HcLoopB B, HcTw
 #pragma unroll
         for (int hi = 0; hi < 16; hi++) { e0[hi] = in[hi * 16 + tid]; e1[hi] = in[65536 + hi * 16 + tid]; }
     }
-    hc_rows_fwd2_lin<FM>(e0, e1, l0, l1, T0fwd, wA, row, rloc, tid, t, Q);
-    __syncthreads();
+    hc_rows_fwd2_lin<FM>(e0, e1, lds, T0fwd, wA, row, rloc, tid, t, Q);
+    __syncthreads();      // every n_1 has been read before the first batch lands on the tile
 #pragma unroll
     for (int b = 0; b < 16; b += HC_B5_ROWS) {
         u64 Y0[HC_B5_ROWS], X0[HC_B5_ROWS], Y1[HC_B5_ROWS], X1[HC_B5_ROWS], K0[HC_B5_ROWS], K1[HC_B5_ROWS], I[HC_B5_ROWS], bs[HC_B5_ROWS], s0[HC_B5_ROWS], s1[HC_B5_ROWS];
@@ -1450,19 +1451,19 @@ __global__ __launch_bounds__(HC_TPB, HC_B5M_WAVES) void hc_k_b5m(HcLoopB B, HcTw
         }
 #pragma unroll
         for (int j = 0; j < HC_B5_ROWS; j++) {
-            const int kk = b + j, a = hc_rows_lds(kk, t);
+            const int kk = b + j, a0 = hc_rows_lds(kk, t), a1 = hc_rows_lds(kk ^ 8, t);                  // polynomial 1 goes through the row eight further on (see above)
             u64 m1 = hc_mont_lazy(X1[j], I[j], q, qinv), m0 = hc_mont_lazy(X0[j], I[j], q, qinv);            // I * x_k, in (0, 2q)
             const u64 T = hc_fold(Y1[j] + Q.q4 - m1, Q.nq4);                                               // t2.c1 (conv.go:288-289) as b1 formed it, lazy < 4q
             u64 g1 = hc_mont_lazy(T, K1[j], q, qinv), g0 = hc_mont_lazy(T, K0[j], q, qinv);                  // (key row / P) * t2.c1, in (0, 2q)
             if (FM == HC_FM_FREE) {
                 s1[j] = Y1[j] + m1; s0[j] = Y0[j] + m0 + bs[j];                                            // conv.go:290 (+ bias), < 4q
-                l1[a] = g1 + HC_FREE_OFF * q - e1[kk];                                                     // (key switch)_1 - n_1: positive (n_k < 70q), < 74q
-                l0[a] = Y0[j] + Q.q4 - m0 + g0 + HC_FREE_OFF * q - e0[kk];                                 // t2.c0 + (key switch)_0 - n_0: positive, < 79q
+                lds[a1] = g1 + HC_FREE_OFF * q - e1[kk];                                                    // (key switch)_1 - n_1: positive (n_k < 70q), < 74q
+                lds[a0] = Y0[j] + Q.q4 - m0 + g0 + HC_FREE_OFF * q - e0[kk];                                // t2.c0 + (key switch)_0 - n_0: positive, < 79q
             } else {
                 m1 = hc_canon4(m1, Q); m0 = hc_canon4(m0, Q); g1 = hc_canon4(g1, Q); g0 = hc_canon4(g0, Q);
                 s1[j] = hc_addmod(Y1[j], m1, q); s0[j] = hc_addmod(hc_addmod(Y0[j], m0, q), bs[j], q);
-                l1[a] = hc_submod(g1, hc_canon8(e1[kk], Q), q);
-                l0[a] = hc_submod(hc_addmod(hc_submod(Y0[j], m0, q), g0, q), hc_canon8(e0[kk], Q), q);
+                lds[a1] = hc_submod(g1, hc_canon8(e1[kk], Q), q);
+                lds[a0] = hc_submod(hc_addmod(hc_submod(Y0[j], m0, q), g0, q), hc_canon8(e0[kk], Q), q);
             }
         }
         __syncthreads();
@@ -1470,8 +1471,7 @@ __global__ __launch_bounds__(HC_TPB, HC_B5M_WAVES) void hc_k_b5m(HcLoopB B, HcTw
         for (int j = 0; j < HC_B5_ROWS; j++) {
             const int kk = b + j;
             const u32 srcidx = hc_perm_src((u32)((HC_TILE * 16 + kk) * 256 + t), B.gal);
-            const int a = hc_rows_lds(kk, (int)(srcidx & 255));                                            // the source is in the same row
-            const u64 d1 = l1[a], d0 = l0[a];
+            const u64 d1 = lds[hc_rows_lds(kk ^ 8, (int)(srcidx & 255))], d0 = lds[hc_rows_lds(kk, (int)(srcidx & 255))];      // the source is in the same 256-coefficient row
             o[65536 + kk * 256] = FM == HC_FM_FREE ? hc_reduce64(s1[j] + d1, B.m0.mu, Q) : hc_addmod(s1[j], d1, q);
             o[kk * 256] = FM == HC_FM_FREE ? hc_reduce64(s0[j] + d0, B.m0.mu, Q) : hc_addmod(s0[j], d0, q);
         }
