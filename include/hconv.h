@@ -293,7 +293,18 @@ int hc_conv_then_pack(hc_ctx *ctx, const uint64_t *ct_in, double ct_scale, const
  * ciphertexts, so the switching keys, idx plaintexts and twiddles are fetched once per launch and the top levels of the pack
  * tree (1..16 nodes each) are n times wider. ct_in, ker, bias (or NULL, or NULL entries), ct_out: HOST arrays of n device
  * pointers / handles (entries of ker and bias may repeat); same shapes and scales for all; results are bit-identical to n
- * separate hc_conv_then_pack calls. */
+ * separate hc_conv_then_pack calls.
+ * SEVERAL INPUT CIPHERTEXTS OF ONE CONVOLUTION (a layer with more than 2^16 / in_wid^2 input channels): consecutive members
+ * that name the SAME ct_out pointer form one group, the m input ciphertexts of ONE convolution; member z of the group contributes
+ * (ct_in[z], ker[z]), ker[z] being the plaintexts of the input channels ciphertext z holds. The group's result is, in canonical
+ * residues, what a Lattigo host gets from acc = MulNew(ct_0, pl_0[i]); Add(acc, MulNew(ct_j, pl_j[i]), acc) for j = 1 .. m-1;
+ * SetScale(acc, out_scale / (max_ob / norm)) for every live channel i, then pack_ctxts and the bias add: the products are summed
+ * at level 1, before the one MultByConst / rescale, and there is ONE pack tree and ONE bias add per group. scale_out is as for one
+ * input. Rules: all groups of a call have the same size m and n = G * m <= 16 (G > 1: an image batch of such convolutions); a
+ * group's members are consecutive; the group's bias is its first member's entry, every other member's entry is NULL or that same
+ * pointer. Groups of unequal size, a ct_out that recurs in a later, non-adjacent position and a conflicting bias entry each
+ * return HC_ERR_ARG (hc_last_error says which) before anything is launched or written. With all ct_out distinct (m = 1) the call
+ * is the one described above, launch for launch. */
 int hc_conv_then_pack_batch(hc_ctx *ctx, int n, const uint64_t *const *ct_in, double ct_scale, const hc_ker *const *ker,
                             double ker_scale, int max_ob, int norm, double out_scale, const uint64_t *const *bias,
                             uint64_t *const *ct_out, double *scale_out);

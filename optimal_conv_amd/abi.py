@@ -588,6 +588,34 @@ class Context:
         self._ck(self.L.hc_conv_then_pack_batch(self.h, n, cin, ct_scale, ck, ker_scale, max_ob, norm, out_scale, cb, co, C.byref(sc)))
         return sc.value
 
+    def conv_then_pack_multi_dev(self, groups, ct_scale, ker_scale, max_ob, norm, out_scale):
+        """convolutions with several input ciphertexts each, through hc_conv_then_pack_batch's grouping rule (consecutive members with one ct_out are the inputs of
+        ONE convolution). groups = [(ct_in_bufs, kers, bias_buf or None, out_buf), ...]: equal sizes, at most 16 members in all; one pack tree and one bias add per group"""
+        ins, kers, biases, outs = [], [], [], []
+        for g_in, g_ker, g_bias, g_out in groups:
+            if len(g_in) != len(g_ker) or not g_in:
+                raise ValueError("conv_then_pack_multi_dev: a group needs as many kernel handles as input ciphertexts, at least one")
+            ins += list(g_in); kers += list(g_ker)
+            biases += [g_bias] + [None] * (len(g_in) - 1)
+            outs += [g_out] * len(g_in)
+        return self.conv_then_pack_batch_dev(ins, ct_scale, kers, ker_scale, max_ob, norm, out_scale, biases, outs)
+
+    def conv_then_pack_multi(self, ct_ins, ct_scale, pl_kers, ker_scale, max_ob, norm, out_scale, bias=None):
+        """ONE convolution of the m input ciphertexts ct_ins[j] (2, 2, N) with their kernel plaintexts pl_kers[j] (max_ob, 2, N): the products summed at level 1, one tree"""
+        hk = [self.ker_load(k) for k in pl_kers]
+        cin = [self.buf(x) for x in ct_ins]
+        b = self.buf(bias) if bias is not None else None
+        out = self.buf(nwords=2 * self.N)
+        try:
+            sc = self.conv_then_pack_multi_dev([(cin, hk, b, out)], ct_scale, ker_scale, max_ob, norm, out_scale)
+            res = out.download((2, self.N))
+        finally:
+            for x in cin + [out] + ([b] if b is not None else []):
+                x.free()
+            for h in hk:
+                self.ker_free(h)
+        return res, sc
+
     def encode_slots(self, values, level, scale, to_ntt=True):
         """hc_encode_slots: values complex128 [count][N/2] (host) -> uint64 [count][level+1][N]"""
         v = np.ascontiguousarray(values, dtype=np.complex128).reshape(-1, self.N // 2)

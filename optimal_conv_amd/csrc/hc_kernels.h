@@ -1023,6 +1023,7 @@ struct HcLoopA {
     int slot0, slot_step;   // its result goes to cts slot slot0 + (j>>1)*slot_step (= the channel index, or a compact ordinal)
     size_t cts_stride;   // blockIdx.z = ciphertext of a batch: ctc is [z][2][2][N]; cts of consecutive ciphertexts are cts_stride words apart
     int njobs;        // jobs per ciphertext in this launch
+    int gm;           // group size m of the grouped kernels (hc_k_a1g / hc_k_a3g): blockIdx.z = group g, its members are ciphertexts g*m .. g*m + m - 1 of ctc and ker; tmp and cts are per group
     HcMod m0, m1;
     HcTw q1inv;       // Q1^-1 mod Q0
     u64 h, negh0;     // (Q1-1)>>1 ; Q0 - (h mod Q0)
@@ -1057,6 +1058,102 @@ __global__ __launch_bounds__(HC_TPB, HC_W_A1) void hc_k_a1p(HcLoopA A, HcTwTab T
 #pragma unroll
         for (int kk = 0; kk < 16; kk++) { f0[kk] = hc_f64_reduce(hc_f64_from_u(e0[kk]), m.q, m.qinv); f1[kk] = hc_f64_reduce(hc_f64_from_u(e1[kk]), m.q, m.qinv); }   // 4*Q1 < 2^51: exact; |f| <= Q1/2
         hc_rows_inv2_f64(f0, f1, lds, T1inv, wA, row, rloc, tid, m);
+#pragma unroll
+        for (int hi = 0; hi < 16; hi++) { o[hi * 16 + tid] = hc_d2u(f0[hi]); o[65536 + hi * 16 + tid] = hc_d2u(f1[hi]); }
+    } else {
+        hc_rows_inv_twl(HcLazy<>{Q}, lds, T1inv, wA, row, rloc, tid, e0, e1);
+#pragma unroll
+        for (int hi = 0; hi < 16; hi++) { o[hi * 16 + tid] = e0[hi]; o[65536 + hi * 16 + tid] = e1[hi]; }
+    }
+}
+// KA1 for a group of m input ciphertexts of ONE convolution (hc_conv_then_pack_batch's members with one ct_out): a_1 = sum_j c'_j,p[1] (*) k_j,i[1] mod Q1, summed before the one
+// rows-inverse pass. grid = (jobs / 2, 16, groups): blockIdx.z = group g, member j is ciphertext g*m + j of ctc and ker; tmp is per group. Every term is a hc_shoup4 product in [0, 4*Q1).
+//   F64 = 1 (Q1 < 2^49, every Q0 class): a term is below 2^51, so TWO terms sum below 2^52, which is what hc_f64_from_u converts exactly (its bit trick ends at 2^52, not 2^53): the
+//     members go in pairs, each pair sum is folded by hc_f64_reduce to |.| <= Q1/2 + 1 and added in fp64. At most 8 pair sums (m <= HC_MAXB = 16): |sum| <= 8 (Q1/2 + 1) < 2^51 + 8,
+//     an exact integer; one more hc_f64_reduce gives the |f| <= Q1/2 + 1 that hc_rows_inv2_f64 takes from hc_k_a1p. An odd m leaves its last member alone in its pair.
+//   F64 = 0 (2^49 <= Q1, 4*Q1 < 2^64): 4*Q1 may reach 2^63 and beyond, so two lazy terms can already pass 2^64. Each term is made canonical (hc_canon4: [0, 4*Q1) -> [0, Q1)) and
+//     added to a canonical sum with one conditional subtraction (hc_fold at Q1: acc + term < 2*Q1 <= 2^63): the sum stays in [0, Q1), inside the [0, 4*Q1) the transform takes.
+// The sums are congruent to the one-input kernel's product summed over the members, and everything after the transform is canonical, so the words are those of the Lattigo sequence.
+// hc_rows_inv2_f64 and hc_k_a3p's front end (hc_rows_fwd_twl on two tiles, then lo-local -> linear) under names of their own: as second callers of those helpers the grouped kernels
+// make the compiler schedule hc_k_a1p<1> and hc_k_a3p differently (152 -> 144 and 147 / 145 -> 143 / 142 VGPRs, 40 - 50 more lines each; as with hc_rows_fwd2_lin, profiles/LEDGER.md),
+// and the one-input path is to stay the machine code it was.
+__device__ __forceinline__ void hc_rows_inv2_f64_g(double (&f0)[16], double (&f1)[16], u64 *lds, const HcTwTab &T, const HcTw &wA, int row, int rloc, int tid, HcF64Mod m) {
+    hc_gs_round2_f64(f0, f1, HcTwB<false, HcTw>{T.rowsB + row * 256 + tid}, m);
+    u64 b0[16], b1[16];
+#pragma unroll
+    for (int i = 0; i < 16; i++) { b0[i] = hc_d2u(f0[i]); b1[i] = hc_d2u(f1[i]); }
+    hc_xchg(lds, [&](int lo) { return hc_rows_lds(rloc, tid * 16 + lo); }, [&](int hi) { return hc_rows_lds(rloc, hi * 16 + tid); }, [] { HC_ROW_SYNC(); }, b0, b1);
+#pragma unroll
+    for (int i = 0; i < 16; i++) { f0[i] = hc_u2d(b0[i]); f1[i] = hc_u2d(b1[i]); }
+    hc_gs_round2_f64(f0, f1, hc_twl_put(lds, wA, rloc, tid), m);        // the A group through LDS (HcTwL), behind the last read-back
+}
+template <int FM>
+__device__ __forceinline__ void hc_rows_fwd2_lin_g(u64 (&e0)[16], u64 (&e1)[16], u64 *lds, const HcTwTab &T, const HcTw &wA, int row, int rloc, int tid, int t, const HcQ &Q) {
+    hc_ct_round(HcLazy<FM>{Q}, hc_twl_put(lds, wA, rloc, tid), e0, e1);      // the A group through LDS (HcTwL), its image in the tile ahead of the first exchange
+    HC_ROW_SYNC();        // the image has been read before the exchange lands on it
+    hc_xchg(lds, [&](int hi) { return hc_rows_lds(rloc, hi * 16 + tid); }, [&](int lo) { return hc_rows_lds(rloc, tid * 16 + lo); }, [] { HC_ROW_SYNC(); }, e0, e1);
+    hc_ct_round(HcLazy<FM>{Q}, HcTwB<false, HcTw>{T.rowsB + row * 256 + tid}, e0, e1);
+    HC_ROW_SYNC();        // row-local: the reads before and the writes after stay inside the 16 lanes of a row
+    hc_xchg(lds, [&](int lo) { return hc_rows_lds(rloc, tid * 16 + lo); }, [&](int kk) { return hc_rows_lds(kk, t); }, [] { __syncthreads(); }, e0, e1);
+}
+template <int F64>
+__global__ __launch_bounds__(HC_TPB, HC_W_A1) void hc_k_a1g(HcLoopA A, HcTwTab T1inv) {
+    __shared__ __attribute__((aligned(16))) u64 lds[HC_ROWS_LDS];
+    const int t = threadIdx.x, tid = t & 15, rloc = t >> 4, row = HC_TILE * 16 + rloc;
+    const int ch = HC_JOB, i = A.i0 + ch * A.norm, g = blockIdx.z, m = A.gm;
+    const size_t tile = (size_t)HC_TILE * 4096 + t;
+    const HcQ Q = hc_q(A.m1.q);
+    const HcTw wA = hc_twl_load(T1inv, HC_TILE, t);
+    const HcF64Mod fm{(double)A.m1.q, 1.0 / (double)A.m1.q};
+    u64 e0[16], e1[16];
+    if (F64) {
+        double f0[16], f1[16];
+#pragma unroll
+        for (int kk = 0; kk < 16; kk++) f0[kk] = f1[kk] = 0.0;
+        for (int j = 0; j < m; j += 2) {
+            const bool two = j + 1 < m;
+            const int za = g * m + j, zb = two ? za + 1 : za;
+            const HcTw *__restrict__ ca = A.ctc + ((size_t)za * 4 + 1) * 65536 + tile, *__restrict__ cb = A.ctc + ((size_t)zb * 4 + 1) * 65536 + tile;
+            const u64 *__restrict__ ka = A.ker.p[za] + ((size_t)i * 2 + 1) * 65536 + tile, *__restrict__ kb = A.ker.p[zb] + ((size_t)i * 2 + 1) * 65536 + tile;
+#pragma unroll
+            for (int kk = 0; kk < 16; kk++) {
+                const u64 kv = ka[kk * 256];
+                const HcTw w0 = ca[kk * 256], w1 = ca[2 * 65536 + kk * 256];
+                u64 s0 = hc_shoup4(kv, w0.w, w0.ws, Q), s1 = hc_shoup4(kv, w1.w, w1.ws, Q);            // [0, 4*Q1) < 2^51
+                if (two) {
+                    const u64 kv2 = kb[kk * 256];
+                    const HcTw x0 = cb[kk * 256], x1 = cb[2 * 65536 + kk * 256];
+                    s0 += hc_shoup4(kv2, x0.w, x0.ws, Q); s1 += hc_shoup4(kv2, x1.w, x1.ws, Q);         // < 2^52
+                }
+                f0[kk] += hc_f64_reduce(hc_f64_from_u(s0), fm.q, fm.qinv); f1[kk] += hc_f64_reduce(hc_f64_from_u(s1), fm.q, fm.qinv);
+            }
+        }
+#pragma unroll
+        for (int kk = 0; kk < 16; kk++) { e0[kk] = hc_d2u(hc_f64_reduce(f0[kk], fm.q, fm.qinv)); e1[kk] = hc_d2u(hc_f64_reduce(f1[kk], fm.q, fm.qinv)); }
+    } else {
+#pragma unroll
+        for (int kk = 0; kk < 16; kk++) e0[kk] = e1[kk] = 0;
+        for (int j = 0; j < m; j++) {
+            const int z = g * m + j;
+            const HcTw *__restrict__ c0 = A.ctc + ((size_t)z * 4 + 1) * 65536 + tile;
+            const u64 *__restrict__ k = A.ker.p[z] + ((size_t)i * 2 + 1) * 65536 + tile;
+#pragma unroll
+            for (int kk = 0; kk < 16; kk++) {
+                const u64 kv = k[kk * 256];
+                const HcTw w0 = c0[kk * 256], w1 = c0[2 * 65536 + kk * 256];
+                e0[kk] = hc_fold(e0[kk] + hc_canon4(hc_shoup4(kv, w0.w, w0.ws, Q), Q), Q.nq);           // [0, Q1)
+                e1[kk] = hc_fold(e1[kk] + hc_canon4(hc_shoup4(kv, w1.w, w1.ws, Q), Q), Q.nq);
+            }
+        }
+    }
+    u64 *o = A.tmp + ((size_t)g * A.njobs + 2 * ch) * 65536 + (size_t)row * 256;     // polynomial 1 is 65536 words on
+    hc_xchg(lds, [&](int kk) { return hc_rows_lds(kk, t); }, [&](int lo) { return hc_rows_lds(rloc, tid * 16 + lo); }, [] { __syncthreads(); }, e0, e1);   // F64: the doubles' bit patterns
+    HC_ROW_SYNC();        // row-local: the reads before and the writes after stay inside the 16 lanes of a row
+    if (F64) {
+        double f0[16], f1[16];
+#pragma unroll
+        for (int kk = 0; kk < 16; kk++) { f0[kk] = hc_u2d(e0[kk]); f1[kk] = hc_u2d(e1[kk]); }
+        hc_rows_inv2_f64_g(f0, f1, lds, T1inv, wA, row, rloc, tid, fm);
 #pragma unroll
         for (int hi = 0; hi < 16; hi++) { o[hi * 16 + tid] = hc_d2u(f0[hi]); o[65536 + hi * 16 + tid] = hc_d2u(f1[hi]); }
     } else {
@@ -1142,6 +1239,53 @@ __global__ __launch_bounds__(HC_TPB, HC_W_A3) void hc_k_a3p(HcLoopA A, HcTwTab T
             // FREE: u = e < 70q stays lazy, a_0 + 72q - u is positive and below 2^64; ALT (8q < 2^64 only): u canonical first
             const u64 d0 = FM == HC_FM_FREE ? a0 + HC_FREE_OFF * Q.q - e0[kk] : a0 + Q.q - hc_canon8(e0[kk], Q);
             const u64 d1 = FM == HC_FM_FREE ? a1 + HC_FREE_OFF * Q.q - e1[kk] : a1 + Q.q - hc_canon8(e1[kk], Q);
+            o[kk * 256] = hc_canon4(hc_shoup4(d0, A.q1inv.w, A.q1inv.ws, Q), Q);
+            o[65536 + kk * 256] = hc_canon4(hc_shoup4(d1, A.q1inv.w, A.q1inv.ws, Q), Q);
+        }
+    }
+}
+// KA3 for a group of m input ciphertexts (see hc_k_a1g): a_0 = sum_j c'_j,p[0] (*) k_j,i[0] is formed in the epilogue, row batch by row batch: per member HC_A3_ROWS plaintext words
+// beside its 2 x HC_A3_ROWS c' pairs, so no plaintext tile is held across the transform (the one-input kernel's kv[16]). grid = (jobs / 2, 16, groups).
+// The running sum is folded once per member (hc_fold at 4q: sum < 4q, term < 4q, sum + term < 8q -> [0, 4q)), which needs 8q < 2^64 - what HC_FM_ALT already asks - and 4q <= 2^63.
+// The sum then has the range of the one-input kernel's single product, and both epilogue forms stand as they are there: FREE a_0 + 72q - u with u < 70q (76q < 2^64 at q < 2^57;
+// the unfolded sum would need (4m + 72) q < 2^64, which m = 16 misses just below 2^57), ALT a_0 + q - canon8(u) < 5q.
+template <int FM>
+__global__ __launch_bounds__(HC_TPB, HC_W_A3) void hc_k_a3g(HcLoopA A, HcTwTab T0fwd) {
+    __shared__ __attribute__((aligned(16))) u64 lds[HC_ROWS_LDS];
+    const int t = threadIdx.x, tid = t & 15, rloc = t >> 4, row = HC_TILE * 16 + rloc;
+    const int ch = HC_JOB, i = A.i0 + ch * A.norm, g = blockIdx.z, m = A.gm;
+    const size_t tile = (size_t)HC_TILE * 4096 + t;
+    const u64 *__restrict__ in = A.tmp + ((size_t)g * A.njobs + 2 * ch) * 65536 + (size_t)row * 256;
+    u64 *__restrict__ o = A.cts + (size_t)g * A.cts_stride + (size_t)(A.slot0 + ch * A.slot_step) * 2 * 65536 + tile;
+    const HcQ Q = hc_q(A.m0.q);
+    const HcTw wA = hc_twl_load(T0fwd, HC_TILE, t);
+    u64 e0[16], e1[16];
+#pragma unroll
+    for (int hi = 0; hi < 16; hi++) { e0[hi] = in[hi * 16 + tid]; e1[hi] = in[65536 + hi * 16 + tid]; }
+    hc_rows_fwd2_lin_g<FM>(e0, e1, lds, T0fwd, wA, row, rloc, tid, t, Q);
+#pragma unroll
+    for (int b = 0; b < 16; b += HC_A3_ROWS) {
+        u64 a0[HC_A3_ROWS], a1[HC_A3_ROWS];
+#pragma unroll
+        for (int r = 0; r < HC_A3_ROWS; r++) a0[r] = a1[r] = 0;
+        for (int j = 0; j < m; j++) {
+            const int z = g * m + j;
+            const HcTw *__restrict__ c0 = A.ctc + (size_t)z * 4 * 65536 + tile;                 // c'_j,0[0] ; c'_j,1[0] is 2 * 65536 pairs on
+            const u64 *__restrict__ k = A.ker.p[z] + ((size_t)i * 2) * 65536 + tile;
+            u64 kv[HC_A3_ROWS]; HcTw w0[HC_A3_ROWS], w1[HC_A3_ROWS];
+#pragma unroll
+            for (int r = 0; r < HC_A3_ROWS; r++) { kv[r] = k[(b + r) * 256]; w0[r] = c0[(b + r) * 256]; w1[r] = c0[2 * 65536 + (b + r) * 256]; }
+#pragma unroll
+            for (int r = 0; r < HC_A3_ROWS; r++) {
+                a0[r] = hc_fold(a0[r] + hc_shoup4(kv[r], w0[r].w, w0[r].ws, Q), Q.nq4);      // [0, 4q)
+                a1[r] = hc_fold(a1[r] + hc_shoup4(kv[r], w1[r].w, w1[r].ws, Q), Q.nq4);
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < HC_A3_ROWS; r++) {
+            const int kk = b + r;
+            const u64 d0 = FM == HC_FM_FREE ? a0[r] + HC_FREE_OFF * Q.q - e0[kk] : a0[r] + Q.q - hc_canon8(e0[kk], Q);
+            const u64 d1 = FM == HC_FM_FREE ? a1[r] + HC_FREE_OFF * Q.q - e1[kk] : a1[r] + Q.q - hc_canon8(e1[kk], Q);
             o[kk * 256] = hc_canon4(hc_shoup4(d0, A.q1inv.w, A.q1inv.ws, Q), Q);
             o[65536 + kk * 256] = hc_canon4(hc_shoup4(d1, A.q1inv.w, A.q1inv.ws, Q), Q);
         }

@@ -867,8 +867,9 @@ static int hc_prepare_ctc(hc_ctx *c, const HcPtrs &ct_in, int n, const u64 cst[2
 }
 
 // loop A over the channels i = i_first + j*i_stride, j < nch, of each of the n ciphertexts of a batch (blockIdx.z); result j goes to
-// cts slot i (compact = false) or j of that ciphertext's array (arrays cts_stride words apart)
-static int hc_loopA_run_set(hc_ctx *c, const HcPtrs &kers, int n, int i_first, int i_stride, int nch, u64 *cts, size_t cts_stride, bool compact) {
+// cts slot i (compact = false) or j of that ciphertext's array (arrays cts_stride words apart). gm > 1: the n outputs are GROUPS of gm input ciphertexts each (c' and kers hold
+// n * gm members, group g's at g*gm ..): the grouped a1 / a3 sum the members' products, a2 and everything sized by output jobs (chunk, tmp, cts) count n. gm = 1 launches what it always did.
+static int hc_loopA_run_set(hc_ctx *c, const HcPtrs &kers, int n, int i_first, int i_stride, int nch, u64 *cts, size_t cts_stride, bool compact, int gm = 1) {
     long chunk = (c->chunk_nodes < 1 ? 1 : c->chunk_nodes) / n; if (chunk < 1) chunk = 1;     // channels per ciphertext per launch
     if (chunk > nch) chunk = nch;
     HC_TRY(hc_ensure_tmp(c, (size_t)n * (size_t)chunk * 2));
@@ -878,8 +879,17 @@ static int hc_loopA_run_set(hc_ctx *c, const HcPtrs &kers, int n, int i_first, i
         const int nj = (int)((nch - j0) < chunk ? (nch - j0) : chunk);
         A.i0 = i_first + j0 * i_stride;
         A.slot0 = compact ? j0 : A.i0; A.slot_step = compact ? 1 : i_stride;
-        A.njobs = 2 * nj;
+        A.njobs = 2 * nj; A.gm = gm;
         const dim3 pair = hc_grid(nj, n), flat = hc_grid(2 * nj * n);            // a1, a3: one workgroup per channel and tile does both polynomials
+        if (gm > 1) {
+            const bool f64 = hc_f64_ok(m1.m.q);
+            const HcTwTab &t1 = f64 ? m1.inv_f64 : m1.inv;
+            HC_TRY(f64 ? hc_launch(c, "a1g_mulsum_rowsinv", hc_k_a1g<1>, pair, A, t1) : hc_launch(c, "a1g_mulsum_rowsinv", hc_k_a1g<0>, pair, A, t1));
+            if (f64) HC_TRY(hc_fm_free(m0.m.q) ? hc_launch(c, "a2_colsinv_lift_colsfwd", hc_k_a2<HC_FM_FREE, 1>, flat, A, t1, m0.fwd) : hc_launch(c, "a2_colsinv_lift_colsfwd", hc_k_a2<HC_FM_ALT, 1>, flat, A, t1, m0.fwd));
+            else HC_TRY(hc_fm_free(m0.m.q) ? hc_launch(c, "a2_colsinv_lift_colsfwd", hc_k_a2<HC_FM_FREE, 0>, flat, A, t1, m0.fwd) : hc_launch(c, "a2_colsinv_lift_colsfwd", hc_k_a2<HC_FM_ALT, 0>, flat, A, t1, m0.fwd));
+            HC_TRY(HC_LAUNCH_FM(m0.m.q, c, "a3g_rowsfwd_sum_rescale", hc_k_a3g, pair, A, m0.fwd));
+            continue;
+        }
         if (hc_f64_ok(m1.m.q)) {
             HC_TRY(hc_launch(c, "a1_mul_rowsinv", hc_k_a1p<1>, pair, A, m1.inv_f64));
             HC_TRY(hc_fm_free(m0.m.q) ? hc_launch(c, "a2_colsinv_lift_colsfwd", hc_k_a2<HC_FM_FREE, 1>, flat, A, m1.inv_f64, m0.fwd)
@@ -1793,14 +1803,17 @@ extern "C" int hc_conv_mult_phase(hc_ctx *c, const uint64_t *ct_in, double ct_sc
 // n convolutions (same shape and scales, independent ciphertexts) as ONE launch set: every kernel of loop A and of the pack tree
 // covers all n ciphertexts (a grid dimension), the switching keys, idx plaintexts and twiddle tables are shared, and the top tree
 // levels (1..16 nodes per ciphertext, latency-bound when launched alone) carry n times the work per launch.
+// gm > 1: the n members are n / gm groups of gm input ciphertexts, each group ONE convolution (loop A sums the members' products at level 1); bias and ct_out are then per GROUP
+// (entries 0 .. n / gm - 1), and the tree, the bias add and the workspaces ws_cts / ws_tmp see n / gm ciphertexts. Only c' (ws_ctc) is per member.
 static int hc_conv_batch_run(hc_ctx *c, int n, const HcPtrs &ct_in, const HcPtrs &kers, const HcPtrs &bias, bool any_bias, u64 *const *ct_out,
-                             int max_ob, int norm, const u64 cst[2]) {
+                             int max_ob, int norm, const u64 cst[2], int gm = 1) {
+    const int G = n / gm;
     HC_TRY(hc_prepare_ctc(c, ct_in, n, cst));
-    HC_TRY(hc_ensure_cts(c, (size_t)n * max_ob * 2));
+    HC_TRY(hc_ensure_cts(c, (size_t)G * max_ob * 2));
     const size_t cstride = (size_t)max_ob * 2 * HC_N;
-    HC_TRY(hc_loopA_run_set(c, kers, n, 0, norm, max_ob / norm, c->ws_cts, cstride, false));
-    HcPtrs outs; memset(&outs, 0, sizeof outs); for (int z = 0; z < n; z++) outs.p[z] = ct_out[z];
-    return hc_pack_run(c, c->ws_cts, cstride, n, max_ob, max_ob / norm, any_bias ? &bias : nullptr, 0, &outs);      // the root node writes ct_out itself
+    HC_TRY(hc_loopA_run_set(c, kers, G, 0, norm, max_ob / norm, c->ws_cts, cstride, false, gm));
+    HcPtrs outs; memset(&outs, 0, sizeof outs); for (int z = 0; z < G; z++) outs.p[z] = ct_out[z];
+    return hc_pack_run(c, c->ws_cts, cstride, G, max_ob, max_ob / norm, any_bias ? &bias : nullptr, 0, &outs);      // the root node writes ct_out itself
 }
 extern "C" int hc_conv_then_pack(hc_ctx *c, const uint64_t *ct_in, double ct_scale, const hc_ker *ker, double ker_scale,
                                  int max_ob, int norm, double out_scale, const uint64_t *bias, uint64_t *ct_out, double *scale_out) {
@@ -1823,16 +1836,27 @@ extern "C" int hc_conv_then_pack_batch(hc_ctx *c, int n, const uint64_t *const *
     if (!ct_in || !ker || !ct_out) return hc_fail(c, HC_ERR_ARG, "hc_conv_then_pack_batch: null");
     HcPtrs pin, pker, pbias; memset(&pin, 0, sizeof pin); memset(&pker, 0, sizeof pker); memset(&pbias, 0, sizeof pbias);
     u64 *outs[HC_MAXB]; bool any_bias = false;
-    for (int z = 0; z < n; z++) {
+    // consecutive members with one ct_out are the input ciphertexts of ONE convolution: G groups of equal size gm, outs / pbias per group. All checks come before any launch.
+    int G = 0, gm = 0;
+    for (int z = 0, z0 = 0; z < n; z++) {
         if (!ct_in[z] || !ker[z] || !ct_out[z] || ker[z]->max_ob < max_ob) return hc_fail(c, HC_ERR_ARG, "hc_conv_then_pack_batch: bad arguments for ciphertext %d", z);
-        pin.p[z] = (const u64 *)ct_in[z]; pker.p[z] = ker[z]->d; outs[z] = (u64 *)ct_out[z];
-        if (bias && bias[z]) { pbias.p[z] = (const u64 *)bias[z]; any_bias = true; }
+        pin.p[z] = (const u64 *)ct_in[z]; pker.p[z] = ker[z]->d;
+        const u64 *b = bias ? (const u64 *)bias[z] : nullptr;
+        if (z == 0 || ct_out[z] != ct_out[z - 1]) {        // a group's first member: it names the output and the bias
+            for (int y = 0; y < G; y++) if (outs[y] == (u64 *)ct_out[z]) return hc_fail(c, HC_ERR_ARG, "hc_conv_then_pack_batch: ct_out of member %d repeats a non-adjacent member's (a group's members must be consecutive)", z);
+            if (G == 1) gm = z;
+            if (G >= 1 && z - z0 != gm) return hc_fail(c, HC_ERR_ARG, "hc_conv_then_pack_batch: groups of unequal size (%d members, then %d)", gm, z - z0);
+            z0 = z; outs[G] = (u64 *)ct_out[z];
+            if (b) { pbias.p[G] = b; any_bias = true; }
+            G++;
+        } else if (b && b != pbias.p[G - 1]) return hc_fail(c, HC_ERR_ARG, "hc_conv_then_pack_batch: bias of member %d conflicts with its group's (the first member's entry; the others NULL or the same pointer)", z);
+        if (z == n - 1) { if (G == 1) gm = n; else if (n - z0 != gm) return hc_fail(c, HC_ERR_ARG, "hc_conv_then_pack_batch: groups of unequal size (%d members, then %d)", gm, n - z0); }
     }
     u64 cst[2]; double target;
     HC_TRY(hc_loopA_consts(c, ct_scale, ker_scale, max_ob, norm, out_scale, cst, &target));
     const double final_scale = target * (double)(max_ob / norm);
     if (final_scale != out_scale) return hc_fail(c, HC_ERR_STATE, "LV or scale after conv then pack, inconsistent");
-    HC_TRY(hc_conv_batch_run(c, n, pin, pker, pbias, any_bias, outs, max_ob, norm, cst));
+    HC_TRY(hc_conv_batch_run(c, n, pin, pker, pbias, any_bias, outs, max_ob, norm, cst, gm));
     if (scale_out) *scale_out = final_scale;
     return HC_OK;
 }

@@ -7,6 +7,9 @@
 // `transconv <ker_wid 3|5|7> <i_batch 0..3> <num_tests <= 10>` (not a reference command; the reference builds TransConv's operators but runs
 // none of them): stride-2 transposed convolution, Ours only (the reference's baseline side of it is unfinished), on
 // test_conv_data/test_transconv{k}_batch_{B}_{in,ker,bna,bnb,out}_{t}.csv with raw width widths[i]/2 - k/2, B in and B/4 out channels.
+// `multiconv <ker_wid 3|5|7> <i_batch 0..3> <num_tests <= 10> <n_in 1..16>` (not a reference command): `conv`'s layer with n_in * B input channels held in n_in input
+// ciphertexts and B output channels, as ONE convolution (the products summed at level 1, one pack tree), Ours only, on
+// test_conv_data/test_multiconv{k}_batch_{B}_in{n_in}_{in,ker,bna,bnb,out}_{t}.csv (tests/golden/gen_multiconv_csv.py). HCONV_IMAGE_BATCH = g: g images, g * n_in <= 16.
 // `resnet_fast <ker_wid> <depth> 1 <test_num> false` (not a reference command: the reference reaches testResNet_crop_fast_in, test.go:372-636, only by swapping
 // main.go:620-622): the same network as `resnet` on full slots, one bootstrapper (hconv_resnet.cpp). Same arguments; wide_case != 1 and cf100 are refused like `resnet`'s.
 // HCONV_SKIP_BL=1 skips the baseline half (not a reference feature; for timing "Ours" alone).
@@ -62,6 +65,17 @@ int main(int argc, char **argv) {
         printf("Ker:  %d batches:  %d widths:  %d\n", ker_wid, batchs[i_batch], widths[i_batch]);
         printf("Ours start.\n");
         hconv::testTransConv_in(batchs[i_batch], widths[i_batch], ker_wid, num_tests);
+        return 0;
+    } else if (test_name == "multiconv") {                              // not a reference command (see the top of this file)
+        if (argc < 6) hconv::panic("runtime error: index out of range (usage: multiconv <ker_wid> <i_batch> <num_tests> <n_in>)");
+        if (num_tests > 10 || i_batch > 3) hconv::panic("Too many tests (>10) or too many batch index (>3)");
+        if (i_batch < 0) hconv::panic("runtime error: index out of range");
+        const int n_in = atoi(argv[5]);
+        if (n_in < 1 || n_in > 16) hconv::panic("Wrong number of input ciphertexts (not in 1..16)");
+        printf("Multi-input convolution test start! (No Bootstrapping)\n");
+        printf("Ker:  %d batches:  %d widths:  %d\n", ker_wid, batchs[i_batch], widths[i_batch]);
+        printf("Ours start.\n");
+        hconv::testMultiConv_in(batchs[i_batch], widths[i_batch], ker_wid, num_tests, n_in);
         return 0;
     } else hconv::panic("wrong test type");
     if (i_batch < 0) hconv::panic("runtime error: index out of range");

@@ -649,6 +649,126 @@ std::vector<Ciphertext> evalConv_BN_batch(Context *c, const std::vector<Cipherte
     return res;
 }
 
+// evalConv_BN for a layer whose real_ib = m * ib input channels fill m input ciphertexts (not a reference routine: the reference's networks split the output side only,
+// test.go:1499-1541, because with its evaluator an input split costs m pack trees). ker_in is HWIO over all real_ib channels; ciphertext j of a group holds the channels
+// j*ib .. (j+1)*ib - 1, and its plaintexts are prep_Ker of that channel slice with the same bn_a. hc_conv_then_pack_batch's grouping rule (members with one ct_out) sums the
+// m products at level 1, ahead of the one SetScale, and runs ONE pack tree and ONE bias add per group. groups: the images of a batch, each its m input ciphertexts.
+std::vector<Ciphertext> evalConv_BN_multi_batch(Context *c, const std::vector<std::vector<Ciphertext>> &groups, const std::vector<double> &ker_in, const std::vector<double> &bn_a,
+                                                const std::vector<double> &bn_b, int in_wid, int ker_wid, int real_ib, int real_ob, int norm, double out_scale) {
+    const int G = (int)groups.size(), m = G ? (int)groups[0].size() : 0, n = G * m;
+    if (G < 1 || m < 1 || n > 16) panic("evalConv_BN_multi: 1..16 input ciphertexts in all (images x ciphertexts per image)");
+    if (real_ib % m) panic("evalConv_BN_multi: the input channels do not divide into the input ciphertexts");
+    const int ib = real_ib / m, k_sz = ker_wid * ker_wid;
+    if ((int)ker_in.size() != k_sz * real_ib * real_ob) panic("evalConv_BN_multi: kernel size inconsistent");
+    const int max_batch = N / (in_wid * in_wid);
+    auto start = now();
+    std::vector<KerPlain> pl_ker((size_t)m);
+    std::vector<double> slice((size_t)k_sz * ib * real_ob);
+    for (int j = 0; j < m; j++) {
+        for (int t = 0; t < k_sz; t++) for (int ch = 0; ch < ib; ch++) for (int o = 0; o < real_ob; o++)
+            slice[(size_t)o + (size_t)ch * real_ob + (size_t)t * real_ob * ib] = ker_in[(size_t)o + (size_t)(j * ib + ch) * real_ob + (size_t)t * real_ob * real_ib];
+        pl_ker[(size_t)j] = prep_Ker(c, slice, bn_a, in_wid, ker_wid, ib, real_ob, norm, c->ECD_LV, 0, false);
+    }
+    std::vector<double> b_coeffs((size_t)N, 0.0);
+    for (size_t i = 0; i < bn_b.size(); i++) for (int j = 0; j < in_wid * in_wid; j++) b_coeffs[(size_t)(norm * (int)i + j * max_batch)] = bn_b[i];   // eval.go:233-238
+    Plaintext pl_bn_b; pl_bn_b.level = 0; pl_bn_b.Scale = out_scale;
+    pl_bn_b.d = dev_upload(c, EncodeCoeffs(b_coeffs, 0, out_scale));
+    HC(c->hc, hc_ntt(c->hc, 0, pl_bn_b.d, pl_bn_b.d, 1));                                                              // eval.go:242-243
+    HC(c->hc, hc_sync(c->hc));
+    printf("Plaintext (kernel) preparation, Done in %s \n", dur(start).c_str());                                      // eval.go:244
+    start = now();
+    std::vector<Ciphertext> res((size_t)G); std::vector<const uint64_t *> ins((size_t)n), bias((size_t)n, nullptr); std::vector<const hc_ker *> kers((size_t)n); std::vector<uint64_t *> outs((size_t)n);
+    const Ciphertext &first = groups[0][0];
+    for (int g = 0; g < G; g++) {
+        if ((int)groups[(size_t)g].size() != m) panic("evalConv_BN_multi: every image has the same number of input ciphertexts");
+        res[(size_t)g].d = dev_rows(c, 2); res[(size_t)g].level = 0;
+        for (int j = 0; j < m; j++) {
+            const Ciphertext &ct = groups[(size_t)g][(size_t)j]; const size_t z = (size_t)g * m + j;
+            if (ct.Scale != first.Scale || ct.level != first.level) panic("evalConv_BN_multi: the input ciphertexts share level and scale");
+            ins[z] = ct.d; kers[z] = pl_ker[(size_t)j].h; outs[z] = res[(size_t)g].d;
+        }
+        bias[(size_t)g * m] = pl_bn_b.d;                                  // the group's bias is its first member's entry
+    }
+    double sc = 0;
+    if (hc_conv_then_pack_batch(c->hc, n, ins.data(), first.Scale, kers.data(), pl_ker[0].Scale, max_batch, norm, out_scale, bias.data(), outs.data(), &sc)) panic(std::string("hc_conv_then_pack_batch: ") + hc_last_error(c->hc));   // conv.go:541-543's panic included
+    // one launch set does both of conv_then_pack's phases: "mult time" is the time to queue it, "Pack time" the time until the results are complete
+    printf("\t mult time:  %s\n", dur(start).c_str());
+    auto mt = now();
+    HC(c->hc, hc_sync(c->hc));
+    printf("\t Pack time:  %s\n", dur(mt).c_str());
+    for (int g = 0; g < G; g++) res[(size_t)g].Scale = sc;
+    if (G > 1) printf("Conv (with BN) Done in %s  (%d images)\n", dur(start).c_str(), G);
+    else printf("Conv (with BN) Done in %s \n", dur(start).c_str());                                                  // eval.go:260
+    for (KerPlain &k : pl_ker) { hc_ker_free(c->hc, k.h); for (size_t g = 1; g < k.shard_h.size(); g++) hc_ker_free(c->shards[g], k.shard_h[g]); }
+    HC(c->hc, hc_free(c->hc, pl_bn_b.d));
+    return res;
+}
+Ciphertext evalConv_BN_multi(Context *c, const std::vector<Ciphertext> &ct_inputs, const std::vector<double> &ker_in, const std::vector<double> &bn_a,
+                             const std::vector<double> &bn_b, int in_wid, int ker_wid, int real_ib, int real_ob, int norm, double out_scale) {
+    return evalConv_BN_multi_batch(c, {ct_inputs}, ker_in, bn_a, bn_b, in_wid, ker_wid, real_ib, real_ob, norm, out_scale)[0];
+}
+
+// ---------------------------------------------------------------- testMultiConv_in (not a reference routine: testConv_in's shape for n_in input ciphertexts)
+// n_in * in_batch input channels on the raw width in_wid - ker_wid/2, in_batch output channels: the layer testConv_in runs, with n_in times the input channels. Ours only,
+// without bootstrapping. HCONV_IMAGE_BATCH = g: g independent encryptions of the image as g groups of one call (g * n_in <= 16).
+void testMultiConv_in(int in_batch, int in_wid, int ker_wid, int total_test_num, int n_in) {
+    const std::string kind = "Conv";
+    const int raw_in_wid = in_wid - ker_wid / 2, norm = 1, m = n_in;
+    const std::string test_dir = "test_conv_data/";
+    const int nimg = imageBatch();
+    if (nimg * m > 16) panic("multiconv: HCONV_IMAGE_BATCH x n_in must be <= 16 (the members of one hc_conv_then_pack_batch call)");
+    int kp_wid, out_batch, logN; bool trans;
+    set_Variables(in_batch, raw_in_wid, in_wid, ker_wid, kind, &kp_wid, &out_batch, &logN, &trans);
+    Context *cont = newContext(logN, ker_wid, {in_wid}, {kp_wid}, false, kind);
+    printf("vec size: log2 =  %d\n", cont->logN);
+    printf("raw input width:  %d\n", raw_in_wid);
+    printf("kernel width:  %d\n", ker_wid);
+    printf("num raw batches in & out:  %d ,  %d\n", m * in_batch, out_batch);
+    printf("num input ciphertexts:  %d\n", m);
+    for (int test_iter = 0; test_iter < total_test_num; test_iter++) {
+        printf("%d -th iter...start\n", test_iter + 1);
+        const std::string pre = test_dir + "test_multiconv" + std::to_string(ker_wid) + "_batch_" + std::to_string(in_batch) + "_in" + std::to_string(m) + "_";
+        const std::string suf = "_" + std::to_string(test_iter) + ".csv";
+        const int px = raw_in_wid * raw_in_wid;
+        std::vector<double> raw_input = readTxt(pre + "in" + suf, px * m * in_batch);
+        std::vector<double> ker_in = readTxt(pre + "ker" + suf, m * in_batch * out_batch * ker_wid * ker_wid);
+        std::vector<double> bn_a = readTxt(pre + "bna" + suf, out_batch);
+        std::vector<double> bn_b = readTxt(pre + "bnb" + suf, out_batch);
+        std::vector<std::vector<double>> input((size_t)m);
+        for (int j = 0; j < m; j++) {                                                                  // ciphertext j: the channels j*in_batch .. (j+1)*in_batch - 1
+            std::vector<double> part((size_t)px * in_batch);
+            for (int p = 0; p < px; p++) for (int ch = 0; ch < in_batch; ch++) part[(size_t)p * in_batch + ch] = raw_input[(size_t)p * m * in_batch + (size_t)j * in_batch + ch];
+            input[(size_t)j] = prep_Input(part, raw_in_wid, in_wid, cont->Nn, norm, trans, false);
+        }
+        auto start = now();
+        std::vector<const std::vector<double> *> ptrs; for (int g = 0; g < nimg; g++) for (int j = 0; j < m; j++) ptrs.push_back(&input[(size_t)j]);
+        std::vector<Ciphertext> enc = EncryptCoeffsBatch(cont, ptrs, cont->ECD_LV, cont->scale);      // ONE call on the device path
+        printf("Encryption done in %s \n", dur(start).c_str());
+        std::vector<std::vector<Ciphertext>> groups((size_t)nimg);
+        for (int g = 0; g < nimg; g++) groups[(size_t)g].assign(enc.begin() + (size_t)g * m, enc.begin() + (size_t)(g + 1) * m);
+        std::vector<Ciphertext> ct_result = evalConv_BN_multi_batch(cont, groups, ker_in, bn_a, bn_b, in_wid, ker_wid, m * in_batch, out_batch, norm, (double)(1 << 30));
+        if (getenv("HCONV_PRINT_DIGEST")) {      // FNV-1a over the result ciphertext: lets tests compare code paths bit for bit
+            std::vector<uint64_t> h = dev_download(cont, ct_result[0].d, 2); uint64_t f = 1469598103934665603ull;
+            for (uint64_t w : h) for (int b = 0; b < 8; b++) { f ^= (w >> (8 * b)) & 0xff; f *= 1099511628211ull; }
+            printf("ciphertext digest: %016llx\n", (unsigned long long)f);
+        }
+        start = now();
+        std::vector<std::vector<double>> dec = DecryptDecodeCoeffsBatch(cont, ct_result);
+        printf("Decryption Done in %s \n", dur(start).c_str());
+        std::vector<double> test_out = post_process(dec[0], raw_in_wid, in_wid);
+        std::vector<double> real_out = readTxt(pre + "out" + suf, px * out_batch);
+        printDebugCfsPlain(test_out, real_out);
+        for (int z = 1; z < nimg; z++) {                                                               // the other encryptions decrypt to the same values up to the scheme's noise
+            std::vector<double> cz = post_process(dec[(size_t)z], raw_in_wid, in_wid);
+            double mx = 0, mr = 0; for (size_t i = 0; i < cz.size(); i++) { mx = std::max(mx, fabs(cz[i] - test_out[i])); mr = std::max(mr, fabs(cz[i] - real_out[i])); }
+            printf("image %d of the batch: max |difference| to image 0 = %.3g, to the expected output = %.3g\n", z, mx, mr);
+        }
+        for (Ciphertext &ct : enc) freeCt(cont, ct);
+        for (Ciphertext &ct : ct_result) freeCt(cont, ct);
+    }
+    freeContext(cont);
+}
+
 // ---------------------------------------------------------------- testConv_in (test.go:15-74)
 void testConv_in(int in_batch, int in_wid, int ker_wid, int total_test_num, bool boot) {
     const std::string kind = "Conv";

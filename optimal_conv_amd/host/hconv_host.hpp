@@ -157,6 +157,15 @@ Ciphertext evalConv_BN(Context *cont, const Ciphertext &ct_input, const std::vec
 void testConv_in(int in_batch, int in_wid, int ker_wid, int total_test_num, bool boot);
 // `transconv` (not a reference command): kind "TransConv" through prep_Input / prep_Ker with trans = true and the same conv_then_pack, Ours only
 void testTransConv_in(int in_batch, int in_wid, int ker_wid, int total_test_num);
+// evalConv_BN for a layer with more input channels than one ciphertext holds (not a reference routine): ker_in is HWIO with real_ib = m * ib input channels, ciphertext j
+// holds the channels j*ib .. (j+1)*ib - 1 and its plaintexts are prep_Ker of that channel slice with the same bn_a. ONE convolution: the m products are summed at level 1
+// (hc_conv_then_pack_batch's members with one ct_out), then one SetScale, one pack tree, one bias add. _batch: the images of a batch, each with its m ciphertexts (<= 16 in all)
+Ciphertext evalConv_BN_multi(Context *cont, const std::vector<Ciphertext> &ct_inputs, const std::vector<double> &ker_in, const std::vector<double> &bn_a,
+                             const std::vector<double> &bn_b, int in_wid, int ker_wid, int real_ib, int real_ob, int norm, double out_scale);
+std::vector<Ciphertext> evalConv_BN_multi_batch(Context *cont, const std::vector<std::vector<Ciphertext>> &groups, const std::vector<double> &ker_in, const std::vector<double> &bn_a,
+                                                const std::vector<double> &bn_b, int in_wid, int ker_wid, int real_ib, int real_ob, int norm, double out_scale);
+// `multiconv` (not a reference command): `conv`'s layer with n_in * in_batch input channels in n_in input ciphertexts, Ours only
+void testMultiConv_in(int in_batch, int in_wid, int ker_wid, int total_test_num, int n_in);
 // ---- convReLU chain (hconv_relu.cpp; eval.go:272-607 for kind "Conv") ----
 Boot *newBoot(const std::vector<int64_t> &sk, const Seed256 &seed, int device, const std::vector<int> &log_sparse_sets, int image_batch = 1);   // one "bootstrapper" per log_sparse; image_batch: images per launch set of the tail (HCONV_IMAGE_BATCH)
 void freeBoot(Boot *);
