@@ -1,5 +1,6 @@
 // hconv_relu.cpp — the `convReLU` chain (scope row 8f-1) on the MI355X engine: everything after the convolution in
-// eval.go:272-607 evalConv_BNRelu_new for kind "Conv" (log_sparse 0, iter 2), with device-resident ciphertexts.
+// eval.go:272-607 evalConv_BNRelu_new (kinds "Conv", "Conv_sparse", "StrConv_sparse", "Conv_inside", "StrConv_inside"), with device-resident
+// ciphertexts, and the baseline's Bootstrapp + ReLU.
 //
 // Reference mapping (file:line -> here):
 //   eval.go:433-437  evalConv_BN at out_scale 2^(round(log2 Q0) - (pow+8)); Scale *= 2^pow      -> evalConv_BNRelu_new
@@ -10,13 +11,18 @@
 //   conv.go:417-431  keep_ctxt, rot_util.go:141-174 gen_keep_vec                                 -> keep_ctxt, gen_keep_vec
 //   eval.go:550      cont.btp.BootstrappConv_StoC                                                 -> Boot::stoc
 //   main.go:464-507  bootstrapping keys (rlk + rotation keys over the five special primes)       -> Boot::key (generated on demand)
-// The bootstrapper exists only inside the un-vendored Lattigo fork; this is a restatement on the same modulus chain and level
-// assignment (parameter set [6]): levels 27..24 CoeffsToSlots, 23..16 sine (Chebyshev degree 63 of the cosine,
-// two double angles, K = 25, message ratio 256), 15..5 the ReLU polynomials, 5 the mask, 3..2 SlotsToCoeffs. It mirrors
-// tests/oracle_ckks.py statement by statement; that file run on the oracle and on this library's C ABI gives bit-identical
-// ciphertexts at every stage (tests/test_gpu_a_parity.py::test_conv_relu_tail_on_gpu). All residue arithmetic is C-ABI calls:
-// hc_lv_* (all limbs per launch), hc_keyswitch (hybrid, alpha = 5), hc_div_round_last, hc_permute; the slot encoder and the
-// float64 scale bookkeeping are host code, as in the reference.
+//   test_BL.go:113-168 the baseline's stock Bootstrapp + ReLU over parameter set [7]                  -> blBootReLU (Boot with chain == 7)
+// The bootstrapper exists only inside the un-vendored Lattigo fork; every stage here issues the fork's own operation sequence, pinned to the
+// reference binary's digests (tests/golden/ref_flow_*.json, ref_trace_*.json; tests/test_gpu_z_cli.py compares the CLI's ciphertexts with them):
+// the fork's DFT matrices and baby-step split (lattigo_dft, lattigo_n1), its LinearTransform in the extended basis (linear_transform_qp), its
+// EvaluatePoly / EvaluateCheby (eval_poly, one recursion for both bases), BootstrappConv_CtoS / the stock Bootstrapp's first half (ctos) and
+// SlotsToCoeffs (stoc). Two modulus chains: parameter set [6] (Ours; SURVEY.md 8(a)-P: levels 27..24 CoeffsToSlots, 23..16 sine - the fork's 63
+// Chebyshev coefficients, two double angles, K = 25, message ratio 256 -, 15..5 the ReLU polynomials, 5 the mask, 3 SlotsToCoeffs; full and sparse
+// slots) and set [7] (the baseline; SlotsToCoeffs on levels 15..14 right behind the sine; full slots only). tests/oracle_ckks.py holds the same
+// paths on the CPU oracle (beside older generic ones that this file no longer has). Every ciphertext is device-resident and has two polynomials:
+// products are relinearised where they are formed. All residue arithmetic is C-ABI calls - hc_lv_* (all limbs, both polynomials per launch),
+// hc_keyswitch_* (hybrid, alpha = 5), hc_div_round_last2, hc_mod_down2, hc_qp_* -; the slot encoder (unless HCONV_DEVICE_ENCODE) and the float64
+// scale bookkeeping are host code, as in the reference.
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -24,10 +30,8 @@
 
 #include <algorithm>
 #include <chrono>
-#include <functional>
 #include <map>
 #include <memory>
-#include <numeric>
 #include <set>
 
 #include "hconv_encoder.hpp"
@@ -39,22 +43,23 @@ namespace hconv {
 
 #define HCR(call) do { int rc_ = (call); if (rc_) panic(std::string(#call) + ": " + hc_last_error(hc)); } while (0)
 static const int LV_CTS_TOP = 27, LV_SINE_TOP = 23, LV_RELU_TOP = 15;     // the same in parameter sets [6] and [7]: CtS 27..24, sine 23..16
-static const int SIN_K = 25, SIN_DEG = 63, SIN_DOUBLE = 2;
+static const int SIN_K = 25, SIN_DOUBLE = 2;
 typedef std::map<int, std::vector<cplx>> DiagMat;        // rotation k -> diagonal (n complex values)
 
 static inline uint64_t mulmod(uint64_t a, uint64_t b, uint64_t q) { return (uint64_t)(((u128)a * b) % q); }
-static std::string dur(std::chrono::steady_clock::time_point t0) {
-    double ns = (double)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count();
+static std::string dur_ns(double ns) {                    // a duration as Go prints it
     char b[64];
     if (ns < 1e6) snprintf(b, sizeof b, "%.6gµs", ns / 1e3); else if (ns < 1e9) snprintf(b, sizeof b, "%.9gms", ns / 1e6); else snprintf(b, sizeof b, "%.9gs", ns / 1e9);
     return b;
 }
+static std::string dur(std::chrono::steady_clock::time_point t0) { return dur_ns((double)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count()); }
 static std::chrono::steady_clock::time_point now() { return std::chrono::steady_clock::now(); }
+static int bit_length(int x) { int b = 0; while (x) { b++; x >>= 1; } return b; }
 
-// device-resident ciphertext: deg+1 polynomials, each a pooled block of NQ rows of which rows 0..level are live
+// device-resident ciphertext: two polynomials, each a pooled block of NQ rows of which rows 0..level are live
 struct DCt {
-    std::shared_ptr<uint64_t> p[3];
-    int deg = 1, level = 0;
+    std::shared_ptr<uint64_t> p[2];
+    int level = 0;
     double scale = 0;
 };
 struct DPt { std::shared_ptr<uint64_t> p; int level = 0; double scale = 0; };
@@ -62,20 +67,16 @@ struct DPt { std::shared_ptr<uint64_t> p; int level = 0; double scale = 0; };
 struct Boot;
 static void profile_dump(Boot *B, const char *label);      // HCONV_PROFILE=1: per-kernel HIP-event totals since the last dump
 static bool profiling() { static const bool on = getenv("HCONV_PROFILE") && atoi(getenv("HCONV_PROFILE")); return on; }
+static bool no_fused_rescale() { static const bool on = getenv("HCONV_NO_FUSED_RESCALE") != nullptr; return on; }      // A/B switch: every Rescale as a pass of its own
 
 struct Boot {
     hc_ctx *hc = nullptr;
     std::vector<uint64_t> Q, P;
     int NQ = 0;
-    // where SlotsToCoeffs sits and what its plaintext scales are: set [6] (Ours, main.go:52): levels 3..2 after the ReLU, two matrices
-    // at sqrt(q3) and one at 2^30 (input scale 2^60 -> output 2^30 at level 1); set [7] (BL, main.go:54: the stock Bootstrapp):
-    // levels 15..14 right after the sine, 2^40 each (input 2^30 -> output 2^30 * 2^120 / (q15 q14) at level 13)
+    // where SlotsToCoeffs sits and what its plaintext scales are (set in build()): set [6] (Ours, main.go:52): level 3 after the ReLU, two matrices
+    // at sqrt(q3) and one at 2^30, rescaled to level 1; set [7] (BL, main.go:54: the stock Bootstrapp): levels 15, 15, 14 right after the sine, sqrt(q15) twice and 2^30
     int chain = 6, LV_STC_TOP = 3, lv_relin_lo = LV_RELU_TOP - 11;
     double stc_scale_top = 0, stc_scale_last = 1073741824.0;
-    // scale the sine leaves its result at (level 15). Ours: 2^30, what evalReLU consumes. Baseline: 2^55 — its SlotsToCoeffs follows
-    // directly and multiplies whatever noise its input carries by ~sqrt(N) relative to the slot values, so the input must sit far above
-    // the key-switch noise (the reference's evaluateSine likewise hands over at 2^55..2^60: gotrace -noplant log of `convReLU 3 0 1`)
-    double sine_out_scale = 1073741824.0;
     const int n = N / 2;
     std::vector<int64_t> sk;
     uint64_t *d_sk = nullptr;                               // [NQ+NP][N] NTT rows of sk on the device
@@ -83,16 +84,14 @@ struct Boot {
     std::vector<uint64_t *> pool;
     ChaChaRng rng;                    // the bootstrapper's own key stream (switching keys, encryption masks)
     Encoder enc;
-    std::shared_ptr<uint64_t> mono_i;                        // NTT(X^(N/2)) for every limb: only for a degree-2 operand of mul_by_i (need_mono_i)
-    struct LT { int n1 = 1; std::map<int, std::map<int, DPt>> giant; double pt_scale = 0; int level = 0; bool qp = false; };   // the diagonals are encoded mod Q_0..Q_level AND mod every P (rows [level+1+np][N]) for linear_transform_qp
+    struct LT { int n1 = 1; std::map<int, std::map<int, DPt>> giant; double pt_scale = 0; int level = 0; };   // the diagonals are encoded mod Q_0..Q_level AND mod every P (rows [level+1+np][N]) for linear_transform_qp
     struct Set { int ls = 0, ns = 0; std::vector<LT> cts, stc; };      // one bootstrapper of the reference (btp, btp2..btp5: main.go:480-500)
     std::map<int, Set> sets;                                           // by log_sparse
     std::map<int, Encoder> sub_enc;                                    // encoders of the rings with fewer slots (sparse embedding), by log2 of their degree
-    std::vector<double> sine;
     long n_keyswitch = 0, n_keys = 0;
     const bool dev_encode = deviceEncode();                  // HCONV_DEVICE_ENCODE: diagonals and masks through hc_encode_slots_ex (the same words as hconv_encoder.hpp gives)
     long n_enc_diag = 0, n_enc_mask = 0;
-    bool parts_merged = false;                               // ctos_fork returned ONE ciphertext of 2 nb images (both halves): see merge2
+    bool parts_merged = false;                               // ctos returned ONE ciphertext of 2 nb images (both halves): see merge2
     // algorithmic traffic of what has been evaluated, in rows of N residues (SURVEY.md 8(d)'s convention carried to the chain: every evaluator operation reads its
     // ciphertext operands once and writes its result once, temporaries stay on chip; switching keys, diagonals and masks are read once per operation and - being common
     // to the images of a batch - once per launch set): alg_ct per ciphertext, alg_shared per launch set
@@ -129,34 +128,25 @@ struct Boot {
         ~Batch() { b->nb = 1; hc_set_batch(b->hc, 1, 0, 0); }
         Batch(const Batch &) = delete; Batch &operator=(const Batch &) = delete;
     };
-    std::shared_ptr<uint64_t> block() {
+    // a block of `bytes` (the one size of its pool) that returns to the pool when its last owner lets go; the pools are emptied by freeBoot
+    std::shared_ptr<uint64_t> pooled(std::vector<uint64_t *> &from, size_t bytes) {
         uint64_t *d;
-        if (!pool.empty()) { d = pool.back(); pool.pop_back(); }
-        else { void *v = nullptr; HCR(hc_malloc(hc, (size_t)nb_max * NQ * N * 8, &v)); d = (uint64_t *)v; }
-        return std::shared_ptr<uint64_t>(d, [this](uint64_t *x) { pool.push_back(x); });
+        if (!from.empty()) { d = from.back(); from.pop_back(); }
+        else { void *v = nullptr; HCR(hc_malloc(hc, bytes, &v)); d = (uint64_t *)v; }
+        return std::shared_ptr<uint64_t>(d, [&from](uint64_t *x) { from.push_back(x); });
     }
-    std::vector<uint64_t *> pool1;
-    std::shared_ptr<uint64_t> block1() {               // one polynomial whatever the batch: plaintexts
-        uint64_t *d;
-        if (!pool1.empty()) { d = pool1.back(); pool1.pop_back(); }
-        else { void *v = nullptr; HCR(hc_malloc(hc, (size_t)NQ * N * 8, &v)); d = (uint64_t *)v; }
-        return std::shared_ptr<uint64_t>(d, [this](uint64_t *x) { pool1.push_back(x); });
-    }
+    std::vector<uint64_t *> pool1, pool_qp;
+    std::shared_ptr<uint64_t> block() { return pooled(pool, (size_t)nb_max * NQ * N * 8); }                // one polynomial of every image of the batch
+    std::shared_ptr<uint64_t> block1() { return pooled(pool1, (size_t)NQ * N * 8); }                       // one polynomial whatever the batch: plaintexts
     // two polynomials in the extended basis, [2][level+1+np][N] at the start of a 2 (NQ+NP)-row allocation (hc_keyswitch_qp / hc_mod_down2 layout), per image
-    std::vector<uint64_t *> pool_qp;
-    std::shared_ptr<uint64_t> block_qp2() {
-        uint64_t *d;
-        if (!pool_qp.empty()) { d = pool_qp.back(); pool_qp.pop_back(); }
-        else { void *v = nullptr; HCR(hc_malloc(hc, (size_t)nb_max * qp_stride() * 8, &v)); d = (uint64_t *)v; }
-        return std::shared_ptr<uint64_t>(d, [this](uint64_t *x) { pool_qp.push_back(x); });
-    }
+    std::shared_ptr<uint64_t> block_qp2() { return pooled(pool_qp, (size_t)nb_max * qp_stride() * 8); }
     // Full slots carry the two coefficient halves of every image as TWO ciphertexts through the sine and the ReLU (eval.go:462-477 loops over them). They see the same
     // operations at the same levels, so with room for 2 nb images per block (merge_parts) they ride as ONE batch of 2 nb "images": image z of the second half sits at
     // slot nb + z. The launches of the most expensive stages are then twice as wide for the same count - what HCONV_IMAGE_BATCH does across images, across the halves.
     bool merge_parts = false;
     DCt merge2(const DCt &a, const DCt &b) {              // called with nb = n: returns the 2n-image ciphertext and switches the batch to 2n
-        if (a.level != b.level || a.deg != 1 || b.deg != 1 || 2 * nb > nb_max) panic("merge2: halves differ or the blocks are too small");
-        DCt r = new_ct(a.level, 1, a.scale); const int n0 = nb;
+        if (a.level != b.level || 2 * nb > nb_max) panic("merge2: halves differ or the blocks are too small");
+        DCt r = new_ct(a.level, a.scale); const int n0 = nb;
         for (int d = 0; d < 2; d++) for (int z = 0; z < n0; z++) {
             HCR(hc_copy(hc, r.p[d].get() + (size_t)z * poly_stride(), a.p[d].get() + (size_t)z * poly_stride(), (size_t)(a.level + 1) * N * 8));
             HCR(hc_copy(hc, r.p[d].get() + (size_t)(n0 + z) * poly_stride(), b.p[d].get() + (size_t)z * poly_stride(), (size_t)(a.level + 1) * N * 8));
@@ -168,7 +158,7 @@ struct Boot {
     void split2(const DCt &m, DCt out[2]) {               // called with nb = 2n: the two halves as n-image ciphertexts; the batch goes back to n
         const int n0 = nb / 2; set_nb(n0); alg_ct += alg_ct - alg_ct_at_merge;
         for (int h = 0; h < 2; h++) {
-            out[h] = new_ct(m.level, 1, m.scale);
+            out[h] = new_ct(m.level, m.scale);
             for (int d = 0; d < 2; d++) for (int z = 0; z < n0; z++)
                 HCR(hc_copy(hc, out[h].p[d].get() + (size_t)z * poly_stride(), m.p[d].get() + (size_t)(h * n0 + z) * poly_stride(), (size_t)(m.level + 1) * N * 8));
         }
@@ -177,7 +167,7 @@ struct Boot {
     void copy_rows(uint64_t *dst, const uint64_t *src, size_t rows, size_t dst_off_rows = 0, size_t src_off_rows = 0) {
         for (int z = 0; z < nb; z++) HCR(hc_copy(hc, dst + (size_t)z * poly_stride() + dst_off_rows * N, src + (size_t)z * poly_stride() + src_off_rows * N, rows * N * 8));
     }
-    DCt new_ct(int level, int deg, double scale) { DCt c; c.deg = deg; c.level = level; c.scale = scale; for (int i = 0; i <= deg; i++) c.p[i] = block(); return c; }
+    DCt new_ct(int level, double scale) { DCt c; c.level = level; c.scale = scale; for (int i = 0; i < 2; i++) c.p[i] = block(); return c; }
     static DCt drop_to(const DCt &a, int level) { if (level > a.level) panic("drop_to: level above the ciphertext's"); DCt c = a; c.level = level; return c; }
 
     // ---------------- sampling (harness only; the reference's randomness is crypto/rand and unseeded): this stream keys the device's key generator
@@ -240,22 +230,9 @@ struct Boot {
     static void same_scale(double a, double b) { if (fabs(a / b - 1.0) > 1e-9) panic("scale mismatch in Add/Sub"); }
     DCt add(const DCt &a0, const DCt &b0) {
         const int L = std::min(a0.level, b0.level); same_scale(a0.scale, b0.scale);
-        DCt r = new_ct(L, std::max(a0.deg, b0.deg), a0.scale);
-        alg_ct += 3.0 * (r.deg + 1) * (L + 1);
-        if (a0.deg == 1 && b0.deg == 1) { HCR(hc_lv_op2(hc, HC_LV_ADD, L, a0.p[0].get(), a0.p[1].get(), b0.p[0].get(), b0.p[1].get(), r.p[0].get(), r.p[1].get(), nullptr)); return r; }   // both polynomials per launch
-        for (int d = 0; d <= r.deg; d++) {
-            if (d <= a0.deg && d <= b0.deg) HCR(hc_lv_add(hc, L, a0.p[d].get(), b0.p[d].get(), r.p[d].get()));
-            else copy_rows(r.p[d].get(), (d <= a0.deg ? a0 : b0).p[d].get(), (size_t)(L + 1));
-        }
-        return r;
-    }
-    DCt sub(const DCt &a0, const DCt &b0) {
-        const int L = std::min(a0.level, b0.level); same_scale(a0.scale, b0.scale);
-        if (a0.deg != b0.deg) panic("sub: degrees differ");
-        DCt r = new_ct(L, a0.deg, a0.scale);
-        alg_ct += 3.0 * (r.deg + 1) * (L + 1);
-        if (r.deg == 1) HCR(hc_lv_op2(hc, HC_LV_SUB, L, a0.p[0].get(), a0.p[1].get(), b0.p[0].get(), b0.p[1].get(), r.p[0].get(), r.p[1].get(), nullptr));
-        else for (int d = 0; d <= r.deg; d++) HCR(hc_lv_sub(hc, L, a0.p[d].get(), b0.p[d].get(), r.p[d].get()));
+        DCt r = new_ct(L, a0.scale);
+        alg_ct += 6.0 * (L + 1);
+        HCR(hc_lv_op2(hc, HC_LV_ADD, L, a0.p[0].get(), a0.p[1].get(), b0.p[0].get(), b0.p[1].get(), r.p[0].get(), r.p[1].get(), nullptr));   // both polynomials per launch
         return r;
     }
     std::vector<uint64_t> consts(const u128 mag, bool neg, int level) const {
@@ -272,9 +249,8 @@ struct Boot {
     DCt mul_const_int(const DCt &a, double k_rounded_value) {      // k given as an integral double
         u128 mag; bool neg; split_int(k_rounded_value, &mag, &neg);
         std::vector<uint64_t> c = consts(mag, neg, a.level);
-        DCt r = new_ct(a.level, a.deg, a.scale); alg_ct += 2.0 * (a.deg + 1) * (a.level + 1);
-        if (a.deg == 1) HCR(hc_lv_op2(hc, HC_LV_MUL_CONST, a.level, a.p[0].get(), a.p[1].get(), nullptr, nullptr, r.p[0].get(), r.p[1].get(), c.data()));
-        else for (int d = 0; d <= a.deg; d++) HCR(hc_lv_mul_const(hc, a.level, a.p[d].get(), c.data(), r.p[d].get()));
+        DCt r = new_ct(a.level, a.scale); alg_ct += 4.0 * (a.level + 1);
+        HCR(hc_lv_op2(hc, HC_LV_MUL_CONST, a.level, a.p[0].get(), a.p[1].get(), nullptr, nullptr, r.p[0].get(), r.p[1].get(), c.data()));
         return r;
     }
     // sum_t k_t * a_t (+ c0) at `level` as ONE launch (hc_lv_lincomb2): what a leaf of the polynomial evaluators computes with a MultByConst per power and an Add chain.
@@ -284,13 +260,13 @@ struct Boot {
         if (nt_ < 1 || nt_ > 8 || ks.size() != nt_) panic("lincomb: 1..8 terms");
         std::vector<uint64_t> cs(nt_ * (size_t)(level + 1)), cadd; std::vector<const uint64_t *> p0(nt_), p1(nt_);
         for (size_t t = 0; t < nt_; t++) {
-            if (as[t].deg != 1 || as[t].level < level) panic("lincomb: degree-1 operands at or above the level");
+            if (as[t].level < level) panic("lincomb: operands at or above the level");
             u128 mag; bool neg; split_int(ks[t], &mag, &neg);
             std::vector<uint64_t> c = consts(mag, neg, level); std::copy(c.begin(), c.end(), cs.begin() + (long)(t * (size_t)(level + 1)));
             p0[t] = as[t].p[0].get(); p1[t] = as[t].p[1].get();
         }
         if (with_c0) { u128 mag; bool neg; split_int(c0, &mag, &neg); cadd = consts(mag, neg, level); }
-        DCt r = new_ct(level, 1, scale); alg_ct += (2.0 * (double)nt_ + 2.0) * (level + 1);
+        DCt r = new_ct(level, scale); alg_ct += (2.0 * (double)nt_ + 2.0) * (level + 1);
         HCR(hc_lv_lincomb2(hc, level, (int)nt_, p0.data(), p1.data(), cs.data(), with_c0 ? cadd.data() : nullptr, r.p[0].get(), r.p[1].get()));
         return r;
     }
@@ -304,7 +280,7 @@ struct Boot {
     // evaluator.AddConst with a real constant: scaleUpExact(c, scale, q) = floor(|c * scale| + 0.5), sign restored modulo q (the AddConst digests of
     // tests/golden/ref_trace_cheby_5_1.json pin the rule)
     DCt add_const(const DCt &a, double c) { const double k = floor(fabs(a.scale * c) + 0.5); return add_const_int(a, c < 0 ? -k : k); }
-    // evaluator.MultByConst with a float64: a constant with a fractional part is carried times q_level (set_scale below uses the same rule)
+    // evaluator.MultByConst with a float64: a constant with a fractional part is carried times q_level
     DCt mul_const_float(const DCt &a, double c) {
         const double mult = c - (double)(int64_t)c != 0 ? (double)Q[(size_t)a.level] : 1.0;
         DCt r = mul_const_int(a, floor(fabs(c * mult) + 0.5) * (c < 0 ? -1.0 : 1.0)); r.scale = a.scale * mult;
@@ -312,37 +288,22 @@ struct Boot {
     }
     DCt mul_plain(const DCt &a, const DPt &pt) {
         if (pt.level < a.level) panic("mul_plain: plaintext below the ciphertext's level");
-        DCt r = new_ct(a.level, a.deg, a.scale * pt.scale); alg_ct += 2.0 * (a.deg + 1) * (a.level + 1); alg_shared += a.level + 1;
-        if (a.deg == 1) HCR(hc_lv_op2(hc, HC_LV_MUL_PLAIN, a.level, a.p[0].get(), a.p[1].get(), pt.p.get(), nullptr, r.p[0].get(), r.p[1].get(), nullptr));
-        else for (int d = 0; d <= a.deg; d++) HCR(hc_lv_mul_plain(hc, a.level, a.p[d].get(), pt.p.get(), r.p[d].get()));
+        DCt r = new_ct(a.level, a.scale * pt.scale); alg_ct += 4.0 * (a.level + 1); alg_shared += a.level + 1;
+        HCR(hc_lv_op2(hc, HC_LV_MUL_PLAIN, a.level, a.p[0].get(), a.p[1].get(), pt.p.get(), nullptr, r.p[0].get(), r.p[1].get(), nullptr));
         return r;
     }
-    // MultByi = the product by X^(N/2): one HC_LV_MONOMIAL launch, the factor formed in the kernel (no plaintext). A degree-2 operand (none in the chains as they stand) takes
-    // the former product by the transformed one-hot plaintext, built when first asked for.
+    // MultByi = the product by X^(N/2): one HC_LV_MONOMIAL launch, the factor formed in the kernel (no plaintext)
     DCt mul_by_i(const DCt &a) {
-        DCt r = new_ct(a.level, a.deg, a.scale); alg_ct += 2.0 * (a.deg + 1) * (a.level + 1); alg_shared += a.level + 1;
+        DCt r = new_ct(a.level, a.scale); alg_ct += 4.0 * (a.level + 1); alg_shared += a.level + 1;
         const uint64_t e[2] = {0, (uint64_t)N / 2};
-        if (a.deg == 1) HCR(hc_lv_op2(hc, HC_LV_MONOMIAL, a.level, a.p[0].get(), a.p[1].get(), nullptr, nullptr, r.p[0].get(), r.p[1].get(), e));
-        else { need_mono_i(); for (int d = 0; d <= a.deg; d++) HCR(hc_lv_mul_plain(hc, a.level, a.p[d].get(), mono_i.get(), r.p[d].get())); }
+        HCR(hc_lv_op2(hc, HC_LV_MONOMIAL, a.level, a.p[0].get(), a.p[1].get(), nullptr, nullptr, r.p[0].get(), r.p[1].get(), e));
         return r;
-    }
-    void need_mono_i() {
-        if (mono_i) return;
-        Single one(this);
-        mono_i = block1();
-        std::vector<uint64_t> m((size_t)NQ * N, 0); for (int l = 0; l < NQ; l++) m[(size_t)l * N + N / 2] = 1;
-        pack_rows(m, NQ); HCR(hc_upload(hc, mono_i.get(), m.data(), m.size() * 8)); HCR(hc_lv_ntt(hc, NQ - 1, mono_i.get(), mono_i.get()));
     }
     // X^e1 (a + X^e0 b) in one pass over the operands (HC_LV_MONOMIAL; exponents below 2N, X^N = -1): re + i im is (N/2, 0), i (a - b) is (N, N/2). Counted as the evaluator
     // operations it stands for: a monomial product of b unless e0 is 0 or N, the addition or subtraction, a monomial product of the sum unless e1 is 0.
     DCt monomial_fma(const DCt &a, const DCt &b, int e0, int e1) {
-        if (a.deg != 1 || b.deg != 1) {
-            if (e0 == N / 2 && e1 == 0) return add(a, mul_by_i(b));
-            if (e0 == N && e1 == N / 2) return mul_by_i(sub(a, b));
-            panic("monomial_fma: degree-1 operands");
-        }
         const int L = std::min(a.level, b.level); same_scale(a.scale, b.scale);
-        DCt r = new_ct(L, 1, a.scale);
+        DCt r = new_ct(L, a.scale);
         if (e0 != 0 && e0 != N) { alg_ct += 4.0 * (b.level + 1); alg_shared += b.level + 1; }
         alg_ct += 6.0 * (L + 1);
         if (e1 != 0) { alg_ct += 4.0 * (L + 1); alg_shared += L + 1; }
@@ -352,7 +313,7 @@ struct Boot {
     }
     DCt mul_relin(const DCt &a, const DCt &b) {                   // evaluator.MulRelin: tensor, key switch of c2 with the rlk
         const int L = std::min(a.level, b.level);
-        DCt r = new_ct(L, 1, a.scale * b.scale); alg_ct += 6.0 * (L + 1); alg_shared += ks_rows(L);
+        DCt r = new_ct(L, a.scale * b.scale); alg_ct += 6.0 * (L + 1); alg_shared += ks_rows(L);
         auto d1 = block(), d2 = block();
         HCR(hc_lv_mul_tensor(hc, L, a.p[0].get(), a.p[1].get(), b.p[0].get(), b.p[1].get(), r.p[0].get(), d1.get(), d2.get()));
         HCR(hc_keyswitch_add(hc, key(0, L), L, d2.get(), r.p[0].get(), d1.get(), r.p[0].get(), r.p[1].get())); n_keyswitch++;      // (d0 + ks0, d1 + ks1) inside ModDown's last pass
@@ -361,9 +322,8 @@ struct Boot {
     // MulRelin followed by one Rescale: the key switch's ModDown and the rescale share one forward transform per limb (hc_keyswitch_add_rescale); the residues of the two steps
     DCt mul_relin_rescale(const DCt &a, const DCt &b) {
         const int L = std::min(a.level, b.level);
-        static const bool split = getenv("HCONV_NO_FUSED_RESCALE") != nullptr;
-        if (L < 2 || split) return rescale(mul_relin(a, b));
-        DCt r = new_ct(L - 1, 1, a.scale * b.scale / (double)Q[(size_t)L]); alg_ct += 6.0 * (L + 1) + 2.0 * (2 * L + 1); alg_shared += ks_rows(L);
+        if (L < 2 || no_fused_rescale()) return rescale(mul_relin(a, b));
+        DCt r = new_ct(L - 1, a.scale * b.scale / (double)Q[(size_t)L]); alg_ct += 6.0 * (L + 1) + 2.0 * (2 * L + 1); alg_shared += ks_rows(L);
         auto d0 = block(), d1 = block(), d2 = block();
         HCR(hc_lv_mul_tensor(hc, L, a.p[0].get(), a.p[1].get(), b.p[0].get(), b.p[1].get(), d0.get(), d1.get(), d2.get()));
         HCR(hc_keyswitch_add_rescale(hc, key(0, L), L, d2.get(), d0.get(), d1.get(), r.p[0].get(), r.p[1].get())); n_keyswitch++;
@@ -371,14 +331,13 @@ struct Boot {
     }
     DCt rescale(const DCt &a) {                                     // one DivRoundByLastModulusNTT
         if (a.level < 1) panic("rescale at level 0");
-        DCt r = new_ct(a.level - 1, a.deg, a.scale / (double)Q[(size_t)a.level]); alg_ct += (double)(a.deg + 1) * (2 * a.level + 1);
-        if (a.deg == 1) HCR(hc_div_round_last2(hc, a.level, a.p[0].get(), a.p[1].get(), r.p[0].get(), r.p[1].get()));     // both polynomials per launch
-        else for (int d = 0; d <= a.deg; d++) HCR(hc_div_round_last(hc, a.level, a.p[d].get(), r.p[d].get()));
+        DCt r = new_ct(a.level - 1, a.scale / (double)Q[(size_t)a.level]); alg_ct += 2.0 * (2 * a.level + 1);
+        HCR(hc_div_round_last2(hc, a.level, a.p[0].get(), a.p[1].get(), r.p[0].get(), r.p[1].get()));     // both polynomials per launch
         return r;
     }
     DCt galois(const DCt &a, uint64_t gal) {                       // evaluator.permuteNTT: key switch c1, + c0, permute both
         const int L = a.level;
-        DCt r = new_ct(L, 1, a.scale); alg_ct += 4.0 * (L + 1); alg_shared += ks_rows(L);
+        DCt r = new_ct(L, a.scale); alg_ct += 4.0 * (L + 1); alg_shared += ks_rows(L);
         HCR(hc_keyswitch_rotate(hc, key(gal, L), gal, L, a.p[0].get(), a.p[1].get(), r.p[0].get(), r.p[1].get(), 0)); n_keyswitch++;   // + c0 and the permutation inside ModDown's last pass
         return r;
     }
@@ -386,18 +345,14 @@ struct Boot {
     DCt conjugate(const DCt &a) { return galois(a, 2ull * N - 1); }
     DCt mod_raise(const DCt &a, int level) {                        // ckks.(*Bootstrapper).modUp
         if (a.level != 0) panic("mod_raise expects a level-0 ciphertext");
-        DCt r = new_ct(level, 1, a.scale); alg_ct += 2.0 + 2.0 * (level + 1);
+        DCt r = new_ct(level, a.scale); alg_ct += 2.0 + 2.0 * (level + 1);
         for (int d = 0; d < 2; d++) HCR(hc_lv_mod_raise(hc, level, a.p[d].get(), r.p[d].get()));
         return r;
     }
-    // evaluator.SetScale: MultByConst(scale / ct.Scale) — a constant with a fractional part is carried times
-    // q_level — then Rescale(scale) (drop while scale/q_L >= scale/2), then the scale is forced
+    // evaluator.SetScale: MultByConst(scale / ct.Scale) unless that is 1, then Rescale(scale) (drop while scale/q_L >= scale/2), then the scale is forced
     DCt set_scale(const DCt &a, double scale) {
-        const double c = scale / a.scale; DCt r = a;
-        if (c != 1.0) {
-            double mult = 1.0; if (c - (double)(int64_t)c != 0) mult = (double)Q[(size_t)a.level];
-            r = mul_const_int(a, floor(fabs(c * mult) + 0.5) * (c < 0 ? -1.0 : 1.0)); r.scale = a.scale * mult;
-        }
+        const double c = scale / a.scale;
+        DCt r = c != 1.0 ? mul_const_float(a, c) : a;
         while (r.level > 0 && r.scale / (double)Q[(size_t)r.level] >= scale / 2) r = rescale(r);
         r.scale = scale;
         return r;
@@ -431,7 +386,6 @@ struct Boot {
         double mx = 0, sum = 0, mag = 0; for (size_t i = 0; i < want.size(); i++) { const double e = std::abs(want[i] - got[i]); mx = std::max(mx, e); sum += e; mag = std::max(mag, std::abs(want[i])); }
         fprintf(stderr, "[debug] %s: max |want| %.4g, error max 2^%.2f mean 2^%.2f\n", what, mag, log2(mx), log2(sum / (double)want.size()));
     }
-    static DCt relabel(const DCt &a, double scale) { if (fabs(a.scale / scale - 1.0) > 1e-6) panic("relabel: scales are not close"); DCt r = a; r.scale = scale; return r; }
 
     // ---------------- encoding
     // a 0/1 slot mask at (level, scale): encoded once per context (the reference re-encodes them in every layer, conv.go:423, 381)
@@ -486,55 +440,7 @@ struct Boot {
         return pt;
     }
 
-    // ---------------- DFT matrices in diagonal form (the encoder's own butterflies, no bit reversal)
-    // `E`: encoder of the ring the DFT belongs to (the full ring, or the subring X^(2^ls) of sparse packing: same butterflies
-    // with that ring's roots, tiled over the n full slots); rotation indices modulo `period` (the slot vector's period)
-    DiagMat dft_stage(int ln, bool inverse, const Encoder &E, int period) const {
-        const int lenh = ln >> 1, lenq = ln << 2, gap = 2 * E.Nn / lenq;
-        std::vector<cplx> d0((size_t)n), dp((size_t)n, cplx(0, 0)), dm((size_t)n, cplx(0, 0));
-        for (int p = 0; p < n; p++) {
-            const int j = p % ln; const bool first = j < lenh; const int jj = first ? j : j - lenh;
-            const int idx = inverse ? (lenq - (E.rotGroup[(size_t)jj] % lenq)) * gap : (E.rotGroup[(size_t)jj] % lenq) * gap;
-            const cplx w = E.roots[(size_t)idx];
-            if (inverse) { d0[(size_t)p] = first ? cplx(1, 0) : -w; if (first) dp[(size_t)p] = cplx(1, 0); else dm[(size_t)p] = w; }
-            else { d0[(size_t)p] = first ? cplx(1, 0) : -w; if (first) dp[(size_t)p] = w; else dm[(size_t)p] = cplx(1, 0); }
-        }
-        DiagMat M; M[0] = d0;
-        const int kp = lenh % period, km = ((-lenh) % period + period) % period;
-        auto acc = [&](int k, const std::vector<cplx> &d) { auto it = M.find(k); if (it == M.end()) M[k] = d; else for (int p = 0; p < n; p++) it->second[(size_t)p] += d[(size_t)p]; };
-        acc(kp, dp); acc(km, dm);
-        return M;
-    }
-    DiagMat matmul_diag(const DiagMat &M2, const DiagMat &M1, int period) const {        // M2 . M1 (M1 applied first)
-        DiagMat out;
-        for (auto &e2 : M2) for (auto &e1 : M1) {
-            const int k2 = e2.first, k = (e1.first + k2) % period;
-            auto it = out.find(k); if (it == out.end()) it = out.emplace(k, std::vector<cplx>((size_t)n, cplx(0, 0))).first;
-            for (int p = 0; p < n; p++) it->second[(size_t)p] += e2.second[(size_t)p] * e1.second[(size_t)((p + k2) % n)];
-        }
-        for (auto it = out.begin(); it != out.end();) { bool nz = false; for (auto &v : it->second) if (v != cplx(0, 0)) { nz = true; break; } if (nz) ++it; else it = out.erase(it); }
-        return out;
-    }
-    static std::vector<int> fit(std::vector<int> g, int logn) {
-        while (std::accumulate(g.begin(), g.end(), 0) > logn) (*std::max_element(g.begin(), g.end()))--;
-        return g;
-    }
-    std::vector<DiagMat> dft_groups(bool inverse, std::vector<int> sizes, double constant, int ls) const {
-        const int logn = LOGN - 1 - ls, ns = n >> ls;
-        sizes = fit(sizes, logn);
-        Encoder sub(LOGN - ls); const Encoder &E = ls ? sub : enc;
-        std::vector<int> lens; for (int s = 0; s < logn; s++) lens.push_back(inverse ? ns >> s : 2 << s);
-        const double c = pow(constant, 1.0 / (double)sizes.size());
-        std::vector<DiagMat> groups; size_t pos = 0;
-        for (int gs : sizes) {
-            DiagMat M; bool have = false;
-            for (int i = 0; i < gs; i++, pos++) { DiagMat S = dft_stage(lens[pos], inverse, E, ns); M = have ? matmul_diag(S, M, ns) : S; have = true; }
-            for (auto &e : M) for (auto &v : e.second) v *= c;
-            groups.push_back(std::move(M));
-        }
-        return groups;
-    }
-    // ---------------- the same matrices as the reference's Lattigo fork builds them (full slots, ls = 0)
+    // ---------------- DFT matrices in diagonal form, as the reference's Lattigo fork builds them (full slots first; sparse slots below)
     // ckks.(*Bootstrapper).genDFTMatrices -> GenCoeffsToSlotsMatrix / GenSlotsToCoeffsMatrix -> computeDFTMatrices (fftPlainVec /
     // fftInvPlainVec, genFFTDiagMatrix, multiplyFFTMatrixWithNextFFTLevel) of github.com/dwkim606/test_lattigo (binary only): the
     // radix-2 levels as (a, b, c) diagonals, merged ceil(remaining / depth-left) at a time, every complex product evaluated as Go does
@@ -620,23 +526,16 @@ struct Boot {
     }
     FILE *dft_digests = nullptr;
     // slots: the length of M's vectors (n, or 2^(logSlots+1) for a sparse-slot matrix: rotations modulo it, sparse embedding)
-    LT plan(const DiagMat &M, int level, double pt_scale, bool lattigo_split = false, const char *tag = "", int slots = 0) {          // BSGS split + the pre-rotated, encoded diagonals
+    LT plan(const DiagMat &M, int level, double pt_scale, const char *tag, int slots) {          // the fork's BSGS split + the pre-rotated, encoded diagonals
         LT lt; lt.level = level; lt.pt_scale = pt_scale;
         const int n = slots ? slots : this->n;
-        int best = -1;
-        for (int n1 = 1; n1 <= n; n1 <<= 1) {
-            std::set<int> babies, giants; for (auto &e : M) { babies.insert(e.first % n1); giants.insert(e.first - e.first % n1); }
-            babies.erase(0); giants.erase(0);
-            const int cost = (int)(babies.size() + giants.size());
-            if (best < 0 || cost < best) { best = cost; lt.n1 = n1; }
-        }
-        if (lattigo_split) lt.n1 = lattigo_n1(M, n);
+        lt.n1 = lattigo_n1(M, n);
         // every linear transform of a bootstrapper runs in the extended basis (linear_transform_qp): the diagonals are encoded mod Q_0..Q_level and mod every P. On the
         // host path one at a time (encode_qp); on the device path a call encodes as many as fit about 256 rows, into ONE allocation the DPts of the batch share
         struct Diag { int k, g, b; std::vector<cplx> rolled; };
         const size_t nt = (size_t)level + 1 + P.size(), per_call = dev_encode ? std::max<size_t>(1, 256 / nt) : 1;
         std::vector<Diag> diags; size_t left = M.size();
-        lt.qp = true; n_enc_diag += (long)M.size();
+        n_enc_diag += (long)M.size();
         for (auto &e : M) {
             Diag d; d.k = e.first; d.g = d.k - d.k % lt.n1; d.b = d.k % lt.n1; d.rolled.resize((size_t)n);
             for (int p = 0; p < n; p++) d.rolled[(size_t)p] = e.second[(size_t)(((p - d.g) % n + n) % n)];     // np.roll(diag, g) = the fork's rotate(v, -N1*j)
@@ -655,7 +554,7 @@ struct Boot {
         }
         return lt;
     }
-    // HCONV_DFT_DIGESTS: what the reference's encodeDiagonal receives and returns (mod Q): values; NTT rows in Montgomery form + the spare zero limb
+    // HCONV_DFT_DIGESTS: what the reference's encodeDiagonal receives and returns: values; mod Q the NTT rows in Montgomery form + the spare zero limb; the same mod P
     void digest_line(const LT &lt, int k, int g, int b, const std::vector<cplx> &rolled, int level, double pt_scale, const char *tag) {
         if (!dft_digests) return;
         Sha256 hv; hv.update(rolled.data(), rolled.size() * sizeof(cplx));
@@ -664,14 +563,11 @@ struct Boot {
         unpack_rows(rows, level + 1);
         for (int l = 0; l <= level; l++) { const uint64_t q = Q[(size_t)l], r = (uint64_t)((((u128)1) << 64) % q); for (int j = 0; j < N; j++) rows[(size_t)l * N + j] = mulmod(rows[(size_t)l * N + j], r, q); }
         Sha256 hq; hq.update(rows.data(), rows.size() * 8); hq.update(zero.data(), zero.size() * 8);
-        std::string mp = "";
-        if (lt.qp) {            // ... and mod P
-            const int np = (int)P.size(); std::vector<uint64_t> prow((size_t)np * N);
-            HCR(hc_download(hc, prow.data(), lt.giant.at(g).at(b).p.get() + (size_t)(level + 1) * N, prow.size() * 8));
-            for (int j = 0; j < np; j++) { const uint64_t q = P[(size_t)j], r = (uint64_t)((((u128)1) << 64) % q); for (int i = 0; i < N; i++) prow[(size_t)j * N + i] = mulmod(prow[(size_t)j * N + i], r, q); }
-            Sha256 hp; hp.update(prow.data(), prow.size() * 8); mp = hp.hex();
-        }
-        fprintf(dft_digests, "{\"matrix\": \"%s\", \"chain\": %d, \"level\": %d, \"scale\": %.17g, \"N1\": %d, \"k\": %d, \"values\": \"%s\", \"mQ\": \"%s\", \"mP\": \"%s\"}\n", tag, chain, level, pt_scale, lt.n1, k, hv.hex().c_str(), hq.hex().c_str(), mp.c_str());
+        const int np = (int)P.size(); std::vector<uint64_t> prow((size_t)np * N);
+        HCR(hc_download(hc, prow.data(), lt.giant.at(g).at(b).p.get() + (size_t)(level + 1) * N, prow.size() * 8));
+        for (int j = 0; j < np; j++) { const uint64_t q = P[(size_t)j], r = (uint64_t)((((u128)1) << 64) % q); for (int i = 0; i < N; i++) prow[(size_t)j * N + i] = mulmod(prow[(size_t)j * N + i], r, q); }
+        Sha256 hp; hp.update(prow.data(), prow.size() * 8);
+        fprintf(dft_digests, "{\"matrix\": \"%s\", \"chain\": %d, \"level\": %d, \"scale\": %.17g, \"N1\": %d, \"k\": %d, \"values\": \"%s\", \"mQ\": \"%s\", \"mP\": \"%s\"}\n", tag, chain, level, pt_scale, lt.n1, k, hv.hex().c_str(), hq.hex().c_str(), hp.hex().c_str());
     }
     // ckks.(*evaluator).LinearTransform -> MultiplyByDiagMatrixBSGS exactly as the reference's fork computes it (test_run @52a580; tests/lattigo_lt.py
     // is the same algorithm on the oracle and reproduces the binary's ModDown inputs / outputs and result on planted data, tests/test_oracle_pin_lt.py;
@@ -732,7 +628,7 @@ struct Boot {
                 rot[b] = r;
             }
         }
-        DCt res = new_ct(L, 1, ct.scale * lt.pt_scale); bool have_res[2] = {false, false};
+        DCt res = new_ct(L, ct.scale * lt.pt_scale); bool have_res[2] = {false, false};
         auto add_to_res = [&](int k, const std::shared_ptr<uint64_t> &x) { if (have_res[k]) HCR(hc_lv_add(hc, L, res.p[k].get(), x.get(), res.p[k].get())); else { res.p[k] = x; have_res[k] = true; } };
         auto B = block_qp2(); bool haveB = false;
         // the diagonal sums of all giant steps first, THREE per pass over the rotations (hc_qp_mul_sum_many, up to four: the rotated ciphertexts - the largest operands of a linear transform - are
@@ -769,8 +665,7 @@ struct Boot {
             HCR(hc_keyswitch_qp_rotate(hc, key(gal, L, 2), gal, L, nullptr, a1.get(), B.get(), 0, haveB ? 1 : 0)); n_keyswitch++; haveB = true;     // SwitchKeysInPlaceNoModDown, permuted into the accumulators
             Aof.erase(j);
         }
-        static const bool split_rescale = getenv("HCONV_NO_FUSED_RESCALE") != nullptr;
-        const bool fuse = fuse_min_scale > 0 && haveB && L >= 2 && !split_rescale && res.scale / (double)Q[(size_t)L] >= fuse_min_scale / 2;
+        const bool fuse = fuse_min_scale > 0 && haveB && L >= 2 && !no_fused_rescale() && res.scale / (double)Q[(size_t)L] >= fuse_min_scale / 2;
         auto diag0 = [&]() {
             if (!(lt.giant.count(0) && lt.giant.at(0).count(0))) return;
             const uint64_t *pt = lt.giant.at(0).at(0).p.get();
@@ -780,7 +675,7 @@ struct Boot {
         if (fuse) {            // every other term first (modular sums commute), then ModDown(B) + them + the first drop of the caller's Rescale in one pass
             diag0();
             if (have_res[0] != have_res[1]) for (int k = 0; k < 2; k++) if (!have_res[k]) { auto z = block(); HCR(hc_lv_mul_const(hc, L, ct.p[k].get(), zeros.data(), z.get())); add_to_res(k, z); }
-            DCt out = new_ct(L - 1, 1, res.scale / (double)Q[(size_t)L]); alg_ct += 2.0 * (2 * L + 1);
+            DCt out = new_ct(L - 1, res.scale / (double)Q[(size_t)L]); alg_ct += 2.0 * (2 * L + 1);
             HCR(hc_mod_down2_add_rescale(hc, L, B.get(), have_res[0] ? res.p[0].get() : nullptr, have_res[0] ? res.p[1].get() : nullptr, out.p[0].get(), out.p[1].get()));
             return out;
         }
@@ -794,153 +689,50 @@ struct Boot {
         return linear_transform_qp(ct, lt, nullptr, -1, fuse_min_scale);
     }
 
-    // ---------------- polynomial evaluation (tests/oracle_ckks.py: _power, _split, _plan_level, _eval_rec, eval_poly)
-    struct PolyEval {
-        Boot *B; bool cheby; std::map<int, DCt> T;
-        const DCt &power(int i) {
-            auto it = T.find(i); if (it != T.end()) return it->second;
-            const int a = (i + 1) / 2, b = i / 2;
-            DCt A = power(a), Bc = power(b);
-            DCt t = B->mul_relin_rescale(A, Bc);
-            if (cheby) {
-                t = B->add(t, t);
-                const int c = a - b;
-                if (c == 0) t = B->add_const(t, -1.0);
-                else { DCt Tc = power(c); const int L = std::min(t.level, Tc.level); t = B->sub(drop_to(t, L), relabel(drop_to(Tc, L), t.scale)); }
-            }
-            return T.emplace(i, t).first->second;
-        }
-        static void split(const std::vector<double> &c, int g, bool cheby, std::vector<double> &cq, std::vector<double> &cr) {
-            const int deg = (int)c.size() - 1;
-            cr.assign(c.begin(), c.begin() + g);
-            if (!cheby) { cq.assign(c.begin() + g, c.end()); return; }
-            cq.assign((size_t)(deg - g + 1), 0.0); cq[0] = c[(size_t)g];
-            for (int j = 1; j <= deg - g; j++) { cq[(size_t)j] = 2.0 * c[(size_t)(g + j)]; cr[(size_t)(g - j)] -= c[(size_t)(g + j)]; }
-        }
-        static int degree(const std::vector<double> &c) { int d = (int)c.size() - 1; while (d > 0 && c[(size_t)d] == 0) d--; return d; }
-        static int bit_length(int x) { int b = 0; while (x) { b++; x >>= 1; } return b; }
-        int plan_level(std::vector<double> c, int log_split, bool lead) {
-            const int deg = degree(c); c.resize((size_t)deg + 1);
-            if (deg < (1 << log_split)) {
-                if (lead && log_split > 1 && deg > (1 << (log_split - 1))) return plan_level(c, bit_length(deg) >> 1, true);
-                int lv = power(1).level; for (int i = 1; i <= deg; i++) if (c[(size_t)i] != 0) lv = std::min(lv, power(i).level);
-                return lv - 1;
-            }
-            int g = 1 << log_split; while (g * 2 <= deg) g *= 2;
-            std::vector<double> cq, cr; split(c, g, cheby, cq, cr);
-            const int lq = plan_level(cq, log_split, lead), lr = plan_level(cr, log_split, false);
-            return std::min(std::min(lq, power(g).level) - 1, lr);
-        }
-        DCt rec(std::vector<double> c, int log_split, bool lead, double target) {
-            const int deg = degree(c); c.resize((size_t)deg + 1);
-            if (deg < (1 << log_split)) {
-                if (lead && log_split > 1 && deg > (1 << (log_split - 1))) return rec(c, bit_length(deg) >> 1, true, target);
-                int lv = power(1).level; for (int i = 1; i <= deg; i++) if (c[(size_t)i] != 0) lv = std::min(lv, power(i).level);
-                const double pre = target * (double)B->Q[(size_t)lv];
-                DCt acc; bool have = false;
-                for (int i = 1; i <= deg; i++) if (c[(size_t)i] != 0) {
-                    DCt Xi = drop_to(power(i), lv);
-                    DCt term = B->mul_const_int(Xi, nearbyint(c[(size_t)i] * pre / Xi.scale)); term.scale = pre;
-                    acc = have ? B->add(acc, term) : term; have = true;
-                }
-                if (!have) panic("polynomial leaf without a non-constant term");
-                if (c[0] != 0) acc = B->add_const_int(acc, nearbyint(c[0] * pre));
-                return relabel(B->rescale(acc), target);
-            }
-            int g = 1 << log_split; while (g * 2 <= deg) g *= 2;
-            std::vector<double> cq, cr; split(c, g, cheby, cq, cr);
-            const DCt Xg = power(g);
-            const int lq = plan_level(cq, log_split, lead), lmul = std::min(lq, Xg.level);
-            DCt resq = rec(cq, log_split, lead, target * (double)B->Q[(size_t)lmul] / Xg.scale);
-            if (resq.level != lq) panic("polynomial evaluation: planned level differs");
-            DCt prod = relabel(B->mul_relin_rescale(resq, Xg), target);
-            bool rnz = false; for (double v : cr) if (v != 0) rnz = true;
-            if (rnz) prod = B->add(prod, rec(cr, log_split, false, target));
-            return prod;
-        }
-    };
-    // ---------------- ckks.(*evaluator).EvaluatePoly in the standard basis, AS THE REFERENCE'S FORK EVALUATES IT (evalReLU's three sign
-    // polynomials, conv.go:460-477): computePowerBasis (C[n] = Rescale(MulRelin(C[ceil n/2], C[n/2]))), recurse / splitCoeffs (baby-step
-    // giant-step, the giant power's level picks the modulus that fixes the quotient's target scale), evaluatePolyFromPowerBasis
-    // (MultByGaussianIntegerAndAdd with int64(c * targetScale * q / scale_of_power): truncation, not rounding; one Rescale), Add with the
-    // smaller-scale operand multiplied by uint64(ratio). tests/lattigo_poly.py is the same code on the oracle and reproduces EVERY nested
-    // ciphertext digest the reference binary produced for these polynomials (tests/test_oracle_pin_poly.py, gotrace -poly).
-    struct LPoly { std::vector<double> c; int max_deg; bool lead; int degree() const { return (int)c.size() - 1; } };
+    // ---------------- ckks.(*evaluator).EvaluatePoly and EvaluateCheby AS THE REFERENCE'S FORK EVALUATES THEM: one evaluator, the basis a value. Standard basis: evalReLU's
+    // three sign polynomials (conv.go:460-477); Chebyshev basis: the sine (EvaluateCheby @52d7c0). computePowerBasis[Cheby] (C[n] from C[ceil n/2], C[n/2], each product
+    // rescaled), recurse[Cheby] / splitCoeffs[Cheby] (baby-step giant-step, the giant power's level picks the modulus that fixes the quotient's target scale),
+    // evaluatePolyFromPowerBasis (MultByGaussianIntegerAndAdd with int64(c * targetScale * q / scale_of_power): truncation, not rounding; one Rescale), Add with the
+    // smaller-scale operand multiplied by uint64(ratio). tests/lattigo_poly.py is the same code on the oracle and reproduces EVERY nested ciphertext digest the reference
+    // binary produced for the sign polynomials (tests/test_oracle_pin_poly.py, gotrace -poly) and for the sine (tests/test_oracle_pin_cheby.py; on the GPU
+    // test_evaluate_cheby_vs_reference_trace_on_gpu). The bases differ in three places, each marked below: the power recurrence, how a polynomial is split, and when a
+    // short leading polynomial is split again.
+    enum Basis { STANDARD, CHEBYSHEV };
+    struct LPoly { std::vector<double> c; int max_deg; bool lead; int top() const { return (int)c.size() - 1; } };      // top: the formal degree (c's last index)
     DCt lt_rescale(DCt a, double min_scale) { while (a.level > 0 && a.scale / (double)Q[(size_t)a.level] >= min_scale / 2) a = rescale(a); return a; }   // ckks Rescale's drop rule
     DCt mul_relin_lt_rescale(const DCt &a, const DCt &b, double min_scale) {                          // lt_rescale(mul_relin(a, b)), the first drop inside the key switch
         const int L = std::min(a.level, b.level);
         if (L > 0 && a.scale * b.scale / (double)Q[(size_t)L] >= min_scale / 2) return lt_rescale(mul_relin_rescale(a, b), min_scale);
         return mul_relin(a, b);
     }
-    DCt lt_add(const DCt &a, const DCt &b) {                           // evaluateInPlace: uint64(ratio) * the smaller-scale operand
-        if (a.scale > b.scale) { const double k = floor(a.scale / b.scale); DCt bb = k > 1 ? mul_const_int(b, k) : b; bb.scale = a.scale; return add(a, bb); }
-        if (b.scale > a.scale) { const double k = floor(b.scale / a.scale); DCt aa = k > 1 ? mul_const_int(a, k) : a; aa.scale = b.scale; return add(aa, b); }
+    DCt lt_add(DCt a, DCt b) {                                         // evaluateInPlace's Add: the smaller-scale operand times uint64(ratio), then the common label
+        DCt &lo = a.scale < b.scale ? a : b; const double hi = std::max(a.scale, b.scale);
+        if (lo.scale < hi) { const double k = floor(hi / lo.scale); if (k > 1) lo = mul_const_int(lo, k); lo.scale = hi; }
         return add(a, b);
     }
     // lt_rescale(lt_add(mul_relin(a, b), tmp), sc) with the first drop inside the key switch: tmp (times evaluateInPlace's integer ratio) joins d0, d1 before the relinearisation
     DCt mul_relin_add_lt_rescale(const DCt &a, const DCt &b, const DCt &tmp, double sc) {
         const int L = std::min(a.level, b.level); const double ps = a.scale * b.scale;
-        static const bool split = getenv("HCONV_NO_FUSED_RESCALE") != nullptr;
-        if (split || L < 2 || tmp.level < L || tmp.deg != 1 || ps < tmp.scale || !(ps / (double)Q[(size_t)L] >= sc / 2)) return lt_rescale(lt_add(mul_relin(a, b), tmp), sc);
+        if (no_fused_rescale() || L < 2 || tmp.level < L || ps < tmp.scale || !(ps / (double)Q[(size_t)L] >= sc / 2)) return lt_rescale(lt_add(mul_relin(a, b), tmp), sc);
         const double k = ps > tmp.scale ? floor(ps / tmp.scale) : 1.0;
         const DCt bb = k > 1 ? mul_const_int(tmp, k) : tmp;
-        DCt r = new_ct(L - 1, 1, ps / (double)Q[(size_t)L]); alg_ct += 6.0 * (L + 1) + 6.0 * (L + 1) + 2.0 * (2 * L + 1); alg_shared += ks_rows(L);
+        DCt r = new_ct(L - 1, ps / (double)Q[(size_t)L]); alg_ct += 6.0 * (L + 1) + 6.0 * (L + 1) + 2.0 * (2 * L + 1); alg_shared += ks_rows(L);
         auto d0 = block(), d1 = block(), d2 = block();
         HCR(hc_lv_mul_tensor(hc, L, a.p[0].get(), a.p[1].get(), b.p[0].get(), b.p[1].get(), d0.get(), d1.get(), d2.get()));
         HCR(hc_lv_op2(hc, HC_LV_ADD, L, d0.get(), d1.get(), bb.p[0].get(), bb.p[1].get(), d0.get(), d1.get(), nullptr));
         HCR(hc_keyswitch_add_rescale(hc, key(0, L), L, d2.get(), d0.get(), d1.get(), r.p[0].get(), r.p[1].get())); n_keyswitch++;
         return lt_rescale(r, sc);
     }
-    void lt_power(std::map<int, DCt> &C, int n, double sc) {
-        if (C.count(n)) return;
-        const int a = (n + 1) / 2, b = n >> 1;
-        lt_power(C, a, sc); lt_power(C, b, sc);
-        C[n] = mul_relin_lt_rescale(C[a], C[b], sc);
-    }
-    DCt lt_leaf(double target, const LPoly &p, std::map<int, DCt> &C, double sc) {
-        if (p.degree() == 0) panic("EvaluatePoly: constant leaf (not produced by the sign polynomials)");
-        const int lv = C[p.degree()].level; const double qi = (double)Q[(size_t)lv];
-        if (fabs(p.c[0]) > 1e-14) panic("EvaluatePoly: constant term in a leaf (AddConst; not produced by the sign polynomials)");
-        std::vector<DCt> as; std::vector<double> ks;
-        for (int key = p.degree(); key > 0; key--) if (fabs(p.c[(size_t)key]) > 1e-14) {
-            const double const_scale = target * qi / C[key].scale;
-            as.push_back(C[key]); ks.push_back(trunc(p.c[(size_t)key] * const_scale));                     // Go's int64(float64)
-        }
-        if (as.empty()) panic("EvaluatePoly: empty leaf");
-        return lt_rescale(lincomb(as, ks, lv, target * qi), sc);                                           // MultByGaussianIntegerAndAdd per power: one launch
-    }
-    DCt lt_recurse(double target, int log_split, int log_degree, const LPoly &p, std::map<int, DCt> &C, double sc) {
-        if (p.degree() < (1 << log_split)) {
-            if (p.lead && log_split > 1 && p.degree() > (1 << (log_split - 1))) { const int ld = PolyEval::bit_length(p.degree()); return lt_recurse(target, ld >> 1, ld, p, C, sc); }
-            return lt_leaf(target, p, C, sc);
-        }
-        int next_power = 1 << log_split; while (next_power < (p.degree() >> 1) + 1) next_power <<= 1;
-        LPoly pr{std::vector<double>(p.c.begin(), p.c.begin() + next_power), p.max_deg == p.degree() ? next_power - 1 : p.max_deg - (p.degree() - next_power + 1), false};
-        LPoly pq{std::vector<double>(p.c.begin() + next_power, p.c.end()), p.max_deg, p.lead};
-        int level = C[next_power].level - 1; if (p.max_deg >= (1 << (log_degree - 1)) && p.lead) level++;
-        DCt res = lt_recurse(target * (double)Q[(size_t)level] / C[next_power].scale, log_split, log_degree, pq, C, sc);
-        DCt tmp = lt_recurse(target, log_split, log_degree, pr, C, sc);
-        if (res.level > tmp.level) res = drop_to(res, tmp.level + 1);                                     // DropLevel
-        if (std::min(res.level, C[next_power].level) > tmp.level) { res = mul_relin_lt_rescale(res, C[next_power], sc); res = lt_add(res, tmp); }
-        else res = mul_relin_add_lt_rescale(res, C[next_power], tmp, sc);
-        return res;
-    }
-    // ---- the Chebyshev basis of the same evaluator (EvaluateCheby @52d7c0: computePowerBasisCheby, splitCoeffsCheby, recurseCheby; the leaf is
-    // shared): tests/lattigo_poly.py's Chebyshev path, which reproduces every nested digest of the binary's sine evaluation
-    // (tests/test_oracle_pin_cheby.py; on the GPU test_evaluate_cheby_vs_reference_trace_on_gpu)
-    DCt lt_sub(const DCt &a, const DCt &b) {
-        if (a.scale > b.scale) { const double k = floor(a.scale / b.scale); DCt bb = k > 1 ? mul_const_int(b, k) : b; bb.scale = a.scale; return sub(a, bb); }
-        if (b.scale > a.scale) { const double k = floor(b.scale / a.scale); DCt aa = k > 1 ? mul_const_int(a, k) : a; aa.scale = b.scale; return sub(aa, b); }
-        return sub(a, b);
-    }
-    void lt_power_cheby(std::map<int, DCt> &C, int n, double sc) {                   // C[n] = 2 C[a] C[b] - C[a-b]
+    // C[n] = C[a] C[b], a = ceil(n/2), b = n/2; Chebyshev: C[n] = 2 C[a] C[b] - C[a-b] (a - b is 0 or 1, and C[1] is the input)
+    void lt_power(std::map<int, DCt> &C, int n, double sc, Basis basis) {
         if (C.count(n)) return;
         const int a = (n + 1) / 2, b = n >> 1, c = a - b;
-        lt_power_cheby(C, a, sc); lt_power_cheby(C, b, sc); if (c) lt_power_cheby(C, c, sc);
+        lt_power(C, a, sc, basis); lt_power(C, b, sc, basis);
         DCt t = mul_relin_lt_rescale(C[a], C[b], sc);
-        // 2 t - 1 (AddConst: floor(|scale| + 0.5)) or 2 t - C[c] (evaluateInPlace's Sub: the smaller-scale operand times uint64(ratio)) as ONE launch: the residues of Add(t, t)
-        // followed by AddConst / Sub, without their passes over the ciphertext
-        if (c == 0) C[n] = lincomb({t}, {2.0}, t.level, t.scale, true, -floor(fabs(t.scale) + 0.5));
+        // Chebyshev: 2 t - 1 (AddConst: floor(|scale| + 0.5)) or 2 t - C[c] (evaluateInPlace's Sub: the smaller-scale operand times uint64(ratio)) as ONE launch: the residues of
+        // Add(t, t) followed by AddConst / Sub, without their passes over the ciphertext
+        if (basis == STANDARD) C[n] = t;
+        else if (c == 0) C[n] = lincomb({t}, {2.0}, t.level, t.scale, true, -floor(fabs(t.scale) + 0.5));
         else {
             const DCt &u = C[c]; const int L = std::min(t.level, u.level);
             double kt = 1, ku = 1, scale = t.scale;
@@ -948,68 +740,56 @@ struct Boot {
             C[n] = lincomb({t, u}, {2.0 * kt, -ku}, L, scale);
         }
     }
-    DCt lt_leaf_any(double target, const LPoly &p, std::map<int, DCt> &C, double sc) {       // evaluatePolyFromPowerBasis incl. the constant term
+    DCt lt_leaf(double target, const LPoly &p, std::map<int, DCt> &C, double sc) {            // evaluatePolyFromPowerBasis incl. the constant term
         const bool c0 = fabs(p.c[0]) > 1e-14;
-        if (p.degree() == 0) { DCt z = mul_const_int(C[1], 0.0); z.scale = target; return c0 ? add_const(z, p.c[0]) : z; }
-        const int lv = C[p.degree()].level; const double qi = (double)Q[(size_t)lv];
+        if (p.top() == 0) { DCt z = mul_const_int(C[1], 0.0); z.scale = target; return c0 ? add_const(z, p.c[0]) : z; }
+        const int lv = C[p.top()].level; const double qi = (double)Q[(size_t)lv];
         std::vector<DCt> as; std::vector<double> ks;
-        for (int key = p.degree(); key > 0; key--) if (fabs(p.c[(size_t)key]) > 1e-14) {
+        for (int key = p.top(); key > 0; key--) if (fabs(p.c[(size_t)key]) > 1e-14) {
             const double const_scale = target * qi / C[key].scale;
             as.push_back(C[key]); ks.push_back(trunc(p.c[(size_t)key] * const_scale));                     // Go's int64(float64)
         }
         if (as.empty()) { as.push_back(C[1]); ks.push_back(0.0); }
-        // the constant term (evaluator.AddConst: floor(|c * scale| + 0.5), sign restored) rides in the same launch; the reference adds it first, residues mod q do not depend on the order
+        // MultByGaussianIntegerAndAdd per power: one launch. The constant term (evaluator.AddConst: floor(|c * scale| + 0.5), sign restored) rides in it; the reference adds it
+        // first, residues mod q do not depend on the order
         const double k0 = floor(fabs(target * qi * p.c[0]) + 0.5) * (p.c[0] < 0 ? -1.0 : 1.0);
         return lt_rescale(lincomb(as, ks, lv, target * qi, c0, k0), sc);
     }
-    DCt lt_recurse_cheby(double target, int log_split, int log_degree, const LPoly &p, std::map<int, DCt> &C, double sc) {
-        if (p.degree() < (1 << log_split)) {
-            if (p.lead && log_split > 1 && p.max_deg > ((1 << log_degree) - (1 << (log_split - 1)))) { const int ld = PolyEval::bit_length(p.degree()); return lt_recurse_cheby(target, ld >> 1, ld, p, C, sc); }
-            return lt_leaf_any(target, p, C, sc);
+    DCt lt_recurse(double target, int log_split, int log_degree, const LPoly &p, std::map<int, DCt> &C, double sc, Basis basis) {
+        if (p.top() < (1 << log_split)) {
+            // a short leading polynomial is split again on its own degree: recurse decides by the degree, recurseCheby by the maximum degree (both pinned by the binary's digests)
+            if (p.lead && log_split > 1 && (basis == STANDARD ? p.top() > (1 << (log_split - 1)) : p.max_deg > ((1 << log_degree) - (1 << (log_split - 1))))) {
+                const int ld = bit_length(p.top()); return lt_recurse(target, ld >> 1, ld, p, C, sc, basis);
+            }
+            return lt_leaf(target, p, C, sc);
         }
-        int next_power = 1 << log_split; while (next_power < (p.degree() >> 1) + 1) next_power <<= 1;
-        LPoly pr{std::vector<double>(p.c.begin(), p.c.begin() + next_power), p.max_deg == p.degree() ? next_power - 1 : p.max_deg - (p.degree() - next_power + 1), false};
-        LPoly pq{std::vector<double>((size_t)(p.degree() - next_power + 1), 0.0), p.max_deg, p.lead};
-        pq.c[0] = p.c[(size_t)next_power];
-        for (int i = next_power + 1, j = 1; i <= p.degree(); i++, j++) { pq.c[(size_t)(i - next_power)] = 2 * p.c[(size_t)i]; pr.c[(size_t)(next_power - j)] -= p.c[(size_t)i]; }
+        int next_power = 1 << log_split; while (next_power < (p.top() >> 1) + 1) next_power <<= 1;
+        // p = pq X^next_power + pr (splitCoeffs); Chebyshev: p = pq T_next_power + pr with T_g T_j = (T_(g+j) + T_(g-j)) / 2 (splitCoeffsCheby)
+        LPoly pr{std::vector<double>(p.c.begin(), p.c.begin() + next_power), p.max_deg == p.top() ? next_power - 1 : p.max_deg - (p.top() - next_power + 1), false};
+        LPoly pq{std::vector<double>(p.c.begin() + next_power, p.c.end()), p.max_deg, p.lead};
+        if (basis == CHEBYSHEV) for (int j = 1; j <= p.top() - next_power; j++) { pq.c[(size_t)j] = 2 * p.c[(size_t)(next_power + j)]; pr.c[(size_t)(next_power - j)] -= p.c[(size_t)(next_power + j)]; }
         int level = C[next_power].level - 1; if (p.max_deg >= (1 << (log_degree - 1)) && p.lead) level++;
-        DCt res = lt_recurse_cheby(target * (double)Q[(size_t)level] / C[next_power].scale, log_split, log_degree, pq, C, sc);
-        DCt tmp = lt_recurse_cheby(target, log_split, log_degree, pr, C, sc);
-        if (res.level > tmp.level) res = drop_to(res, tmp.level + 1);
+        DCt res = lt_recurse(target * (double)Q[(size_t)level] / C[next_power].scale, log_split, log_degree, pq, C, sc, basis);
+        DCt tmp = lt_recurse(target, log_split, log_degree, pr, C, sc, basis);
+        if (res.level > tmp.level) res = drop_to(res, tmp.level + 1);                                     // DropLevel
         if (std::min(res.level, C[next_power].level) > tmp.level) { res = mul_relin_lt_rescale(res, C[next_power], sc); res = lt_add(res, tmp); }
         else res = mul_relin_add_lt_rescale(res, C[next_power], tmp, sc);
         return res;
     }
-    DCt eval_cheby_lattigo(const DCt &ct, const std::vector<double> &coeffs, double target, double sc) {
+    // coeffs in `basis` at ct, result at scale `target`; sc = the evaluator's scale, the minimum every Rescale keeps
+    DCt eval_poly(const DCt &ct, const std::vector<double> &coeffs, double target, double sc, Basis basis) {
         std::map<int, DCt> C; C[1] = ct;
         LPoly p{coeffs, (int)coeffs.size() - 1, true};
-        const int log_degree = PolyEval::bit_length(p.degree()), log_split = log_degree >> 1;
-        for (int i = 2; i < (1 << log_split); i++) lt_power_cheby(C, i, sc);
-        for (int i = log_split; i < log_degree; i++) lt_power_cheby(C, 1 << i, sc);
-        return lt_recurse_cheby(target, log_split, log_degree, p, C, sc);
-    }
-    DCt eval_poly_lattigo(const DCt &ct, const std::vector<double> &coeffs, double target) {
-        std::map<int, DCt> C; C[1] = ct;
-        LPoly p{coeffs, (int)coeffs.size() - 1, true};
-        const double sc = 1073741824.0;                                                                  // evaluator.scale = params.Scale()
-        const int log_degree = PolyEval::bit_length(p.degree()), log_split = log_degree >> 1;
-        for (int i = 2; i < (1 << log_split); i++) lt_power(C, i, sc);
-        for (int i = log_split; i < log_degree; i++) lt_power(C, 1 << i, sc);
-        return lt_recurse(target, log_split, log_degree, p, C, sc);
-    }
-    DCt eval_poly(const DCt &ct, const std::vector<double> &coeffs, double target, bool cheby) {
-        if (!cheby) return eval_poly_lattigo(ct, coeffs, target);
-        PolyEval pe{this, cheby, {}};
-        pe.T[1] = ct;
-        const int deg = (int)coeffs.size() - 1, log_deg = PolyEval::bit_length(deg), log_split = log_deg >> 1;
-        for (int i = 2; i < (1 << log_split); i++) pe.power(i);
-        for (int i = log_split; i < log_deg; i++) pe.power(1 << i);
-        return pe.rec(coeffs, log_split, true, target);
+        const int log_degree = bit_length(p.top()), log_split = log_degree >> 1;
+        for (int i = 2; i < (1 << log_split); i++) lt_power(C, i, sc, basis);
+        for (int i = log_split; i < log_degree; i++) lt_power(C, 1 << i, sc, basis);
+        return lt_recurse(target, log_split, log_degree, p, C, sc, basis);
     }
 
     // ---------------- the bootstrapper
     void build(const std::vector<int64_t> &sk_in, const Seed256 &seed, int device, int chain_ = 6) {
         chain = chain_;
+        if (chain != 6 && chain != 7) panic("the bootstrapper runs on parameter set [6] or [7]: unsupported chain");
         if (chain == 7 && testOnlyEnv("HCONV_CHAIN_REPLAY_BL")) { replay_seed = strtoull(testOnlyEnv("HCONV_CHAIN_REPLAY_BL"), nullptr, 0); fprintf(stderr, "hconv: HCONV_CHAIN_REPLAY_BL: planted keys and input for the baseline's Bootstrapp (test mode; the run ends behind it)\n"); }
         if (chain == 6 && testOnlyEnv("HCONV_CHAIN_REPLAY")) { replay_seed = strtoull(testOnlyEnv("HCONV_CHAIN_REPLAY"), nullptr, 0); fprintf(stderr, "hconv: HCONV_CHAIN_REPLAY: planted keys and input (test mode; results are meaningless as ciphertexts)\n"); }
         Q = chain == 7 ? PARAMS7_Q : PARAMS6_Q; P = PARAMS6_P; NQ = (int)Q.size(); sk = sk_in; rng.reseed(seed, 0xB007B007ull + (uint64_t)chain_);
@@ -1028,14 +808,6 @@ struct Boot {
             for (int j = 0; j < N; j++) h[(size_t)j] = sk[(size_t)j] >= 0 ? (uint64_t)sk[(size_t)j] : q - (uint64_t)(-sk[(size_t)j]);
             HCR(hc_upload(hc, d_sk + (size_t)m * N, h.data(), (size_t)N * 8)); HCR(hc_ntt(hc, m, d_sk + (size_t)m * N, d_sk + (size_t)m * N, 1));
         }
-        // Chebyshev interpolant of cos(2 pi (K u - 1/4) / 2^r) on [-1,1]
-        const int m = SIN_DEG + 1; sine.assign((size_t)m, 0.0);
-        for (int j = 0; j < m; j++) {
-            double s = 0;
-            for (int k = 0; k < m; k++) { const double u = cos(M_PI * (k + 0.5) / m); s += cos(2.0 * M_PI * (SIN_K * u - 0.25) / (double)(1 << SIN_DOUBLE)) * cos(j * M_PI * (k + 0.5) / m); }
-            sine[(size_t)j] = 2.0 / m * s;
-        }
-        sine[0] /= 2;
         key(2ull * N - 1, LV_SINE_TOP);                                      // conjugation
         for (int l = LV_SINE_TOP; l >= lv_relin_lo; l--) if (chain == 6 || l > LV_RELU_TOP || l <= 12) key(0, l);     // kgen.GenRelinearizationKey (main.go:411), at the levels that multiply
         if (chain == 7) { key(2ull * N - 1, 1); key(2ull * N - 1, 12); }       // pack_evaluator.ConjugateNew before / after Bootstrapp (test_BL.go:116, 155)
@@ -1048,35 +820,27 @@ struct Boot {
         auto it = sets.find(ls); if (it != sets.end()) return it->second;
         Set S; S.ls = ls; S.ns = n >> ls;
         if (!dft_digests && getenv("HCONV_DFT_DIGESTS") && *getenv("HCONV_DFT_DIGESTS")) { dft_digests = fopen(getenv("HCONV_DFT_DIGESTS"), "a"); if (!dft_digests) panic("HCONV_DFT_DIGESTS: cannot open the file"); }
-        const int D = 1 << ls, ns = S.ns;
-        // CoeffsToSlots: (1/n_s) prod(stages), times 1/2 (real/imaginary extraction), 1/K (Chebyshev argument in [-1,1]), 1/D (SubSum)
-        // Full slots: the fork's own matrices (lattigo_dft) with its constant coeffsToSlotsDiffScale = (2 / ((b-a) N scFac qDiff))^(1/4), b-a = 2K/scFac,
-        // qDiff = q0 / 2^round(log2 q0) (genDFTMatrices) - the same 1/(2 n K) as below divided by qDiff, which ctos() accounts for by
-        // labelling the raised ciphertext 2^round(log2 q0) instead of q0 - and its baby-step size N1. For parameter set [6] these are the
-        // reference binary's diagonals bit for bit (tests/golden/ref_trace_diag_5_1.json). Sparse slots keep this file's own generator.
+        if (chain == 7 && ls) panic("the baseline's chain (parameter set [7]) has the full-slot bootstrapper only");
+        const int ns = S.ns;
+        // CoeffsToSlots: the fork's own matrices (lattigo_dft), four on levels 27..24 at plaintext scale q_level, with its constant coeffsToSlotsDiffScale =
+        // (2 / ((b-a) N scFac qDiff))^(1/4), b-a = 2K/scFac, qDiff = q0 / 2^round(log2 q0) (genDFTMatrices) - 1/(2 n K) divided by qDiff, which ctos() accounts for by labelling
+        // the raised ciphertext 2^round(log2 q0) instead of q0 - and its baby-step size N1 (plan). These are the reference binary's diagonals bit for bit, full slots
+        // (tests/golden/ref_trace_diag_5_1.json) and sparse (ref_trace_diag_sparse_ls*.json: vectors of 2 n_s entries, rotations modulo that period).
         const double scfac = (double)(1 << SIN_DOUBLE), qdiff = (double)Q[0] / exp2(round(log2((double)Q[0])));
-        const bool fork = chain == 6;           // parameter set [6] (Ours): the fork's matrices, sparse slots included (round 3); the baseline's chain keeps this file's generator for ls > 0
-        const int period = ls && fork ? 2 * ns : 0;
-        std::vector<DiagMat> G = ls && !fork ? dft_groups(true, {4, 4, 4, 3}, 1.0 / (2.0 * (double)ns * SIN_K * D), ls)
-                                             : lattigo_dft(true, 4, pow(2.0 / ((2.0 * SIN_K / scfac) * (double)N * scfac * qdiff), 1.0 / 4.0), ls);
-        if (ls && !fork) for (auto &e : G.back()) for (int p = 0; p < n; p++) if (p % (2 * ns) >= ns) e.second[(size_t)p] = cplx(0, 0);   // keep w on the first half of every 2 n_s slots
+        const int period = ls ? 2 * ns : 0;
+        std::vector<DiagMat> G = lattigo_dft(true, 4, pow(2.0 / ((2.0 * SIN_K / scfac) * (double)N * scfac * qdiff), 1.0 / 4.0), ls);
         static const char *cts_tag[4] = {"cts0", "cts1", "cts2", "cts3"}, *stc_tag[3] = {"stc0", "stc1", "stc2"};
-        for (size_t i = 0; i < G.size(); i++) { const int lv = LV_CTS_TOP - (int)i; S.cts.push_back(plan(G[i], lv, (double)Q[(size_t)lv], ls == 0 || fork, cts_tag[i], period)); }
-        // SlotsToCoeffs: level 3 carries all but the last matrix (plaintext scales multiply to q3), level 2 the last at 2^30
-        // (the fork: the set NewBootstrapper_mod builds with scale 1 - the reference's SlotsToCoeffs call uses it - at the same three scales)
-        // (the stock Bootstrapp of parameter set [7]: the set with the bootstrapping scale, (qDiff * params.scale / prescale)^(1/3) per matrix - matrices 4-6 of ref_trace_diag_5_1.json)
+        for (size_t i = 0; i < G.size(); i++) { const int lv = LV_CTS_TOP - (int)i; S.cts.push_back(plan(G[i], lv, (double)Q[(size_t)lv], cts_tag[i], period)); }
+        // SlotsToCoeffs: three matrices, the first two at plaintext scale sqrt(q_top), the last at 2^30.
+        // Parameter set [6]: the set NewBootstrapper_mod builds with scale 1 - the reference's SlotsToCoeffs call uses it -; the fork applies all three on level 3 and
+        // rescales afterwards (ckks.SlotsToCoeffs -> dft: the Rescale after each LinearTransform finds nothing to drop).
+        // Parameter set [7] (the stock Bootstrapp): the set with the bootstrapping scale, (qDiff * params.scale / prescale)^(1/3) per matrix - matrices 4-6 of
+        // ref_trace_diag_5_1.json -, on levels 15, 15, 14.
         const double stc_const = chain == 7 ? pow(qdiff * 1073741824.0 / exp2(round(log2((double)Q[0] / 256.0))), 1.0 / 3.0) : 1.0;
-        G = ls && !fork ? dft_groups(false, {5, 5, 5}, 1.0, ls) : lattigo_dft(false, 3, stc_const, ls);
-        if (ls && !fork) {       // packed a = (re | im)  ->  w = re + i im on both halves:  w = (m1 + i m2) a + (i m1 + m2) rot_{n_s}(a)
-            DiagMat W; W[0].resize((size_t)n); W[ns].resize((size_t)n);
-            for (int p = 0; p < n; p++) { const bool first = p % (2 * ns) < ns; W[0][(size_t)p] = first ? cplx(1, 0) : cplx(0, 1); W[ns][(size_t)p] = first ? cplx(0, 1) : cplx(1, 0); }
-            G[0] = matmul_diag(G[0], W, 2 * ns);
-        }
+        G = lattigo_dft(false, 3, stc_const, ls);
         if (G.size() != 3) panic("SlotsToCoeffs is planned as three matrices");
-        for (size_t i = 0; i + 1 < G.size(); i++) S.stc.push_back(plan(G[i], LV_STC_TOP, stc_scale_top, ls == 0 || fork, stc_tag[i], period));
-        // the fork applies all three matrices on level 3 and rescales twice afterwards (ckks.SlotsToCoeffs -> dft: the Rescale after each
-        // LinearTransform finds nothing to drop); full slots on parameter set [6] do the same, the other bootstrappers keep the split above
-        S.stc.push_back(plan(G.back(), fork ? LV_STC_TOP : LV_STC_TOP - 1, stc_scale_last, ls == 0 || fork, stc_tag[2], period));
+        for (size_t i = 0; i + 1 < G.size(); i++) S.stc.push_back(plan(G[i], LV_STC_TOP, stc_scale_top, stc_tag[i], period));
+        S.stc.push_back(plan(G.back(), chain == 6 ? LV_STC_TOP : LV_STC_TOP - 1, stc_scale_last, stc_tag[2], period));
         for (auto *grp : {&S.cts, &S.stc}) for (auto &lt : *grp) for (auto &g : lt.giant) {
             if (g.first) key(gal_rot(g.first), lt.level, 2);
             for (auto &b : g.second) if (b.first) key(gal_rot(b.first), lt.level, 1);
@@ -1091,7 +855,7 @@ struct Boot {
     }
     // level-0 coefficient-encoded ciphertext -> slot-encoded at level 15, scale 2^30: two ciphertexts (low / high coefficient
     // half, bit-reversed order) for ls = 0, one packed ciphertext for ls > 0
-    // Full slots on parameter set [6]: ckks.(*Bootstrapper).BootstrappConv_CtoS op for op as the reference's fork runs it (gotrace -flow,
+    // Parameter set [6], full slots: ckks.(*Bootstrapper).BootstrappConv_CtoS op for op as the reference's fork runs it (gotrace -flow,
     // tests/golden/ref_flow_5_1.json; tests/oracle_ckks.py Bootstrapper._ctos_fork is the same on the oracle): ScaleUp to prescale =
     // 2^round(log2(q0 / MessageRatio)), modUp, ScaleUp to sinescale / MessageRatio, four times LinearTransform + Rescale(min = the scale
     // before), ct + conj and (ct - conj) / i, the label sinescale = 2^round(log2 q0), AddConst(-0.5 / (scFac (b - a))), EvaluateCheby with the
@@ -1099,11 +863,11 @@ struct Boot {
     // MultByConst(q0 / sinescale * params.scale / prescale) and Rescale: two ciphertexts at level 14, scale 2^30.
     // Sparse slots (ls > 0, round 3; gotrace -flow -logslots 13 shows the binary's op sequence): subSum after the second ScaleUp (Rotate by 2^i,
     // Add, i = logSlots .. logN-2), and after DivByi the repacking Rotate(ct1, 2^logSlots) + Add(ct0, ct1): one ciphertext through the sine.
-    // stock = true: the first half of the stock ckks.(*Bootstrapper).Bootstrapp (the baseline, parameter set [7]; gotrace -flow-bl, tests/golden/ref_flow_bl_5_1.json): SetScale(ct,
+    // Parameter set [7] (stock): the first half of the stock ckks.(*Bootstrapper).Bootstrapp (the baseline, parameter set [7]; gotrace -flow-bl, tests/golden/ref_flow_bl_5_1.json): SetScale(ct,
     // prescale) - MultByConst + Rescale down to level 0 - instead of the first ScaleUp, the same modUp / ScaleUp / CoeffsToSlots / evaluateSine, and no MultByConst + Rescale at
     // the end: two ciphertexts at level 15, scale 2^30, for SlotsToCoeffs.
-    int ctos_fork(const DCt &ct0, DCt out[2], int ls = 0, bool stock = false) {
-        Set &S = set(ls);
+    int ctos(const DCt &ct0, int ls, DCt out[2]) {
+        Set &S = set(ls); const bool stock = chain == 7;
         const double q0 = (double)Q[0], msg_ratio = 256.0, pscale = 1073741824.0;
         const double prescale = exp2(round(log2(q0 / msg_ratio))), sinescale = exp2(round(log2(q0)));
         DCt ct;
@@ -1135,7 +899,7 @@ struct Boot {
         for (int h = 0; h < (merged ? 1 : nparts); h++) {
             DCt c = parts[h]; c.scale = sinescale;
             c = add_const(c, -0.5 / (scfac * (2.0 * SIN_K / scfac)));
-            c = eval_cheby_lattigo(c, coeffs, target, sinescale);
+            c = eval_poly(c, coeffs, target, sinescale, CHEBYSHEV);
             double sqrt2pi = pow(0.15915494309189535, 1.0 / scfac);
             for (int r = 0; r < SIN_DOUBLE; r++) { sqrt2pi *= sqrt2pi; c = mul_relin(c, c); c = add(c, c); c = lt_rescale(add_const(c, -sqrt2pi), sinescale); }
             if (c.level != LV_RELU_TOP) panic("sine evaluation ended at the wrong level");
@@ -1144,35 +908,11 @@ struct Boot {
         }
         return nparts;
     }
-    int ctos(const DCt &ct0, int ls, DCt out[2]) {
-        if (chain == 6) return ctos_fork(ct0, out, ls);
-        if (chain == 7 && ls == 0) return ctos_fork(ct0, out, 0, true);
-        Set &S = set(ls);
-        const double q0 = (double)Q[0], msg_scale = ct0.scale;
-        DCt ct = mod_raise(ct0, LV_CTS_TOP); ct.scale = ls ? q0 : exp2(round(log2(q0)));   // slot values are now t'/Q0 = I + msg/Q0, |.| <= K (full slots: the 1/qDiff sits in the matrices)
-        for (int j = 0; j < ls; j++) ct = add(ct, rotate(ct, S.ns << j));                                  // SubSum: trace onto X^D
-        for (auto &lt : S.cts) ct = rescale(linear_transform(ct, lt));
-        if (ct.level != LV_SINE_TOP) panic("CoeffsToSlots ended at the wrong level");
-        DCt cc = conjugate(ct);
-        DCt parts[2] = {add(ct, cc), monomial_fma(cc, ct, N, N / 2)};           // (w + conj w), -i (w - conj w); the 1/2 is in the matrices
-        int np = 2;
-        if (ls) { parts[0] = add(parts[0], rotate(parts[1], S.ns)); np = 1; }
-        const double c_m = q0 / (2.0 * M_PI * msg_scale);
-        double s = sine_out_scale * c_m;
-        for (int r = 0; r < SIN_DOUBLE; r++) s = sqrt(s * (double)Q[(size_t)(LV_RELU_TOP + 1 + r)]);
-        for (int h = 0; h < np; h++) {
-            DCt c = eval_poly(parts[h], sine, s, true);
-            for (int r = 0; r < SIN_DOUBLE; r++) { c = mul_relin(c, c); c = add(c, c); c = rescale(add_const(c, -1.0)); }
-            if (c.level != LV_RELU_TOP) panic("sine evaluation ended at the wrong level");
-            c.scale = c.scale / c_m;                                     // value *= c_m: now msg / msg_scale
-            out[h] = c;
-        }
-        return np;
-    }
+    // slot-encoded (re, im halves; sparse slots: one packed ciphertext) -> coefficient-encoded
     DCt stoc(const DCt &re, const DCt *im, int ls) {
         Set &S = set(ls);
         if (ls && im) panic("sparse SlotsToCoeffs takes one packed ciphertext");
-        if (chain == 7 && ls == 0) {      // ckks.SlotsToCoeffs inside the stock Bootstrapp (ref_flow_bl_5_1.json): MultByi + Add, LinearTransform on the matrices' own levels 15, 15, 14, each followed by a Rescale(min = the scale before) that finds nothing to drop: level 14, scale ~2^120
+        if (chain == 7) {      // ckks.SlotsToCoeffs inside the stock Bootstrapp (ref_flow_bl_5_1.json): MultByi + Add, LinearTransform on the matrices' own levels 15, 15, 14, each followed by a Rescale(min = the scale before) that finds nothing to drop: level 14, scale ~2^120
             DCt ct = monomial_fma(re, *im, N / 2, 0);
             std::shared_ptr<uint64_t> prev_c1;                                       // the second polynomial of the previous LinearTransform's input (see linear_transform_qp)
             for (auto &lt : S.stc) {
@@ -1188,14 +928,11 @@ struct Boot {
             }
             return ct;
         }
+        // parameter set [6]: ckks.SlotsToCoeffs as the fork runs it (sparse slots: one packed ciphertext, no MultByi + Add) (ref_flow_5_1.json): MultByi + Add, three LinearTransforms
+        // each followed by Rescale(min = the scale before), then eval.go:564's Rescale(2^30): level 3 -> 1
         DCt ct = drop_to(ls ? re : monomial_fma(re, *im, N / 2, 0), LV_STC_TOP);
-        if (chain == 6) {        // ckks.SlotsToCoeffs as the fork runs it (sparse slots: one packed ciphertext, no MultByi + Add) (ref_flow_5_1.json): MultByi + Add, three LinearTransforms each followed by Rescale(min = the scale before), then eval.go:564's Rescale(2^30): level 3 -> 1
-            for (auto &lt : S.stc) { const double s_in = ct.scale; ct = lt_rescale(linear_transform(ct, lt, s_in), s_in); }
-            return lt_rescale(ct, 1073741824.0);
-        }
-        for (size_t i = 0; i + 1 < S.stc.size(); i++) ct = linear_transform(ct, S.stc[i]);
-        ct = rescale(ct);
-        return rescale(linear_transform(ct, S.stc.back()));
+        for (auto &lt : S.stc) { const double s_in = ct.scale; ct = lt_rescale(linear_transform(ct, lt, s_in), s_in); }
+        return lt_rescale(ct, 1073741824.0);
     }
 };
 // rot_util.go:141-174
@@ -1284,9 +1021,9 @@ static DCt evalReLU(Boot *B, const DCt &ct_in, double alpha) {
     std::vector<double> c3 = {0.0, 3.29956739043733, 0.0, -7.84227260291355, 0.0, 12.8907764115564, 0.0, -12.4917112584486, 0.0, 6.94167991428074, 0.0, -2.04298067399942, 0.0, 0.246407138926031};
     for (auto &v : c3) v *= b;
     printf("Eval: ");
-    DCt s = B->eval_poly(ct_in, c1, sc, false);
-    s = B->eval_poly(s, c2, sc, false);
-    s = B->eval_poly(s, c3, sc, false);
+    DCt s = B->eval_poly(ct_in, c1, sc, sc, Boot::STANDARD);             // target scale and evaluator.scale: both params.Scale()
+    s = B->eval_poly(s, c2, sc, sc, Boot::STANDARD);
+    s = B->eval_poly(s, c3, sc, sc, Boot::STANDARD);
     s = B->add_const(s, a);
     return B->mul_relin(s, Boot::drop_to(ct_in, s.level));            // Mul + Relinearize, no rescale (conv.go:475-477)
 }
@@ -1315,7 +1052,7 @@ void bootPrepareCompress(Boot *B, int in_wid, int kp_wid, int log_sparse) {
 }
 void freeBoot(Boot *b) {
     if (!b) return;
-    b->sets.clear(); b->pt_cache.clear(); b->mono_i.reset();      // every block returns to the pool
+    b->sets.clear(); b->pt_cache.clear();      // every block returns to the pool
     for (uint64_t *blk : b->pool) hc_free(b->hc, blk);
     b->pool.clear();
     for (uint64_t *blk : b->pool_qp) hc_free(b->hc, blk);
@@ -1347,7 +1084,7 @@ static void replay_digest_line(Boot *B, const char *what, const DCt &c, int firs
         const int img = first_image + z;
         std::string line = std::string("replay digest") + (img ? "[" + std::to_string(img) + "] " : " ") + what + " level " + std::to_string(c.level);
         char sc[40]; snprintf(sc, sizeof sc, " scale %.17g", c.scale); line += sc;
-        for (int d = 0; d <= c.deg; d++) { std::vector<uint64_t> rows((size_t)(c.level + 1) * N); HCR(hc_download(hc, rows.data(), c.p[d].get() + (size_t)z * B->poly_stride(), rows.size() * 8)); B->unpack_rows(rows, c.level + 1); Sha256 h; h.update(rows.data(), rows.size() * 8); line += " " + h.hex(); }
+        for (int d = 0; d < 2; d++) { std::vector<uint64_t> rows((size_t)(c.level + 1) * N); HCR(hc_download(hc, rows.data(), c.p[d].get() + (size_t)z * B->poly_stride(), rows.size() * 8)); B->unpack_rows(rows, c.level + 1); Sha256 h; h.update(rows.data(), rows.size() * 8); line += " " + h.hex(); }
         printf("%s\n", line.c_str());
     }
 }
@@ -1386,7 +1123,7 @@ struct LayerDebug {
     std::vector<double> decode(const std::vector<const DCt *> &cts, int ls) {
         hc_ctx *hc = B->hc; const DCt &f = *cts[0]; std::vector<const uint64_t *> c0, c1;
         for (const DCt *c : cts) {
-            if (c->deg != 1 || c->level != f.level || c->scale != f.scale) panic("HCONV_DEBUG_LAYERS: the ciphertexts of a stage differ in degree, level or scale");
+            if (c->level != f.level || c->scale != f.scale) panic("HCONV_DEBUG_LAYERS: the ciphertexts of a stage differ in level or scale");
             for (int z = 0; z < B->nb; z++) { c0.push_back(c->p[0].get() + (size_t)z * B->poly_stride()); c1.push_back(c->p[1].get() + (size_t)z * B->poly_stride()); }
         }
         const int count = (int)c0.size(); const size_t per = ls < 0 ? (size_t)N : (size_t)2 << ls;
@@ -1500,7 +1237,7 @@ std::vector<BootCiphertext> evalConv_BNRelu_tail_batch(Boot *B, const std::strin
     const int nimg = (int)ct_conv_dev.size();
     if (nimg < 1 || nimg > (B->merge_parts ? B->nb_max / 2 : B->nb_max)) panic("evalConv_BNRelu_tail: more images than the bootstrapper's image batch (HCONV_IMAGE_BATCH)");
     Boot::Batch batch_scope(B, nimg); B->alg_ct = B->alg_shared = 0;                                  // hc_set_batch(nimg) here, hc_set_batch(1) wherever this function is left
-    DCt ct = B->new_ct(0, 1, ct_scale * pow(2.0, pow_));                                            // eval.go:437
+    DCt ct = B->new_ct(0, ct_scale * pow(2.0, pow_));                                           // eval.go:437
     for (int z = 0; z < nimg; z++) for (int d = 0; d < 2; d++) HCR(hc_copy(hc, ct.p[d].get() + (size_t)z * B->poly_stride(), ct_conv_dev[(size_t)z] + (size_t)d * N, (size_t)N * 8));
     // ct_conv_dev belongs to ANOTHER context (the convolution's): the copies above are queued on this context's stream, and the caller frees
     // the sources as soon as this function returns. Wait for them (the stream holds nothing else at this point) so that the hand-over
@@ -1519,7 +1256,7 @@ std::vector<BootCiphertext> evalConv_BNRelu_tail_batch(Boot *B, const std::strin
             HCR(hc_upload(hc, ct.p[k].get() + (size_t)z * B->poly_stride(), row.data(), (size_t)N * 8));
         }
     }
-    const bool prof = getenv("HCONV_PROFILE") && atoi(getenv("HCONV_PROFILE"));
+    const bool prof = profiling();
     std::unique_ptr<LayerDebug> dbg;
     if (debugLayers()) {
         const char *ck = testOnlyEnv("HCONV_DEBUG_LAYERS_CHECK");                                       // fatal outside test mode
@@ -1595,7 +1332,7 @@ void blBootReLU(Boot *B, const uint64_t *ct_res0, const uint64_t *ct_res1, doubl
     auto img_eval = now();
     DCt c[2];
     for (int pos = 0; pos < 2; pos++) {
-        DCt t = B->new_ct(1, 1, scale); const uint64_t *src = pos ? ct_res1 : ct_res0;
+        DCt t = B->new_ct(1, scale); const uint64_t *src = pos ? ct_res1 : ct_res0;
         for (int d = 0; d < 2; d++) HCR(hc_copy(hc, t.p[d].get(), src + (size_t)d * 2 * N, (size_t)2 * N * 8));
         c[pos] = B->add(B->conjugate(t), t);                                                             // test_BL.go:116
         if (pos == 1) c[pos] = B->mul_by_i(c[pos]);                                                      // MultByiNew (118)
@@ -1635,9 +1372,7 @@ void blBootReLU(Boot *B, const uint64_t *ct_res0, const uint64_t *ct_res1, doubl
     DCt ct_iboot = B->conjugate(ct_boot);                                                                // test_BL.go:155
     DCt res[2] = {B->add(ct_boot, ct_iboot), B->monomial_fma(ct_iboot, ct_boot, N, N / 2)};                    // DivByi(a - b) = i (b - a)
     HCR(hc_sync(hc));
-    { double ns = (img_part + std::chrono::duration<double>(now() - img_eval).count()) * 1e9; char b[64];
-      if (ns < 1e6) snprintf(b, sizeof b, "%.6gµs", ns / 1e3); else if (ns < 1e9) snprintf(b, sizeof b, "%.9gms", ns / 1e6); else snprintf(b, sizeof b, "%.9gs", ns / 1e9);
-      printf("Imaginary packing and unpacking done in %s \n", b); }
+    printf("Imaginary packing and unpacking done in %s \n", dur_ns((img_part + std::chrono::duration<double>(now() - img_eval).count()) * 1e9).c_str());
     auto start = now();
     for (int pos = 0; pos < 2; pos++) {                                                                  // test_BL.go:160-167
         DCt r = evalReLU(B, res[pos], alpha);
