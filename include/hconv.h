@@ -250,7 +250,15 @@ int hc_qp_mul_sum2(hc_ctx *ctx, int level, int nterms, const uint64_t *const *a,
 int hc_qp_mul_sum_many(hc_ctx *ctx, int level, int nterms, int ngiant, const uint64_t *const *a, const uint64_t *const *pt, uint64_t *const *out, const int *accumulate);
 
 /* ---- L1: the fused hot path ---- */
-/* pl_ker as prep_Ker leaves it (conv.go:510-515): HOST array [max_ob][2][N], level 1, NTT domain. */
+/* pl_ker as prep_Ker leaves it (conv.go:510-515): HOST array [max_ob][2][N], level 1, NTT domain.
+ * WHAT A HANDLE HOLDS. The plaintexts as loaded, never modified ([max_ob][2][N]: hc_ker_download, hc_conv_mult_phase, hc_conv_then_pack_sharded and a handle used at
+ * several shapes see exactly these). And, from the first hc_conv_then_pack / hc_conv_then_pack_batch call that can use it, a FOLDED COPY of the x-role half of the
+ * live channels - channels i >= max_ob / 2 with i % norm == 0, the ones the pack tree's leaf level multiplies by its idx plaintext - each limb already multiplied by
+ * that level's monomial NTT(X^(2^s)), s = log2(max_ob / 2), modulo Q0 and modulo Q1: [(max_ob / 2) / norm][2][N] words, HALF the live channels' plaintexts again
+ * in device memory (128 MiB beside the 256 MiB of a 256-channel layer). It is made by one pointwise kernel on the context's stream (the first call with a handle is slower
+ * by that), belongs to the (max_ob, norm) of that call and to the idx table then in force, is remade when a later call on the handle uses another (max_ob, norm), is out
+ * of date after any later hc_idx_load (dropped at the handle's next use) and is freed by hc_ker_free. If it cannot be allocated the call runs without it. The copy
+ * is made and read on the stream of the context the handle is used with: a handle belongs to one context, the one that loaded it and frees it. */
 int hc_ker_load(hc_ctx *ctx, const uint64_t *pl_ker_host, int max_ob, hc_ker **out);
 /* same from a DEVICE array (e.g. produced by hc_ntt); the input buffer is not retained */
 int hc_ker_load_device(hc_ctx *ctx, const uint64_t *pl_ker_dptr, int max_ob, hc_ker **out);
@@ -276,7 +284,9 @@ int hc_prep_ker_ex2(hc_ctx *ctx, const double *ker_in, int ker_len, const double
 /* the plaintexts of a handle as Lattigo would hold them: HOST out [max_ob][2][N], canonical NTT residues */
 int hc_ker_download(hc_ctx *ctx, const hc_ker *ker, uint64_t *host_out);
 void hc_ker_free(hc_ctx *ctx, hc_ker *ker);
-/* plain_idx (conv.go:241-261): NULL => derive idx[s] = NTT(X^(2^s)) on the device; else HOST array [logN][N] */
+/* plain_idx (conv.go:241-261): NULL => derive idx[s] = NTT(X^(2^s)) on the device; else HOST array [logN][N], taken as it comes and compared on the device with the
+ * derived table: only under the monomial table do hc_conv_then_pack(_batch) fold the leaf level into the kernel plaintexts (hc_ker_load). Every call makes the folded
+ * copies of all handles out of date. */
 int hc_idx_load(hc_ctx *ctx, const uint64_t *idx_host);
 
 /* conv_then_pack (conv.go:522-546) followed by eval.go:258's bias add when bias != NULL.
@@ -304,7 +314,13 @@ int hc_conv_then_pack(hc_ctx *ctx, const uint64_t *ct_in, double ct_scale, const
  * group's members are consecutive; the group's bias is its first member's entry, every other member's entry is NULL or that same
  * pointer. Groups of unequal size, a ct_out that recurs in a later, non-adjacent position and a conflicting bias entry each
  * return HC_ERR_ARG (hc_last_error says which) before anything is launched or written. With all ct_out distinct (m = 1) the call
- * is the one described above, launch for launch. */
+ * is the one described above, launch for launch.
+ * THE LEAF LEVEL WITHOUT ITS idx PRODUCT (this call and hc_conv_then_pack). idx[s] is a monomial and loop A's rescale is odd-symmetric coefficient by coefficient, so
+ * SetScale(ct (*) (idx[s] (*) k_i)) = idx[s] (*) SetScale(ct (*) k_i) in canonical residues. When the idx table in force is the monomial table (hc_idx_load), the leaf
+ * level's switching key permutes inside 256-coefficient rows and the leaf level has more nodes over the batch than option small_levels, the x-role channels of loop A
+ * run in launches of their own on every member's folded copy (hc_ker_load: built on the first such call, kept in the handle, half the live channels' plaintexts of extra
+ * memory per handle) and the leaf level runs on kernels that neither load idx[s] nor multiply by it. Same words out as otherwise; any condition missing, or no memory
+ * for a copy, and the call makes the launches it always made. */
 int hc_conv_then_pack_batch(hc_ctx *ctx, int n, const uint64_t *const *ct_in, double ct_scale, const hc_ker *const *ker,
                             double ker_scale, int max_ob, int norm, double out_scale, const uint64_t *const *bias,
                             uint64_t *const *ct_out, double *scale_out);

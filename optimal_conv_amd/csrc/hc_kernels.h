@@ -1622,6 +1622,123 @@ __global__ __launch_bounds__(HC_TPB, HC_B5M_WAVES) void hc_k_b5m(HcLoopB B, HcTw
     }
 }
 
+// ---- the leaf level of a convolution whose x-role kernel plaintexts carry the level's monomial (hconv.hip, hc_ker_fold): idx[s] = NTT(X^(2^s)) times a polynomial is a signed
+// permutation of its coefficients, loop A's rescale acts coefficient by coefficient and is odd-symmetric, so Rescale(c' (*) (I (*) k_i)) = I (*) Rescale(c' (*) k_i) word for word
+// and hc_k_a3p, run on the folded plaintexts, writes m_k = I*x_k (canonical) into the x slots of src. hc_k_b1x / hc_k_b5x are hc_k_b1 / hc_k_b5m for such a level: no idx load,
+// no I*x products (16 hc_shoup4 of b1's thread, 32 of the 64 hc_mont_lazy of b5m's). Names of their own and no template parameter on the kernels above: their instantiations are
+// counted (tests/test_b5m_budget.py) and their machine code stays what it was. The stored words are the ones the kernels above store: every value below is congruent to its
+// counterpart there and what leaves a kernel is canonical (b2's hc_canon4 behind b1's transform, hc_reduce64 / hc_addmod here).
+// KB1X: t2.c1 = y1 - m1 as y1 + q - m1, in [1, 2q) with both canonical: inside the [0, 4q) that hc_rows_inv takes, no fold. Row-local levels only (hc_k_b5x follows): no tmpT.
+__global__ __launch_bounds__(HC_TPB, HC_W_B1) void hc_k_b1x(HcLoopB B, HcTwTab T0inv) {
+    __shared__ __attribute__((aligned(16))) u64 lds[HC_ROWS_LDS];
+    const int t = threadIdx.x, tid = t & 15, rloc = t >> 4, row = HC_TILE * 16 + rloc;
+    const int job = HC_JOB, z = job / B.nodes, node = job - z * B.nodes, i = (B.n0 + node) * B.norm;
+    const size_t tile = (size_t)HC_TILE * 4096 + t;
+    const u64 *__restrict__ y1 = B.src + (size_t)z * B.src_stride + ((size_t)i * 2 + 1) * 65536 + tile;
+    const u64 *__restrict__ m1 = B.src + (size_t)z * B.src_stride + ((size_t)(i + B.step) * 2 + 1) * 65536 + tile;
+    const HcQ Q = hc_q(B.m0.q);
+    u64 e[16], yy[16];
+#pragma unroll
+    for (int kk = 0; kk < 16; kk++) { e[kk] = m1[kk * 256]; yy[kk] = y1[kk * 256]; }
+#pragma unroll
+    for (int kk = 0; kk < 16; kk++) e[kk] = yy[kk] + Q.q - e[kk];                                    // t2.c1 (conv.go:288-289), in [1, 2q)
+    hc_rows_lin_to_lo(lds, t, rloc, tid, e);
+    const HcTw wA = hc_twl_load(T0inv, HC_TILE, t);        // behind the first exchange, as in hc_k_b1
+    HC_ROW_SYNC();        // row-local: the reads before and the writes after stay inside the 16 lanes of a row
+    hc_rows_inv(HcLazy<>{Q}, lds, T0inv, row, rloc, tid, e, &wA);
+    u64 *__restrict__ o = B.tmpC + (size_t)job * 65536 + (size_t)row * 256;
+#pragma unroll
+    for (int hi = 0; hi < 16; hi++) o[hi * 16 + tid] = e[hi];
+}
+// KB5X: hc_k_b5m with m_k = xs[k] read where it read x_k. Per row batch:
+//   T = y1 + q - m1 ; t1_k = y_k + m_k (+ bias, k = 0) ; F_1 = (a_Q/P)*T ; F_0 = y0 - m0 + (b_Q/P)*T ; d_k = F_k - n_k ; dst_k = reduce(t1_k + perm(d_k))
+// The lazy bounds of hc_k_b5m only get smaller, m_k being canonical where it was in (0, 2q): FREE mode t1 < 3q, T < 2q, g_k in (0, 2q), d_1 < 74q, d_0 = y0 + q - m0 + g0 + 72q - n_0
+// positive (n_k < 70q) and < 76q, t1 + d < 79q < 2^64; ALT mode works on canonical terms and has m_k canonical already.
+// hc_rows_fwd2_lin under a name of its own: as its second caller hc_k_b5x makes the compiler schedule hc_k_b5m differently (123 / 125 VGPRs for 127 / 124, 16 LDS instructions
+// fewer; tools/asm_compare.py), as hc_k_b5m did to hc_k_a3p.
+template <int FM>
+__device__ __forceinline__ void hc_rows_fwd2_lin_x(u64 (&e0)[16], u64 (&e1)[16], u64 *lds, const HcTwTab &T, const HcTw &wA, int row, int rloc, int tid, int t, const HcQ &Q) {
+    hc_ct_round(HcLazy<FM>{Q}, hc_twl_put(lds, wA, rloc, tid), e0, e1);      // the A group through LDS (HcTwL), its image in the tile ahead of the first exchange
+    HC_ROW_SYNC();        // the image has been read before the exchange lands on it
+    hc_xchg(lds, [&](int hi) { return hc_rows_lds(rloc, hi * 16 + tid); }, [&](int lo) { return hc_rows_lds(rloc, tid * 16 + lo); }, [] { HC_ROW_SYNC(); }, e0, e1);
+    hc_ct_round(HcLazy<FM>{Q}, HcTwB<false, HcTw>{T.rowsB + row * 256 + tid}, e0, e1);
+    HC_ROW_SYNC();        // row-local: the reads before and the writes after stay inside the 16 lanes of a row
+    hc_xchg(lds, [&](int lo) { return hc_rows_lds(rloc, tid * 16 + lo); }, [&](int kk) { return hc_rows_lds(kk, t); }, [] { __syncthreads(); }, e0, e1);
+}
+template <int FM>
+__global__ __launch_bounds__(HC_TPB, HC_B5M_WAVES) void hc_k_b5x(HcLoopB B, HcTwTab T0fwd, HcPtrs biases, HcPtrs outs) {
+    __shared__ __attribute__((aligned(16))) u64 lds[HC_ROWS_LDS];
+    const int t = threadIdx.x, tid = t & 15, rloc = t >> 4, row = HC_TILE * 16 + rloc;
+    const int zn = HC_JOB, z = zn / B.nodes, node = zn - z * B.nodes, i = (B.n0 + node) * B.norm;
+    const HcQ Q = hc_q(B.m0.q);
+    const u64 q = Q.q, qinv = B.m0.qinv;
+    const size_t tile = (size_t)HC_TILE * 4096 + t;
+    const u64 *__restrict__ ys = B.src + (size_t)z * B.src_stride + (size_t)i * 2 * 65536 + tile;                  // y_k = ys[k * 65536 + ...]
+    const u64 *__restrict__ ms = B.src + (size_t)z * B.src_stride + (size_t)(i + B.step) * 2 * 65536 + tile;       // m_k = I*x_k
+    const u64 *__restrict__ evk = B.evkQM + tile;                                                                  // b_Q/P, then a_Q/P 65536 words on
+    u64 *__restrict__ o = (outs.p[z] != nullptr ? const_cast<u64 *>(outs.p[z]) : B.dst + (size_t)z * B.dst_stride + (size_t)i * 2 * 65536) + tile;
+    const u64 *__restrict__ bias = biases.p[z] != nullptr ? biases.p[z] + tile : nullptr;        // null except on the last node of the tree (eval.go:258)
+    const HcTw wA = hc_twl_load(T0fwd, HC_TILE, t);
+    u64 e0[16], e1[16];
+    {
+        const u64 *__restrict__ in = B.tmpE + (size_t)zn * 2 * 65536 + (size_t)row * 256;
+#pragma unroll
+        for (int hi = 0; hi < 16; hi++) { e0[hi] = in[hi * 16 + tid]; e1[hi] = in[65536 + hi * 16 + tid]; }
+    }
+    hc_rows_fwd2_lin_x<FM>(e0, e1, lds, T0fwd, wA, row, rloc, tid, t, Q);
+    __syncthreads();      // every n_1 has been read before the first batch lands on the tile
+#pragma unroll
+    for (int b = 0; b < 16; b += HC_B5_ROWS) {
+        u64 Y0[HC_B5_ROWS], M0[HC_B5_ROWS], Y1[HC_B5_ROWS], M1[HC_B5_ROWS], K0[HC_B5_ROWS], K1[HC_B5_ROWS], bs[HC_B5_ROWS], s0[HC_B5_ROWS], s1[HC_B5_ROWS];
+#pragma unroll
+        for (int j = 0; j < HC_B5_ROWS; j++) {
+            const int off = (b + j) * 256;
+            Y1[j] = ys[65536 + off]; M1[j] = ms[65536 + off]; Y0[j] = ys[off]; M0[j] = ms[off]; K0[j] = evk[off]; K1[j] = evk[65536 + off];
+            bs[j] = bias != nullptr ? bias[off] : 0;
+        }
+#pragma unroll
+        for (int j = 0; j < HC_B5_ROWS; j++) {
+            const int kk = b + j, a0 = hc_rows_lds(kk, t), a1 = hc_rows_lds(kk ^ 8, t);                  // polynomial 1 goes through the row eight further on (hc_k_b5m)
+            const u64 T = Y1[j] + q - M1[j];                                                               // t2.c1 (conv.go:288-289), in [1, 2q)
+            u64 g1 = hc_mont_lazy(T, K1[j], q, qinv), g0 = hc_mont_lazy(T, K0[j], q, qinv);                  // (key row / P) * t2.c1, in (0, 2q)
+            if (FM == HC_FM_FREE) {
+                s1[j] = Y1[j] + M1[j]; s0[j] = Y0[j] + M0[j] + bs[j];                                      // conv.go:290 (+ bias), < 3q
+                lds[a1] = g1 + HC_FREE_OFF * q - e1[kk];                                                    // (key switch)_1 - n_1: positive (n_k < 70q), < 74q
+                lds[a0] = Y0[j] + q - M0[j] + g0 + HC_FREE_OFF * q - e0[kk];                                // t2.c0 + (key switch)_0 - n_0: positive, < 76q
+            } else {
+                g1 = hc_canon4(g1, Q); g0 = hc_canon4(g0, Q);
+                s1[j] = hc_addmod(Y1[j], M1[j], q); s0[j] = hc_addmod(hc_addmod(Y0[j], M0[j], q), bs[j], q);
+                lds[a1] = hc_submod(g1, hc_canon8(e1[kk], Q), q);
+                lds[a0] = hc_submod(hc_addmod(hc_submod(Y0[j], M0[j], q), g0, q), hc_canon8(e0[kk], Q), q);
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < HC_B5_ROWS; j++) {
+            const int kk = b + j;
+            const u32 srcidx = hc_perm_src((u32)((HC_TILE * 16 + kk) * 256 + t), B.gal);
+            const u64 d1 = lds[hc_rows_lds(kk ^ 8, (int)(srcidx & 255))], d0 = lds[hc_rows_lds(kk, (int)(srcidx & 255))];      // the source is in the same 256-coefficient row
+            o[65536 + kk * 256] = FM == HC_FM_FREE ? hc_reduce64(s1[j] + d1, B.m0.mu, Q) : hc_addmod(s1[j], d1, q);
+            o[kk * 256] = FM == HC_FM_FREE ? hc_reduce64(s0[j] + d0, B.m0.mu, Q) : hc_addmod(s0[j], d0, q);
+        }
+    }
+}
+// The folded copy of a handle's x-role plaintexts: fold[j][l][x] = ker[(i0 + j * norm)][l][x] * mono[l][x] mod Q_l, canonical, mono[l] = NTT_{Q_l}(X^(2^s)) as plain residues
+// (derived on the device: hc_ker_fold). One-off per handle and shape. grid = hc_pw_grid over nch * 2 * N words.
+__global__ __launch_bounds__(HC_TPB) void hc_k_ker_fold(const u64 *ker, const u64 *mono, u64 *fold, int i0, int norm, int nch, HcMod m0, HcMod m1) {
+    const size_t n = (size_t)nch * 2 * 65536;
+    for (size_t id = (size_t)blockIdx.x * HC_TPB + threadIdx.x; id < n; id += (size_t)gridDim.x * HC_TPB) {
+        const size_t x = id & 65535, r = id >> 16; const int l = (int)(r & 1); const size_t j = r >> 1;
+        const HcMod m = l ? m1 : m0;
+        const u64 k = ker[(((size_t)i0 + j * (size_t)norm) * 2 + l) * 65536 + x];
+        fold[id] = hc_mont(k, hc_mont(mono[(size_t)l * 65536 + x], m.r2, m.q, m.qinv), m.q, m.qinv);
+    }
+}
+// hc_idx_load of a host table: *differs becomes 1 if any word of a differs from b (it was cleared before the launch; every writer writes the same value)
+__global__ __launch_bounds__(HC_TPB) void hc_k_words_differ(const u64 *a, const u64 *b, size_t n, u32 *differs) {
+    for (size_t i = (size_t)blockIdx.x * HC_TPB + threadIdx.x; i < n; i += (size_t)gridDim.x * HC_TPB) if (a[i] != b[i]) *differs = 1;
+}
+
 // ================================================================ loop B for SMALL tree levels (round 3)
 // The top levels of a pack tree have 1..16 nodes: 16..256 workgroups for 256 CUs, one wave per SIMD, and a level costs the LATENCY of five
 // kernels (77..105 us whatever the node count; 0.45 ms of a lone convolution's 1.76) - each thread of the kernels above walks 64..192 butterflies

@@ -12,6 +12,7 @@
 #include <stdio.h>
 #include <string.h>
 
+#include <atomic>
 #include <map>
 #include <utility>
 #include <string>
@@ -112,6 +113,8 @@ struct hc_ctx {
     std::map<u64, HcSwk> swk;
     HcTw *idx_pairs = nullptr;   // [logN][N] idx plaintexts as Shoup pairs
     u64 *idx_mont = nullptr;     // [logN][N] the same residues as 8-byte Montgomery words (w * 2^64 mod Q0: hc_k_b5m), behind the pairs in idx_pairs' allocation
+    bool idx_mono = false;       // the table in force is the monomial table idx[s] = NTT(X^(2^s)): derived by hc_idx_load(NULL), or a host table found equal to the derived one on the device
+    u64 idx_gen = 0;             // which load of which context the table is (hc_idx_load draws it from one counter for all contexts): a handle's folded plaintexts belong to one table (hc_ker_fold)
     // workspace
     u64 *ws_cts = nullptr; size_t ws_cts_rows = 0;     // loop A output / tree ping
     u64 *ws_cts2 = nullptr; size_t ws_cts2_rows = 0;   // tree pong
@@ -160,7 +163,9 @@ struct hc_ctx {
     hipEvent_t t0 = nullptr, t1 = nullptr;
     std::string err;
 };
-struct hc_ker { u64 *d = nullptr; int max_ob = 0; };
+// fold: the x-role half of the leaf level's live channels times that level's monomial, [(max_ob / 2) / norm][2 limbs][N] (hc_ker_fold): made at the first hc_conv_then_pack(_batch)
+// that can use it, for the (max_ob, norm) of that call and the idx table then in force (fold_gen); remade when either changes, freed by hc_ker_free. d is never modified.
+struct hc_ker { u64 *d = nullptr; int max_ob = 0; mutable u64 *fold = nullptr; mutable int fold_ob = 0, fold_norm = 0; mutable u64 fold_gen = 0; };
 
 static std::string g_create_err;
 static int hc_fail(hc_ctx *c, int code, const char *fmt, ...) {
@@ -869,16 +874,17 @@ static int hc_prepare_ctc(hc_ctx *c, const HcPtrs &ct_in, int n, const u64 cst[2
 // loop A over the channels i = i_first + j*i_stride, j < nch, of each of the n ciphertexts of a batch (blockIdx.z); result j goes to
 // cts slot i (compact = false) or j of that ciphertext's array (arrays cts_stride words apart). gm > 1: the n outputs are GROUPS of gm input ciphertexts each (c' and kers hold
 // n * gm members, group g's at g*gm ..): the grouped a1 / a3 sum the members' products, a2 and everything sized by output jobs (chunk, tmp, cts) count n. gm = 1 launches what it always did.
-static int hc_loopA_run_set(hc_ctx *c, const HcPtrs &kers, int n, int i_first, int i_stride, int nch, u64 *cts, size_t cts_stride, bool compact, int gm = 1) {
+// folded: kers are the handles' folded arrays (hc_ker_fold), which hold the channels of this call alone, one after the other: channel j's plaintexts are entry j there.
+static int hc_loopA_run_set(hc_ctx *c, const HcPtrs &kers, int n, int i_first, int i_stride, int nch, u64 *cts, size_t cts_stride, bool compact, int gm = 1, bool folded = false) {
     long chunk = (c->chunk_nodes < 1 ? 1 : c->chunk_nodes) / n; if (chunk < 1) chunk = 1;     // channels per ciphertext per launch
     if (chunk > nch) chunk = nch;
     HC_TRY(hc_ensure_tmp(c, (size_t)n * (size_t)chunk * 2));
-    HcLoopA A; HC_TRY(hc_fill_loopA(c, &A, kers, cts, cts_stride, i_stride));
+    HcLoopA A; HC_TRY(hc_fill_loopA(c, &A, kers, cts, cts_stride, folded ? 1 : i_stride));
     const HcModHost &m0 = c->mods[0], &m1 = c->mods[1];
     for (int j0 = 0; j0 < nch; j0 += (int)chunk) {
         const int nj = (int)((nch - j0) < chunk ? (nch - j0) : chunk);
-        A.i0 = i_first + j0 * i_stride;
-        A.slot0 = compact ? j0 : A.i0; A.slot_step = compact ? 1 : i_stride;
+        A.i0 = folded ? j0 : i_first + j0 * i_stride;
+        A.slot0 = compact ? j0 : i_first + j0 * i_stride; A.slot_step = compact ? 1 : i_stride;
         A.njobs = 2 * nj; A.gm = gm;
         const dim3 pair = hc_grid(nj, n), flat = hc_grid(2 * nj * n);            // a1, a3: one workgroup per channel and tile does both polynomials
         if (gm > 1) {
@@ -1025,22 +1031,36 @@ extern "C" int hc_evk_load(hc_ctx *c, uint64_t galEl, const uint64_t *b_q, const
     return HC_OK;
 }
 
+// NTT_q(X^(2^s)), s = s0 .. s0 + rows - 1, as canonical residues into out[rows][N], on the device (conv.go:248-253: coeffs[1<<i] = 1 -> EncodeCoeffs(scale 1) -> ToNTT). tmp: [rows][N]
+static int hc_monomial_rows(hc_ctx *c, const HcModHost &m, int s0, int rows, u64 *out, u64 *tmp) {
+    HC_HIP(c, hipMemsetAsync(out, 0, (size_t)rows * HC_N * sizeof(u64), c->stream));
+    u64 one = 1;
+    for (int i = 0; i < rows; i++) HC_HIP(c, hcx_h2d_async(c, out + (size_t)i * HC_N + ((size_t)1 << (s0 + i)), &one, sizeof one));
+    HC_HIP(c, hipStreamSynchronize(c->stream));
+    HC_TRY(HC_LAUNCH_FM(m.m.q, c, "cols_fwd", hc_k_cols_fwd, dim3(16, (unsigned)rows), (const u64 *)out, tmp, m.fwd, m.m.q));
+    return HC_LAUNCH_FM(m.m.q, c, "rows_fwd_canon", hc_k_rows_fwd_canon, dim3(16, (unsigned)rows), (const u64 *)tmp, out, m.fwd, m.m.q, m.m.mu);
+}
+static std::atomic<u64> g_idx_gen{0};
 extern "C" int hc_idx_load(hc_ctx *c, const uint64_t *idx_host) {
     HC_ENTER(c);
     const HcModHost &m0 = c->mods[0];
     HcScratch S(c);
     u64 *stage = nullptr; HC_HIP(c, S.alloc(&stage, (size_t)HC_LOGN * HC_N * sizeof(u64)));
+    u64 *tmp = nullptr; HC_HIP(c, S.alloc(&tmp, (size_t)HC_LOGN * HC_N * sizeof(u64)));
+    bool mono = true;
     if (idx_host) {
+        // a host table is taken as it comes; whether it is the monomial table (which lets a convolution fold its leaf level into the kernel plaintexts: hc_ker_fold) is found
+        // by deriving that table beside it and comparing the two on the device
+        u64 *der = nullptr; u32 *differs = nullptr, h = 0;
+        HC_HIP(c, S.alloc(&der, (size_t)HC_LOGN * HC_N * sizeof(u64))); HC_HIP(c, S.alloc(&differs, sizeof(u32)));
+        HC_TRY(hc_monomial_rows(c, m0, 0, HC_LOGN, der, tmp));
         HC_HIP(c, hcx_h2d_async(c, stage, idx_host, (size_t)HC_LOGN * HC_N * sizeof(u64)));
-    } else {   // conv.go:248-253: coeffs[1<<i] = 1 -> EncodeCoeffs(scale 1) -> ToNTT, on the device
-        HC_HIP(c, hipMemsetAsync(stage, 0, (size_t)HC_LOGN * HC_N * sizeof(u64), c->stream));
-        u64 one = 1;
-        for (int i = 0; i < HC_LOGN; i++) HC_HIP(c, hcx_h2d_async(c, stage + (size_t)i * HC_N + ((size_t)1 << i), &one, sizeof one));
+        HC_HIP(c, hipMemsetAsync(differs, 0, sizeof(u32), c->stream));
+        HC_TRY(hc_launch(c, "idx_compare", hc_k_words_differ, hc_pw_grid((size_t)HC_LOGN * HC_N), (const u64 *)stage, (const u64 *)der, (size_t)HC_LOGN * HC_N, differs));
+        HC_HIP(c, hipMemcpyAsync(&h, differs, sizeof h, hipMemcpyDeviceToHost, c->stream));
         HC_HIP(c, hipStreamSynchronize(c->stream));
-        u64 *tmp = nullptr; HC_HIP(c, S.alloc(&tmp, (size_t)HC_LOGN * HC_N * sizeof(u64)));
-        HC_TRY(HC_LAUNCH_FM(m0.m.q, c, "cols_fwd", hc_k_cols_fwd, dim3(16, HC_LOGN), (const u64 *)stage, tmp, m0.fwd, m0.m.q));
-        HC_TRY(HC_LAUNCH_FM(m0.m.q, c, "rows_fwd_canon", hc_k_rows_fwd_canon, dim3(16, HC_LOGN), (const u64 *)tmp, stage, m0.fwd, m0.m.q, m0.m.mu));
-    }
+        mono = h == 0;
+    } else HC_TRY(hc_monomial_rows(c, m0, 0, HC_LOGN, stage, tmp));
     HcTw *pairs = nullptr; HC_HIP(c, S.alloc(&pairs, (size_t)HC_LOGN * HC_N * (sizeof(HcTw) + sizeof(u64))));      // the pairs, then the 8-byte Montgomery words of the same residues
     u64 *mont = reinterpret_cast<u64 *>(pairs + (size_t)HC_LOGN * HC_N);
     HcTw z; z.w = z.ws = 0;
@@ -1050,6 +1070,7 @@ extern "C" int hc_idx_load(hc_ctx *c, const uint64_t *idx_host) {
     S.keep(pairs);
     if (c->idx_pairs) HC_HIP(c, hcx_free(c, c->idx_pairs));
     c->idx_pairs = pairs; c->idx_mont = mont;
+    c->idx_mono = mono; c->idx_gen = ++g_idx_gen;          // a new table: every handle's folded plaintexts are out of date (dropped at the handle's next use or by hc_ker_free)
     return HC_OK;
 }
 
@@ -1143,7 +1164,7 @@ extern "C" int hc_ker_download(hc_ctx *c, const hc_ker *k, uint64_t *host_out) {
     HC_HIP(c, hipStreamSynchronize(c->stream));
     return HC_OK;
 }
-extern "C" void hc_ker_free(hc_ctx *c, hc_ker *k) { if (!k) return; if (c) { hipSetDevice(c->device); hipStreamSynchronize(c->stream); } hcx_free(c, k->d); delete k; }
+extern "C" void hc_ker_free(hc_ctx *c, hc_ker *k) { if (!k) return; if (c) { hipSetDevice(c->device); hipStreamSynchronize(c->stream); } hcx_free(c, k->d); hcx_free(c, k->fold); delete k; }
 
 // ------------------------------------------------------------------ loop B plumbing
 static int hc_fill_loopB(hc_ctx *c, HcLoopB *B, const u64 *src, u64 *dst, const HcEvk &e, int logStep, int step, int norm, u64 galEl, int chunk) {
@@ -1168,7 +1189,8 @@ static int hc_fill_loopB(hc_ctx *c, HcLoopB *B, const u64 *src, u64 *dst, const 
     return HC_OK;
 }
 // one tree level of each of the n ciphertexts of a batch: nodes i = 0, norm, 2*norm, ... < step; arrays sstride / dstride words apart
-static int hc_pack_level(hc_ctx *c, const u64 *src, u64 *dst, size_t sstride, size_t dstride, int n, int step, int logStep, int norm, u64 galEl, const HcPtrs *bias_last, const HcPtrs *outs_last = nullptr) {
+// folded: the x slots of src hold I*x already (hc_conv_fold_leaf said so before loop A ran): every launch of the level runs hc_k_b1x / hc_k_b5x, a short last launch included
+static int hc_pack_level(hc_ctx *c, const u64 *src, u64 *dst, size_t sstride, size_t dstride, int n, int step, int logStep, int norm, u64 galEl, const HcPtrs *bias_last, const HcPtrs *outs_last = nullptr, bool folded = false) {
     auto it = c->evk.find(galEl);
     if (it == c->evk.end()) return hc_fail(c, HC_ERR_STATE, "pack: no switching key loaded for galEl=%llu (the reference panics in permuteNTT)", (unsigned long long)galEl);
     if (!it->second.row_local) return hc_fail(c, HC_ERR_UNSUPPORTED, "pack: galEl=%llu does not permute inside 4096-coefficient tiles (needs max_cnum <= 4096)", (unsigned long long)galEl);
@@ -1186,7 +1208,7 @@ static int hc_pack_level(hc_ctx *c, const u64 *src, u64 *dst, size_t sstride, si
         const int nn = (nodes - n0) < chunk ? (nodes - n0) : chunk;
         B.n0 = n0; B.nodes = nn;
         const dim3 g1 = hc_grid(n * nn), g2 = hc_grid(2 * n * nn);
-        if (c->small_levels > 0 && (long)n * nn <= c->small_levels && it->second.row256) {
+        if (!folded && c->small_levels > 0 && (long)n * nn <= c->small_levels && it->second.row256) {
             // a level of a few nodes is one partial wave of workgroups and costs the latency of its five kernels: quarter tiles (1024 residues per workgroup, four per
             // thread: hc_kernels.h, "loop B for SMALL tree levels") spread a row over 64 CUs instead of 16. Same tables, same tmp layouts, same bits.
             const HcPtrs pb = bias_last ? *bias_last : nobias, po = outs_last ? *outs_last : nobias;
@@ -1199,19 +1221,22 @@ static int hc_pack_level(hc_ctx *c, const u64 *src, u64 *dst, size_t sstride, si
             HC_TRY(hc_launch<HC_STPB>(c, "b5_rowsfwd_moddown_perm_add", hc_k_sb5, s2, B, m0.fwd, pb, po));
             continue;
         }
-        HC_TRY(hc_launch(c, "b1_node_rowsinv", hc_k_b1, g1, B, m0.inv));
+        if (folded) HC_TRY(hc_launch(c, "b1_node_rowsinv", hc_k_b1x, g1, B, m0.inv));
+        else HC_TRY(hc_launch(c, "b1_node_rowsinv", hc_k_b1, g1, B, m0.inv));
         HC_TRY(HC_LAUNCH_FM(mp.m.q, c, "b2_colsinv_colsfwdP", hc_k_b2, g1, B, m0.inv, mp.fwd));
         HC_TRY(HC_LAUNCH_FM(mp.m.q, c, "b3_rowsfwdP_mac_rowsinvP", hc_k_b3p, g1, B, mp.fwd, mp.inv));
         HC_TRY(HC_LAUNCH_FM(m0.m.q, c, "b4_colsinvP_modup_colsfwd", hc_k_b4, g2, B, mp.inv, m0.fwd));
         const HcPtrs pb = bias_last ? *bias_last : nobias, po = outs_last ? *outs_last : nobias;
-        if (it->second.row256) HC_TRY(HC_LAUNCH_FM(m0.m.q, c, "b5_rowsfwd_moddown_perm_add", hc_k_b5m, g1, B, m0.fwd, pb, po));      // one workgroup per (node, tile), both polynomials
+        if (folded) HC_TRY(HC_LAUNCH_FM(m0.m.q, c, "b5_rowsfwd_moddown_perm_add", hc_k_b5x, g1, B, m0.fwd, pb, po));                         // hc_k_b5m on x slots that hold I*x
+        else if (it->second.row256) HC_TRY(HC_LAUNCH_FM(m0.m.q, c, "b5_rowsfwd_moddown_perm_add", hc_k_b5m, g1, B, m0.fwd, pb, po));      // one workgroup per (node, tile), both polynomials
         else HC_TRY(HC_LAUNCH_FM(m0.m.q, c, "b5_rowsfwd_moddown_perm_add", hc_k_b5, g2, B, m0.fwd, pb, po));                        // tile-local permutation (2^j + 1, j = 5..8)
     }
     return HC_OK;
 }
 // conv.go:266-300 on device-resident level-0 ciphertexts, in place (result in slot 0), for each of the n ciphertext arrays of a batch
 // outs != null: the root node writes ciphertext z straight to outs->p[z] ([2][N]) instead of slot 0 of its array
-static int hc_pack_run(hc_ctx *c, u64 *cts, size_t cstride, int n, int max_cnum, int real_cnum, const HcPtrs *bias, int stride_log2 = 0, const HcPtrs *outs = nullptr) {
+// leaf_folded: the first (leaf) level's x slots hold I*x (hc_conv_fold_leaf)
+static int hc_pack_run(hc_ctx *c, u64 *cts, size_t cstride, int n, int max_cnum, int real_cnum, const HcPtrs *bias, int stride_log2 = 0, const HcPtrs *outs = nullptr, bool leaf_folded = false) {
     if (max_cnum < 1 || real_cnum < 1 || max_cnum % real_cnum || (max_cnum & (max_cnum - 1)) || (real_cnum & (real_cnum - 1)))
         return hc_fail(c, HC_ERR_ARG, "pack: max_cnum=%d real_cnum=%d must be powers of two", max_cnum, real_cnum);
     const int norm = max_cnum / real_cnum;
@@ -1234,7 +1259,8 @@ static int hc_pack_run(hc_ctx *c, u64 *cts, size_t cstride, int n, int max_cnum,
     bool bias_done = false, out_done = false;
     while (step >= norm && step >= 1) {
         const bool last = (step / 2 < norm) || step == 1;
-        HC_TRY(hc_pack_level(c, src, dst, sstride, dstride, n, step, logStep + stride_log2, norm, (1ull << j) + 1, last ? bias : nullptr, last ? outs : nullptr));
+        HC_TRY(hc_pack_level(c, src, dst, sstride, dstride, n, step, logStep + stride_log2, norm, (1ull << j) + 1, last ? bias : nullptr, last ? outs : nullptr, leaf_folded));
+        leaf_folded = false;
         if (last) { bias_done = true; out_done = outs != nullptr; }
         u64 *t = src; src = dst; dst = t;
         size_t ts = sstride; sstride = dstride; dstride = ts;
@@ -1805,15 +1831,63 @@ extern "C" int hc_conv_mult_phase(hc_ctx *c, const uint64_t *ct_in, double ct_sc
 // levels (1..16 nodes per ciphertext, latency-bound when launched alone) carry n times the work per launch.
 // gm > 1: the n members are n / gm groups of gm input ciphertexts, each group ONE convolution (loop A sums the members' products at level 1); bias and ct_out are then per GROUP
 // (entries 0 .. n / gm - 1), and the tree, the bias add and the workspaces ws_cts / ws_tmp see n / gm ciphertexts. Only c' (ws_ctc) is per member.
-static int hc_conv_batch_run(hc_ctx *c, int n, const HcPtrs &ct_in, const HcPtrs &kers, const HcPtrs &bias, bool any_bias, u64 *const *ct_out,
+// The leaf level's product with its idx plaintext, taken out of the tree (hc_kernels.h, above hc_k_b1x). The leaf level of hc_pack_run pairs y = channel i with x = channel
+// i + max_ob / 2 and forms I*x, I = idx[s] = NTT(X^(2^s)), s = log2(max_ob / 2). The kernel plaintexts are a layer's weights and stay the same from call to call, so the x-role
+// channels' plaintexts are multiplied by the monomial ONCE per handle - limb 0 by NTT_Q0(X^(2^s)), limb 1 by NTT_Q1(X^(2^s)), both derived here on the device as
+// hc_idx_load(NULL) derives its rows - and loop A, run on that copy, writes I*x itself. k->d is never touched: the copy is a second array of half the live channels' plaintexts,
+// (max_ob / 2) / norm * 2 * N words, kept in the handle for the (max_ob, norm) and the idx table it was made for.
+// *out stays null when the copy cannot be had (no memory): the caller then makes the unfolded launches.
+static int hc_ker_fold(hc_ctx *c, const hc_ker *k, int max_ob, int norm, int s, const u64 **out) {
+    *out = nullptr;
+    if (k->fold && k->fold_ob == max_ob && k->fold_norm == norm && k->fold_gen == c->idx_gen) { *out = k->fold; return HC_OK; }
+    if (k->fold) { HC_HIP(c, hcx_free(c, k->fold)); k->fold = nullptr; }        // made for another shape or another idx table
+    const int nch = (max_ob / 2) / norm;
+    HcScratch S(c);
+    u64 *f = nullptr, *mono = nullptr, *tmp = nullptr;
+    if (S.alloc(&f, (size_t)nch * 2 * HC_N * sizeof(u64)) != hipSuccess || S.alloc(&mono, (size_t)2 * HC_N * sizeof(u64)) != hipSuccess || S.alloc(&tmp, (size_t)HC_N * sizeof(u64)) != hipSuccess) {
+        (void)hipGetLastError();
+        return HC_OK;
+    }
+    for (int l = 0; l < 2; l++) HC_TRY(hc_monomial_rows(c, c->mods[(size_t)l], s, 1, mono + (size_t)l * HC_N, tmp));
+    HC_TRY(hc_launch(c, "ker_fold_monomial", hc_k_ker_fold, hc_pw_grid((size_t)nch * 2 * HC_N), (const u64 *)k->d, (const u64 *)mono, f, max_ob / 2, norm, nch, c->mods[0].m, c->mods[1].m));
+    S.keep(f);
+    k->fold = f; k->fold_ob = max_ob; k->fold_norm = norm; k->fold_gen = c->idx_gen;
+    *out = f;
+    return HC_OK;
+}
+// Whether this call folds its leaf level, decided before loop A runs, and if so the folded arrays of its n members' handles. All of: the idx table in force is the monomial table;
+// the leaf level's key is loaded and permutes inside 256-coefficient rows (hc_k_b5m's levels); the level runs on the 256-thread kernels (more nodes over the batch than
+// small_levels); every member's folded array could be had. Otherwise *use = false and the call makes the launches it always made.
+static int hc_conv_fold_leaf(hc_ctx *c, int n, int G, const hc_ker *const *handles, int max_ob, int norm, HcPtrs *folded, bool *use) {
+    *use = false;
+    const int step = max_ob / 2;
+    if (step < 1 || step < norm || (max_ob & (max_ob - 1)) || (norm & (norm - 1))) return HC_OK;          // no tree level (or arguments hc_pack_run refuses)
+    int s = 0; for (int i = step; i > 1; i /= 2) s++;
+    if (!c->idx_pairs) HC_TRY(hc_idx_load(c, nullptr));
+    if (!c->idx_mono) return HC_OK;
+    const auto it = c->evk.find((1ull << (HC_LOGN - s)) + 1);
+    if (it == c->evk.end() || !it->second.row256) return HC_OK;
+    if (c->small_levels > 0 && (long)G * (step / norm) <= c->small_levels) return HC_OK;
+    memset(folded, 0, sizeof *folded);
+    for (int z = 0; z < n; z++) { HC_TRY(hc_ker_fold(c, handles[z], max_ob, norm, s, &folded->p[z])); if (!folded->p[z]) return HC_OK; }
+    *use = true;
+    return HC_OK;
+}
+static int hc_conv_batch_run(hc_ctx *c, int n, const HcPtrs &ct_in, const hc_ker *const *handles, const HcPtrs &bias, bool any_bias, u64 *const *ct_out,
                              int max_ob, int norm, const u64 cst[2], int gm = 1) {
     const int G = n / gm;
+    HcPtrs kers, folded; memset(&kers, 0, sizeof kers); for (int z = 0; z < n; z++) kers.p[z] = handles[z]->d;
+    bool fold; HC_TRY(hc_conv_fold_leaf(c, n, G, handles, max_ob, norm, &folded, &fold));
     HC_TRY(hc_prepare_ctc(c, ct_in, n, cst));
     HC_TRY(hc_ensure_cts(c, (size_t)G * max_ob * 2));
     const size_t cstride = (size_t)max_ob * 2 * HC_N;
-    HC_TRY(hc_loopA_run_set(c, kers, G, 0, norm, max_ob / norm, c->ws_cts, cstride, false, gm));
+    if (fold) {      // the y-role channels from the handles, the x-role channels (launches of their own, the same kernels) from the folded arrays
+        const int half = (max_ob / 2) / norm;
+        HC_TRY(hc_loopA_run_set(c, kers, G, 0, norm, half, c->ws_cts, cstride, false, gm));
+        HC_TRY(hc_loopA_run_set(c, folded, G, max_ob / 2, norm, half, c->ws_cts, cstride, false, gm, true));
+    } else HC_TRY(hc_loopA_run_set(c, kers, G, 0, norm, max_ob / norm, c->ws_cts, cstride, false, gm));
     HcPtrs outs; memset(&outs, 0, sizeof outs); for (int z = 0; z < G; z++) outs.p[z] = ct_out[z];
-    return hc_pack_run(c, c->ws_cts, cstride, G, max_ob, max_ob / norm, any_bias ? &bias : nullptr, 0, &outs);      // the root node writes ct_out itself
+    return hc_pack_run(c, c->ws_cts, cstride, G, max_ob, max_ob / norm, any_bias ? &bias : nullptr, 0, &outs, fold);      // the root node writes ct_out itself
 }
 extern "C" int hc_conv_then_pack(hc_ctx *c, const uint64_t *ct_in, double ct_scale, const hc_ker *ker, double ker_scale,
                                  int max_ob, int norm, double out_scale, const uint64_t *bias, uint64_t *ct_out, double *scale_out) {
@@ -1825,7 +1899,7 @@ extern "C" int hc_conv_then_pack(hc_ctx *c, const uint64_t *ct_in, double ct_sca
     const double final_scale = target * (double)(max_ob / norm);
     if (final_scale != out_scale) return hc_fail(c, HC_ERR_STATE, "LV or scale after conv then pack, inconsistent");
     u64 *outs[1] = {(u64 *)ct_out};
-    HC_TRY(hc_conv_batch_run(c, 1, hc_ptrs1((const u64 *)ct_in), hc_ptrs1(ker->d), hc_ptrs1((const u64 *)bias), bias != nullptr, outs, max_ob, norm, cst));
+    HC_TRY(hc_conv_batch_run(c, 1, hc_ptrs1((const u64 *)ct_in), &ker, hc_ptrs1((const u64 *)bias), bias != nullptr, outs, max_ob, norm, cst));
     if (scale_out) *scale_out = final_scale;
     return HC_OK;
 }
@@ -1834,13 +1908,13 @@ extern "C" int hc_conv_then_pack_batch(hc_ctx *c, int n, const uint64_t *const *
     HC_ENTER(c);
     if (n < 1 || n > HC_MAXB) return hc_fail(c, HC_ERR_ARG, "hc_conv_then_pack_batch: n=%d outside 1..%d", n, HC_MAXB);
     if (!ct_in || !ker || !ct_out) return hc_fail(c, HC_ERR_ARG, "hc_conv_then_pack_batch: null");
-    HcPtrs pin, pker, pbias; memset(&pin, 0, sizeof pin); memset(&pker, 0, sizeof pker); memset(&pbias, 0, sizeof pbias);
+    HcPtrs pin, pbias; memset(&pin, 0, sizeof pin); memset(&pbias, 0, sizeof pbias);
     u64 *outs[HC_MAXB]; bool any_bias = false;
     // consecutive members with one ct_out are the input ciphertexts of ONE convolution: G groups of equal size gm, outs / pbias per group. All checks come before any launch.
     int G = 0, gm = 0;
     for (int z = 0, z0 = 0; z < n; z++) {
         if (!ct_in[z] || !ker[z] || !ct_out[z] || ker[z]->max_ob < max_ob) return hc_fail(c, HC_ERR_ARG, "hc_conv_then_pack_batch: bad arguments for ciphertext %d", z);
-        pin.p[z] = (const u64 *)ct_in[z]; pker.p[z] = ker[z]->d;
+        pin.p[z] = (const u64 *)ct_in[z];
         const u64 *b = bias ? (const u64 *)bias[z] : nullptr;
         if (z == 0 || ct_out[z] != ct_out[z - 1]) {        // a group's first member: it names the output and the bias
             for (int y = 0; y < G; y++) if (outs[y] == (u64 *)ct_out[z]) return hc_fail(c, HC_ERR_ARG, "hc_conv_then_pack_batch: ct_out of member %d repeats a non-adjacent member's (a group's members must be consecutive)", z);
@@ -1856,7 +1930,7 @@ extern "C" int hc_conv_then_pack_batch(hc_ctx *c, int n, const uint64_t *const *
     HC_TRY(hc_loopA_consts(c, ct_scale, ker_scale, max_ob, norm, out_scale, cst, &target));
     const double final_scale = target * (double)(max_ob / norm);
     if (final_scale != out_scale) return hc_fail(c, HC_ERR_STATE, "LV or scale after conv then pack, inconsistent");
-    HC_TRY(hc_conv_batch_run(c, n, pin, pker, pbias, any_bias, outs, max_ob, norm, cst, gm));
+    HC_TRY(hc_conv_batch_run(c, n, pin, ker, pbias, any_bias, outs, max_ob, norm, cst, gm));
     if (scale_out) *scale_out = final_scale;
     return HC_OK;
 }
