@@ -17,6 +17,9 @@
 // Argument checks are those of `transconv` / `multiconv`; HCONV_IMAGE_BATCH, HCONV_DEVICE_ENCRYPT, HCONV_DEBUG_LAYERS and HCONV_BOOT_STATS apply as for convReLU.
 // `resnet_fast <ker_wid> <depth> 1 <test_num> false` (not a reference command: the reference reaches testResNet_crop_fast_in, test.go:372-636, only by swapping
 // main.go:620-622): the same network as `resnet` on full slots, one bootstrapper (hconv_resnet.cpp). Same arguments; wide_case != 1 and cf100 are refused like `resnet`'s.
+// `resnet_packed <ker_wid 3|7> <depth> 1 <test_num> false` (not a reference command): resnet_fast's network, weight, image and result files with 4 / 8 / 16 images per ciphertext
+// of block 1 / 2 / 3 (hconv_host.hpp packed_slot; DESIGN.md "The packed layout"), in groups of up to 16 images. Refused: wide_case != 1, cf100, ker_wid 5, the replay switches and
+// HCONV_DEBUG_LAYERS. HCONV_PACKED_DUMP_LAYERS=<layers> (test mode) writes every image's activation after the listed layers to packed_act_L<layer>_<image>.csv.
 // HCONV_SKIP_BL=1 skips the baseline half (not a reference feature; for timing "Ours" alone).
 // `conv --test-mode <args>` honours the test-only overrides HCONV_SEED / HCONV_CHAIN_REPLAY; without the flag they are fatal when set.
 #include <stdio.h>
@@ -35,7 +38,7 @@ int main(int argc, char **argv) {
     const std::string test_name = argv[1];
     // The bootstrapping chains allocate and free a few buffers per evaluator operation, and hipFree drains the device every time: the chain commands run on cached
     // allocations (hconv.hip hcx_malloc) unless HCONV_ASYNC_ALLOC=0 says otherwise - ResNet-20 at 8 images per launch set 2.12 -> 2.02 s per set (profiles/round4_cached_alloc_ab.txt)
-    if (test_name == "convReLU" || test_name == "resnet" || test_name == "resnet_fast" || test_name == "transconvReLU" || test_name == "multiconvReLU") setenv("HCONV_ASYNC_ALLOC", "1", 0);
+    if (test_name == "convReLU" || test_name == "resnet" || test_name == "resnet_fast" || test_name == "resnet_packed" || test_name == "transconvReLU" || test_name == "multiconvReLU") setenv("HCONV_ASYNC_ALLOC", "1", 0);
     const int ker_wid = atoi(argv[2]), i_batch = atoi(argv[3]), num_tests = atoi(argv[4]);
     if (!(ker_wid == 3 || ker_wid == 5 || ker_wid == 7)) hconv::panic("Wrong kernel wid (not in 3,5,7)");
     if (test_name == "resnet_fast") {                                    // not a reference command (see the top of this file); main.go:609-621's argument handling
@@ -46,6 +49,22 @@ int main(int argc, char **argv) {
         if (wide_case != 1 || cf100) hconv::panic("resnet_fast: wide_case 2 / 3 and cf100 = true are out of scope in this build (SURVEY.md section 2, row 14)");
         if (!(depth == 8 || depth == 14 || depth == 20)) hconv::panic("wrong depth (not in 8, 14, 20)!");  // test.go:397-405, before any device work
         hconv::testResNet_crop_fast_in(0, test_num, ker_wid, depth, false);
+        return 0;
+    }
+    if (test_name == "resnet_packed") {                                  // not a reference command (see the top of this file); resnet_fast's arguments
+        if (argc < 7) hconv::panic("runtime error: index out of range (usage: resnet_packed <ker_wid> <depth> <wide_case> <test_num> <cf100>)");
+        const int depth = atoi(argv[3]), wide_case = atoi(argv[4]), test_num = atoi(argv[5]);
+        const bool cf100 = std::string(argv[6]) == "true" || std::string(argv[6]) == "1";
+        if (wide_case < 1 || wide_case > 3) hconv::panic("Wrong wide case!");
+        if (wide_case != 1 || cf100) hconv::panic("resnet_packed: wide_case 2 / 3 and cf100 = true are out of scope in this build (SURVEY.md section 2, row 14)");
+        if (ker_wid == 5) hconv::panic("resnet_packed: kernel width 5 is not packed: its even keep widths 30, 14, 6 put the first kept position at step - 1, not 0 "
+                                       "(and that network differs from the plain model anyway); use 3 or 7");
+        if (!(depth == 8 || depth == 14 || depth == 20)) hconv::panic("wrong depth (not in 8, 14, 20)!");
+        // the replays' and the per-stage report's shadows know one image per ciphertext
+        for (const char *v : {"HCONV_RESNET_REPLAY", "HCONV_CHAIN_REPLAY", "HCONV_CHAIN_REPLAY_BL", "HCONV_DEBUG_LAYERS"})
+            if (getenv(v) && *getenv(v) && std::string(getenv(v)) != "0") hconv::panic(std::string("resnet_packed: ") + v + " follows one image per ciphertext and is not available here");
+        hconv::testOnlyEnv("HCONV_PACKED_DUMP_LAYERS");                    // fatal without --test-mode, before any device work
+        hconv::testResNet_crop_packed(0, test_num, ker_wid, depth);
         return 0;
     }
     bool boot = false;

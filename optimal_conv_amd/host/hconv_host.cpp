@@ -172,7 +172,7 @@ void applyEnvOptions(hc_ctx *hc, int pack32_default) {
 
 Context *newContext(int logN, int ker_wid, const std::vector<int> &in_wids, const std::vector<int> &kp_wids, bool boot, const std::string &kind) {
     (void)ker_wid;
-    if (kind != "Conv" && kind != "Resnet_crop_sparse" && kind != "Resnet_crop_fast" && kind != "TransConv" && !(kind == "TransConv_sparse" && boot)) panic("Wrong kinds!");       // main.go:404 (the kinds the built command lines use; "TransConv_sparse": TransConv with the log_sparse = 2 bootstrapper)
+    if (kind != "Conv" && kind != "Resnet_crop_sparse" && kind != "Resnet_crop_fast" && kind != "Resnet_crop_packed" && kind != "TransConv" && !(kind == "TransConv_sparse" && boot)) panic("Wrong kinds!");       // main.go:404 (the kinds the built command lines use; "TransConv_sparse": TransConv with the log_sparse = 2 bootstrapper)
     Context *c = new Context();
     double logqp = 0; for (uint64_t q : PARAMS6_Q) logqp += log2((double)q); for (uint64_t p : PARAMS6_P) logqp += log2((double)p);
     printf("CKKS parameters: logN = %d, logSlots = %d, h = %d, logQP = %d, levels = %d, scale= 2^%f, sigma = %f \n",
@@ -210,7 +210,7 @@ Context *newContext(int logN, int ker_wid, const std::vector<int> &in_wids, cons
         auto start = now();
         // DFT matrices and every switching key, same secret key. "Conv" and "Resnet_crop_fast": one full-slot bootstrapper; the sparse resnet kind: the
         // four sparse ones its layers use (btp2..btp5 of main.go:480-500; log_sparse 1..4)
-        const bool full = kind == "Conv" || kind == "Resnet_crop_fast" || kind == "TransConv";
+        const bool full = kind == "Conv" || kind == "Resnet_crop_fast" || kind == "Resnet_crop_packed" || kind == "TransConv";
         if (kind == "TransConv_sparse") c->btp = newBoot(c->sk, c->seed, dev, std::vector<int>{2}, imageBatch());      // a quarter of the channel slots live: btp3's slot set alone
         else c->btp = full ? newBoot(c->sk, c->seed, dev, {0}, imageBatch()) : newBoot(c->sk, c->seed, dev, std::vector<int>{2, 1, 3, 4}, imageBatch());
         if (kind == "Resnet_crop_sparse") { bootPrepareCompress(c->btp, in_wids[0], kp_wids[1], 1); bootPrepareCompress(c->btp, in_wids[1], kp_wids[2], 2); }   // main.go:163-215
@@ -221,6 +221,15 @@ Context *newContext(int logN, int ker_wid, const std::vector<int> &in_wids, cons
             const int step = 1 << i;
             c->ext_idx[step].resize(2);
             for (int ul = 0; ul < 2; ul++) c->ext_idx[step][(size_t)ul] = gen_keep_vec_stride(N / 2, in_wids[0], kp_wids[i], step, ul, kp_wids[i] % 2 != 0);
+        }
+    }
+    if (kind == "Resnet_crop_packed") {                                                                // not a reference kind: the packed layout's masks (hconv_host.hpp), entries of their own
+        for (size_t i = 0; i < in_wids.size(); i++) {
+            const int step = 1 << i;
+            for (int ul = 0; ul < 2; ul++) {
+                c->ext_idx[packedMaskKey(step)].push_back(gen_keep_vec_packed(N / 2, in_wids[0], kp_wids[i], step, step, ul));
+                if (i) c->ext_idx[packedStrideMaskKey(step)].push_back(gen_keep_vec_packed(N / 2, in_wids[0], kp_wids[i], step, step / 2, ul));
+            }
         }
     }
     return c;
@@ -380,7 +389,26 @@ Ciphertext EncryptNew(Context *c, const std::vector<uint64_t> &pt_rows, int leve
     Ciphertext r; r.d = dev_upload(c, ct); r.level = level; r.Scale = scale;
     return r;
 }
-std::vector<double> DecryptDecodeCoeffs(Context *c, const Ciphertext &ct) {       // Decrypt + DecodeCoeffs at level 0 (test.go:59-60)
+// Decrypt + DecodeCoeffs of a level-1 ciphertext (what a layer hands on: its scale is whatever the chain's last Rescale left, so the value is reconstructed over q0 q1, as
+// bootDecryptDecodeCoeffs does it on the bootstrapper's context)
+static std::vector<double> decryptDecodeCoeffsLevel1(Context *c, const Ciphertext &ct) {
+    std::vector<uint64_t> sk2((size_t)2 * N);
+    for (int l = 0; l < 2; l++) std::copy(c->sk_ntt[l].begin(), c->sk_ntt[l].end(), sk2.begin() + (size_t)l * N);
+    uint64_t *d_sk2 = dev_upload(c, sk2), *t = dev_rows(c, 2);
+    HC(c->hc, hc_lv_mul_plain(c->hc, 1, ct.d + (size_t)2 * N, d_sk2, t)); HC(c->hc, hc_lv_add(c->hc, 1, ct.d, t, t)); HC(c->hc, hc_lv_intt(c->hc, 1, t, t));
+    const std::vector<uint64_t> m = dev_download(c, t, 2);
+    HC(c->hc, hc_free(c->hc, t)); HC(c->hc, hc_free(c->hc, d_sk2));
+    const uint64_t q0 = MODQ[0], q1 = MODQ[1]; uint64_t inv = 1; { uint64_t b = q0 % q1, e = q1 - 2; while (e) { if (e & 1) inv = mulmod(inv, b, q1); b = mulmod(b, b, q1); e >>= 1; } }
+    const u128 QQ = (u128)q0 * q1; std::vector<double> cf((size_t)N);
+    for (int j = 0; j < N; j++) {
+        const uint64_t a0 = m[(size_t)j], a1 = m[(size_t)N + (size_t)j], d = (a1 % q1 + q1 - a0 % q1) % q1;
+        const u128 x = (u128)a0 + (u128)q0 * mulmod(d, inv, q1);
+        cf[(size_t)j] = x > QQ / 2 ? -(double)(QQ - x) / ct.Scale : (double)x / ct.Scale;
+    }
+    return cf;
+}
+std::vector<double> DecryptDecodeCoeffs(Context *c, const Ciphertext &ct) {       // Decrypt + DecodeCoeffs at level 0 (test.go:59-60); level 1: a layer's output, on the host path
+    if (ct.level == 1) return decryptDecodeCoeffsLevel1(c, ct);
     if (ct.level != 0) panic("DecryptDecodeCoeffs: level 0 expected on the conv path");
     if (deviceEncrypt()) return DecryptDecodeCoeffsBatch(c, {ct})[0];
     std::vector<uint64_t> h = dev_download(c, ct.d, 2), m(N);
@@ -392,6 +420,19 @@ std::vector<double> DecryptDecodeCoeffs(Context *c, const Ciphertext &ct) {     
     return out;
 }
 void freeCt(Context *c, Ciphertext &ct) { if (ct.d) HC(c->hc, hc_free(c->hc, ct.d)); ct.d = nullptr; }
+Ciphertext mergePackedInputs(Context *c, std::vector<Ciphertext> &cts) {
+    if (cts.empty() || cts.size() > 4) panic("mergePackedInputs: 1..4 ciphertexts");
+    Ciphertext acc = cts[0];
+    const size_t poly = (size_t)(acc.level + 1) * N;
+    for (size_t g = 1; g < cts.size(); g++) {
+        if (cts[g].level != acc.level || cts[g].Scale != acc.Scale) panic("mergePackedInputs: the ciphertexts share level and scale");
+        const uint64_t e[2] = {(uint64_t)g, 0};                                 // acc + X^g cts[g]: the channel slot is the innermost coefficient index
+        HC(c->hc, hc_lv_op2(c->hc, HC_LV_MONOMIAL, acc.level, acc.d, acc.d + poly, cts[g].d, cts[g].d + poly, acc.d, acc.d + poly, e));
+        freeCt(c, cts[g]);
+    }
+    cts.clear();
+    return acc;
+}
 
 // ---------------------------------------------------------------- prep_Ker (conv.go:487-518)
 KerPlain prep_Ker(Context *c, const std::vector<double> &ker_in, const std::vector<double> &BN_a, int in_wid, int ker_wid,

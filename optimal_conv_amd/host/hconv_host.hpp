@@ -95,7 +95,8 @@ struct Context {
     uint64_t *d_sk = nullptr;                 // device [3][N]: NTT(s) mod Q0, Q1, P, the sk_ntt operand of hc_encrypt_sk / hc_decrypt_decode_coeffs (uploaded once)
     uint32_t enc_seed8[8] = {0};              // key of the device encryptor's draws: eight draws of g at context creation
     uint64_t enc_stream = 0;                  // hc_encrypt_sk's stream id: one per call, never reused
-    std::map<int, std::vector<std::vector<int>>> ext_idx;   // kind "Resnet_crop_fast": ext_idx[step][ul], the keep masks of the "inside" layers (main.go:123-136)
+    std::map<int, std::vector<std::vector<int>>> ext_idx;   // kind "Resnet_crop_fast": ext_idx[step][ul], the keep masks of the "inside" layers (main.go:123-136);
+                                              // kind "Resnet_crop_packed": the entries packedMaskKey(step) and packedStrideMaskKey(step) instead
 };
 
 // rot_util.go:226-267 gen_keep_vec_stride: gen_keep_vec (ul = 0 upper, 1 lower half of the full-slot bootstrapping) that keeps only the outputs at
@@ -143,6 +144,57 @@ inline std::vector<int> gen_keep_vec_sparse(int vec_size, int in_wid, int kp_wid
     const int post_slot = 2 * vec_size / sparsity;
     for (int i = 0; i < post_slot; i++) for (int j = 1; j < sparsity / 2; j++) idx[(size_t)(i + post_slot * j)] = idx[(size_t)i];
     return idx;
+}
+
+// ---- the packed layout of `resnet_packed` (not a reference layout; DESIGN.md "The packed layout"). Header-only, like the masks above, so that a test can build it without a device.
+// Block b = 0, 1, 2 of the full-slot network holds its C = 16, 32, 64 channels norm = 4, 2, 1 slots apart on the cells of the lattice of step s = 1, 2, 4. An IMAGE SLOT of block b
+// is (g, py, px), g < norm, py, px < s: channel c at channel slot norm*c + g, activation cell (i, j) at grid cell (py + s*i, px + s*j). norm * s^2 = 4, 8, 16 images per ciphertext.
+static const int PACKED_GROUP = 16;                                            // images of a group: one ciphertext of block 2, two of block 1, four of block 0
+struct PackedSlot { int ct, g, py, px; };
+// THE slot assignment: where image m (0..15) of a group lives in block blk. Block 0 takes images 4q..4q+3 into ciphertext q at g = m mod 4 (the input merge sum_g X^g ct_g). A stride
+// layer sends (ciphertext q, channel offset g) of its input block, norm_out = norm_in / 2, to result r = 2q + (g / norm_out): channel offset g mod norm_out, output ciphertext r / 4,
+// moved by s_in * (t / 2, t mod 2) cells, t = r mod 4. The three cases below are that rule applied once and twice to block 0's assignment.
+inline PackedSlot packed_slot(int blk, int m) {
+    if (m < 0 || m >= PACKED_GROUP) panic("packed_slot: image index outside the group");
+    if (blk == 0) return {m / 4, m % 4, 0, 0};
+    if (blk == 1) return {m / 8, m % 2, (m / 4) % 2, (m / 2) % 2};
+    if (blk == 2) return {0, 0, (m / 4) % 2 + 2 * (m / 8), (m / 2) % 2 + 2 * (m % 2)};
+    panic("packed_slot: block not in 0..2");
+}
+// ext_idx keys of a "Resnet_crop_packed" context (the "Resnet_crop_fast" kind's are the steps 1, 2, 4 themselves): the mask of block `step`'s layers, all step^2 phases; and the mask
+// of the stride layer that enters it, the (step/2)^2 phases its images reach by themselves
+inline int packedMaskKey(int step) { return 100 + step; }
+inline int packedStrideMaskKey(int step) { return 200 + step; }
+// keep mask (ul = 0 upper, 1 lower half; gen_keep_vec_stride's slot order) of the cells (py + step*i, px + step*j), py, px < n_phase, i, j < kp_wid, every channel slot
+inline std::vector<int> gen_keep_vec_packed(int vec_size, int in_wid, int kp_wid, int step, int n_phase, int ul) {
+    int logN = 0; for (; (1 << logN) < 2 * vec_size; logN++) {}
+    if (ul != 0 && ul != 1) panic("ul not 0 nor 1");
+    if (n_phase < 1 || n_phase > step || (kp_wid - 1) * step + n_phase > in_wid) panic("gen_keep_vec_packed: phases outside the lattice, or cells outside the grid");
+    std::vector<int> idx((size_t)vec_size, 0);
+    const int batch = 2 * vec_size / (in_wid * in_wid);
+    auto rev = [&](int x) { uint32_t v = (uint32_t)x, r = 0; for (int k = 0; k < logN - 1; k++) r |= ((v >> k) & 1u) << (logN - 2 - k); return (size_t)r; };
+    auto live = [&](int x) { return x % step < n_phase && x / step < kp_wid; };
+    for (int row = ul * in_wid / 2; row < (ul + 1) * in_wid / 2; row++) if (live(row))
+        for (int col = 0; col < in_wid; col++) if (live(col))
+            for (int b = 0; b < batch; b++) idx[rev(in_wid * batch * (row - ul * in_wid / 2) + batch * col + b)] = 1;
+    return idx;
+}
+// The block-diagonal kernel over all `slots` channel slots that the packed layers hand to hc_prep_ker_ex2 at norm 1 (dilation stays the library's): ker is HWIO (ker_size, cin,
+// cout); for the channel offsets g = g_lo .. g_lo + g_cnt - 1, input slot norm_in*c + g feeds output slot norm_out*o + (g mod norm_out) and nothing else. A layer inside a block:
+// norm_in = norm_out = norm, g_lo = 0, g_cnt = norm. Half h of a stride layer: norm_in = 2 norm_out, g_lo = h * norm_out, g_cnt = norm_out.
+inline std::vector<double> packed_expand_ker(const std::vector<double> &ker, int ker_size, int cin, int cout, int norm_in, int norm_out, int g_lo, int g_cnt, int slots = 64) {
+    if ((int)ker.size() != ker_size * cin * cout) panic("packed_expand_ker: input size inconsistent");
+    if (g_lo < 0 || g_cnt < 1 || g_lo + g_cnt > norm_in || norm_in * cin > slots || norm_out * cout > slots) panic("packed_expand_ker: channel slots exceeded");
+    std::vector<double> out((size_t)ker_size * slots * slots, 0.0);
+    for (int t = 0; t < ker_size; t++) for (int c = 0; c < cin; c++) for (int o = 0; o < cout; o++) for (int g = g_lo; g < g_lo + g_cnt; g++)
+        out[((size_t)t * slots + (size_t)(norm_in * c + g)) * slots + (size_t)(norm_out * o + g % norm_out)] = ker[((size_t)t * cin + c) * cout + o];
+    return out;
+}
+// bn_a / bn_b of the same layers: channel o's value on the slots norm_out*o + g, g < norm_out
+inline std::vector<double> packed_expand_bn(const std::vector<double> &v, int norm_out) {
+    std::vector<double> out(v.size() * (size_t)norm_out);
+    for (size_t o = 0; o < v.size(); o++) for (int g = 0; g < norm_out; g++) out[o * (size_t)norm_out + (size_t)g] = v[o];
+    return out;
 }
 
 // ---- harness / reference-shaped API ----
@@ -248,6 +300,11 @@ void testResNet_crop_sparse(int st, int end, int ker_wid, int depth, bool debug)
 // test.go:372-636 — `resnet_fast ker depth 1 n false` (not a reference command; the reference's main.go:622 alternative to the line above): full slots on the 32-wide grid,
 // stride layers keep their outputs in place (gen_keep_vec_stride), later layers use dilated kernels; one full-slot bootstrapper
 void testResNet_crop_fast_in(int st, int end, int ker_wid, int depth, bool debug);
+// `resnet_packed ker depth 1 n false` (not a reference command): resnet_fast's network, files and results with up to 16 images per ciphertext (packed_slot above); ker 3 and 7
+void testResNet_crop_packed(int st, int end, int ker_wid, int depth);
+// sum_g X^g cts[g] into cts[0] (HC_LV_MONOMIAL, one pass per further ciphertext), the others freed: resnet_fast's inputs, channel b at slot 4b, become one block-0 ciphertext of
+// cts.size() <= 4 images, image g at the channel slots 4b + g. Same level and scale throughout.
+Ciphertext mergePackedInputs(Context *cont, std::vector<Ciphertext> &cts);
 // test_BL.go:16 — the slot-packed baseline the reference runs first (hconv_bl.cpp); boot = true adds Bootstrapp + ReLU (test_BL.go:113-168)
 void testConv_BL_in(int real_batch, int in_wid, int ker_wid, int total_test_num, bool boot);
 

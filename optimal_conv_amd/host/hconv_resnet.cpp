@@ -42,6 +42,8 @@ static std::string dur(std::chrono::steady_clock::time_point t0) {
 }
 static std::chrono::steady_clock::time_point now() { return std::chrono::steady_clock::now(); }
 static double secs(std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); }
+static std::vector<Ciphertext> tail_of_conv(Context *cont, const std::string &kind, int log_sparse, std::vector<Ciphertext> &ct_conv, double alpha, double pow_, int in_wid, int kp_wid,
+                                            const std::vector<std::vector<int>> *keep_idx, const std::string &mask_key);
 
 // eval.go:272-607 for the kinds the conv / convReLU / resnet command lines reach, for the images of a batch (ct_inputs.size() <= HCONV_IMAGE_BATCH): every image
 // sees the operations of the reference's per-image flow, but a launch covers all of them (hc_conv_then_pack_batch; hc_set_batch inside the tail)
@@ -81,17 +83,23 @@ std::vector<Ciphertext> evalConv_BNRelu_new_batch(Context *cont, const std::vect
         const int in_step = kind == "StrConv_inside" ? step / 2 : step;
         ct_conv = evalConv_BN_batch(cont, ct_inputs, ker_in, bn_a, bn_b, in_wid, ker_wid, real_ib, real_ob, norm, out_scale, false, in_step, ib_stride);
     } else panic("No kind!");
-    // hand-over to the bootstrapper's context (its own stream): everything queued on the convolution context - the stride layers end on a product and an addition that
-    // nothing has waited for - must be complete before the other stream reads ct_conv
-    HCX(cont->hc, hc_sync(cont->hc));
-    std::vector<const uint64_t *> conv_d; for (const Ciphertext &c : ct_conv) conv_d.push_back(c.d);
     const std::vector<std::vector<int>> *keep_idx = nullptr;
     if (inside) {                                                                                         // eval.go:526-528: keep_ctxt(ext_idx[step][ul])
         auto it = cont->ext_idx.find(step);
         if (it == cont->ext_idx.end()) panic("evalConv_BNRelu_new: no ext_idx for step " + std::to_string(step) + " (the inside kinds need a Resnet_crop_fast context)");
         keep_idx = &it->second;
     }
-    std::vector<BootCiphertext> r = evalConv_BNRelu_tail_batch(cont->btp, kind, log_sparse, conv_d, ct_conv[0].Scale, alpha, pow_, in_wid, kp_wid, keep_idx, "step" + std::to_string(step));
+    return tail_of_conv(cont, kind, log_sparse, ct_conv, alpha, pow_, in_wid, kp_wid, keep_idx, "step" + std::to_string(step));
+}
+// the tail of a layer for the convolution results of one launch set (freed here), and its outputs as blocks of the convolution context
+static std::vector<Ciphertext> tail_of_conv(Context *cont, const std::string &kind, int log_sparse, std::vector<Ciphertext> &ct_conv, double alpha, double pow_, int in_wid, int kp_wid,
+                                            const std::vector<std::vector<int>> *keep_idx, const std::string &mask_key) {
+    const int nimg = (int)ct_conv.size();
+    // hand-over to the bootstrapper's context (its own stream): everything queued on the convolution context - the stride layers end on a product and an addition that
+    // nothing has waited for - must be complete before the other stream reads ct_conv
+    HCX(cont->hc, hc_sync(cont->hc));
+    std::vector<const uint64_t *> conv_d; for (const Ciphertext &c : ct_conv) conv_d.push_back(c.d);
+    std::vector<BootCiphertext> r = evalConv_BNRelu_tail_batch(cont->btp, kind, log_sparse, conv_d, ct_conv[0].Scale, alpha, pow_, in_wid, kp_wid, keep_idx, mask_key);
     for (Ciphertext &c : ct_conv) freeCt(cont, c);
     // [2][2][N] over (Q0, Q1): what the next convolution reads. The result blocks belong to the bootstrapper's context and go back to it; the layer's outputs are
     // blocks of the convolution context (a block released into a context that did not allocate it would leave the owner's block table pointing at memory it no longer
@@ -274,5 +282,169 @@ static void testResNet_crop(int st, int end, int ker_wid, int depth, bool fast) 
 }
 void testResNet_crop_sparse(int st, int end, int ker_wid, int depth, bool debug) { (void)debug; testResNet_crop(st, end, ker_wid, depth, false); }
 void testResNet_crop_fast_in(int st, int end, int ker_wid, int depth, bool debug) { (void)debug; testResNet_crop(st, end, ker_wid, depth, true); }
+
+// ---------------------------------------------------------------- `resnet_packed` (not a reference command): the network of `resnet_fast` with every coefficient in use
+// The layout, the slot assignment (packed_slot) and the expanded kernels are stated in hconv_host.hpp; DESIGN.md "The packed layout" says why the stride layers merge after the mask.
+// Every convolution is 64 slots to 64 slots at norm 1: the block-diagonal expansion of the layer's weights through hc_prep_ker_ex2, dilated by the input lattice's step.
+static const int PK_W = 32, PK_SLOTS = 64;
+// the tails of convolution results (freed here) in launch sets of HCONV_IMAGE_BATCH, kept with the context's ext_idx[mask_id]
+static std::vector<Ciphertext> packed_tails(Context *cont, std::vector<Ciphertext> &ct_conv, const char *kind, double alpha, double pow_, int kp_wid, int mask_id, const std::string &mask_key) {
+    auto it = cont->ext_idx.find(mask_id);
+    if (it == cont->ext_idx.end()) panic("resnet_packed: no ext_idx entry " + std::to_string(mask_id) + " (a Resnet_crop_packed context holds the packed masks)");
+    std::vector<Ciphertext> outs; const size_t nb = (size_t)imageBatch();
+    for (size_t i0 = 0; i0 < ct_conv.size(); i0 += nb) {
+        std::vector<Ciphertext> set(ct_conv.begin() + (long)i0, ct_conv.begin() + (long)std::min(ct_conv.size(), i0 + nb));
+        for (const Ciphertext &c : tail_of_conv(cont, kind, 0, set, alpha, pow_, PK_W, kp_wid, &it->second, mask_key)) outs.push_back(c);
+    }
+    ct_conv.clear();
+    return outs;
+}
+static double packed_out_scale(double pow_) { return exp2(round(log2((double)PARAMS6_Q[0]) - (pow_ + 8))); }      // eval.go:433
+// a layer inside block blk (norm, step s, keep width raw): ONE kernel preparation and one convolution call for the group's ciphertexts, then their tails with the all-phases mask
+static std::vector<Ciphertext> packed_layer(Context *cont, const std::vector<Ciphertext> &in, const std::vector<double> &ker, const std::vector<double> &a, const std::vector<double> &b,
+                                            double alpha, double pow_, int ker_wid, int cin, int cout, int norm, int s, int raw) {
+    std::vector<Ciphertext> ct_conv = evalConv_BN_batch(cont, in, packed_expand_ker(ker, ker_wid * ker_wid, cin, cout, norm, norm, 0, norm, PK_SLOTS), packed_expand_bn(a, norm), packed_expand_bn(b, norm),
+                                                        PK_W, ker_wid, PK_SLOTS, PK_SLOTS, 1, packed_out_scale(pow_), false, s, 1);
+    return packed_tails(cont, ct_conv, "Conv_inside", alpha, pow_, raw, packedMaskKey(s), "packed" + std::to_string(s));
+}
+// the stride layer that enters the block of (norm, step s, keep width raw) from the block of (2 norm, s / 2). Result r = 2q + h is input ciphertext q convolved with the kernel of
+// half h of its channel offsets, through a tail of its own whose mask keeps the (s/2)^2 phases those images reach by themselves; only then do results 4o .. 4o + 3 meet in output
+// ciphertext o, result 4o + t moved by (s/2) * (t / 2, t mod 2) cells. (Merging BEFORE the tails - two inputs into one convolution - fails: a stride layer's convolution is computed
+// at every cell of the input lattice, and the three quarters of its outputs that the mask drops would land on the cells of the images merged in.)
+static std::vector<Ciphertext> packed_stride_layer(Context *cont, const std::vector<Ciphertext> &in, const std::vector<double> &ker, const std::vector<double> &a, const std::vector<double> &b,
+                                                   double alpha, double pow_, int ker_wid, int cin, int cout, int norm, int s, int raw) {
+    const size_t nin = in.size();
+    std::vector<Ciphertext> ct_conv(2 * nin);
+    for (int h = 0; h < 2; h++) {
+        std::vector<Ciphertext> r = evalConv_BN_batch(cont, in, packed_expand_ker(ker, ker_wid * ker_wid, cin, cout, 2 * norm, norm, h * norm, norm, PK_SLOTS), packed_expand_bn(a, norm), packed_expand_bn(b, norm),
+                                                      PK_W, ker_wid, PK_SLOTS, PK_SLOTS, 1, packed_out_scale(pow_), false, s / 2, 1);
+        for (size_t q = 0; q < nin; q++) ct_conv[2 * q + (size_t)h] = r[q];
+    }
+    std::vector<Ciphertext> res = packed_tails(cont, ct_conv, "StrConv_inside", alpha, pow_, raw, packedStrideMaskKey(s), "packedstride" + std::to_string(s));
+    std::vector<Ciphertext> outs;
+    for (size_t r = 0; r < res.size(); r++) {
+        const int t = (int)(r % 4);
+        if (t == 0) { outs.push_back(res[r]); continue; }
+        Ciphertext &acc = outs.back(); const size_t poly = (size_t)(acc.level + 1) * N;
+        if (res[r].level != acc.level || res[r].Scale != acc.Scale) panic("resnet_packed: the results of a stride layer share level and scale");
+        // whole cells: (dy, dx) is the exponent (32 dy + dx) * 64; the live cells end at row and column (s/2 - 1) + s (raw - 1) + s/2 < 32, so none wraps past the ring's end
+        const uint64_t e[2] = {(uint64_t)((PK_W * (s / 2) * (t / 2) + (s / 2) * (t % 2)) * PK_SLOTS), 0};
+        HCX(cont->hc, hc_lv_op2(cont->hc, HC_LV_MONOMIAL, acc.level, acc.d, acc.d + poly, res[r].d, res[r].d + poly, acc.d, acc.d + poly, e));
+        freeCt(cont, res[r]);
+    }
+    HCX(cont->hc, hc_sync(cont->hc));
+    return outs;
+}
+// HCONV_PACKED_DUMP_LAYERS (test mode): every image slot of a ciphertext the layer hands on, unpacked to its raw x raw x C activation (an observer: the ciphertext is only read)
+static void packed_dump(Context *cont, const std::vector<Ciphertext> &cts, int blk, int layer_no, int g0, int nimg, int raw, int C, const std::string &out_dir) {
+    const int norm = 4 >> blk, s = 1 << blk;
+    for (size_t z = 0; z < cts.size(); z++) {
+        const std::vector<double> cf = DecryptDecodeCoeffs(cont, cts[z]);          // level 1, the chain's own scale: reconstructed over q0 q1
+        for (int m = 0; m < nimg; m++) {
+            const PackedSlot p = packed_slot(blk, m);
+            if (p.ct != (int)z) continue;
+            std::vector<double> act((size_t)raw * raw * C);
+            for (int i = 0; i < raw; i++) for (int j = 0; j < raw; j++) for (int c = 0; c < C; c++)
+                act[((size_t)i * raw + j) * C + c] = cf[((size_t)(p.py + s * i) * PK_W + (size_t)(p.px + s * j)) * PK_SLOTS + (size_t)(norm * c + p.g)];
+            writeTxt(out_dir + "packed_act_L" + std::to_string(layer_no) + "_" + std::to_string(g0 + m) + ".csv", act);
+        }
+    }
+}
+void testResNet_crop_packed(int st, int end, int ker_wid, int depth) {
+    if (ker_wid != 3 && ker_wid != 7) panic("resnet_packed: kernel width 3 or 7 (the even keep widths of 5 put init at step - 1)");
+    const std::string ker_name = "ker" + std::to_string(ker_wid), tag = "crop_" + ker_name + "_d" + std::to_string(depth) + "_wid1/";
+    const std::string weight_dir = "Resnet_weights/weights_" + tag, out_dir = "Resnet_enc_results/results_" + tag, img_dir = "Resnet_plain_data/" + tag;
+    const int fc_out = 10; const double pow_ = 6.0, alpha = 0.0;
+    int num_blcs[3];
+    if (depth == 20) { num_blcs[0] = 7; num_blcs[1] = 5; num_blcs[2] = 5; } else if (depth == 14) { num_blcs[0] = 5; num_blcs[1] = 3; num_blcs[2] = 3; }
+    else if (depth == 8) { num_blcs[0] = 3; num_blcs[1] = 1; num_blcs[2] = 1; } else panic("wrong depth (not in 8, 14, 20)!");
+    const int real_batch[3] = {16, 32, 64}, norm[3] = {4, 2, 1}, steps[3] = {1, 2, 4};
+    const std::vector<int> in_wids = {32, 16, 8}, raw = {32 - ker_wid / 2, 16 - ker_wid / 2, 8 - ker_wid / 2};
+    const int ker_size = ker_wid * ker_wid;
+    std::vector<int> dump_layers;
+    if (const char *dl = testOnlyEnv("HCONV_PACKED_DUMP_LAYERS")) for (const char *p = dl; *p;) {
+        char *e; const long v = strtol(p, &e, 10);
+        if (e == p || (*e && *e != ',')) panic("HCONV_PACKED_DUMP_LAYERS: a comma list of layer numbers");
+        dump_layers.push_back((int)v); p = *e ? e + 1 : e;
+    }
+    mkdir("Resnet_enc_results", 0755); mkdir(out_dir.c_str(), 0755);
+    auto W = [&](int i, const char *what, int size) { return readTxt(weight_dir + "w" + std::to_string(i) + "-" + what + ".csv", size); };
+    Context *cont = newContext(LOGN, ker_wid, in_wids, raw, true, "Resnet_crop_packed");
+    auto run_start = now();
+    for (int g0 = st; g0 < end; g0 += PACKED_GROUP) {
+        const int nimg = std::min(PACKED_GROUP, end - g0);
+        std::vector<Ciphertext> ct_layer;
+        auto enc_start = now();
+        for (int q0 = 0; q0 < nimg; q0 += 4) {                                                          // block 0: images 4q .. 4q + 3 of the group into ciphertext q
+            std::vector<Ciphertext> four;
+            for (int m = q0; m < std::min(nimg, q0 + 4); m++) {
+                printf("Running  %d -th iter... ker size:  %d\n", g0 + m, ker_wid);
+                std::vector<double> image = readTxt(img_dir + "test_image_" + std::to_string(g0 + m) + ".csv", PK_W * PK_W * 3);
+                std::vector<double> input((size_t)N, 0.0); int k = 0;
+                for (int i = 0; i < PK_W; i++) for (int j = 0; j < PK_W; j++) for (int b = 0; b < 3; b++) {
+                    if (i < raw[0] && j < raw[0]) input[(size_t)(i * PK_W * PK_SLOTS + j * PK_SLOTS + b * norm[0])] = image[(size_t)k];   // as resnet_fast encodes it: channel b at slot 4b
+                    k++;
+                }
+                four.push_back(EncryptNew(cont, EncodeCoeffs(input, cont->ECD_LV, cont->scale), cont->ECD_LV, cont->scale));
+            }
+            ct_layer.push_back(mergePackedInputs(cont, four));
+        }
+        HCX(cont->hc, hc_sync(cont->hc));
+        printf("Encryption done in %s  (%d images in %zu ciphertexts)\n", dur(enc_start).c_str(), nimg, ct_layer.size());
+        double timings[6]; auto begin_start = now(), start = now();
+        int layer_no = 0;
+        auto step = [&](std::vector<Ciphertext> next, int blk) {
+            for (Ciphertext &c : ct_layer) freeCt(cont, c);
+            ct_layer = std::move(next);
+            if (std::find(dump_layers.begin(), dump_layers.end(), layer_no) != dump_layers.end()) packed_dump(cont, ct_layer, blk, layer_no, g0, nimg, raw[(size_t)blk], real_batch[blk], out_dir);
+            layer_no++;
+        };
+        auto inside = [&](int w, int cin, int blk) {
+            step(packed_layer(cont, ct_layer, W(w, "conv", cin * real_batch[blk] * ker_size), W(w, "a", real_batch[blk]), W(w, "b", real_batch[blk]), alpha, pow_, ker_wid, cin, real_batch[blk],
+                              norm[blk], steps[blk], raw[(size_t)blk]), blk);
+        };
+        auto strided = [&](int w, int blk) {
+            step(packed_stride_layer(cont, ct_layer, W(w, "conv", real_batch[blk - 1] * real_batch[blk] * ker_size), W(w, "a", real_batch[blk]), W(w, "b", real_batch[blk]), alpha, pow_, ker_wid,
+                                     real_batch[blk - 1], real_batch[blk], norm[blk], steps[blk], raw[(size_t)blk]), blk);
+        };
+        for (int i = 1; i <= num_blcs[0]; i++) { inside(i - 1, i == 1 ? 3 : real_batch[0], 0); printf("Block1, Layer  %d done!\n", i); }
+        printf("Block1 done.\n"); timings[0] = secs(start); start = now();
+        strided(num_blcs[0], 1);
+        printf("Block1 to 2 done!\n"); timings[1] = secs(start); start = now();
+        for (int i = 1; i <= num_blcs[1]; i++) { inside(num_blcs[0] + i, real_batch[1], 1); printf("Block2, Layer  %d done!\n", i); }
+        printf("Block2 done.\n"); timings[2] = secs(start); start = now();
+        strided(num_blcs[0] + num_blcs[1] + 1, 2);
+        printf("Block2 to 3 done!\n"); timings[3] = secs(start); start = now();
+        for (int i = 1; i <= num_blcs[2]; i++) { inside(num_blcs[0] + num_blcs[1] + i + 1, real_batch[2], 2); printf("Block3, Layer  %d done!\n", i); }
+        printf("Block3 done.\n"); timings[4] = secs(start); start = now();
+
+        // reduce-mean and FC as ONE convolution at norm 1: raw[2] x raw[2] taps of the FC weights over raw[2]^2, dilated by 4, so that a tap set reads the cells of ONE phase
+        // (resnet_fast's undilated 31-wide kernel would sum across the phases). The image at phase (py, px) has its scores at cell (kd/2 + py, kd/2 + px).
+        const int kd = steps[2] * (raw[2] - 1) + 1;
+        std::vector<double> ker_inf = readTxt(weight_dir + "final-fckernel.csv", real_batch[2] * fc_out), bn_bf = readTxt(weight_dir + "final-fcbias.csv", fc_out);
+        std::vector<double> ker_inf_((size_t)(raw[2] * raw[2] * real_batch[2] * fc_out));
+        for (size_t i = 0; i < ker_inf.size(); i++) for (int b = 0; b < raw[2] * raw[2]; b++) ker_inf_[i + (size_t)b * ker_inf.size()] = ker_inf[i];
+        std::vector<double> bn_af((size_t)fc_out, 1.0 / (double)(raw[2] * raw[2]));
+        std::vector<Ciphertext> ct_result = evalConv_BN_batch(cont, ct_layer, ker_inf_, bn_af, bn_bf, PK_W, raw[2], real_batch[2], fc_out, 1, (double)(1 << 30), false, steps[2], 1);
+        printf("Final FC done.\n"); timings[5] = secs(start); start = now();
+        printf("\n===============  DECRYPTION  ===============\n\n");
+        const std::vector<double> res_tmp = DecryptDecodeCoeffs(cont, ct_result[0]);
+        printf("Decryption Done in %s \n", dur(start).c_str());
+        for (int m = 0; m < nimg; m++) {
+            const PackedSlot p = packed_slot(2, m);
+            std::vector<double> res_out((size_t)fc_out);
+            for (int o = 0; o < fc_out; o++) res_out[(size_t)o] = res_tmp[((size_t)(kd / 2 + p.py) * PK_W + (size_t)(kd / 2 + p.px)) * PK_SLOTS + (size_t)o];
+            printf("\n result %d:  [", g0 + m); for (double v : res_out) printf("%.10f ", v);
+            printf("]\n");
+            writeTxt(out_dir + "class_result_" + ker_name + "_" + std::to_string(g0 + m) + ".csv", res_out);
+        }
+        for (Ciphertext &c : ct_layer) freeCt(cont, c);
+        for (Ciphertext &c : ct_result) freeCt(cont, c);
+        printf("Blc1:  %g  sec\nBlc1->2:  %g  sec\nBlc2:  %g  sec\nBlc2->3:  %g  sec\nBlc3:  %g  sec\nFinal (reduce_mean & FC):  %g  sec\n", timings[0], timings[1], timings[2], timings[3], timings[4], timings[5]);
+        printf("Total done in %s (%d images)\n", dur(begin_start).c_str(), nimg);
+    }
+    printf("All %d images done in %s  (first encryption to last result)\n", end - st, dur(run_start).c_str());
+    freeContext(cont);
+}
 
 }  // namespace hconv
