@@ -281,6 +281,13 @@ int hc_prep_ker_ex(hc_ctx *ctx, const double *ker_in, int ker_len, const double 
  * hc_prep_ker_ex refuses (norm*real_ib*ib_stride > max_bat, a dilated width whose encode_ker_final shift 2*adj exceeds N). */
 int hc_prep_ker_ex2(hc_ctx *ctx, const double *ker_in, int ker_len, const double *bn_a, int in_wid, int ker_wid,
                     int real_ib, int real_ob, int norm, double scale, int trans, int dilation, int ib_stride, hc_ker **out);
+/* prep_Ker of the reduce-mean + FC head (no new hc_version() number: detect it by symbol): the ker_wid x ker_wid kernel whose every tap holds
+ * the same matrix. fc is a HOST array [real_ib][real_ob], value at c*real_ob + o, and the only kernel data uploaded (real_ib*real_ob doubles
+ * instead of ker_wid^2 times as many). The handle is bit for bit what hc_prep_ker_ex2(..., trans = 0, dilation, ib_stride = 1) returns on the
+ * host-replicated kernel ker_in[t*real_ib*real_ob + c*real_ob + o] = fc[c*real_ob + o], t < ker_wid^2, and every shape that call refuses is
+ * HC_ERR_ARG here. */
+int hc_prep_ker_fc(hc_ctx *ctx, const double *fc, const double *bn_a, int in_wid, int ker_wid, int real_ib, int real_ob,
+                   int norm, double scale, int dilation, hc_ker **out);
 /* the plaintexts of a handle as Lattigo would hold them: HOST out [max_ob][2][N], canonical NTT residues */
 int hc_ker_download(hc_ctx *ctx, const hc_ker *ker, uint64_t *host_out);
 void hc_ker_free(hc_ctx *ctx, hc_ker *ker);

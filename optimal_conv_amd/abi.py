@@ -84,6 +84,8 @@ SYMBOLS = {
                                C.c_double, C.c_int, C.POINTER(C.c_void_p)]),
     "hc_prep_ker_ex2": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_double), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                 C.c_double, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
+    "hc_prep_ker_fc": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                               C.c_double, C.c_int, C.POINTER(C.c_void_p)]),
     "hc_ker_download": (C.c_int, [C.c_void_p, C.c_void_p, u64p]),
     "hc_ker_free": (None, [C.c_void_p, C.c_void_p]),
     "hc_idx_load": (C.c_int, [C.c_void_p, u64p]),
@@ -562,6 +564,18 @@ class Context:
             return k
         self._ck(self.L.hc_prep_ker(self.h, ker_in.ctypes.data_as(f64p), ker_in.size, bn_a.ctypes.data_as(f64p), in_wid, ker_wid, real_ib,
                                     real_ob, norm, scale, C.byref(k)))
+        return k
+
+    def prep_ker_fc(self, fc, bn_a, in_wid, ker_wid, real_ib, real_ob, norm=1, scale=2.0 ** 30, dilation=1):
+        """hc_prep_ker_fc: the plaintexts of the ker_wid x ker_wid kernel whose every tap is the matrix fc [real_ib][real_ob] (the reduce-mean + FC head)"""
+        fc = np.ascontiguousarray(fc, dtype=np.float64).reshape(-1)
+        bn_a = np.ascontiguousarray(bn_a, dtype=np.float64)
+        if fc.size != real_ib * real_ob:
+            raise HconvError(f"prep_ker_fc: fc holds {fc.size} values, not real_ib*real_ob = {real_ib * real_ob}")
+        k = C.c_void_p()
+        f64p = C.POINTER(C.c_double)
+        self._ck(self.L.hc_prep_ker_fc(self.h, fc.ctypes.data_as(f64p), bn_a.ctypes.data_as(f64p), in_wid, ker_wid, real_ib, real_ob, norm, scale,
+                                       dilation, C.byref(k)))
         return k
 
     def ker_download(self, k, max_ob):

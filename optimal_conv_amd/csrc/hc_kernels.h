@@ -901,9 +901,12 @@ __device__ __forceinline__ void hc_prep_ker_put(const HcPrepKer &P, int k_sz, in
 // EXP (hc_prep_ker_ex2, never with TRANS): ker_in is the undilated src_wid x src_wid HWIO kernel; source tap (ty, tx) goes to (dil*ty, dil*tx)
 // of the dilated ker_wid x ker_wid kernel and input channel c to ib_stride*c, exactly where the host-expanded kernel's non-zero would go. The
 // expanded kernel's zeros are the stage's clear. k_sz, adj and hc_prep_ker_put's row / column split are those of the dilated width.
-template <bool TRANS, bool EXP = false>
+// FC (hc_prep_ker_fc, a form of EXP): ker_in is ONE real_ib x real_ob matrix, fc[o + c*real_ob], that every one of the src_wid^2 taps holds (the reduce-mean + FC head):
+// the thread of (o, c, t) reads it at o + c*real_ob and goes where EXP's thread goes. At dil = 1 that is the plain form's place (td = t), so the words are hc_prep_ker's.
+template <bool TRANS, bool EXP = false, bool FC = false>
 __global__ __launch_bounds__(HC_TPB) void hc_k_prep_ker(HcPrepKer P) {
     static_assert(!(TRANS && EXP), "dilated / channel-strided kernels have no transposed form");
+    static_assert(!FC || EXP, "the shared-matrix form is a form of the dilated scatter");
     const int k_sz = P.ker_wid * P.ker_wid;
     const long total = (long)P.real_ob * P.real_ib * (EXP ? P.src_wid * P.src_wid : k_sz);
     const int vec_size = P.in_wid * P.in_wid * P.max_bat;
@@ -911,7 +914,7 @@ __global__ __launch_bounds__(HC_TPB) void hc_k_prep_ker(HcPrepKer P) {
     for (long id = (long)blockIdx.x * HC_TPB + threadIdx.x; id < total; id += (long)gridDim.x * HC_TPB) {
         if constexpr (EXP) {
             const int o = (int)(id % P.real_ob), c = (int)((id / P.real_ob) % P.real_ib), t = (int)(id / ((long)P.real_ob * P.real_ib));
-            const double v = P.ker_in[id] * P.bn_a[o];                                                   // id = o + c*real_ob + t*real_ob*real_ib
+            const double v = P.ker_in[FC ? (long)o + (long)c * P.real_ob : id] * P.bn_a[o];             // id = o + c*real_ob + t*real_ob*real_ib
             const int td = P.dil * (t / P.src_wid) * P.ker_wid + P.dil * (t % P.src_wid);               // dilated tap
             hc_prep_ker_put(P, k_sz, vec_size, adj, P.norm * o, P.norm * P.ib_stride * c * k_sz + td, v);
         } else if constexpr (!TRANS) {

@@ -1105,14 +1105,14 @@ extern "C" int hc_ker_load_device(hc_ctx *c, const uint64_t *dptr, int max_ob, h
 // trans = 1: reshape_ker's transposed form (conv.go:192); the scatter is hc_k_prep_ker<true>, everything after it is shared.
 // dil / ib_stride (hc_prep_ker_ex2) != 1: the plaintexts of the dilated, channel-spread kernel; the scatter is hc_k_prep_ker<false, true>.
 static int hc_prep_ker_impl(hc_ctx *c, const char *fn, const double *ker_in, int ker_len, const double *bn_a, int in_wid, int ker_wid,
-                            int real_ib, int real_ob, int norm, double scale, int trans, int dil, int ib_stride, hc_ker **out) {
+                            int real_ib, int real_ob, int norm, double scale, int trans, int dil, int ib_stride, hc_ker **out, bool fc = false) {
     if (!ker_in || !bn_a || !out || c->nq < 2 || in_wid < 1 || ker_wid < 1 || real_ib < 1 || real_ob < 1 || norm < 1 || (trans != 0 && trans != 1) ||
         dil < 1 || ib_stride < 1 || (trans && (dil != 1 || ib_stride != 1)))
         return hc_fail(c, HC_ERR_ARG, "%s: bad arguments", fn);
     if (HC_N % (in_wid * in_wid)) return hc_fail(c, HC_ERR_ARG, "%s: in_wid^2 must divide N", fn);
     const bool exp = dil != 1 || ib_stride != 1;
     const int max_bat = HC_N / (in_wid * in_wid), k_sz = ker_wid * ker_wid;
-    if (ker_len != k_sz * real_ib * real_ob) return hc_fail(c, HC_ERR_ARG, "input size inconsistent!");   // readTxt's panic text (main.go:986)
+    if (ker_len != (fc ? 1 : k_sz) * real_ib * real_ob) return hc_fail(c, HC_ERR_ARG, "input size inconsistent!");   // readTxt's panic text (main.go:986)
     const long kd = (long)dil * (ker_wid - 1) + 1;                                                           // the width the plaintexts encode
     if ((long)norm * real_ib * ib_stride > max_bat || norm * real_ob > max_bat) return hc_fail(c, HC_ERR_ARG, "%s: norm*batch exceeds max_bat=%d", fn, max_bat);
     if (kd > in_wid) return hc_fail(c, HC_ERR_ARG, "%s: kernel too wide for this input width", fn);
@@ -1130,7 +1130,8 @@ static int hc_prep_ker_impl(hc_ctx *c, const char *fn, const double *ker_in, int
     HcPrepKer P; P.ker_in = dk; P.bn_a = da; P.stage = stage; P.in_wid = in_wid; P.ker_wid = (int)kd; P.real_ib = real_ib; P.real_ob = real_ob;
     P.norm = norm; P.max_bat = max_bat; P.scale = scale; P.q0 = c->mods[0].m.q; P.q1 = c->mods[1].m.q;
     P.src_wid = ker_wid; P.dil = dil; P.ib_stride = ib_stride;
-    int rc = exp ? hc_launch(c, "prep_ker_scatter_dilated", hc_k_prep_ker<false, true>, hc_pw_grid((size_t)ker_len), P)
+    int rc = fc ? hc_launch(c, "prep_ker_scatter_fc", hc_k_prep_ker<false, true, true>, hc_pw_grid((size_t)ker_len * k_sz), P)
+           : exp ? hc_launch(c, "prep_ker_scatter_dilated", hc_k_prep_ker<false, true>, hc_pw_grid((size_t)ker_len), P)
            : trans ? hc_launch(c, "prep_ker_scatter_trans", hc_k_prep_ker<true>, hc_pw_grid((size_t)ker_len), P)
                    : hc_launch(c, "prep_ker_scatter", hc_k_prep_ker<false>, hc_pw_grid((size_t)ker_len), P);
     HC_HIP(c, hipStreamSynchronize(c->stream));      // host buffers may go away after return; hc_ntt below may regrow ws_tmp
@@ -1146,6 +1147,12 @@ extern "C" int hc_prep_ker_ex2(hc_ctx *c, const double *ker_in, int ker_len, con
                                int real_ib, int real_ob, int norm, double scale, int trans, int dilation, int ib_stride, hc_ker **out) {
     HC_ENTER(c);
     return hc_prep_ker_impl(c, "hc_prep_ker_ex2", ker_in, ker_len, bn_a, in_wid, ker_wid, real_ib, real_ob, norm, scale, trans, dilation, ib_stride, out);
+}
+// the reduce-mean + FC head: every tap of the ker_wid x ker_wid kernel is the matrix fc[c*real_ob + o]; the upload is that matrix alone (hc_k_prep_ker's FC form)
+extern "C" int hc_prep_ker_fc(hc_ctx *c, const double *fc, const double *bn_a, int in_wid, int ker_wid, int real_ib, int real_ob, int norm, double scale, int dilation, hc_ker **out) {
+    HC_ENTER(c);
+    if (real_ib < 1 || real_ob < 1 || (long)real_ib * real_ob > 0x7fffffffL) return hc_fail(c, HC_ERR_ARG, "hc_prep_ker_fc: bad arguments");
+    return hc_prep_ker_impl(c, "hc_prep_ker_fc", fc, real_ib * real_ob, bn_a, in_wid, ker_wid, real_ib, real_ob, norm, scale, 0, dilation, 1, out, true);
 }
 extern "C" int hc_prep_ker_ex(hc_ctx *c, const double *ker_in, int ker_len, const double *bn_a, int in_wid, int ker_wid,
                               int real_ib, int real_ob, int norm, double scale, int trans, hc_ker **out) {

@@ -20,6 +20,13 @@
 // `resnet_packed <ker_wid 3|7> <depth> 1 <test_num> false` (not a reference command): resnet_fast's network, weight, image and result files with 4 / 8 / 16 images per ciphertext
 // of block 1 / 2 / 3 (hconv_host.hpp packed_slot; DESIGN.md "The packed layout"), in groups of up to 16 images. Refused: wide_case != 1, cf100, ker_wid 5, the replay switches and
 // HCONV_DEBUG_LAYERS. HCONV_PACKED_DUMP_LAYERS=<layers> (test mode) writes every image's activation after the listed layers to packed_act_L<layer>_<image>.csv.
+// `strconvReLU <ker_wid 3|5|7> <i_batch 0..3> <num_tests <= 10> [pos 0..3]` (not a reference command; Ours only): the full-packing stride layer alone - the convolution at the chain's
+// out_scale, then the bootstrapping chain of kind "StrConv" (eval.go:303, 507-520: ext_ctxt with gen_comprs_full after the ReLU) at pack position pos - on
+// test_conv_data/test_strconv{k}_batch_{B}_{in,ker,bna,bnb,reluout}_{t}.csv (tests/golden/gen_strconv_relu_csv.py): raw width kp_wid = 2 (widths[i]/2 - k/2), reluout = the ReLU of the
+// stride-2 outputs, (kp_wid/2, kp_wid/2, B). Widths divisible by 4. It prints convReLU's Ours-column lines and the largest coefficient outside the kept cells.
+// `imagenet <ker_wid 3|5> <test_num> [c1 1..256]` (test.go:1209-1400 testImagenet_final_fast_in, which the reference reaches by editing main.go:570-575): the ImageNet tail on
+// weight_imgnet_ker{k}_h5/, ker{k}_data/test_image_{i}.csv -> ker{k}_enc_result/enc_result_{i}.csv. c1 (default 256; not a reference argument): the real channel count of block 1
+// (block 2 has 2 c1) of the files (tests/golden/gen_imagenet_csv.py). HCONV_IMAGE_BATCH, HCONV_SEED (test mode), HCONV_PROFILE and HCONV_DEBUG_LAYERS as for resnet_fast; the replay switches are refused.
 // HCONV_SKIP_BL=1 skips the baseline half (not a reference feature; for timing "Ours" alone).
 // `conv --test-mode <args>` honours the test-only overrides HCONV_SEED / HCONV_CHAIN_REPLAY; without the flag they are fatal when set.
 #include <stdio.h>
@@ -34,11 +41,23 @@ int main(int argc, char **argv) {
         fprintf(stderr, "hconv: --test-mode: test-only overrides from the environment are honoured\n");
     }
     const int batchs[5] = {4, 16, 64, 256, 1024}, widths[5] = {128, 64, 32, 16, 8};   // main.go:578-579
+    if (argc > 1 && std::string(argv[1]) == "imagenet") {                  // imagenet <ker_wid> <test_num> [c1]: test.go:1209's (st = 0, end, ker) with the arguments in this CLI's order
+        if (argc < 4 || argc > 5) hconv::panic("runtime error: index out of range (usage: imagenet <ker_wid 3|5> <test_num> [c1 1..256])");
+        const int ker = atoi(argv[2]), test_num = atoi(argv[3]), c1 = argc > 4 ? atoi(argv[4]) : 256;
+        if (!(ker == 3 || ker == 5)) hconv::panic("strange ker name!");                                    // test.go:1236
+        if (test_num < 1) hconv::panic("imagenet: test_num must be at least 1");
+        if (c1 < 1 || c1 > 256) hconv::panic("imagenet: c1 not in 1..256");
+        for (const char *v : {"HCONV_RESNET_REPLAY", "HCONV_CHAIN_REPLAY", "HCONV_CHAIN_REPLAY_BL"})
+            if (getenv(v) && *getenv(v) && std::string(getenv(v)) != "0") hconv::panic(std::string("imagenet: ") + v + " replays a pinned run of another command and is not available here");
+        setenv("HCONV_ASYNC_ALLOC", "1", 0);                                                               // a chain command (see below)
+        hconv::testImagenet_final_fast_in(0, test_num, ker, c1);
+        return 0;
+    }
     if (argc < 5) hconv::panic("runtime error: index out of range (usage: conv|convReLU|transconv <ker_wid> <i_batch> <num_tests>)");
     const std::string test_name = argv[1];
     // The bootstrapping chains allocate and free a few buffers per evaluator operation, and hipFree drains the device every time: the chain commands run on cached
     // allocations (hconv.hip hcx_malloc) unless HCONV_ASYNC_ALLOC=0 says otherwise - ResNet-20 at 8 images per launch set 2.12 -> 2.02 s per set (profiles/round4_cached_alloc_ab.txt)
-    if (test_name == "convReLU" || test_name == "resnet" || test_name == "resnet_fast" || test_name == "resnet_packed" || test_name == "transconvReLU" || test_name == "multiconvReLU") setenv("HCONV_ASYNC_ALLOC", "1", 0);
+    if (test_name == "convReLU" || test_name == "resnet" || test_name == "resnet_fast" || test_name == "resnet_packed" || test_name == "transconvReLU" || test_name == "multiconvReLU" || test_name == "strconvReLU") setenv("HCONV_ASYNC_ALLOC", "1", 0);
     const int ker_wid = atoi(argv[2]), i_batch = atoi(argv[3]), num_tests = atoi(argv[4]);
     if (!(ker_wid == 3 || ker_wid == 5 || ker_wid == 7)) hconv::panic("Wrong kernel wid (not in 3,5,7)");
     if (test_name == "resnet_fast") {                                    // not a reference command (see the top of this file); main.go:609-621's argument handling
@@ -93,6 +112,20 @@ int main(int argc, char **argv) {
         printf("Ker:  %d batches:  %d widths:  %d\n", ker_wid, batchs[i_batch], widths[i_batch]);
         printf("Ours start.\n");
         hconv::testTransConv_in(batchs[i_batch], widths[i_batch], ker_wid, num_tests, relu, sparse);
+        return 0;
+    } else if (test_name == "strconvReLU") {                                // not a reference command (see the top of this file)
+        if (argc > 6) hconv::panic("strconvReLU: at most one optional argument, the pack position");
+        if (num_tests > 10 || i_batch > 3) hconv::panic("Too many tests (>10) or too many batch index (>3)");
+        if (i_batch < 0) hconv::panic("runtime error: index out of range");
+        const int pos = argc > 5 ? atoi(argv[5]) : 0;
+        if (pos < 0 || pos > 3 || (argc > 5 && (argv[5][0] < '0' || argv[5][0] > '3' || argv[5][1]))) hconv::panic("strconvReLU: the pack position is 0..3");
+        if (widths[i_batch] % 4 != 0) hconv::panic("input wid not divisible by 4");
+        for (const char *v : {"HCONV_RESNET_REPLAY", "HCONV_CHAIN_REPLAY", "HCONV_CHAIN_REPLAY_BL"})
+            if (getenv(v) && *getenv(v) && std::string(getenv(v)) != "0") hconv::panic(std::string("strconvReLU: ") + v + " replays a pinned run of another command and is not available here");
+        printf("Stride-2 convolution followed by ReLU (& Bootstrapping) on full packing test start!\n");
+        printf("Ker:  %d batches:  %d widths:  %d\n", ker_wid, batchs[i_batch], widths[i_batch]);
+        printf("Ours start.\n");
+        hconv::testStrConv_in(batchs[i_batch], widths[i_batch], ker_wid, num_tests, pos);
         return 0;
     } else if (test_name == "multiconv" || test_name == "multiconvReLU") {   // not reference commands (see the top of this file)
         const bool relu = test_name == "multiconvReLU";

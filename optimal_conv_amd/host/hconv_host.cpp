@@ -172,7 +172,9 @@ void applyEnvOptions(hc_ctx *hc, int pack32_default) {
 
 Context *newContext(int logN, int ker_wid, const std::vector<int> &in_wids, const std::vector<int> &kp_wids, bool boot, const std::string &kind) {
     (void)ker_wid;
-    if (kind != "Conv" && kind != "Resnet_crop_sparse" && kind != "Resnet_crop_fast" && kind != "Resnet_crop_packed" && kind != "TransConv" && !(kind == "TransConv_sparse" && boot)) panic("Wrong kinds!");       // main.go:404 (the kinds the built command lines use; "TransConv_sparse": TransConv with the log_sparse = 2 bootstrapper)
+    const bool stride_full = kind == "StrConv" || kind == "Imagenet_final_fast";      // the kinds whose stride layer is ext_ctxt with gen_comprs_full (main.go:378-402); "StrConv": that layer alone (not a reference kind)
+    if (stride_full && !boot) panic("Wrong kinds! (" + kind + " is a bootstrapping context)");
+    if (kind != "Conv" && kind != "Resnet_crop_sparse" && kind != "Resnet_crop_fast" && kind != "Resnet_crop_packed" && kind != "TransConv" && !(kind == "TransConv_sparse" && boot) && !stride_full) panic("Wrong kinds!");       // main.go:404 (the kinds the built command lines use; "TransConv_sparse": TransConv with the log_sparse = 2 bootstrapper)
     Context *c = new Context();
     double logqp = 0; for (uint64_t q : PARAMS6_Q) logqp += log2((double)q); for (uint64_t p : PARAMS6_P) logqp += log2((double)p);
     printf("CKKS parameters: logN = %d, logSlots = %d, h = %d, logQP = %d, levels = %d, scale= 2^%f, sigma = %f \n",
@@ -210,11 +212,18 @@ Context *newContext(int logN, int ker_wid, const std::vector<int> &in_wids, cons
         auto start = now();
         // DFT matrices and every switching key, same secret key. "Conv" and "Resnet_crop_fast": one full-slot bootstrapper; the sparse resnet kind: the
         // four sparse ones its layers use (btp2..btp5 of main.go:480-500; log_sparse 1..4)
-        const bool full = kind == "Conv" || kind == "Resnet_crop_fast" || kind == "Resnet_crop_packed" || kind == "TransConv";
+        const bool full = kind == "Conv" || kind == "Resnet_crop_fast" || kind == "Resnet_crop_packed" || kind == "TransConv" || stride_full;
         if (kind == "TransConv_sparse") c->btp = newBoot(c->sk, c->seed, dev, std::vector<int>{2}, imageBatch());      // a quarter of the channel slots live: btp3's slot set alone
         else c->btp = full ? newBoot(c->sk, c->seed, dev, {0}, imageBatch()) : newBoot(c->sk, c->seed, dev, std::vector<int>{2, 1, 3, 4}, imageBatch());
         if (kind == "Resnet_crop_sparse") { bootPrepareCompress(c->btp, in_wids[0], kp_wids[1], 1); bootPrepareCompress(c->btp, in_wids[1], kp_wids[2], 2); }   // main.go:163-215
+        // the rotation keys of the stride layer's table, generated with the bootstrapper's own: "StrConv" one (in_wid, kp_wid) at every pos, "Imagenet_final_fast" the first
+        // width's at the kept width 2 * kp_wids[1] of the next block, pos 0 and 1 (main.go:390-401)
+        if (kind == "StrConv") for (int pos = 0; pos < 4; pos++) bootPrepareCompressFull(c->btp, in_wids[0], kp_wids[0], pos);
+        if (kind == "Imagenet_final_fast") for (int pos = 0; pos < 2; pos++) bootPrepareCompressFull(c->btp, in_wids[0], 2 * kp_wids[1], pos);
         printf("Done in %s \n", dur(start).c_str());
+    }
+    if (kind == "Imagenet_final_fast") {                                                               // main.go:380-384: ext_idx[in_wid][ul] = gen_keep_vec per width
+        for (size_t i = 0; i < in_wids.size(); i++) { c->ext_idx[in_wids[i]].resize(2); for (int ul = 0; ul < 2; ul++) c->ext_idx[in_wids[i]][(size_t)ul] = gen_keep_vec(N / 2, in_wids[i], kp_wids[i], ul); }
     }
     if (kind == "Resnet_crop_fast") {                                                                  // main.go:123-136: masks only, no rotation keys
         for (size_t i = 0; i < in_wids.size(); i++) {
@@ -948,6 +957,74 @@ void testConv_in(int in_batch, int in_wid, int ker_wid, int total_test_num, bool
         std::vector<double> real_out = readTxt(pre + "out" + suf, raw_in_wid * raw_in_wid * raw_in_batch);
         printDebugCfsPlain(test_out, real_out);
         freeCt(cont, ctxt_input); freeCt(cont, ct_result);
+    }
+    freeContext(cont);
+}
+
+// ---------------------------------------------------------------- testStrConv_in (not a reference routine: testConv_in's boot branch for kind "StrConv")
+// The full-packing stride layer alone: B channels on the raw width kp_wid = 2 (in_wid/2 - ker_wid/2) (set_Variables' keep width of the NEXT block, doubled), the
+// convolution at the chain's out_scale, the "StrConv" tail at pack_pos = pos. The result lives on the in_wid/2 grid with 4 B channel slots: the stride-2 outputs
+// (odd row and column) of channel c at slot c + B pos. test_strconv{k}_batch_{B}_reluout_{t}.csv holds them as (kp_wid/2, kp_wid/2, B); every other coefficient of the
+// result is expected to be zero, and the largest one is printed.
+void testStrConv_in(int in_batch, int in_wid, int ker_wid, int total_test_num, int pos) {
+    if (in_wid % 4 != 0) panic("input wid not divisible by 4");
+    const int kp_wid = 2 * (in_wid / 2 - ker_wid / 2), raw_in_wid = kp_wid, out_wid = in_wid / 2, raw_out_wid = kp_wid / 2, out_slots = 4 * in_batch, norm = 1;
+    const std::string test_dir = "test_conv_data/";
+    Context *cont = newContext(LOGN, ker_wid, {in_wid}, {kp_wid}, true, "StrConv");
+    printf("vec size: log2 =  %d\n", cont->logN);
+    printf("raw input width:  %d\n", raw_in_wid);
+    printf("kernel width:  %d\n", ker_wid);
+    printf("num raw batches in & out:  %d ,  %d\n", in_batch, in_batch);
+    printf("stride layer: keep width  %d , pack position  %d , output width  %d , output slots  %d\n", kp_wid, pos, raw_out_wid, out_slots);
+    for (int test_iter = 0; test_iter < total_test_num; test_iter++) {
+        printf("%d -th iter...start\n", test_iter + 1);
+        const std::string pre = test_dir + "test_strconv" + std::to_string(ker_wid) + "_batch_" + std::to_string(in_batch) + "_";
+        const std::string suf = "_" + std::to_string(test_iter) + ".csv";
+        std::vector<double> raw_input = readTxt(pre + "in" + suf, raw_in_wid * raw_in_wid * in_batch);
+        std::vector<double> ker_in = readTxt(pre + "ker" + suf, in_batch * in_batch * ker_wid * ker_wid);
+        std::vector<double> bn_a = readTxt(pre + "bna" + suf, in_batch);
+        std::vector<double> bn_b = readTxt(pre + "bnb" + suf, in_batch);
+        std::vector<double> input = prep_Input(raw_input, raw_in_wid, in_wid, cont->Nn, norm, false, false);
+        auto start = now();
+        const int nimg = imageBatch();
+        std::vector<Ciphertext> enc = EncryptCoeffsBatch(cont, std::vector<const std::vector<double> *>((size_t)nimg, &input), cont->ECD_LV, cont->scale);
+        printf("Encryption done in %s \n", dur(start).c_str());
+        const double pow_ = 4.0, alpha = 0.0;                                                          // test.go:22
+        std::vector<Ciphertext> ct_conv = evalConv_BN_batch(cont, enc, ker_in, bn_a, bn_b, in_wid, ker_wid, in_batch, in_batch, norm, chain_out_scale(pow_), false);
+        HC(cont->hc, hc_sync(cont->hc));                                                               // hand-over to the bootstrapper's context (another stream)
+        std::vector<const uint64_t *> conv_d; for (const Ciphertext &ct : ct_conv) conv_d.push_back(ct.d);
+        auto layer = now();
+        std::vector<BootCiphertext> ct_res = evalConv_BNRelu_tail_batch(cont->btp, "StrConv", 0, conv_d, ct_conv[0].Scale, alpha, pow_, in_wid, kp_wid, nullptr, "", pos);
+        if (nimg > 1) printf("Bootstrapping + ReLU of %d ciphertexts done in %s \n", nimg, dur(layer).c_str());
+        start = now();
+        std::vector<double> cfs = bootDecryptDecodeCoeffs(cont->btp, ct_res[0]);
+        printf("Decryption Done in %s \n", dur(start).c_str());
+        if (const char *dump = testOnlyEnv("HCONV_STRCONV_DUMP")) {                                     // test mode: the N decoded coefficients of image 0, raw doubles, for a check outside this driver
+            FILE *f = fopen(dump, "wb"); if (!f || fwrite(cfs.data(), sizeof(double), cfs.size(), f) != cfs.size()) panic(std::string("HCONV_STRCONV_DUMP: cannot write ") + dump); fclose(f);
+        }
+        // the kept cells: (y', x', c + B pos) of the out_wid grid, y', x' < raw_out_wid; everything else is outside
+        auto kept_of = [&](const std::vector<double> &cf, double *outside) {
+            std::vector<double> kept((size_t)raw_out_wid * raw_out_wid * in_batch); double mx = 0;
+            for (int y = 0; y < out_wid; y++) for (int x = 0; x < out_wid; x++) for (int s = 0; s < out_slots; s++) {
+                const double v = cf[(size_t)(y * out_wid + x) * out_slots + s];
+                if (y < raw_out_wid && x < raw_out_wid && s / in_batch == pos) kept[(size_t)(y * raw_out_wid + x) * in_batch + (size_t)(s % in_batch)] = v; else mx = std::max(mx, fabs(v));
+            }
+            *outside = mx; return kept; };
+        double outside = 0;
+        std::vector<double> test_out = kept_of(cfs, &outside);
+        std::vector<double> real_out = readTxt(pre + "reluout" + suf, raw_out_wid * raw_out_wid * in_batch);
+        printDebugCfsPlain(test_out, real_out);
+        double err = 0; for (size_t i = 0; i < real_out.size(); i++) err = std::max(err, fabs(test_out[i] - real_out[i]));
+        printf("stride layer: max |error| on the kept cells = %.6g, max |coefficient| outside them = %.6g\n", err, outside);
+        for (int z = 1; z < nimg; z++) {
+            double oz = 0; std::vector<double> cz = kept_of(bootDecryptDecodeCoeffs(cont->btp, ct_res[(size_t)z]), &oz);
+            double mx = 0, mr = 0; for (size_t i = 0; i < cz.size(); i++) { mx = std::max(mx, fabs(cz[i] - test_out[i])); mr = std::max(mr, fabs(cz[i] - real_out[i])); }
+            printf("image %d of the batch: max |difference| to image 0 = %.3g, to the expected output = %.3g, outside the kept cells = %.3g\n", z, mx, mr, oz);
+        }
+        print_boot_stats(cont);
+        for (Ciphertext &ct : enc) freeCt(cont, ct);
+        for (Ciphertext &ct : ct_conv) freeCt(cont, ct);
+        for (BootCiphertext &ct : ct_res) freeBootCt(cont->btp, ct);
     }
     freeContext(cont);
 }

@@ -132,6 +132,29 @@ inline std::vector<int> gen_keep_vec(int vec_size, int in_wid, int kp_wid, int u
     }
     return idx;
 }
+// rot_util.go:428-492 gen_comprs_full (its padding = false branch, the one the reference runs): rotation -> 0/1 mask of ext_ctxt for the full-packing stride layer (kind
+// "StrConv"). Half ul (0 upper, 1 lower) of a full-slot ciphertext on the in_wid grid goes through sum over (rot, mask) of Rotate(ct (.) mask, rot): the stride-2 positions
+// (odd row and column below kp_wid) land on the in_wid/2 grid with four times the channel slots, in quarter pos (0..3) of that channel axis (DESIGN.md "Full-packing stride
+// layer"). 2 * (in_wid/4) rotations, the same set for both halves. Header-only, like the masks above.
+inline std::map<int, std::vector<int>> gen_comprs_full(int vec_size, int in_wid, int kp_wid, int pos, int ul) {
+    if (kp_wid < in_wid / 2) panic("keep width too small. less than in_wid/2");
+    if (in_wid % 4 != 0) panic("input wid not divisible by 4");
+    if (pos < 0 || pos > 3) panic("pos not in 0..3");
+    if (ul != 0 && ul != 1) panic("ul not 0 nor 1");
+    const int batch = 2 * vec_size / (in_wid * in_wid), min_wid = in_wid / 4;
+    int log_in_wid = 0; for (; (1 << log_in_wid) < in_wid; log_in_wid++) {}
+    auto rev = [](int x, int bits) { int r = 0; for (int k = 0; k < bits; k++) r |= ((x >> k) & 1) << (bits - 1 - k); return r; };
+    const int rpos = rev(pos, 2);
+    std::map<int, std::vector<int>> r_idx;
+    for (int j = 0; j < 2 * min_wid; j++) {                                                   // the kind of move depends on j
+        std::vector<int> tmp((size_t)vec_size, 0);
+        if (rev(in_wid / 2 + j, log_in_wid) < kp_wid)
+            for (int b = 0; b < batch; b++) for (int i = 0; i < min_wid; i++)
+                if (ul == 0 || rev(3 * min_wid + i, log_in_wid - 1) < kp_wid - in_wid / 2) tmp[(size_t)(2 * min_wid * in_wid * b + 2 * min_wid * j + i + in_wid * min_wid + min_wid)] = 1;
+        r_idx[j * min_wid - 2 * rpos * min_wid * min_wid + min_wid + in_wid * min_wid] = tmp;
+    }
+    return r_idx;
+}
 // rot_util.go:179-218: one mask for the packed (low | high) ciphertext of sparse bootstrapping, period 2 n_s
 inline std::vector<int> gen_keep_vec_sparse(int vec_size, int in_wid, int kp_wid, int log_sparse) {
     int logN = 0; for (; (1 << logN) < 2 * vec_size; logN++) {}
@@ -264,13 +287,16 @@ std::vector<BootCiphertext> evalConv_BNRelu_multi_batch(Context *cont, const std
 Boot *newBoot(const std::vector<int64_t> &sk, const Seed256 &seed, int device, const std::vector<int> &log_sparse_sets, int image_batch = 1);   // one "bootstrapper" per log_sparse; image_batch: images per launch set of the tail (HCONV_IMAGE_BATCH)
 void freeBoot(Boot *);
 void bootPrepareCompress(Boot *B, int in_wid, int kp_wid, int log_sparse);   // rotation keys of a stride layer's ext_double_ctxt
+void bootPrepareCompressFull(Boot *B, int in_wid, int kp_wid, int pos);      // rotation keys of the full-packing stride layer's ext_ctxt (gen_comprs_full, both halves), main.go:378-402
 // everything after evalConv_BN: Scale *= 2^pow, BootstrappConv_CtoS, evalReLU + MulByPow2, keep_ctxt, BootstrappConv_StoC
 BootCiphertext evalConv_BNRelu_tail(Boot *B, const std::string &kind, int log_sparse, const uint64_t *ct_conv_dev, double ct_scale, double alpha, double pow, int in_wid, int kp_wid);
 // the same tail for the images of a batch (same layer, same weights) as ONE set of launches; at most the image_batch the bootstrapper was built with
 // kinds "TransConv" (the "Conv" tail; kp_wid = 2 * raw_in_wid) and "TransConv_sparse" (the "Conv_sparse" tail, log_sparse = 2 only): a stride-2 transposed layer's output.
 // kinds "Conv_inside" / "StrConv_inside" (the "Conv" tail on full slots) keep with keep_idx[ul] (Context::ext_idx[step]) instead of gen_keep_vec; mask_key names them in the mask cache
+// kind "StrConv" (eval.go:303, 507-520: the full-packing stride layer): instead of a keep mask each half goes through ext_ctxt with gen_comprs_full(N/2, in_wid, kp_wid, pack_pos, ul),
+// as ONE hoisted linear transform; the result lives on the in_wid/2 grid, quarter pack_pos of its channel slots (DESIGN.md "Full-packing stride layer")
 std::vector<BootCiphertext> evalConv_BNRelu_tail_batch(Boot *B, const std::string &kind, int log_sparse, const std::vector<const uint64_t *> &ct_conv_dev, double ct_scale, double alpha, double pow, int in_wid, int kp_wid,
-                                                       const std::vector<std::vector<int>> *keep_idx = nullptr, const std::string &mask_key = "");
+                                                       const std::vector<std::vector<int>> *keep_idx = nullptr, const std::string &mask_key = "", int pack_pos = 0);
 std::vector<double> bootDecryptDecodeCoeffs(Boot *B, const BootCiphertext &ct);
 void freeBootCt(Boot *B, BootCiphertext &ct);
 void bootStats(Boot *B, long *keys, long *keyswitches);
@@ -290,7 +316,7 @@ std::vector<Ciphertext> evalConv_BN_batch(Context *cont, const std::vector<Ciphe
 // (StrConv_inside: step / 2). ib_stride: input channel c of ker_in is channel ib_stride*c of the kernel (test.go:484-492), real_ib counts ker_in's channels.
 std::vector<Ciphertext> evalConv_BNRelu_new_batch(Context *cont, const std::vector<Ciphertext> &ct_inputs, const std::vector<double> &ker_in, const std::vector<double> &bn_a,
                                                   const std::vector<double> &bn_b, double alpha, double pow, int in_wid, int kp_wid, int ker_wid, int real_ib, int real_ob,
-                                                  int norm, int log_sparse, const std::string &kind, int step = 1, int ib_stride = 1);
+                                                  int norm, int log_sparse, const std::string &kind, int step = 1, int ib_stride = 1, int pack_pos = 0);   // pack_pos: kind "StrConv" (kp_wid = the kept width on the INPUT grid)
 int imageBatch();                                // HCONV_IMAGE_BATCH (1..8; default 1): images that go through a layer as one launch set
 Ciphertext evalConv_BNRelu_new(Context *cont, const Ciphertext &ct_input, const std::vector<double> &ker_in, const std::vector<double> &bn_a,
                                const std::vector<double> &bn_b, double alpha, double pow, int in_wid, int kp_wid, int ker_wid, int real_ib, int real_ob,
@@ -305,6 +331,10 @@ void testResNet_crop_packed(int st, int end, int ker_wid, int depth);
 // sum_g X^g cts[g] into cts[0] (HC_LV_MONOMIAL, one pass per further ciphertext), the others freed: resnet_fast's inputs, channel b at slot 4b, become one block-0 ciphertext of
 // cts.size() <= 4 images, image g at the channel slots 4b + g. Same level and scale throughout.
 Ciphertext mergePackedInputs(Context *cont, std::vector<Ciphertext> &cts);
+// `strconvReLU ker i_batch n [pos]` (not a reference command): the full-packing stride layer alone - kind "StrConv" at pack_pos = pos on testConv_in's shapes, Ours only
+void testStrConv_in(int in_batch, int in_wid, int ker_wid, int total_test_num, int pos);
+// test.go:1209-1400 — `imagenet ker n [c1]`: the ImageNet tail (3 layers of c1 channels on the 16-grid, the stride layer to 2 c1 on the 8-grid, 3 layers, reduce-mean + FC to 1000 classes)
+void testImagenet_final_fast_in(int st, int end, int ker_wid, int c1 = 256);
 // test_BL.go:16 — the slot-packed baseline the reference runs first (hconv_bl.cpp); boot = true adds Bootstrapp + ReLU (test_BL.go:113-168)
 void testConv_BL_in(int real_batch, int in_wid, int ker_wid, int total_test_num, bool boot);
 

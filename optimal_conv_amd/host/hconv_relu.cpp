@@ -98,6 +98,7 @@ struct Boot {
     double alg_ct = 0, alg_shared = 0;
     int ks_rows(int L) const { const int a = (int)P.size(), nl = L + 1, nt = nl + a; return 2 * ((nl + a - 1) / a) * nt; }      // rows of one switching key at level L
     std::map<std::string, DPt> pt_cache;                     // encoded 0/1 masks (keep_ctxt, ext_double_ctxt), by what defines them
+    std::map<std::string, LT> lt_cache;                      // the mask tables that run as a linear transform (ext_ctxt of kind "StrConv"), by what defines them
 
     // ---------------- memory and the image batch
     // HCONV_IMAGE_BATCH = nb_max > 1: every ciphertext object below stands for the ciphertexts of nb <= nb_max images going through the layer together (test.go:128 runs
@@ -526,10 +527,11 @@ struct Boot {
     }
     FILE *dft_digests = nullptr;
     // slots: the length of M's vectors (n, or 2^(logSlots+1) for a sparse-slot matrix: rotations modulo it, sparse embedding)
-    LT plan(const DiagMat &M, int level, double pt_scale, const char *tag, int slots) {          // the fork's BSGS split + the pre-rotated, encoded diagonals
+    // n1 != 0: that baby-step count instead of the fork's split (n1 = the slot count: every rotation a hoisted baby step of giant step 0)
+    LT plan(const DiagMat &M, int level, double pt_scale, const char *tag, int slots, int n1 = 0) {          // the fork's BSGS split + the pre-rotated, encoded diagonals
         LT lt; lt.level = level; lt.pt_scale = pt_scale;
         const int n = slots ? slots : this->n;
-        lt.n1 = lattigo_n1(M, n);
+        lt.n1 = n1 ? n1 : lattigo_n1(M, n);
         // every linear transform of a bootstrapper runs in the extended basis (linear_transform_qp): the diagonals are encoded mod Q_0..Q_level and mod every P. On the
         // host path one at a time (encode_qp); on the device path a call encodes as many as fit about 256 rows, into ONE allocation the DPts of the batch share
         struct Diag { int k, g, b; std::vector<cplx> rolled; };
@@ -1007,6 +1009,28 @@ static DCt keep_ctxt(Boot *B, const DCt &ct, const std::vector<int> &idx, const 
     DPt pt = B->encode_mask(key, idx, ct.level, (double)B->Q[(size_t)ct.level]);
     return B->rescale(B->mul_plain(ct, pt));
 }
+// conv.go:347-371 ext_ctxt with gen_comprs_full's table (kind "StrConv"): sum over (rot, mask) of Rotate(ct (.) mask, rot), masks at scale q_level, one rescale. The sum
+// equals sum_rot roll(mask_rot) (.) Rotate(ct, rot), roll(mask)[p] = mask[p + rot]: a linear transform whose diagonals are the rolled masks. It runs through linear_transform
+// with every rotation a baby step of giant step 0: ONE decomposition of c1 shared by the 8 (in_wid 16) or 16 (in_wid 32) rotations, the products summed in the extended basis
+// and ONE ModDown. The encoded diagonals are cached by what defines them, like the masks of keep_ctxt.
+static DCt ext_ctxt_full(Boot *B, const DCt &ct, int in_wid, int kp_wid, int pos, int ul) {
+    const std::string key = "comprs_full/" + std::to_string(in_wid) + "/" + std::to_string(kp_wid) + "/" + std::to_string(pos) + "/" + std::to_string(ul) + "/" + std::to_string(ct.level);
+    auto it = B->lt_cache.find(key);
+    if (it == B->lt_cache.end()) {
+        const int n = B->n; DiagMat M;
+        for (auto &e : gen_comprs_full(n, in_wid, kp_wid, pos, ul)) {
+            const int rot = ((e.first % n) + n) % n; std::vector<cplx> d((size_t)n);
+            for (int p = 0; p < n; p++) d[(size_t)p] = cplx((double)e.second[(size_t)((p + rot) % n)], 0);
+            if (M.count(rot)) panic("ext_ctxt: two masks of the table share a rotation");
+            M.emplace(rot, std::move(d));
+        }
+        B->n_enc_mask += (long)M.size(); const long nd = B->n_enc_diag;
+        Boot::Single one(B);
+        it = B->lt_cache.emplace(key, B->plan(M, ct.level, (double)B->Q[(size_t)ct.level], "comprs_full", 0, n)).first;
+        B->n_enc_diag = nd;                                                       // counted as masks, which is what they are
+    }
+    return B->rescale(B->linear_transform(ct, it->second));
+}
 
 // ---------------------------------------------------------------- public surface (hconv_host.hpp)
 Boot *newBoot(const std::vector<int64_t> &sk, const Seed256 &seed, int device, const std::vector<int> &log_sparse_sets, int image_batch) {
@@ -1025,9 +1049,13 @@ void bootPrepareCompress(Boot *B, int in_wid, int kp_wid, int log_sparse) {
         for (auto *m : {&m_idx, &r_idx}) for (auto &e : *m) { const int k = ((e.first % B->n) + B->n) % B->n; if (k) B->key(B->gal_rot(k), LV_RELU_TOP - 10); }
     }
 }
+// main.go:378-402: the rotations of gen_comprs_full's tables, both halves, at the level the masks run at (the ReLU's output level)
+void bootPrepareCompressFull(Boot *B, int in_wid, int kp_wid, int pos) {
+    for (int ul = 0; ul < 2; ul++) for (auto &e : gen_comprs_full(N / 2, in_wid, kp_wid, pos, ul)) { const int k = ((e.first % B->n) + B->n) % B->n; if (k) B->key(B->gal_rot(k), B->lv_relin_lo, 1); }      // evalReLU ends on a MulRelin at lv_relin_lo, without a rescale
+}
 void freeBoot(Boot *b) {
     if (!b) return;
-    b->sets.clear(); b->pt_cache.clear();      // every block returns to the pool
+    b->sets.clear(); b->pt_cache.clear(); b->lt_cache.clear();      // every block returns to the pool
     for (uint64_t *blk : b->pool) hc_free(b->hc, blk);
     b->pool.clear();
     for (uint64_t *blk : b->pool_qp) hc_free(b->hc, blk);
@@ -1091,6 +1119,7 @@ struct LayerDebug {
     Boot *B; std::string kind; int log_sparse, nimg, in_wid, kp_wid; double alpha, pow_; const std::vector<std::vector<int>> *keep_idx; bool check;
     std::vector<std::vector<double>> cfs_preB;                 // per image: the decoded convolution result
     std::vector<std::vector<cplx>> seen[2];                    // per half, per image: what the stage before decrypted to
+    int pack_pos = 0;                                          // kind "StrConv"
     static int brev15(int i) { int r = 0; for (int b = 0; b < LOGN - 1; b++) r |= ((i >> b) & 1) << (LOGN - 2 - b); return r; }
     int log_slots() const { return log_sparse ? LOGN - log_sparse : LOGN - 1; }      // printDebug: LogSlots - (log_sparse - 1) for a packed ciphertext
     // ONE hc_decrypt_decode_lv call over every image of every ciphertext given, in that order (the halves, each with the B->nb images it holds): log_slots = -1: [count][N]
@@ -1169,6 +1198,13 @@ struct LayerDebug {
                 for (auto &e : idx) { const int rot = ((e.first % n) + n) % n; for (int j = 0; j < n; j++) { const int src = (j + rot) % n; o[(size_t)j] += in[(size_t)src] * (double)e.second[(size_t)src]; } }
                 return o; };
             halves_of(pass(pass(fl[0], m_idx), r_idx));
+        } else if (kind == "StrConv") {                                                                   // the kind's layout itself (DESIGN.md "Full-packing stride layer"), not the table the layer evaluates
+            std::vector<double> in((size_t)N), cfs((size_t)N, 0.0);
+            for (int h = 0; h < 2; h++) for (int i = 0; i < n; i++) in[(size_t)(brev15(i) + h * n)] = fl[h][(size_t)i];      // debugCtoS backwards: slot i of half h is coefficient brev(i) + h N/2
+            const int B = N / (in_wid * in_wid), ow = in_wid / 2;
+            for (int y = 1; y < kp_wid; y += 2) for (int x = 1; x < kp_wid; x += 2) for (int c = 0; c < B; c++)
+                cfs[(size_t)((y / 2) * ow + x / 2) * 4 * B + (size_t)(c + B * pack_pos)] = in[(size_t)(y * in_wid + x) * B + (size_t)c];
+            return cfs;
         } else if (iter == 1) halves_of(masked(fl[0], gen_keep_vec_sparse(n, in_wid, kp_wid, log_sparse)));         // keep_vec_sparse
         else if (keep_idx) for (int h = 0; h < 2; h++) tmp[h] = masked(fl[h], (*keep_idx)[(size_t)h]);              // keep_vec_stride: the context's ext_idx[step]
         else for (int h = 0; h < 2; h++) tmp[h] = masked(fl[h], gen_keep_vec(n, in_wid, kp_wid, h));                // keep_vec
@@ -1203,13 +1239,15 @@ struct LayerDebug {
 // gen_keep_vec_stride masks keep_idx[ul] of the context's ext_idx[step]: eval.go:522-531).
 // The images of a batch (ct_conv_dev.size() <= the bootstrapper's HCONV_IMAGE_BATCH) go through the tail as ONE set of launches; results in the same order.
 std::vector<BootCiphertext> evalConv_BNRelu_tail_batch(Boot *B, const std::string &kind, int log_sparse, const std::vector<const uint64_t *> &ct_conv_dev, double ct_scale, double alpha, double pow_, int in_wid, int kp_wid,
-                                                       const std::vector<std::vector<int>> *keep_idx, const std::string &mask_key) {
+                                                       const std::vector<std::vector<int>> *keep_idx, const std::string &mask_key, int pack_pos) {
     hc_ctx *hc = B->hc;
     // "TransConv" is the "Conv" tail and "TransConv_sparse" the "Conv_sparse" tail at log_sparse 2 (not reference kinds: the reference's TransConv stops at the convolution);
     // the caller passes kp_wid = 2 * raw_in_wid, and for the sparse kind a convolution whose output channels sit at slots 4*o (prep_Ker with ob_stride 4)
     const bool trans_sparse = kind == "TransConv_sparse";
     const bool stride = kind == "StrConv_sparse", sparse = kind == "Conv_sparse" || stride || trans_sparse, inside = kind == "Conv_inside" || kind == "StrConv_inside";
-    if (!sparse && !inside && kind != "Conv" && kind != "TransConv") panic("No kind!");
+    const bool stride_full = kind == "StrConv";                                                       // eval.go:303, 515-519: ext_ctxt with gen_comprs_full at pack_pos
+    if (!sparse && !inside && !stride_full && kind != "Conv" && kind != "TransConv") panic("No kind!");
+    if (pack_pos != 0 && !stride_full) panic("evalConv_BNRelu_tail: pack_pos is kind StrConv's");
     if (trans_sparse && log_sparse != 2) panic("TransConv_sparse runs at log_sparse 2 (a quarter of the channel slots live)");
     if (inside && (!keep_idx || keep_idx->size() != 2)) panic("evalConv_BNRelu_tail: the inside kinds keep with the context's ext_idx[step] (kind Resnet_crop_fast)");
     if (!sparse && log_sparse != 0) panic("No cases for log_sparse");
@@ -1239,7 +1277,7 @@ std::vector<BootCiphertext> evalConv_BNRelu_tail_batch(Boot *B, const std::strin
     std::unique_ptr<LayerDebug> dbg;
     if (debugLayers()) {
         const char *ck = testOnlyEnv("HCONV_DEBUG_LAYERS_CHECK");                                       // fatal outside test mode
-        dbg.reset(new LayerDebug{B, kind, log_sparse, nimg, in_wid, kp_wid, alpha, pow_, inside ? keep_idx : nullptr, ck && atoi(ck) != 0, {}, {}});
+        dbg.reset(new LayerDebug{B, kind, log_sparse, nimg, in_wid, kp_wid, alpha, pow_, inside ? keep_idx : nullptr, ck && atoi(ck) != 0, {}, {}, pack_pos});
         dbg->after_conv(ct);
     }
     if (prof) { HCR(hc_set_option(hc, "profile", 1)); hc_profile_get(hc, nullptr, nullptr, nullptr); }
@@ -1276,6 +1314,7 @@ std::vector<BootCiphertext> evalConv_BNRelu_tail_batch(Boot *B, const std::strin
     const std::string mk = std::to_string(in_wid) + "/" + std::to_string(kp_wid) + "/" + std::to_string(log_sparse);
     if (stride) for (int ul = 0; ul < iter; ul++) {                                                                                                                            // eval.go:500-506: m_idx / m_idx_l
         IdxMap m_idx, r_idx; gen_comprs_sparse(N / 2, in_wid, kp_wid, log_sparse, ul, m_idx, r_idx); keep[ul] = ext_double_ctxt(B, boots[ul], m_idx, r_idx, "comprs/" + mk + "/" + std::to_string(ul)); }
+    else if (stride_full) for (int ul = 0; ul < 2; ul++) keep[ul] = ext_ctxt_full(B, boots[ul], in_wid, kp_wid, pack_pos, ul);                                                    // eval.go:515-519
     else if (sparse && log_sparse) keep[0] = keep_ctxt(B, boots[0], gen_keep_vec_sparse(N / 2, in_wid, kp_wid, log_sparse), "keep/" + mk);                                         // eval.go:534
     else if (inside) for (int ul = 0; ul < 2; ul++) keep[ul] = keep_ctxt(B, boots[ul], (*keep_idx)[(size_t)ul], "keep_stride/" + mask_key + "/" + std::to_string(ul));            // eval.go:526-528
     // "Conv_sparse" on full packing (wide_case 3, block 1) keeps with gen_keep_vec per half, like "Conv" (main.go:155-156)
@@ -1298,7 +1337,7 @@ std::vector<BootCiphertext> evalConv_BNRelu_tail_batch(Boot *B, const std::strin
     return outs;
 }
 BootCiphertext evalConv_BNRelu_tail(Boot *B, const std::string &kind, int log_sparse, const uint64_t *ct_conv_dev, double ct_scale, double alpha, double pow_, int in_wid, int kp_wid) {
-    return evalConv_BNRelu_tail_batch(B, kind, log_sparse, {ct_conv_dev}, ct_scale, alpha, pow_, in_wid, kp_wid, nullptr, "")[0];
+    return evalConv_BNRelu_tail_batch(B, kind, log_sparse, {ct_conv_dev}, ct_scale, alpha, pow_, in_wid, kp_wid, nullptr, "", 0)[0];
 }
 // ---------------------------------------------------------------- baseline: Bootstrapp + ReLU (test_BL.go:113-168)
 Boot *newBootBL(const std::vector<int64_t> &sk, const Seed256 &seed, int device) {

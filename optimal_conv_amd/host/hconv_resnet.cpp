@@ -43,13 +43,13 @@ static std::string dur(std::chrono::steady_clock::time_point t0) {
 static std::chrono::steady_clock::time_point now() { return std::chrono::steady_clock::now(); }
 static double secs(std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); }
 static std::vector<Ciphertext> tail_of_conv(Context *cont, const std::string &kind, int log_sparse, std::vector<Ciphertext> &ct_conv, double alpha, double pow_, int in_wid, int kp_wid,
-                                            const std::vector<std::vector<int>> *keep_idx, const std::string &mask_key);
+                                            const std::vector<std::vector<int>> *keep_idx, const std::string &mask_key, int pack_pos = 0);
 
 // eval.go:272-607 for the kinds the conv / convReLU / resnet command lines reach, for the images of a batch (ct_inputs.size() <= HCONV_IMAGE_BATCH): every image
 // sees the operations of the reference's per-image flow, but a launch covers all of them (hc_conv_then_pack_batch; hc_set_batch inside the tail)
 std::vector<Ciphertext> evalConv_BNRelu_new_batch(Context *cont, const std::vector<Ciphertext> &ct_inputs, const std::vector<double> &ker_in, const std::vector<double> &bn_a,
                                                   const std::vector<double> &bn_b, double alpha, double pow_, int in_wid, int kp_wid, int ker_wid, int real_ib, int real_ob,
-                                                  int norm, int log_sparse, const std::string &kind, int step, int ib_stride) {
+                                                  int norm, int log_sparse, const std::string &kind, int step, int ib_stride, int pack_pos) {
     if (!cont->btp) panic("evalConv_BNRelu_new needs a context built with boot = true");
     const bool inside = kind == "Conv_inside" || kind == "StrConv_inside";
     if (ib_stride != 1 && !inside) panic("evalConv_BNRelu_new: ib_stride is for the inside kinds only");
@@ -76,7 +76,7 @@ std::vector<Ciphertext> evalConv_BNRelu_new_batch(Context *cont, const std::vect
             freeCt(cont, r2[(size_t)z]);
         }
         ct_conv = r1;
-    } else if (kind == "Conv_sparse" || kind == "Conv") {
+    } else if (kind == "Conv_sparse" || kind == "Conv" || kind == "StrConv") {                            // "StrConv": the stride is the tail's (eval.go:303, 515-519)
         ct_conv = evalConv_BN_batch(cont, ct_inputs, ker_in, bn_a, bn_b, in_wid, ker_wid, real_ib, real_ob, norm, out_scale, false);             // eval.go:433
     } else if (inside) {                                                                                  // eval.go:295-302, 418-431
         if (kind == "StrConv_inside" && step % 2 != 0) panic("step can not be divided by 2 (for strided conv)");
@@ -89,17 +89,17 @@ std::vector<Ciphertext> evalConv_BNRelu_new_batch(Context *cont, const std::vect
         if (it == cont->ext_idx.end()) panic("evalConv_BNRelu_new: no ext_idx for step " + std::to_string(step) + " (the inside kinds need a Resnet_crop_fast context)");
         keep_idx = &it->second;
     }
-    return tail_of_conv(cont, kind, log_sparse, ct_conv, alpha, pow_, in_wid, kp_wid, keep_idx, "step" + std::to_string(step));
+    return tail_of_conv(cont, kind, log_sparse, ct_conv, alpha, pow_, in_wid, kp_wid, keep_idx, "step" + std::to_string(step), pack_pos);
 }
 // the tail of a layer for the convolution results of one launch set (freed here), and its outputs as blocks of the convolution context
 static std::vector<Ciphertext> tail_of_conv(Context *cont, const std::string &kind, int log_sparse, std::vector<Ciphertext> &ct_conv, double alpha, double pow_, int in_wid, int kp_wid,
-                                            const std::vector<std::vector<int>> *keep_idx, const std::string &mask_key) {
+                                            const std::vector<std::vector<int>> *keep_idx, const std::string &mask_key, int pack_pos) {
     const int nimg = (int)ct_conv.size();
     // hand-over to the bootstrapper's context (its own stream): everything queued on the convolution context - the stride layers end on a product and an addition that
     // nothing has waited for - must be complete before the other stream reads ct_conv
     HCX(cont->hc, hc_sync(cont->hc));
     std::vector<const uint64_t *> conv_d; for (const Ciphertext &c : ct_conv) conv_d.push_back(c.d);
-    std::vector<BootCiphertext> r = evalConv_BNRelu_tail_batch(cont->btp, kind, log_sparse, conv_d, ct_conv[0].Scale, alpha, pow_, in_wid, kp_wid, keep_idx, mask_key);
+    std::vector<BootCiphertext> r = evalConv_BNRelu_tail_batch(cont->btp, kind, log_sparse, conv_d, ct_conv[0].Scale, alpha, pow_, in_wid, kp_wid, keep_idx, mask_key, pack_pos);
     for (Ciphertext &c : ct_conv) freeCt(cont, c);
     // [2][2][N] over (Q0, Q1): what the next convolution reads. The result blocks belong to the bootstrapper's context and go back to it; the layer's outputs are
     // blocks of the convolution context (a block released into a context that did not allocate it would leave the owner's block table pointing at memory it no longer
@@ -118,7 +118,7 @@ static std::vector<Ciphertext> tail_of_conv(Context *cont, const std::string &ki
 Ciphertext evalConv_BNRelu_new(Context *cont, const Ciphertext &ct_input, const std::vector<double> &ker_in, const std::vector<double> &bn_a,
                                const std::vector<double> &bn_b, double alpha, double pow_, int in_wid, int kp_wid, int ker_wid, int real_ib, int real_ob,
                                int norm, int log_sparse, const std::string &kind) {
-    return evalConv_BNRelu_new_batch(cont, {ct_input}, ker_in, bn_a, bn_b, alpha, pow_, in_wid, kp_wid, ker_wid, real_ib, real_ob, norm, log_sparse, kind, 1, 1)[0];
+    return evalConv_BNRelu_new_batch(cont, {ct_input}, ker_in, bn_a, bn_b, alpha, pow_, in_wid, kp_wid, ker_wid, real_ib, real_ob, norm, log_sparse, kind, 1, 1, 0)[0];
 }
 
 // main.go:920-939
@@ -282,6 +282,128 @@ static void testResNet_crop(int st, int end, int ker_wid, int depth, bool fast) 
 }
 void testResNet_crop_sparse(int st, int end, int ker_wid, int depth, bool debug) { (void)debug; testResNet_crop(st, end, ker_wid, depth, false); }
 void testResNet_crop_fast_in(int st, int end, int ker_wid, int depth, bool debug) { (void)debug; testResNet_crop(st, end, ker_wid, depth, true); }
+
+// ---------------------------------------------------------------- `imagenet ker n [c1]`: test.go:1209-1400 testImagenet_final_fast_in, the reference's ImageNet tail
+// Full packing throughout: three c1 -> c1 layers on the 16-grid (kind "Conv"), the stride-2 layer to 2 c1 channels on the 8-grid as two "StrConv" calls on the halves of the
+// output channels at pack_pos 0 and 1 and one addition, three 2 c1 -> 2 c1 layers, and the reduce-mean + FC head as one 7 x 7 convolution to 1000 classes whose plaintexts
+// come from hc_prep_ker_fc (the FC matrix is uploaded once, not once per tap). File names, the weight numbering (a layer's conv file is w<i>, its BN files w<i+1>: test.go:1293-1296),
+// widths, the pow schedule and the console lines are the reference's. c1 = 256 is the reference's network; a smaller c1 (not a reference feature) reads files of c1 / 2 c1
+// channels and zero-embeds them into the same 256 / 1024 channel slots, block-2 channel h c1 + j at slot 256 h + j - where the stride layer puts it. Same launches either way.
+void testImagenet_final_fast_in(int st, int end, int ker_wid, int c1) {
+    const std::string ker_name = "ker" + std::to_string(ker_wid), weight_dir = "weight_imgnet_" + ker_name + "_h5/", img_dir = ker_name + "_data/", out_dir = ker_name + "_enc_result/";
+    const int logN = 16, num_blc1 = 3, num_blc2 = 3, full_b1 = 256, full_b2 = 512, fin_out_batch = 1000;
+    const std::vector<int> raw_in_wids = {14, 7}, in_wids = {16, 8};
+    std::vector<int> kp_wids;
+    if (ker_wid == 3) kp_wids = {14, 7}; else if (ker_wid == 5) kp_wids = {14, 6}; else panic("strange ker name!");
+    if (c1 < 1 || c1 > full_b1) panic("imagenet: c1 not in 1..256");
+    const int real_batch[2] = {c1, 2 * c1}, ker_size = ker_wid * ker_wid, norm = 1;
+    Context *cont = newContext(logN, ker_wid, in_wids, kp_wids, true, "Imagenet_final_fast");
+    const int max_batch[2] = {N / (in_wids[0] * in_wids[0]), N / (in_wids[1] * in_wids[1])};
+    const double alpha = 0.0, init_pow = 6.0, mid_pow = 5.0, final_pow = 6.0;
+    mkdir(out_dir.c_str(), 0755);
+    auto W = [&](int i, const char *what, int size) { return readTxt(weight_dir + "w" + std::to_string(i) + "-" + what + ".csv", size); };
+    auto slot2 = [&](int ch) { return full_b1 * (ch / c1) + ch % c1; };                                    // block-2 channel -> channel slot
+    const int nbatch = imageBatch();
+    for (int g0 = st; g0 < end; g0 += nbatch) {
+        const int nimg = std::min(nbatch, end - g0);
+        int weight_num = 10;
+        std::vector<std::vector<double>> inputs((size_t)nimg, std::vector<double>((size_t)N, 0.0));
+        for (int z = 0; z < nimg; z++) {
+            printf("Start  %d -th iter..\n", g0 + z);
+            const std::vector<double> raw_input = readTxt(img_dir + "test_image_" + std::to_string(g0 + z) + ".csv", raw_in_wids[0] * raw_in_wids[0] * real_batch[0]);
+            for (int i = 0; i < raw_in_wids[0]; i++) for (int j = 0; j < raw_in_wids[0]; j++) for (int b = 0; b < real_batch[0]; b++)
+                inputs[(size_t)z][(size_t)(i * in_wids[0] * max_batch[0] + j * max_batch[0] + b)] = raw_input[(size_t)(i * raw_in_wids[0] * real_batch[0] + j * real_batch[0] + b)];
+        }
+        printf("vec size:  %d\n", N); printf("input width:  [%d %d]\n", raw_in_wids[0], raw_in_wids[1]);
+        printf("kernel width:  %d\n", ker_wid); printf("num batches:  [%d %d]\n", real_batch[0], real_batch[1]);
+        auto start = now();
+        std::vector<const std::vector<double> *> ptrs; for (auto &v : inputs) ptrs.push_back(&v);
+        std::vector<Ciphertext> ct_layer = EncryptCoeffsBatch(cont, ptrs, cont->ECD_LV, cont->scale);
+        printf("Encryption done in %s \n", dur(start).c_str());
+        double timings[4]; auto begin_start = now(); start = now();
+        auto step = [&](std::vector<Ciphertext> next) { for (Ciphertext &c : ct_layer) freeCt(cont, c); ct_layer = std::move(next); };
+
+        double pow_ = init_pow;                                                                          // Block 1
+        for (int i = 1; i <= num_blc1; i++) {
+            const std::vector<double> ker = W(weight_num, "conv", real_batch[0] * real_batch[0] * ker_size); weight_num++;
+            const std::vector<double> a = W(weight_num, "a", real_batch[0]), b = W(weight_num, "b", real_batch[0]);
+            if (i == num_blc1) pow_ = mid_pow;
+            step(evalConv_BNRelu_new_batch(cont, ct_layer, ker, a, b, alpha, pow_, in_wids[0], kp_wids[0], ker_wid, real_batch[0], real_batch[0], norm, 0, "Conv"));
+            printf("Block1, Layer  %d done!\n", i);
+        }
+        printf("Block1 done!\n"); timings[0] = secs(start); start = now();
+        {                                                                                                // block 1 to 2: the halves of the output channels at pack_pos 0 and 1
+            const std::vector<double> ker = W(weight_num, "conv", real_batch[0] * real_batch[1] * ker_size); weight_num++;
+            const std::vector<double> a = W(weight_num, "a", real_batch[1]), b = W(weight_num, "b", real_batch[1]);
+            std::vector<Ciphertext> half[2];
+            for (int h = 0; h < 2; h++) {
+                std::vector<double> kh(ker.size() / 2), ah((size_t)c1), bh((size_t)c1);
+                for (int k = 0; k < ker_size; k++) for (int i = 0; i < c1; i++) for (int j = 0; j < c1; j++) kh[(size_t)(k * c1 * c1 + i * c1 + j)] = ker[(size_t)(k * c1 * 2 * c1 + i * 2 * c1 + h * c1 + j)];
+                for (int j = 0; j < c1; j++) { ah[(size_t)j] = a[(size_t)(h * c1 + j)]; bh[(size_t)j] = b[(size_t)(h * c1 + j)]; }
+                half[h] = evalConv_BNRelu_new_batch(cont, ct_layer, kh, ah, bh, alpha, pow_, in_wids[0], 2 * kp_wids[1], ker_wid, c1, c1, norm, 0, "StrConv", 1, 1, h);
+            }
+            for (int z = 0; z < nimg; z++) {                                                             // AddNew (test.go:1336)
+                Ciphertext &x = half[0][(size_t)z], &y = half[1][(size_t)z];
+                if (x.level != y.level || x.Scale != y.Scale) panic("imagenet: the halves of the stride layer differ in level or scale");
+                const size_t poly = (size_t)(x.level + 1) * N;
+                HCX(cont->hc, hc_lv_op2(cont->hc, HC_LV_ADD, x.level, x.d, x.d + poly, y.d, y.d + poly, x.d, x.d + poly, nullptr));
+                freeCt(cont, y);
+            }
+            step(half[0]);
+        }
+        printf("Block1 to 2 done!\n"); timings[1] = secs(start); start = now();
+        for (int i = 1; i <= num_blc2; i++) {                                                            // Block 2, on all 512 channel slots of the layout
+            const std::vector<double> ker = W(weight_num, "conv", real_batch[1] * real_batch[1] * ker_size); weight_num++;
+            const std::vector<double> a = W(weight_num, "a", real_batch[1]), b = W(weight_num, "b", real_batch[1]);
+            std::vector<double> kf((size_t)ker_size * full_b2 * full_b2, 0.0), af((size_t)full_b2, 0.0), bf((size_t)full_b2, 0.0);
+            for (int k = 0; k < ker_size; k++) for (int ci = 0; ci < real_batch[1]; ci++) for (int co = 0; co < real_batch[1]; co++)
+                kf[((size_t)k * full_b2 + (size_t)slot2(ci)) * full_b2 + (size_t)slot2(co)] = ker[((size_t)k * real_batch[1] + ci) * real_batch[1] + co];
+            for (int co = 0; co < real_batch[1]; co++) { af[(size_t)slot2(co)] = a[(size_t)co]; bf[(size_t)slot2(co)] = b[(size_t)co]; }
+            if (i == num_blc2) pow_ = final_pow;
+            step(evalConv_BNRelu_new_batch(cont, ct_layer, kf, af, bf, alpha, pow_, in_wids[1], kp_wids[1], ker_wid, full_b2, full_b2, norm, 0, "Conv"));
+            printf("Block2, Layer  %d done!\n", i);
+        }
+        printf("Block2 done!\n"); timings[2] = secs(start); start = now();
+        std::vector<Ciphertext> ct_result((size_t)nimg);                                                 // RMFC (test.go:1359-1384): bn_a = the mean's factor, no bias
+        {
+            const std::vector<double> fc = readTxt(weight_dir + "fc.csv", real_batch[1] * fin_out_batch);
+            std::vector<double> fcf((size_t)full_b2 * fin_out_batch, 0.0);
+            for (int ci = 0; ci < real_batch[1]; ci++) std::copy(fc.begin() + (long)ci * fin_out_batch, fc.begin() + (long)(ci + 1) * fin_out_batch, fcf.begin() + (long)slot2(ci) * fin_out_batch);
+            const std::vector<double> bn_af((size_t)fin_out_batch, ker_wid == 3 ? 1.0 / (7 * 7) : 1.0 / (6 * 6));
+            const double out_scale = (double)(1 << 30);
+            auto t0 = now();
+            KerPlain pl_ker; pl_ker.max_bat = max_batch[1]; pl_ker.Scale = cont->scale;
+            HCX(cont->hc, hc_prep_ker_fc(cont->hc, fcf.data(), bn_af.data(), in_wids[1], 7, full_b2, fin_out_batch, norm, cont->scale, 1, &pl_ker.h));
+            HCX(cont->hc, hc_sync(cont->hc));
+            printf("Plaintext (kernel) preparation, Done in %s \n", dur(t0).c_str());
+            t0 = now();
+            if (nimg == 1) ct_result[0] = conv_then_pack(cont, ct_layer[0], pl_ker, max_batch[1], norm, cont->ECD_LV, out_scale, nullptr);
+            else {
+                std::vector<const uint64_t *> ins; std::vector<const hc_ker *> kers((size_t)nimg, pl_ker.h); std::vector<uint64_t *> outs; double sc = 0;
+                for (int z = 0; z < nimg; z++) { void *v = nullptr; HCX(cont->hc, hc_malloc(cont->hc, (size_t)2 * N * 8, &v)); ct_result[(size_t)z].d = (uint64_t *)v; ct_result[(size_t)z].level = 0; ins.push_back(ct_layer[(size_t)z].d); outs.push_back(ct_result[(size_t)z].d); }
+                HCX(cont->hc, hc_conv_then_pack_batch(cont->hc, nimg, ins.data(), ct_layer[0].Scale, kers.data(), pl_ker.Scale, max_batch[1], norm, out_scale, nullptr, outs.data(), &sc));
+                HCX(cont->hc, hc_sync(cont->hc));
+                for (Ciphertext &c : ct_result) c.Scale = sc;
+            }
+            if (nimg > 1) printf("Conv (with BN) Done in %s  (%d images)\n", dur(t0).c_str(), nimg); else printf("Conv (with BN) Done in %s \n", dur(t0).c_str());
+            hc_ker_free(cont->hc, pl_ker.h);
+        }
+        timings[3] = secs(start);
+        for (int z = 0; z < nimg; z++) {
+            start = now();
+            std::vector<double> res_tmp = DecryptDecodeCoeffs(cont, ct_result[(size_t)z]);
+            printf("Decryption done in %s \n", dur(start).c_str());
+            std::vector<double> final_result = prt_mat_one_norm(res_tmp, max_batch[1], 1, 4, 4);        // cell (3, 3) of the 8-grid: the centre of the 7 x 7 window
+            final_result.resize((size_t)fin_out_batch);
+            writeTxt(out_dir + "enc_result_" + std::to_string(g0 + z) + ".csv", final_result);
+            freeCt(cont, ct_layer[(size_t)z]); freeCt(cont, ct_result[(size_t)z]);
+        }
+        printf("Blc1:  %g  sec\nBlc1->2:  %g  sec\nBlc2:  %g  sec\nFinal (reduce_mean & FC):  %g  sec\n", timings[0], timings[1], timings[2], timings[3]);
+        printf("Total done in %s \n", dur(begin_start).c_str());                                       // test.go:1398
+        if (nimg > 1) printf("(%d images of one launch set)\n", nimg);
+    }
+    freeContext(cont);
+}
 
 // ---------------------------------------------------------------- `resnet_packed` (not a reference command): the network of `resnet_fast` with every coefficient in use
 // The layout, the slot assignment (packed_slot) and the expanded kernels are stated in hconv_host.hpp; DESIGN.md "The packed layout" says why the stride layers merge after the mask.
