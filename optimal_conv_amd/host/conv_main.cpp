@@ -31,9 +31,35 @@
 // `conv --test-mode <args>` honours the test-only overrides HCONV_SEED / HCONV_CHAIN_REPLAY; without the flag they are fatal when set.
 #include <stdio.h>
 #include <stdlib.h>
+
+#include <initializer_list>
 #include <string>
 
 #include "hconv_host.hpp"
+
+// `<name> <ker_wid> <depth> <wide_case> <test_num> <cf100>` of the three resnet commands (main.go:609-621's argument handling), refused before any device work
+struct ResnetArgs { int depth, test_num; };
+static ResnetArgs resnet_args(const std::string &name, int argc, char **argv) {
+    if (argc < 7) hconv::panic("runtime error: index out of range (usage: " + name + " <ker_wid> <depth> <wide_case> <test_num> <cf100>)");
+    const int depth = atoi(argv[3]), wide_case = atoi(argv[4]), test_num = atoi(argv[5]);
+    const bool cf100 = std::string(argv[6]) == "true" || std::string(argv[6]) == "1";
+    if (wide_case < 1 || wide_case > 3) hconv::panic("Wrong wide case!");                                  // main.go:628
+    // BASELINE config 5 is `resnet 3 20 1 n false`; the wide networks and the CIFAR-100 head are outside the scope table and not built
+    if (wide_case != 1 || cf100) hconv::panic(name + ": wide_case 2 / 3 and cf100 = true are out of scope in this build (SURVEY.md section 2, row 14)");
+    return {depth, test_num};
+}
+static void check_depth(int depth) { if (!(depth == 8 || depth == 14 || depth == 20)) hconv::panic("wrong depth (not in 8, 14, 20)!"); }   // test.go:397-405
+// a command that cannot honour these switches refuses them when they are set (to anything but 0)
+static void refuse_env(const std::string &name, std::initializer_list<const char *> vars, const char *why) {
+    for (const char *v : vars) if (getenv(v) && *getenv(v) && std::string(getenv(v)) != "0") hconv::panic(name + ": " + v + " " + why);
+}
+static const std::initializer_list<const char *> REPLAYS = {"HCONV_RESNET_REPLAY", "HCONV_CHAIN_REPLAY", "HCONV_CHAIN_REPLAY_BL"};
+static const char *const PINNED = "replays a pinned run of another command and is not available here";
+// main.go:583-585's bounds of the layer commands, and the index Go would panic on
+static void check_layer_args(int num_tests, int i_batch) {
+    if (num_tests > 10 || i_batch > 3) hconv::panic("Too many tests (>10) or too many batch index (>3)");
+    if (i_batch < 0) hconv::panic("runtime error: index out of range");
+}
 
 int main(int argc, char **argv) {
     if (argc > 1 && std::string(argv[1]) == "--test-mode") {      // not a reference feature: enables HCONV_SEED / HCONV_CHAIN_REPLAY (hconv_host.hpp)
@@ -47,8 +73,7 @@ int main(int argc, char **argv) {
         if (!(ker == 3 || ker == 5)) hconv::panic("strange ker name!");                                    // test.go:1236
         if (test_num < 1) hconv::panic("imagenet: test_num must be at least 1");
         if (c1 < 1 || c1 > 256) hconv::panic("imagenet: c1 not in 1..256");
-        for (const char *v : {"HCONV_RESNET_REPLAY", "HCONV_CHAIN_REPLAY", "HCONV_CHAIN_REPLAY_BL"})
-            if (getenv(v) && *getenv(v) && std::string(getenv(v)) != "0") hconv::panic(std::string("imagenet: ") + v + " replays a pinned run of another command and is not available here");
+        refuse_env("imagenet", REPLAYS, PINNED);
         setenv("HCONV_ASYNC_ALLOC", "1", 0);                                                               // a chain command (see below)
         hconv::testImagenet_final_fast_in(0, test_num, ker, c1);
         return 0;
@@ -60,95 +85,61 @@ int main(int argc, char **argv) {
     if (test_name == "convReLU" || test_name == "resnet" || test_name == "resnet_fast" || test_name == "resnet_packed" || test_name == "transconvReLU" || test_name == "multiconvReLU" || test_name == "strconvReLU") setenv("HCONV_ASYNC_ALLOC", "1", 0);
     const int ker_wid = atoi(argv[2]), i_batch = atoi(argv[3]), num_tests = atoi(argv[4]);
     if (!(ker_wid == 3 || ker_wid == 5 || ker_wid == 7)) hconv::panic("Wrong kernel wid (not in 3,5,7)");
-    if (test_name == "resnet_fast") {                                    // not a reference command (see the top of this file); main.go:609-621's argument handling
-        if (argc < 7) hconv::panic("runtime error: index out of range (usage: resnet_fast <ker_wid> <depth> <wide_case> <test_num> <cf100>)");
-        const int depth = atoi(argv[3]), wide_case = atoi(argv[4]), test_num = atoi(argv[5]);
-        const bool cf100 = std::string(argv[6]) == "true" || std::string(argv[6]) == "1";
-        if (wide_case < 1 || wide_case > 3) hconv::panic("Wrong wide case!");                              // main.go:628
-        if (wide_case != 1 || cf100) hconv::panic("resnet_fast: wide_case 2 / 3 and cf100 = true are out of scope in this build (SURVEY.md section 2, row 14)");
-        if (!(depth == 8 || depth == 14 || depth == 20)) hconv::panic("wrong depth (not in 8, 14, 20)!");  // test.go:397-405, before any device work
-        hconv::testResNet_crop_fast_in(0, test_num, ker_wid, depth, false);
+    if (test_name == "resnet" || test_name == "resnet_fast") {             // main.go:609-621: resnet ker depth wide_case test_num cf100; resnet_fast: not a reference command (see the top of this file)
+        const ResnetArgs a = resnet_args(test_name, argc, argv);
+        check_depth(a.depth);
+        if (test_name == "resnet") hconv::testResNet_crop_sparse(0, a.test_num, ker_wid, a.depth, false);
+        else hconv::testResNet_crop_fast_in(0, a.test_num, ker_wid, a.depth, false);
         return 0;
     }
     if (test_name == "resnet_packed") {                                  // not a reference command (see the top of this file); resnet_fast's arguments
-        if (argc < 7) hconv::panic("runtime error: index out of range (usage: resnet_packed <ker_wid> <depth> <wide_case> <test_num> <cf100>)");
-        const int depth = atoi(argv[3]), wide_case = atoi(argv[4]), test_num = atoi(argv[5]);
-        const bool cf100 = std::string(argv[6]) == "true" || std::string(argv[6]) == "1";
-        if (wide_case < 1 || wide_case > 3) hconv::panic("Wrong wide case!");
-        if (wide_case != 1 || cf100) hconv::panic("resnet_packed: wide_case 2 / 3 and cf100 = true are out of scope in this build (SURVEY.md section 2, row 14)");
+        const ResnetArgs a = resnet_args(test_name, argc, argv);
         if (ker_wid == 5) hconv::panic("resnet_packed: kernel width 5 is not packed: its even keep widths 30, 14, 6 put the first kept position at step - 1, not 0 "
                                        "(and that network differs from the plain model anyway); use 3 or 7");
-        if (!(depth == 8 || depth == 14 || depth == 20)) hconv::panic("wrong depth (not in 8, 14, 20)!");
+        check_depth(a.depth);
         // the replays' and the per-stage report's shadows know one image per ciphertext
-        for (const char *v : {"HCONV_RESNET_REPLAY", "HCONV_CHAIN_REPLAY", "HCONV_CHAIN_REPLAY_BL", "HCONV_DEBUG_LAYERS"})
-            if (getenv(v) && *getenv(v) && std::string(getenv(v)) != "0") hconv::panic(std::string("resnet_packed: ") + v + " follows one image per ciphertext and is not available here");
+        refuse_env(test_name, {"HCONV_RESNET_REPLAY", "HCONV_CHAIN_REPLAY", "HCONV_CHAIN_REPLAY_BL", "HCONV_DEBUG_LAYERS"}, "follows one image per ciphertext and is not available here");
         hconv::testOnlyEnv("HCONV_PACKED_DUMP_LAYERS");                    // fatal without --test-mode, before any device work
-        hconv::testResNet_crop_packed(0, test_num, ker_wid, depth);
+        hconv::testResNet_crop_packed(0, a.test_num, ker_wid, a.depth);
         return 0;
     }
-    bool boot = false;
-    if (test_name == "conv") {
-        if (num_tests > 10 || i_batch > 3) hconv::panic("Too many tests (>10) or too many batch index (>3)");
-    } else if (test_name == "convReLU") {
-        boot = true;
-        if (num_tests > 10 || i_batch > 3) hconv::panic("Too many tests (>10) or too many batch index (>3)");
-    } else if (test_name == "resnet") {                                   // main.go:609-621: resnet ker depth wide_case test_num cf100
-        if (argc < 7) hconv::panic("runtime error: index out of range (usage: resnet <ker_wid> <depth> <wide_case> <test_num> <cf100>)");
-        const int depth = atoi(argv[3]), wide_case = atoi(argv[4]), test_num = atoi(argv[5]);
-        const bool cf100 = std::string(argv[6]) == "true" || std::string(argv[6]) == "1";
-        if (wide_case < 1 || wide_case > 3) hconv::panic("Wrong wide case!");                              // main.go:628
-        // BASELINE config 5 is `resnet 3 20 1 n false`; the wide networks and the CIFAR-100 head are outside the scope table and not built
-        if (wide_case != 1 || cf100) hconv::panic("resnet: wide_case 2 / 3 and cf100 = true are out of scope in this build (SURVEY.md section 2, row 14)");
-        hconv::testResNet_crop_sparse(0, test_num, ker_wid, depth, false);
-        return 0;
-    } else if (test_name == "transconv" || test_name == "transconvReLU") {   // not reference commands (see the top of this file)
-        const bool relu = test_name == "transconvReLU";
-        if (num_tests > 10 || i_batch > 3) hconv::panic("Too many tests (>10) or too many batch index (>3)");
-        if (i_batch < 0) hconv::panic("runtime error: index out of range");
+    if (test_name != "conv" && test_name != "convReLU" && test_name != "transconv" && test_name != "transconvReLU" && test_name != "strconvReLU" && test_name != "multiconv" && test_name != "multiconvReLU")
+        hconv::panic("wrong test type");
+    const bool relu = test_name == "convReLU" || test_name == "transconvReLU" || test_name == "multiconvReLU";
+    auto banner = [&](const char *line) { printf("%s\n", line); printf("Ker:  %d batches:  %d widths:  %d\n", ker_wid, batchs[i_batch], widths[i_batch]); };
+    if (test_name == "transconv" || test_name == "transconvReLU") {        // not reference commands (see the top of this file)
+        check_layer_args(num_tests, i_batch);
         bool sparse = false;
         if (relu && argc > 5) { if (std::string(argv[5]) != "sparse") hconv::panic("transconvReLU: the optional fourth argument is `sparse`"); sparse = true; }
-        if (relu) printf("Transposed convolution followed by ReLU (& Bootstrapping) test start!\n");
-        else printf("Transposed convolution test start! (No Bootstrapping)\n");
-        printf("Ker:  %d batches:  %d widths:  %d\n", ker_wid, batchs[i_batch], widths[i_batch]);
+        banner(relu ? "Transposed convolution followed by ReLU (& Bootstrapping) test start!" : "Transposed convolution test start! (No Bootstrapping)");
         printf("Ours start.\n");
         hconv::testTransConv_in(batchs[i_batch], widths[i_batch], ker_wid, num_tests, relu, sparse);
-        return 0;
     } else if (test_name == "strconvReLU") {                                // not a reference command (see the top of this file)
         if (argc > 6) hconv::panic("strconvReLU: at most one optional argument, the pack position");
-        if (num_tests > 10 || i_batch > 3) hconv::panic("Too many tests (>10) or too many batch index (>3)");
-        if (i_batch < 0) hconv::panic("runtime error: index out of range");
+        check_layer_args(num_tests, i_batch);
         const int pos = argc > 5 ? atoi(argv[5]) : 0;
         if (pos < 0 || pos > 3 || (argc > 5 && (argv[5][0] < '0' || argv[5][0] > '3' || argv[5][1]))) hconv::panic("strconvReLU: the pack position is 0..3");
         if (widths[i_batch] % 4 != 0) hconv::panic("input wid not divisible by 4");
-        for (const char *v : {"HCONV_RESNET_REPLAY", "HCONV_CHAIN_REPLAY", "HCONV_CHAIN_REPLAY_BL"})
-            if (getenv(v) && *getenv(v) && std::string(getenv(v)) != "0") hconv::panic(std::string("strconvReLU: ") + v + " replays a pinned run of another command and is not available here");
-        printf("Stride-2 convolution followed by ReLU (& Bootstrapping) on full packing test start!\n");
-        printf("Ker:  %d batches:  %d widths:  %d\n", ker_wid, batchs[i_batch], widths[i_batch]);
+        refuse_env(test_name, REPLAYS, PINNED);
+        banner("Stride-2 convolution followed by ReLU (& Bootstrapping) on full packing test start!");
         printf("Ours start.\n");
         hconv::testStrConv_in(batchs[i_batch], widths[i_batch], ker_wid, num_tests, pos);
-        return 0;
     } else if (test_name == "multiconv" || test_name == "multiconvReLU") {   // not reference commands (see the top of this file)
-        const bool relu = test_name == "multiconvReLU";
         if (argc < 6) hconv::panic(std::string("runtime error: index out of range (usage: ") + test_name + " <ker_wid> <i_batch> <num_tests> <n_in>)");
-        if (num_tests > 10 || i_batch > 3) hconv::panic("Too many tests (>10) or too many batch index (>3)");
-        if (i_batch < 0) hconv::panic("runtime error: index out of range");
+        check_layer_args(num_tests, i_batch);
         const int n_in = atoi(argv[5]);
         if (n_in < 1 || n_in > 16) hconv::panic("Wrong number of input ciphertexts (not in 1..16)");
-        if (relu) printf("Multi-input convolution followed by ReLU (& Bootstrapping) test start!\n");
-        else printf("Multi-input convolution test start! (No Bootstrapping)\n");
-        printf("Ker:  %d batches:  %d widths:  %d\n", ker_wid, batchs[i_batch], widths[i_batch]);
+        banner(relu ? "Multi-input convolution followed by ReLU (& Bootstrapping) test start!" : "Multi-input convolution test start! (No Bootstrapping)");
         printf("Ours start.\n");
         hconv::testMultiConv_in(batchs[i_batch], widths[i_batch], ker_wid, num_tests, n_in, relu);
-        return 0;
-    } else hconv::panic("wrong test type");
-    if (i_batch < 0) hconv::panic("runtime error: index out of range");
-    if (boot) printf("Convolution followed by ReLU (& Bootstrapping) test start!\n");
-    else printf("Convolution test start! (No Bootstrapping)\n");
-    printf("Ker:  %d batches:  %d widths:  %d\n", ker_wid, batchs[i_batch], widths[i_batch]);
-    printf("Base Line start.\n");
-    if (getenv("HCONV_SKIP_BL") && atoi(getenv("HCONV_SKIP_BL"))) printf("(HCONV_SKIP_BL set: baseline skipped)\n");
-    else hconv::testConv_BL_in(batchs[i_batch], widths[i_batch], ker_wid, num_tests, boot);
-    printf("Ours start.\n");
-    hconv::testConv_in(batchs[i_batch], widths[i_batch], ker_wid, num_tests, boot);
+    } else {                                                                // conv, convReLU: the baseline, then Ours (main.go:639-643)
+        check_layer_args(num_tests, i_batch);
+        banner(relu ? "Convolution followed by ReLU (& Bootstrapping) test start!" : "Convolution test start! (No Bootstrapping)");
+        printf("Base Line start.\n");
+        if (getenv("HCONV_SKIP_BL") && atoi(getenv("HCONV_SKIP_BL"))) printf("(HCONV_SKIP_BL set: baseline skipped)\n");
+        else hconv::testConv_BL_in(batchs[i_batch], widths[i_batch], ker_wid, num_tests, relu);
+        printf("Ours start.\n");
+        hconv::testConv_in(batchs[i_batch], widths[i_batch], ker_wid, num_tests, relu);
+    }
     return 0;
 }

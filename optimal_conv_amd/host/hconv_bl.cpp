@@ -32,20 +32,7 @@
 
 namespace hconv {
 
-#define HCB(c, call) do { int rc_ = (call); if (rc_) panic(std::string(#call) + ": " + hc_last_error(c)); } while (0)
-
 static const uint64_t BLQ[4] = {0x80000000080001ull, 0x10000000006e0001ull, 0x1fffffffffe00001ull, 0x1fffffffffc80001ull};   // Q0, Q1 of set [7]; P0, P1
-static inline uint64_t mulmod(uint64_t a, uint64_t b, uint64_t q) { return (uint64_t)(((u128)a * b) % q); }
-static inline uint64_t addmod(uint64_t a, uint64_t b, uint64_t q) { uint64_t r = a + b; return r >= q ? r - q : r; }
-static inline uint64_t submod(uint64_t a, uint64_t b, uint64_t q) { return a >= b ? a - b : a + q - b; }
-static inline uint64_t to_mont(uint64_t a, uint64_t q) { return (uint64_t)((((u128)a) << 64) % q); }
-static std::string dur(std::chrono::steady_clock::time_point t0) {
-    double ns = (double)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count();
-    char b[64];
-    if (ns < 1e6) snprintf(b, sizeof b, "%.6gµs", ns / 1e3); else if (ns < 1e9) snprintf(b, sizeof b, "%.9gms", ns / 1e6); else snprintf(b, sizeof b, "%.9gs", ns / 1e9);
-    return b;
-}
-static std::chrono::steady_clock::time_point now() { return std::chrono::steady_clock::now(); }
 
 struct BLContext {
     hc_ctx *hc = nullptr;
@@ -63,11 +50,11 @@ struct BLContext {
 };
 struct BLCt { uint64_t *d = nullptr; double Scale = 0; };     // level-1 ciphertext: device [poly 2][limb 2][N]
 
-static uint64_t *bl_rows(BLContext *c, size_t rows) { void *p = nullptr; HCB(c->hc, hc_malloc(c->hc, rows * N * 8, &p)); return (uint64_t *)p; }
+static uint64_t *bl_rows(BLContext *c, size_t rows) { void *p = nullptr; HC(c->hc, hc_malloc(c->hc, rows * N * 8, &p)); return (uint64_t *)p; }
 static std::vector<uint64_t> bl_ntt(BLContext *c, int mod, std::vector<uint64_t> rows, bool inverse = false) {
-    uint64_t *d = bl_rows(c, rows.size() / N); HCB(c->hc, hc_upload(c->hc, d, rows.data(), rows.size() * 8));
-    HCB(c->hc, inverse ? hc_intt(c->hc, mod, d, d, (int)(rows.size() / N)) : hc_ntt(c->hc, mod, d, d, (int)(rows.size() / N)));
-    HCB(c->hc, hc_download(c->hc, rows.data(), d, rows.size() * 8)); HCB(c->hc, hc_free(c->hc, d));
+    uint64_t *d = bl_rows(c, rows.size() / N); HC(c->hc, hc_upload(c->hc, d, rows.data(), rows.size() * 8));
+    HC(c->hc, inverse ? hc_intt(c->hc, mod, d, d, (int)(rows.size() / N)) : hc_ntt(c->hc, mod, d, d, (int)(rows.size() / N)));
+    HC(c->hc, hc_download(c->hc, rows.data(), d, rows.size() * 8)); HC(c->hc, hc_free(c->hc, d));
     return rows;
 }
 static std::vector<uint64_t> signed_row(const std::vector<int64_t> &v, uint64_t q) {
@@ -109,30 +96,30 @@ static void bl_gen_key(BLContext *c, uint64_t galEl) {
             rows[((size_t)0 * 4 + T) * N + j] = to_mont(v, q); rows[((size_t)1 * 4 + T) * N + j] = to_mont(a[(size_t)j], q);
         }
     }
-    HCB(c->hc, hc_swk_load(c->hc, galEl, 1, rows.data()));
+    HC(c->hc, hc_swk_load(c->hc, galEl, 1, rows.data()));
     c->keys.insert(galEl);
 }
 
 // ---------------------------------------------------------------- level-1 evaluator ops on the C ABI
 static BLCt bl_alloc(BLContext *c, double scale) { BLCt r; r.d = bl_rows(c, 4); r.Scale = scale; return r; }
-static void bl_free(BLContext *c, BLCt &ct) { if (ct.d) HCB(c->hc, hc_free(c->hc, ct.d)); ct.d = nullptr; }
+static void bl_free(BLContext *c, BLCt &ct) { if (ct.d) HC(c->hc, hc_free(c->hc, ct.d)); ct.d = nullptr; }
 static BLCt MulNew(BLContext *c, const BLCt &ct, const uint64_t *pt, double pt_scale) {           // conv.go:168,170
     BLCt r = bl_alloc(c, ct.Scale * pt_scale);
-    for (int p = 0; p < 2; p++) for (int l = 0; l < 2; l++) HCB(c->hc, hc_mul(c->hc, l, ct.d + ((size_t)p * 2 + l) * N, pt + (size_t)l * N, r.d + ((size_t)p * 2 + l) * N, 1));
+    for (int p = 0; p < 2; p++) for (int l = 0; l < 2; l++) HC(c->hc, hc_mul(c->hc, l, ct.d + ((size_t)p * 2 + l) * N, pt + (size_t)l * N, r.d + ((size_t)p * 2 + l) * N, 1));
     return r;
 }
 static void Add(BLContext *c, const BLCt &a, const BLCt &b, BLCt &out) {                             // conv.go:171, eval.go:123
-    for (int p = 0; p < 2; p++) for (int l = 0; l < 2; l++) HCB(c->hc, hc_add(c->hc, l, a.d + ((size_t)p * 2 + l) * N, b.d + ((size_t)p * 2 + l) * N, out.d + ((size_t)p * 2 + l) * N, 1));
+    for (int p = 0; p < 2; p++) for (int l = 0; l < 2; l++) HC(c->hc, hc_add(c->hc, l, a.d + ((size_t)p * 2 + l) * N, b.d + ((size_t)p * 2 + l) * N, out.d + ((size_t)p * 2 + l) * N, 1));
 }
 static BLCt RotateNew(BLContext *c, const BLCt &ct, int k) {       // evaluator.RotateNew -> permuteNTT: key switch c1, + c0, permute both
     const uint64_t gal = gal_for_rotation(k);
     BLCt r = bl_alloc(c, ct.Scale);
-    if (gal == 1) { HCB(c->hc, hc_copy(c->hc, r.d, ct.d, (size_t)4 * N * 8)); return r; }
+    if (gal == 1) { HC(c->hc, hc_copy(c->hc, r.d, ct.d, (size_t)4 * N * 8)); return r; }
     uint64_t *d = bl_rows(c, 4);                                   // d0[2 limbs] | d1[2 limbs]
-    HCB(c->hc, hc_keyswitch(c->hc, gal, 1, ct.d + (size_t)2 * N, d, d + (size_t)2 * N));
-    for (int l = 0; l < 2; l++) HCB(c->hc, hc_add(c->hc, l, d + (size_t)l * N, ct.d + (size_t)l * N, d + (size_t)l * N, 1));
-    HCB(c->hc, hc_permute(c->hc, gal, d, r.d, 4));
-    HCB(c->hc, hc_free(c->hc, d));
+    HC(c->hc, hc_keyswitch(c->hc, gal, 1, ct.d + (size_t)2 * N, d, d + (size_t)2 * N));
+    for (int l = 0; l < 2; l++) HC(c->hc, hc_add(c->hc, l, d + (size_t)l * N, ct.d + (size_t)l * N, d + (size_t)l * N, 1));
+    HC(c->hc, hc_permute(c->hc, gal, d, r.d, 4));
+    HC(c->hc, hc_free(c->hc, d));
     return r;
 }
 
@@ -167,18 +154,18 @@ static std::vector<double> post_process_BL(const std::vector<double> &in_vals, i
 // conv.go:120-143: evaluator.RotateHoisted of the input by every kernel offset: one digit decomposition of c1 for all of them
 static std::vector<BLCt> preConv_BL(BLContext *c, const BLCt &ct_in, int in_wid, int ker_wid) {
     std::vector<BLCt> rots; const int st = -(ker_wid / 2), end = ker_wid / 2;
-    HCB(c->hc, hc_keyswitch_decompose(c->hc, 1, ct_in.d + (size_t)2 * N));
+    HC(c->hc, hc_keyswitch_decompose(c->hc, 1, ct_in.d + (size_t)2 * N));
     uint64_t *d = bl_rows(c, 4);
     for (int i = st; i <= end; i++) for (int j = st; j <= end; j++) {
         const uint64_t gal = gal_for_rotation(i * in_wid + j);
         BLCt r = bl_alloc(c, ct_in.Scale);
-        if (gal == 1) { HCB(c->hc, hc_copy(c->hc, r.d, ct_in.d, (size_t)4 * N * 8)); rots.push_back(r); continue; }
-        HCB(c->hc, hc_keyswitch_hoisted(c->hc, gal, 1, ct_in.d + (size_t)2 * N, d, d + (size_t)2 * N));
-        for (int l = 0; l < 2; l++) HCB(c->hc, hc_add(c->hc, l, d + (size_t)l * N, ct_in.d + (size_t)l * N, d + (size_t)l * N, 1));
-        HCB(c->hc, hc_permute(c->hc, gal, d, r.d, 4));
+        if (gal == 1) { HC(c->hc, hc_copy(c->hc, r.d, ct_in.d, (size_t)4 * N * 8)); rots.push_back(r); continue; }
+        HC(c->hc, hc_keyswitch_hoisted(c->hc, gal, 1, ct_in.d + (size_t)2 * N, d, d + (size_t)2 * N));
+        for (int l = 0; l < 2; l++) HC(c->hc, hc_add(c->hc, l, d + (size_t)l * N, ct_in.d + (size_t)l * N, d + (size_t)l * N, 1));
+        HC(c->hc, hc_permute(c->hc, gal, d, r.d, 4));
         rots.push_back(r);
     }
-    HCB(c->hc, hc_free(c->hc, d));
+    HC(c->hc, hc_free(c->hc, d));
     return rots;
 }
 // conv.go:146-178 for one output rotation. The k^2 plaintexts of a rotation are built ON THE DEVICE: hc_bl_post_ker_slots writes the slot
@@ -187,12 +174,12 @@ static std::vector<BLCt> preConv_BL(BLContext *c, const BLCt &ct_in, int in_wid,
 // with the oracle that is pinned to the reference binary's own Encode digests).
 static BLCt postConv_BL(BLContext *c, const std::vector<BLCt> &ct_in_rots, int in_wid, int ker_wid, int rot, int pad, const double *d_max_ker_rs, int max_batch, double *d_slots, uint64_t *d_pl) {
     const int taps = ker_wid * ker_wid;
-    HCB(c->hc, hc_bl_post_ker_slots(c->hc, d_max_ker_rs, in_wid, ker_wid, pad, max_batch, rot, d_slots));
-    HCB(c->hc, hc_encode_slots(c->hc, d_slots, taps, 1, c->scale, 1, d_pl));                              // conv.go:165-166 for every tap
+    HC(c->hc, hc_bl_post_ker_slots(c->hc, d_max_ker_rs, in_wid, ker_wid, pad, max_batch, rot, d_slots));
+    HC(c->hc, hc_encode_slots(c->hc, d_slots, taps, 1, c->scale, 1, d_pl));                              // conv.go:165-166 for every tap
     BLCt ct_out = bl_alloc(c, ct_in_rots[0].Scale * c->scale);                                             // conv.go:167-172: MulNew per tap, Add
     std::vector<const uint64_t *> cts((size_t)taps);
     for (int it = 0; it < taps; it++) cts[(size_t)it] = ct_in_rots[(size_t)it].d;
-    HCB(c->hc, hc_lv_mul_sum(c->hc, 1, cts.data(), d_pl, taps, ct_out.d));
+    HC(c->hc, hc_lv_mul_sum(c->hc, 1, cts.data(), d_pl, taps, ct_out.d));
     return ct_out;
 }
 static BLCt evalConv_BN_BL_test(BLContext *c, const Encoder &enc, const BLCt &ct_input, const std::vector<double> &ker_in, const std::vector<double> &bn_a,
@@ -207,16 +194,16 @@ static BLCt evalConv_BN_BL_test(BLContext *c, const Encoder &enc, const BLCt &ct
         bn_b_slots[(size_t)(j + k * in_wid + norm * out_size * (int)i)] = cplx(bn_b[i], 0);             // eval.go:93-99
     uint64_t *pl_bn_b = bl_rows(c, 2);
     const int taps = ker_wid * ker_wid;
-    void *vp = nullptr; HCB(c->hc, hc_malloc(c->hc, (size_t)taps * (N / 2) * 16, &vp)); double *d_slots = (double *)vp;     // [taps][N/2] complex128
-    HCB(c->hc, hc_malloc(c->hc, max_ker_rs.size() * sizeof(double), &vp)); double *d_ker = (double *)vp;
-    HCB(c->hc, hc_upload(c->hc, d_ker, max_ker_rs.data(), max_ker_rs.size() * sizeof(double)));
+    void *vp = nullptr; HC(c->hc, hc_malloc(c->hc, (size_t)taps * (N / 2) * 16, &vp)); double *d_slots = (double *)vp;     // [taps][N/2] complex128
+    HC(c->hc, hc_malloc(c->hc, max_ker_rs.size() * sizeof(double), &vp)); double *d_ker = (double *)vp;
+    HC(c->hc, hc_upload(c->hc, d_ker, max_ker_rs.data(), max_ker_rs.size() * sizeof(double)));
     uint64_t *d_pl = bl_rows(c, (size_t)taps * 2);
-    HCB(c->hc, hc_upload(c->hc, d_slots, bn_b_slots.data(), bn_b_slots.size() * 16));
-    HCB(c->hc, hc_encode_slots(c->hc, d_slots, 1, 1, scale_exp, 1, pl_bn_b));                                          // eval.go:101-102 EncodeNTT
+    HC(c->hc, hc_upload(c->hc, d_slots, bn_b_slots.data(), bn_b_slots.size() * 16));
+    HC(c->hc, hc_encode_slots(c->hc, d_slots, 1, 1, scale_exp, 1, pl_bn_b));                                          // eval.go:101-102 EncodeNTT
     printf("Plaintext (kernel) preparation, Done in %s \n", dur(start).c_str());
     start = now();
     std::vector<BLCt> ct_inputs_rots = preConv_BL(c, ct_input, in_wid, ker_wid);
-    HCB(c->hc, hc_sync(c->hc));
+    HC(c->hc, hc_sync(c->hc));
     printf("preConv done in %s \n", dur(start).c_str());
     const int rot_iters = (norm * real_ob == max_batch) ? real_ob : max_batch;
     BLCt ct_res;
@@ -226,11 +213,11 @@ static BLCt evalConv_BN_BL_test(BLContext *c, const Encoder &enc, const BLCt &ct
         else { BLCt r = RotateNew(c, ct_tmp, norm * i * out_size); Add(c, ct_res, r, ct_res); bl_free(c, r); bl_free(c, ct_tmp); }   // eval.go:123
     }
     if (ct_res.Scale != scale_exp) panic("Different scale between pl_bn_b and ctxt");                    // eval.go:127-129
-    for (int l = 0; l < 2; l++) HCB(c->hc, hc_add(c->hc, l, ct_res.d + (size_t)l * N, pl_bn_b + (size_t)l * N, ct_res.d + (size_t)l * N, 1));   // eval.go:130
-    HCB(c->hc, hc_sync(c->hc));
+    for (int l = 0; l < 2; l++) HC(c->hc, hc_add(c->hc, l, ct_res.d + (size_t)l * N, pl_bn_b + (size_t)l * N, ct_res.d + (size_t)l * N, 1));   // eval.go:130
+    HC(c->hc, hc_sync(c->hc));
     printf("Conv (with BN) Done in %s \n", dur(start).c_str());
     for (auto &r : ct_inputs_rots) bl_free(c, r);
-    HCB(c->hc, hc_free(c->hc, pl_bn_b)); HCB(c->hc, hc_free(c->hc, d_slots)); HCB(c->hc, hc_free(c->hc, d_ker)); HCB(c->hc, hc_free(c->hc, d_pl));
+    HC(c->hc, hc_free(c->hc, pl_bn_b)); HC(c->hc, hc_free(c->hc, d_slots)); HC(c->hc, hc_free(c->hc, d_ker)); HC(c->hc, hc_free(c->hc, d_pl));
     (void)enc;
     return ct_res;
 }
@@ -252,7 +239,7 @@ static BLContext *bl_newContext(int logN, int ker_wid, int in_wid, bool boot) {
     for (int m = 0; m < 4; m++) c->sk_ntt[m] = bl_ntt(c, m, signed_row(c->sk, BLQ[m]));
     if (deviceEncrypt()) {      // as newContext does for the Ours column: the secret key on the device once, and the key of the encryptor's draws (g is left as it is when the device path is off)
         c->d_sk = bl_rows(c, 4);
-        for (int m = 0; m < 4; m++) HCB(c->hc, hc_upload(c->hc, c->d_sk + (size_t)m * N, c->sk_ntt[m].data(), (size_t)N * 8));
+        for (int m = 0; m < 4; m++) HC(c->hc, hc_upload(c->hc, c->d_sk + (size_t)m * N, c->sk_ntt[m].data(), (size_t)N * 8));
         for (uint32_t &w : c->enc_seed8) w = (uint32_t)c->g();
         printf("Base Line: encryption and decryption on the device (hc_encode_slots / hc_encrypt_sk / hc_decrypt_decode_slots)\n");
     }
@@ -279,12 +266,12 @@ static BLCt bl_encrypt(BLContext *c, const std::vector<uint64_t> &pt_rows, doubl
         t = bl_ntt(c, l, t);
         for (int j = 0; j < N; j++) { ct[(size_t)l * N + j] = submod(t[(size_t)j], mulmod(c1[(size_t)j], c->sk_ntt[l][(size_t)j], q), q); ct[(size_t)(2 + l) * N + j] = c1[(size_t)j]; }
     }
-    BLCt r = bl_alloc(c, scale); HCB(c->hc, hc_upload(c->hc, r.d, ct.data(), ct.size() * 8));
+    BLCt r = bl_alloc(c, scale); HC(c->hc, hc_upload(c->hc, r.d, ct.data(), ct.size() * 8));
     return r;
 }
 // Decrypt at level 1 + encoder.Decode: CRT over Q0*Q1 (115 bits), centre, /scale, special FFT
 static std::vector<cplx> bl_decrypt_decode(BLContext *c, const Encoder &enc, const BLCt &ct) {
-    std::vector<uint64_t> h((size_t)4 * N); HCB(c->hc, hc_download(c->hc, h.data(), ct.d, h.size() * 8));
+    std::vector<uint64_t> h((size_t)4 * N); HC(c->hc, hc_download(c->hc, h.data(), ct.d, h.size() * 8));
     std::vector<uint64_t> m[2];
     for (int l = 0; l < 2; l++) {
         const uint64_t q = BLQ[l]; m[l].resize(N);
@@ -310,25 +297,25 @@ static std::vector<cplx> bl_decrypt_decode(BLContext *c, const Encoder &enc, con
 // 1), hc_encrypt_sk (count = 2)
 static void bl_encrypt_device(BLContext *c, const std::vector<cplx> &v1, const std::vector<cplx> &v2, BLCt &ct1, BLCt &ct2) {
     if (v1.size() != (size_t)N / 2 || v2.size() != (size_t)N / 2) panic("bl_encrypt_device: full-slot vectors expected");
-    void *vp = nullptr; HCB(c->hc, hc_malloc(c->hc, (size_t)2 * (N / 2) * 16, &vp)); double *d_vals = (double *)vp;            // [2][N/2] complex128
-    HCB(c->hc, hc_upload(c->hc, d_vals, v1.data(), v1.size() * 16)); HCB(c->hc, hc_upload(c->hc, d_vals + N, v2.data(), v2.size() * 16));
+    void *vp = nullptr; HC(c->hc, hc_malloc(c->hc, (size_t)2 * (N / 2) * 16, &vp)); double *d_vals = (double *)vp;            // [2][N/2] complex128
+    HC(c->hc, hc_upload(c->hc, d_vals, v1.data(), v1.size() * 16)); HC(c->hc, hc_upload(c->hc, d_vals + N, v2.data(), v2.size() * 16));
     uint64_t *pt = bl_rows(c, 4);                                                                                                 // [2][limb 2][N]
-    HCB(c->hc, hc_encode_slots(c->hc, d_vals, 2, 1, c->scale, 0, pt));
+    HC(c->hc, hc_encode_slots(c->hc, d_vals, 2, 1, c->scale, 0, pt));
     ct1 = bl_alloc(c, c->scale); ct2 = bl_alloc(c, c->scale);
     uint64_t *ptrs[2] = {ct1.d, ct2.d};
-    HCB(c->hc, hc_encrypt_sk(c->hc, 2, 1, pt, c->d_sk, c->enc_seed8, c->enc_stream++, ptrs));
-    HCB(c->hc, hc_sync(c->hc));                                                                                                   // the caller times the encryption
-    HCB(c->hc, hc_free(c->hc, d_vals)); HCB(c->hc, hc_free(c->hc, pt));
+    HC(c->hc, hc_encrypt_sk(c->hc, 2, 1, pt, c->d_sk, c->enc_seed8, c->enc_stream++, ptrs));
+    HC(c->hc, hc_sync(c->hc));                                                                                                   // the caller times the encryption
+    HC(c->hc, hc_free(c->hc, d_vals)); HC(c->hc, hc_free(c->hc, pt));
 }
 // Decrypt at level 1 + encoder.Decode of both results: hc_decrypt_decode_slots (count = 2), one download
 static void bl_decrypt_decode_device(BLContext *c, const BLCt &a, const BLCt &b, std::vector<cplx> &va, std::vector<cplx> &vb) {
     if (a.Scale != b.Scale) panic("bl_decrypt_decode_device: one scale expected");
-    void *vp = nullptr; HCB(c->hc, hc_malloc(c->hc, (size_t)2 * (N / 2) * 16, &vp)); double *d_vals = (double *)vp;
+    void *vp = nullptr; HC(c->hc, hc_malloc(c->hc, (size_t)2 * (N / 2) * 16, &vp)); double *d_vals = (double *)vp;
     const uint64_t *ptrs[2] = {a.d, b.d};
-    HCB(c->hc, hc_decrypt_decode_slots(c->hc, 2, 1, ptrs, c->d_sk, a.Scale, LOGN - 1, d_vals));
+    HC(c->hc, hc_decrypt_decode_slots(c->hc, 2, 1, ptrs, c->d_sk, a.Scale, LOGN - 1, d_vals));
     va.resize((size_t)N / 2); vb.resize((size_t)N / 2);
-    HCB(c->hc, hc_download(c->hc, va.data(), d_vals, va.size() * 16)); HCB(c->hc, hc_download(c->hc, vb.data(), d_vals + N, vb.size() * 16));
-    HCB(c->hc, hc_free(c->hc, d_vals));
+    HC(c->hc, hc_download(c->hc, va.data(), d_vals, va.size() * 16)); HC(c->hc, hc_download(c->hc, vb.data(), d_vals + N, vb.size() * 16));
+    HC(c->hc, hc_free(c->hc, d_vals));
 }
 
 // ---------------------------------------------------------------- test_BL.go:16-185 (boot = false)
@@ -379,7 +366,7 @@ void testConv_BL_in(int real_batch, int in_wid, int ker_wid, int total_test_num,
             BLCt b = evalConv_BN_BL_test(cont, enc, ct_input2, ker_in_sep[pos][1], bn_a_sep[pos], zeros, in_wid, ker_wid, hb, hb, 0, 1, pad);
             Add(cont, a, b, a); bl_free(cont, b); ct_res[pos] = a;                                        // test_BL.go:108 AddNew
         }
-        HCB(cont->hc, hc_sync(cont->hc));
+        HC(cont->hc, hc_sync(cont->hc));
         printf("Evaluation total done in %s \n", dur(start_eval).c_str());
         if (boot) {                                                                                       // test_BL.go:113-168
             const double alpha = 0.0, pow_ = 4.0;
@@ -400,7 +387,7 @@ void testConv_BL_in(int real_batch, int in_wid, int ker_wid, int total_test_num,
         bl_free(cont, ct_input1); bl_free(cont, ct_input2); bl_free(cont, ct_res[0]); bl_free(cont, ct_res[1]);
     }
     if (cont->btp) freeBoot(cont->btp);
-    if (cont->d_sk) HCB(cont->hc, hc_free(cont->hc, cont->d_sk));
+    if (cont->d_sk) HC(cont->hc, hc_free(cont->hc, cont->d_sk));
     hc_ctx_destroy(cont->hc); delete cont;
 }
 

@@ -8,8 +8,8 @@
 #include <string.h>
 
 #include <algorithm>
-#include <chrono>
 #include <fstream>
+#include <functional>
 #include <random>
 #include <sstream>
 
@@ -48,26 +48,7 @@ const char *testOnlyEnv(const char *name) {
     if (!testMode()) panic(std::string(name) + " is set but the CLI was not started with --test-mode: refusing to run with test-only key / input overrides");
     return v;
 }
-#define HC(c, call) do { int rc_ = (call); if (rc_) panic(std::string(#call) + ": " + hc_last_error(c)); } while (0)
-
 static const uint64_t MODQ[3] = {0x80000000080001ull, 0x1ffffffea0001ull, PACK_P};   // Q0, Q1, P (ABI indices 0,1,2)
-
-static inline uint64_t mulmod(uint64_t a, uint64_t b, uint64_t q) { return (uint64_t)(((u128)a * b) % q); }
-static inline uint64_t addmod(uint64_t a, uint64_t b, uint64_t q) { uint64_t r = a + b; return r >= q ? r - q : r; }
-static inline uint64_t submod(uint64_t a, uint64_t b, uint64_t q) { return a >= b ? a - b : a + q - b; }
-static inline uint64_t to_mont(uint64_t a, uint64_t q) { return (uint64_t)((((u128)a) << 64) % q); }
-
-// Go's time.Duration.String() shape ("57.154502ms", "3.40439908s")
-static std::string dur(std::chrono::steady_clock::time_point t0) {
-    double ns = (double)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count();
-    char b[64];
-    if (ns < 1e3) snprintf(b, sizeof b, "%.0fns", ns);
-    else if (ns < 1e6) snprintf(b, sizeof b, "%.6gµs", ns / 1e3);
-    else if (ns < 1e9) snprintf(b, sizeof b, "%.9gms", ns / 1e6);
-    else snprintf(b, sizeof b, "%.9gs", ns / 1e9);
-    return b;
-}
-static std::chrono::steady_clock::time_point now() { return std::chrono::steady_clock::now(); }
 
 // ---------------------------------------------------------------- device helpers
 static uint64_t *dev_rows(Context *c, size_t rows) { void *p = nullptr; HC(c->hc, hc_malloc(c->hc, rows * N * sizeof(uint64_t), &p)); return (uint64_t *)p; }
@@ -640,17 +621,25 @@ Ciphertext conv_then_pack(Context *c, const Ciphertext &ctxt_in, const KerPlain 
     (void)pl_bn_b;
     return r;
 }
+// eval.go:233-243: the bias plaintext of a layer - bn_b[i] on coefficient out_norm*i of every cell of the in_wid grid, encoded at out_scale, level 0, NTT domain
+static Plaintext prep_bias(Context *c, const std::vector<double> &bn_b, int in_wid, int out_norm, double out_scale) {
+    const int max_batch = N / (in_wid * in_wid);
+    std::vector<double> b_coeffs((size_t)N, 0.0);
+    for (size_t i = 0; i < bn_b.size(); i++) for (int j = 0; j < in_wid * in_wid; j++) b_coeffs[(size_t)(out_norm * (int)i + j * max_batch)] = bn_b[i];   // eval.go:233-238
+    Plaintext pl; pl.level = 0; pl.Scale = out_scale;
+    pl.d = dev_upload(c, EncodeCoeffs(b_coeffs, 0, out_scale));
+    HC(c->hc, hc_ntt(c->hc, 0, pl.d, pl.d, 1));                                                                        // eval.go:242-243
+    HC(c->hc, hc_sync(c->hc));
+    return pl;
+}
+static void free_ker(Context *c, KerPlain &k) { hc_ker_free(c->hc, k.h); for (size_t g = 1; g < k.shard_h.size(); g++) hc_ker_free(c->shards[g], k.shard_h[g]); }
+
 Ciphertext evalConv_BN(Context *c, const Ciphertext &ct_input, const std::vector<double> &ker_in, const std::vector<double> &bn_a,
                        const std::vector<double> &bn_b, int in_wid, int ker_wid, int real_ib, int real_ob, int norm, double out_scale, bool trans, int dilation, int ib_stride, int ob_stride) {
     const int max_batch = N / (in_wid * in_wid), out_norm = norm * ob_stride;      // out_norm: the rows out_norm*o hold the output channels; the pack tree and the bias step by it
     auto start = now();
     KerPlain pl_ker = prep_Ker(c, ker_in, bn_a, in_wid, ker_wid, real_ib, real_ob, norm, c->ECD_LV, 0, trans, dilation, ib_stride, ob_stride);      // eval.go:231
-    std::vector<double> b_coeffs((size_t)N, 0.0);
-    for (size_t i = 0; i < bn_b.size(); i++) for (int j = 0; j < in_wid * in_wid; j++) b_coeffs[(size_t)(out_norm * (int)i + j * max_batch)] = bn_b[i];   // eval.go:233-238
-    Plaintext pl_bn_b; pl_bn_b.level = 0; pl_bn_b.Scale = out_scale;
-    pl_bn_b.d = dev_upload(c, EncodeCoeffs(b_coeffs, 0, out_scale));
-    HC(c->hc, hc_ntt(c->hc, 0, pl_bn_b.d, pl_bn_b.d, 1));                                                              // eval.go:242-243
-    HC(c->hc, hc_sync(c->hc));
+    Plaintext pl_bn_b = prep_bias(c, bn_b, in_wid, out_norm, out_scale);
     printf("Plaintext (kernel) preparation, Done in %s \n", dur(start).c_str());                                      // eval.go:244
     start = now();
     dbg_digest(c, "bias plaintext", pl_bn_b.d, 1);
@@ -662,8 +651,7 @@ Ciphertext evalConv_BN(Context *c, const Ciphertext &ct_input, const std::vector
     HC(c->hc, hc_add(c->hc, 0, ct_res.d, pl_bn_b.d, ct_res.d, 1));                                                     // eval.go:258
     HC(c->hc, hc_sync(c->hc));
     printf("Conv (with BN) Done in %s \n", dur(start).c_str());                                                       // eval.go:260
-    hc_ker_free(c->hc, pl_ker.h);
-    for (size_t g = 1; g < pl_ker.shard_h.size(); g++) hc_ker_free(c->shards[g], pl_ker.shard_h[g]);
+    free_ker(c, pl_ker);
     HC(c->hc, hc_free(c->hc, pl_bn_b.d));
     return ct_res;
 }
@@ -674,6 +662,26 @@ int imageBatch() {
     const char *e = getenv("HCONV_IMAGE_BATCH"); const int n = e ? atoi(e) : 1;
     if (n < 1 || n > 8) panic("HCONV_IMAGE_BATCH must be 1..8");
     return n;
+}
+std::vector<Ciphertext> conv_then_pack_batch(Context *c, const std::vector<std::vector<Ciphertext>> &groups, const std::vector<const hc_ker *> &kers, double ker_scale, const Plaintext *bias,
+                                             int max_batch, int out_norm, double out_scale) {
+    const int G = (int)groups.size(), m = (int)kers.size(), n = G * m;
+    if (G < 1 || m < 1 || n > 16) panic("conv_then_pack_batch: 1..16 input ciphertexts in all (groups x ciphertexts per group)");
+    std::vector<Ciphertext> res((size_t)G); std::vector<const uint64_t *> ins((size_t)n), bs((size_t)n, nullptr); std::vector<const hc_ker *> ks((size_t)n); std::vector<uint64_t *> outs((size_t)n);
+    for (int g = 0; g < G; g++) {
+        if ((int)groups[(size_t)g].size() != m) panic("conv_then_pack_batch: every group has one input ciphertext per kernel handle");
+        res[(size_t)g].d = dev_rows(c, 2); res[(size_t)g].level = 0;
+        for (int j = 0; j < m; j++) {
+            const Ciphertext &ct = groups[(size_t)g][(size_t)j], &first = groups[0][0]; const size_t z = (size_t)g * m + j;
+            if (ct.Scale != first.Scale || ct.level != first.level) panic("conv_then_pack_batch: the input ciphertexts share level and scale");
+            ins[z] = ct.d; ks[z] = kers[(size_t)j]; outs[z] = res[(size_t)g].d;
+        }
+        if (bias) bs[(size_t)g * m] = bias->d;                              // the group's bias is its first member's entry
+    }
+    double sc = 0;
+    if (hc_conv_then_pack_batch(c->hc, n, ins.data(), groups[0][0].Scale, ks.data(), ker_scale, max_batch, out_norm, out_scale, bias ? bs.data() : nullptr, outs.data(), &sc)) panic(std::string("hc_conv_then_pack_batch: ") + hc_last_error(c->hc));   // conv.go:541-543's panic included
+    for (Ciphertext &r : res) r.Scale = sc;
+    return res;
 }
 // eval.go:224-263 for the images of a batch: prep_Ker and the bias plaintext once (they depend on the layer only), conv_then_pack + the bias add of all images as ONE launch set
 std::vector<Ciphertext> evalConv_BN_batch(Context *c, const std::vector<Ciphertext> &ct_inputs, const std::vector<double> &ker_in, const std::vector<double> &bn_a,
@@ -688,25 +696,14 @@ std::vector<Ciphertext> evalConv_BN_batch(Context *c, const std::vector<Cipherte
     const int max_batch = N / (in_wid * in_wid), out_norm = norm * ob_stride;      // out_norm: the rows out_norm*o hold the output channels; the pack tree and the bias step by it
     auto start = now();
     KerPlain pl_ker = prep_Ker(c, ker_in, bn_a, in_wid, ker_wid, real_ib, real_ob, norm, c->ECD_LV, 0, trans, dilation, ib_stride, ob_stride);      // eval.go:231
-    std::vector<double> b_coeffs((size_t)N, 0.0);
-    for (size_t i = 0; i < bn_b.size(); i++) for (int j = 0; j < in_wid * in_wid; j++) b_coeffs[(size_t)(out_norm * (int)i + j * max_batch)] = bn_b[i];   // eval.go:233-238
-    Plaintext pl_bn_b; pl_bn_b.level = 0; pl_bn_b.Scale = out_scale;
-    pl_bn_b.d = dev_upload(c, EncodeCoeffs(b_coeffs, 0, out_scale));
-    HC(c->hc, hc_ntt(c->hc, 0, pl_bn_b.d, pl_bn_b.d, 1));                                                              // eval.go:242-243
-    HC(c->hc, hc_sync(c->hc));
+    Plaintext pl_bn_b = prep_bias(c, bn_b, in_wid, out_norm, out_scale);
     printf("Plaintext (kernel) preparation, Done in %s \n", dur(start).c_str());                                      // eval.go:244
     start = now();
-    std::vector<Ciphertext> res((size_t)n); std::vector<const uint64_t *> ins((size_t)n), bias((size_t)n, pl_bn_b.d); std::vector<const hc_ker *> kers((size_t)n, pl_ker.h); std::vector<uint64_t *> outs((size_t)n);
-    for (int z = 0; z < n; z++) {
-        if (ct_inputs[(size_t)z].Scale != ct_inputs[0].Scale || ct_inputs[(size_t)z].level != ct_inputs[0].level) panic("evalConv_BN_batch: the images of a batch share level and scale");
-        res[(size_t)z].d = dev_rows(c, 2); res[(size_t)z].level = 0; ins[(size_t)z] = ct_inputs[(size_t)z].d; outs[(size_t)z] = res[(size_t)z].d;
-    }
-    double sc = 0;
-    if (hc_conv_then_pack_batch(c->hc, n, ins.data(), ct_inputs[0].Scale, kers.data(), pl_ker.Scale, max_batch, out_norm, out_scale, bias.data(), outs.data(), &sc)) panic(std::string("hc_conv_then_pack_batch: ") + hc_last_error(c->hc));   // conv.go:541-543's panic included
+    std::vector<std::vector<Ciphertext>> groups; for (const Ciphertext &ct : ct_inputs) groups.push_back({ct});         // one input ciphertext per image
+    std::vector<Ciphertext> res = conv_then_pack_batch(c, groups, {pl_ker.h}, pl_ker.Scale, &pl_bn_b, max_batch, out_norm, out_scale);
     HC(c->hc, hc_sync(c->hc));
-    for (int z = 0; z < n; z++) res[(size_t)z].Scale = sc;
     printf("Conv (with BN) Done in %s  (%d images)\n", dur(start).c_str(), n);                                       // eval.go:260
-    hc_ker_free(c->hc, pl_ker.h);
+    free_ker(c, pl_ker);
     HC(c->hc, hc_free(c->hc, pl_bn_b.d));
     return res;
 }
@@ -724,44 +721,26 @@ std::vector<Ciphertext> evalConv_BN_multi_batch(Context *c, const std::vector<st
     if ((int)ker_in.size() != k_sz * real_ib * real_ob) panic("evalConv_BN_multi: kernel size inconsistent");
     const int max_batch = N / (in_wid * in_wid);
     auto start = now();
-    std::vector<KerPlain> pl_ker((size_t)m);
+    std::vector<KerPlain> pl_ker((size_t)m); std::vector<const hc_ker *> kers;
     std::vector<double> slice((size_t)k_sz * ib * real_ob);
     for (int j = 0; j < m; j++) {
         for (int t = 0; t < k_sz; t++) for (int ch = 0; ch < ib; ch++) for (int o = 0; o < real_ob; o++)
             slice[(size_t)o + (size_t)ch * real_ob + (size_t)t * real_ob * ib] = ker_in[(size_t)o + (size_t)(j * ib + ch) * real_ob + (size_t)t * real_ob * real_ib];
         pl_ker[(size_t)j] = prep_Ker(c, slice, bn_a, in_wid, ker_wid, ib, real_ob, norm, c->ECD_LV, 0, false);
+        kers.push_back(pl_ker[(size_t)j].h);
     }
-    std::vector<double> b_coeffs((size_t)N, 0.0);
-    for (size_t i = 0; i < bn_b.size(); i++) for (int j = 0; j < in_wid * in_wid; j++) b_coeffs[(size_t)(norm * (int)i + j * max_batch)] = bn_b[i];   // eval.go:233-238
-    Plaintext pl_bn_b; pl_bn_b.level = 0; pl_bn_b.Scale = out_scale;
-    pl_bn_b.d = dev_upload(c, EncodeCoeffs(b_coeffs, 0, out_scale));
-    HC(c->hc, hc_ntt(c->hc, 0, pl_bn_b.d, pl_bn_b.d, 1));                                                              // eval.go:242-243
-    HC(c->hc, hc_sync(c->hc));
+    Plaintext pl_bn_b = prep_bias(c, bn_b, in_wid, norm, out_scale);
     printf("Plaintext (kernel) preparation, Done in %s \n", dur(start).c_str());                                      // eval.go:244
     start = now();
-    std::vector<Ciphertext> res((size_t)G); std::vector<const uint64_t *> ins((size_t)n), bias((size_t)n, nullptr); std::vector<const hc_ker *> kers((size_t)n); std::vector<uint64_t *> outs((size_t)n);
-    const Ciphertext &first = groups[0][0];
-    for (int g = 0; g < G; g++) {
-        if ((int)groups[(size_t)g].size() != m) panic("evalConv_BN_multi: every image has the same number of input ciphertexts");
-        res[(size_t)g].d = dev_rows(c, 2); res[(size_t)g].level = 0;
-        for (int j = 0; j < m; j++) {
-            const Ciphertext &ct = groups[(size_t)g][(size_t)j]; const size_t z = (size_t)g * m + j;
-            if (ct.Scale != first.Scale || ct.level != first.level) panic("evalConv_BN_multi: the input ciphertexts share level and scale");
-            ins[z] = ct.d; kers[z] = pl_ker[(size_t)j].h; outs[z] = res[(size_t)g].d;
-        }
-        bias[(size_t)g * m] = pl_bn_b.d;                                  // the group's bias is its first member's entry
-    }
-    double sc = 0;
-    if (hc_conv_then_pack_batch(c->hc, n, ins.data(), first.Scale, kers.data(), pl_ker[0].Scale, max_batch, norm, out_scale, bias.data(), outs.data(), &sc)) panic(std::string("hc_conv_then_pack_batch: ") + hc_last_error(c->hc));   // conv.go:541-543's panic included
+    std::vector<Ciphertext> res = conv_then_pack_batch(c, groups, kers, pl_ker[0].Scale, &pl_bn_b, max_batch, norm, out_scale);
     // one launch set does both of conv_then_pack's phases: "mult time" is the time to queue it, "Pack time" the time until the results are complete
     printf("\t mult time:  %s\n", dur(start).c_str());
     auto mt = now();
     HC(c->hc, hc_sync(c->hc));
     printf("\t Pack time:  %s\n", dur(mt).c_str());
-    for (int g = 0; g < G; g++) res[(size_t)g].Scale = sc;
     if (G > 1) printf("Conv (with BN) Done in %s  (%d images)\n", dur(start).c_str(), G);
     else printf("Conv (with BN) Done in %s \n", dur(start).c_str());                                                  // eval.go:260
-    for (KerPlain &k : pl_ker) { hc_ker_free(c->hc, k.h); for (size_t g = 1; g < k.shard_h.size(); g++) hc_ker_free(c->shards[g], k.shard_h[g]); }
+    for (KerPlain &k : pl_ker) free_ker(c, k);
     HC(c->hc, hc_free(c->hc, pl_bn_b.d));
     return res;
 }
@@ -771,39 +750,46 @@ Ciphertext evalConv_BN_multi(Context *c, const std::vector<Ciphertext> &ct_input
 }
 
 // ---------------------------------------------------------------- layers of the transposed and the multi-input convolution (not reference routines)
-// What evalConv_BNRelu_new is for kind "Conv": the convolution at eval.go:433's out_scale, the hand-over to the bootstrapper's context (its own stream) as testConv_in does
-// it, and the tail. The transposed layer's sparse form asks prep_Ker for ob_stride = 4: with norm = 1 on the input side (the B input channels fill the slots)
-// the B/4 output channels land on rows 4*o, the pack tree runs with norm = 4 over those rows and the bias sits at slots 4*o: every coefficient of the result is on a
-// multiple of 4, which is what the log_sparse = 2 bootstrapper packs into one ciphertext.
-static double chain_out_scale(double pow_) { return exp2(round(log2((double)MODQ[0]) - (pow_ + 8))); }      // eval.go:433
-static std::vector<BootCiphertext> conv_tail(Context *c, std::vector<Ciphertext> &ct_conv, const std::string &kind, int log_sparse, double alpha, double pow_, int in_wid, int kp_wid,
-                                             std::vector<Ciphertext> *ct_conv_out) {
-    HC(c->hc, hc_sync(c->hc));                                                                         // hand-over to the bootstrapper's context (another stream)
+// The hand-over from the convolution context to the bootstrapper's (its own stream), then the tail: everything queued on the convolution context - the stride layers end on a
+// product and an addition that nothing has waited for - must be complete before the other stream reads ct_conv
+std::vector<BootCiphertext> conv_tail(Context *c, const std::vector<Ciphertext> &ct_conv, const std::string &kind, int log_sparse, double alpha, double pow_, int in_wid, int kp_wid,
+                                      const std::vector<std::vector<int>> *keep_idx, const std::string &mask_key, int pack_pos) {
+    HC(c->hc, hc_sync(c->hc));
     std::vector<const uint64_t *> conv_d; for (const Ciphertext &ct : ct_conv) conv_d.push_back(ct.d);
-    std::vector<BootCiphertext> r = evalConv_BNRelu_tail_batch(c->btp, kind, log_sparse, conv_d, ct_conv[0].Scale, alpha, pow_, in_wid, kp_wid);
-    if (ct_conv_out) *ct_conv_out = ct_conv; else for (Ciphertext &ct : ct_conv) freeCt(c, ct);
-    return r;
+    return evalConv_BNRelu_tail_batch(c->btp, kind, log_sparse, conv_d, ct_conv[0].Scale, alpha, pow_, in_wid, kp_wid, keep_idx, mask_key, pack_pos);
 }
+static void free_cts(Context *c, std::vector<Ciphertext> &cts) { for (Ciphertext &ct : cts) freeCt(c, ct); }
+static void free_boot_cts(Context *c, std::vector<BootCiphertext> &cts) { for (BootCiphertext &ct : cts) freeBootCt(c->btp, ct); }
+// What evalConv_BNRelu_new is for kind "Conv": the convolution at chain_out_scale, conv_tail. The transposed layer's sparse form asks prep_Ker for ob_stride = 4: with norm = 1
+// on the input side (the B input channels fill the slots) the B/4 output channels land on rows 4*o, the pack tree runs with norm = 4 over those rows and the bias sits at
+// slots 4*o: every coefficient of the result is on a multiple of 4, which is what the log_sparse = 2 bootstrapper packs into one ciphertext.
 std::vector<BootCiphertext> evalTransConv_BNRelu_batch(Context *c, const std::vector<Ciphertext> &ct_inputs, const std::vector<double> &ker_in, const std::vector<double> &bn_a,
                                                        const std::vector<double> &bn_b, double alpha, double pow_, int in_wid, int kp_wid, int ker_wid, int real_ib, int real_ob,
                                                        bool sparse, std::vector<Ciphertext> *ct_conv_out) {
     if (!c->btp) panic("evalTransConv_BNRelu needs a context built with boot = true");
     if (sparse && 4 * real_ob > N / (in_wid * in_wid)) panic("evalTransConv_BNRelu: the sparse form puts output channel o at slot 4*o");
     std::vector<Ciphertext> ct_conv = evalConv_BN_batch(c, ct_inputs, ker_in, bn_a, bn_b, in_wid, ker_wid, real_ib, real_ob, 1, chain_out_scale(pow_), true, 1, 1, sparse ? 4 : 1);
-    return conv_tail(c, ct_conv, sparse ? "TransConv_sparse" : "TransConv", sparse ? 2 : 0, alpha, pow_, in_wid, kp_wid, ct_conv_out);
+    std::vector<BootCiphertext> r = conv_tail(c, ct_conv, sparse ? "TransConv_sparse" : "TransConv", sparse ? 2 : 0, alpha, pow_, in_wid, kp_wid);
+    if (ct_conv_out) *ct_conv_out = ct_conv; else free_cts(c, ct_conv);
+    return r;
 }
 std::vector<BootCiphertext> evalConv_BNRelu_multi_batch(Context *c, const std::vector<std::vector<Ciphertext>> &groups, const std::vector<double> &ker_in, const std::vector<double> &bn_a,
                                                         const std::vector<double> &bn_b, double alpha, double pow_, int in_wid, int kp_wid, int ker_wid, int real_ib, int real_ob) {
     if (!c->btp) panic("evalConv_BNRelu_multi needs a context built with boot = true");
     std::vector<Ciphertext> ct_conv = evalConv_BN_multi_batch(c, groups, ker_in, bn_a, bn_b, in_wid, ker_wid, real_ib, real_ob, 1, chain_out_scale(pow_));
-    return conv_tail(c, ct_conv, "Conv", 0, alpha, pow_, in_wid, kp_wid, nullptr);
+    std::vector<BootCiphertext> r = conv_tail(c, ct_conv, "Conv", 0, alpha, pow_, in_wid, kp_wid);
+    free_cts(c, ct_conv);
+    return r;
 }
-// HCONV_BOOT_STATS lines of the layer commands: testConv_in's two, and which bootstrappers (slot sets) the context built
-static void print_boot_stats(Context *cont) {
+
+// ---------------------------------------------------------------- what the layer drivers share
+// HCONV_BOOT_STATS lines of the layer commands; sets: also which bootstrappers (slot sets) the context built (testConv_in prints the first two lines only)
+static void print_boot_stats(Context *cont, bool sets = true) {
     if (!getenv("HCONV_BOOT_STATS")) return;
     long nk, nks; bootStats(cont->btp, &nk, &nks);
     printf("boot stats: %ld switching keys generated, %ld key switches\n", nk, nks);
     long nd, nm; bool dev; bootEncodeStats(cont->btp, &nd, &nm, &dev); printf("boot stats: %ld diagonals and %ld masks encoded on the %s\n", nd, nm, dev ? "device" : "host");
+    if (!sets) return;
     printf("boot stats: bootstrapper sets (log_sparse):"); for (int ls : bootSets(cont->btp)) printf(" %d", ls); printf("\n");
 }
 static void print_ct_digest(Context *cont, const Ciphertext &ct) {      // FNV-1a over a level-0 ciphertext: lets tests compare code paths bit for bit
@@ -811,81 +797,95 @@ static void print_ct_digest(Context *cont, const Ciphertext &ct) {      // FNV-1
     for (uint64_t w : h) for (int b = 0; b < 8; b++) { f ^= (w >> (8 * b)) & 0xff; f *= 1099511628211ull; }
     printf("ciphertext digest: %016llx\n", (unsigned long long)f);
 }
+static void print_shapes(Context *cont, int raw_in_wid, int ker_wid, int in_ch, int out_ch) {
+    printf("vec size: log2 =  %d\n", cont->logN);
+    printf("raw input width:  %d\n", raw_in_wid);
+    printf("kernel width:  %d\n", ker_wid);
+    printf("num raw batches in & out:  %d ,  %d\n", in_ch, out_ch);
+}
+// One test case: test_conv_data/test_<stem>_{in,ker,bna,bnb}_<iter>.csv read at the given sizes, and ..._{out,reluout}_<iter>.csv, the expected output of the command without / with the chain
+struct TestCase {
+    std::string pre, suf;
+    std::vector<double> raw_input, ker_in, bn_a, bn_b;
+    std::vector<double> expected(bool relu, int size) const { return readTxt(pre + (relu ? "reluout" : "out") + suf, size); }
+};
+static TestCase read_case(const std::string &stem, int test_iter, int in_size, int ker_size, int out_ch) {
+    printf("%d -th iter...start\n", test_iter + 1);
+    TestCase t; t.pre = "test_conv_data/test_" + stem + "_"; t.suf = "_" + std::to_string(test_iter) + ".csv";
+    t.raw_input = readTxt(t.pre + "in" + t.suf, in_size); t.ker_in = readTxt(t.pre + "ker" + t.suf, ker_size);
+    t.bn_a = readTxt(t.pre + "bna" + t.suf, out_ch); t.bn_b = readTxt(t.pre + "bnb" + t.suf, out_ch);
+    return t;
+}
+static std::string case_stem(const char *layer, int ker_wid, int in_batch) { return layer + std::to_string(ker_wid) + "_batch_" + std::to_string(in_batch); }
+// ONE EncryptCoeffsBatch call (one launch set on the device path) at the context's level and scale, and its console line
+static std::vector<Ciphertext> encrypt_inputs(Context *cont, const std::vector<const std::vector<double> *> &inputs) {
+    auto start = now();
+    std::vector<Ciphertext> enc = EncryptCoeffsBatch(cont, inputs, cont->ECD_LV, cont->scale);
+    printf("Encryption done in %s \n", dur(start).c_str());
+    return enc;
+}
+// cells_of(z, &outside): the driver's output cells of image z, decoded; outside: the stride layer's largest coefficient outside them (the other drivers leave it alone)
+typedef std::function<std::vector<double>(int, double *)> CellsOf;
+// images 1 .. nimg - 1 of a batch against image 0 and the expected output: independent encryptions of one input decrypt to the same values up to the scheme's noise
+static void print_batch_agreement(const std::vector<double> &test_out, const std::vector<double> &real_out, int nimg, const CellsOf &cells_of, bool with_outside = false) {
+    for (int z = 1; z < nimg; z++) {
+        double oz = 0; const std::vector<double> cz = cells_of(z, &oz);
+        double mx = 0, mr = 0; for (size_t i = 0; i < cz.size(); i++) { mx = std::max(mx, fabs(cz[i] - test_out[i])); mr = std::max(mr, fabs(cz[i] - real_out[i])); }
+        printf("image %d of the batch: max |difference| to image 0 = %.3g, to the expected output = %.3g", z, mx, mr);
+        if (with_outside) printf(", outside the kept cells = %.3g", oz);
+        printf("\n");
+    }
+}
+// the report of a test case: image 0 against the expected output (printDebugCfsPlain), then the batch's agreement. decrypt_start: when the decryption began
+static void report_case(std::chrono::steady_clock::time_point decrypt_start, const TestCase &tc, bool relu, int out_size, int nimg, const CellsOf &cells_of) {
+    double unused = 0; const std::vector<double> test_out = cells_of(0, &unused);
+    printf("Decryption Done in %s \n", dur(decrypt_start).c_str());
+    const std::vector<double> real_out = tc.expected(relu, out_size);
+    printDebugCfsPlain(test_out, real_out);
+    print_batch_agreement(test_out, real_out, nimg, cells_of);
+}
 
 // ---------------------------------------------------------------- testMultiConv_in (not a reference routine: testConv_in's shape for n_in input ciphertexts)
-// n_in * in_batch input channels on the raw width in_wid - ker_wid/2, in_batch output channels: the layer testConv_in runs, with n_in times the input channels. Ours only,
-// without bootstrapping. HCONV_IMAGE_BATCH = g: g independent encryptions of the image as g groups of one call (g * n_in <= 16).
+// n_in * in_batch input channels on the raw width in_wid - ker_wid/2, in_batch output channels: the layer testConv_in runs, with n_in times the input channels. Ours only.
+// HCONV_IMAGE_BATCH = g: g independent encryptions of the image as g groups of one call (g * n_in <= 16).
 void testMultiConv_in(int in_batch, int in_wid, int ker_wid, int total_test_num, int n_in, bool boot) {
     const std::string kind = "Conv";
-    const int raw_in_wid = in_wid - ker_wid / 2, norm = 1, m = n_in;
-    const std::string test_dir = "test_conv_data/";
+    const int raw_in_wid = in_wid - ker_wid / 2, norm = 1, m = n_in, px = raw_in_wid * raw_in_wid;
     const int nimg = imageBatch();
     if (nimg * m > 16) panic("multiconv: HCONV_IMAGE_BATCH x n_in must be <= 16 (the members of one hc_conv_then_pack_batch call)");
     int kp_wid, out_batch, logN; bool trans;
     set_Variables(in_batch, raw_in_wid, in_wid, ker_wid, kind, &kp_wid, &out_batch, &logN, &trans);
     Context *cont = newContext(logN, ker_wid, {in_wid}, {kp_wid}, boot, kind);
-    printf("vec size: log2 =  %d\n", cont->logN);
-    printf("raw input width:  %d\n", raw_in_wid);
-    printf("kernel width:  %d\n", ker_wid);
-    printf("num raw batches in & out:  %d ,  %d\n", m * in_batch, out_batch);
+    print_shapes(cont, raw_in_wid, ker_wid, m * in_batch, out_batch);
     printf("num input ciphertexts:  %d\n", m);
     for (int test_iter = 0; test_iter < total_test_num; test_iter++) {
-        printf("%d -th iter...start\n", test_iter + 1);
-        const std::string pre = test_dir + "test_multiconv" + std::to_string(ker_wid) + "_batch_" + std::to_string(in_batch) + "_in" + std::to_string(m) + "_";
-        const std::string suf = "_" + std::to_string(test_iter) + ".csv";
-        const int px = raw_in_wid * raw_in_wid;
-        std::vector<double> raw_input = readTxt(pre + "in" + suf, px * m * in_batch);
-        std::vector<double> ker_in = readTxt(pre + "ker" + suf, m * in_batch * out_batch * ker_wid * ker_wid);
-        std::vector<double> bn_a = readTxt(pre + "bna" + suf, out_batch);
-        std::vector<double> bn_b = readTxt(pre + "bnb" + suf, out_batch);
+        const TestCase tc = read_case(case_stem("multiconv", ker_wid, in_batch) + "_in" + std::to_string(m), test_iter, px * m * in_batch, m * in_batch * out_batch * ker_wid * ker_wid, out_batch);
         std::vector<std::vector<double>> input((size_t)m);
         for (int j = 0; j < m; j++) {                                                                  // ciphertext j: the channels j*in_batch .. (j+1)*in_batch - 1
             std::vector<double> part((size_t)px * in_batch);
-            for (int p = 0; p < px; p++) for (int ch = 0; ch < in_batch; ch++) part[(size_t)p * in_batch + ch] = raw_input[(size_t)p * m * in_batch + (size_t)j * in_batch + ch];
+            for (int p = 0; p < px; p++) for (int ch = 0; ch < in_batch; ch++) part[(size_t)p * in_batch + ch] = tc.raw_input[(size_t)p * m * in_batch + (size_t)j * in_batch + ch];
             input[(size_t)j] = prep_Input(part, raw_in_wid, in_wid, cont->Nn, norm, trans, false);
         }
-        auto start = now();
         std::vector<const std::vector<double> *> ptrs; for (int g = 0; g < nimg; g++) for (int j = 0; j < m; j++) ptrs.push_back(&input[(size_t)j]);
-        std::vector<Ciphertext> enc = EncryptCoeffsBatch(cont, ptrs, cont->ECD_LV, cont->scale);      // ONE call on the device path
-        printf("Encryption done in %s \n", dur(start).c_str());
+        std::vector<Ciphertext> enc = encrypt_inputs(cont, ptrs);
         std::vector<std::vector<Ciphertext>> groups((size_t)nimg);
         for (int g = 0; g < nimg; g++) groups[(size_t)g].assign(enc.begin() + (size_t)g * m, enc.begin() + (size_t)(g + 1) * m);
         if (boot) {                                                                                    // `multiconvReLU`: testConv_in's boot branch over the groups
             const double pow_ = 4.0, alpha = 0.0;                                                      // test.go:22
             auto layer = now();
-            std::vector<BootCiphertext> ct_res = evalConv_BNRelu_multi_batch(cont, groups, ker_in, bn_a, bn_b, alpha, pow_, in_wid, kp_wid, ker_wid, m * in_batch, out_batch);
+            std::vector<BootCiphertext> ct_res = evalConv_BNRelu_multi_batch(cont, groups, tc.ker_in, tc.bn_a, tc.bn_b, alpha, pow_, in_wid, kp_wid, ker_wid, m * in_batch, out_batch);
             if (nimg > 1) printf("Convolution + Bootstrapping + ReLU of %d ciphertexts done in %s \n", nimg, dur(layer).c_str());
-            start = now();
-            std::vector<double> cfs = bootDecryptDecodeCoeffs(cont->btp, ct_res[0]);
-            printf("Decryption Done in %s \n", dur(start).c_str());
-            std::vector<double> test_out = post_process(cfs, raw_in_wid, in_wid);
-            std::vector<double> real_out = readTxt(pre + "reluout" + suf, px * out_batch);
-            printDebugCfsPlain(test_out, real_out);
-            for (int z = 1; z < nimg; z++) {
-                std::vector<double> cz = post_process(bootDecryptDecodeCoeffs(cont->btp, ct_res[(size_t)z]), raw_in_wid, in_wid);
-                double mx = 0, mr = 0; for (size_t i = 0; i < cz.size(); i++) { mx = std::max(mx, fabs(cz[i] - test_out[i])); mr = std::max(mr, fabs(cz[i] - real_out[i])); }
-                printf("image %d of the batch: max |difference| to image 0 = %.3g, to the expected output = %.3g\n", z, mx, mr);
-            }
+            report_case(now(), tc, true, px * out_batch, nimg, [&](int z, double *) { return post_process(bootDecryptDecodeCoeffs(cont->btp, ct_res[(size_t)z]), raw_in_wid, in_wid); });
             print_boot_stats(cont);
-            for (Ciphertext &ct : enc) freeCt(cont, ct);
-            for (BootCiphertext &ct : ct_res) freeBootCt(cont->btp, ct);
+            free_cts(cont, enc); free_boot_cts(cont, ct_res);
             continue;
         }
-        std::vector<Ciphertext> ct_result = evalConv_BN_multi_batch(cont, groups, ker_in, bn_a, bn_b, in_wid, ker_wid, m * in_batch, out_batch, norm, (double)(1 << 30));
+        std::vector<Ciphertext> ct_result = evalConv_BN_multi_batch(cont, groups, tc.ker_in, tc.bn_a, tc.bn_b, in_wid, ker_wid, m * in_batch, out_batch, norm, (double)(1 << 30));
         if (getenv("HCONV_PRINT_DIGEST")) print_ct_digest(cont, ct_result[0]);      // lets tests compare code paths bit for bit
-        start = now();
-        std::vector<std::vector<double>> dec = DecryptDecodeCoeffsBatch(cont, ct_result);
-        printf("Decryption Done in %s \n", dur(start).c_str());
-        std::vector<double> test_out = post_process(dec[0], raw_in_wid, in_wid);
-        std::vector<double> real_out = readTxt(pre + "out" + suf, px * out_batch);
-        printDebugCfsPlain(test_out, real_out);
-        for (int z = 1; z < nimg; z++) {                                                               // the other encryptions decrypt to the same values up to the scheme's noise
-            std::vector<double> cz = post_process(dec[(size_t)z], raw_in_wid, in_wid);
-            double mx = 0, mr = 0; for (size_t i = 0; i < cz.size(); i++) { mx = std::max(mx, fabs(cz[i] - test_out[i])); mr = std::max(mr, fabs(cz[i] - real_out[i])); }
-            printf("image %d of the batch: max |difference| to image 0 = %.3g, to the expected output = %.3g\n", z, mx, mr);
-        }
-        for (Ciphertext &ct : enc) freeCt(cont, ct);
-        for (Ciphertext &ct : ct_result) freeCt(cont, ct);
+        auto start = now();
+        const std::vector<std::vector<double>> dec = DecryptDecodeCoeffsBatch(cont, ct_result);
+        report_case(start, tc, false, px * out_batch, nimg, [&](int z, double *) { return post_process(dec[(size_t)z], raw_in_wid, in_wid); });
+        free_cts(cont, enc); free_cts(cont, ct_result);
     }
     freeContext(cont);
 }
@@ -894,69 +894,32 @@ void testMultiConv_in(int in_batch, int in_wid, int ker_wid, int total_test_num,
 void testConv_in(int in_batch, int in_wid, int ker_wid, int total_test_num, bool boot) {
     const std::string kind = "Conv";
     const int raw_in_batch = in_batch, raw_in_wid = in_wid - ker_wid / 2, norm = in_batch / raw_in_batch;
-    const std::string test_dir = "test_conv_data/";
     int kp_wid, out_batch, logN; bool trans;
     set_Variables(in_batch, raw_in_wid, in_wid, ker_wid, kind, &kp_wid, &out_batch, &logN, &trans);
-    const int raw_out_batch = out_batch / norm;
+    const int raw_out_batch = out_batch / norm, out_size = raw_in_wid * raw_in_wid * raw_in_batch;
     Context *cont = newContext(logN, ker_wid, {in_wid}, {kp_wid}, boot, kind);
-    printf("vec size: log2 =  %d\n", cont->logN);
-    printf("raw input width:  %d\n", raw_in_wid);
-    printf("kernel width:  %d\n", ker_wid);
-    printf("num raw batches in & out:  %d ,  %d\n", raw_in_batch, raw_out_batch);
+    print_shapes(cont, raw_in_wid, ker_wid, raw_in_batch, raw_out_batch);
+    // HCONV_IMAGE_BATCH = n > 1 with the bootstrapping chain (not a reference feature): n independent encryptions of the input go through the layer as ONE set of launches
+    const int nimg = boot ? imageBatch() : 1;
     for (int test_iter = 0; test_iter < total_test_num; test_iter++) {
-        printf("%d -th iter...start\n", test_iter + 1);
-        const std::string pre = test_dir + "test_conv" + std::to_string(ker_wid) + "_batch_" + std::to_string(in_batch) + "_";
-        const std::string suf = "_" + std::to_string(test_iter) + ".csv";
-        std::vector<double> raw_input = readTxt(pre + "in" + suf, raw_in_wid * raw_in_wid * raw_in_batch);
-        std::vector<double> ker_in = readTxt(pre + "ker" + suf, raw_in_batch * raw_out_batch * ker_wid * ker_wid);
-        std::vector<double> bn_a = readTxt(pre + "bna" + suf, raw_out_batch);
-        std::vector<double> bn_b = readTxt(pre + "bnb" + suf, raw_out_batch);
-        std::vector<double> input = prep_Input(raw_input, raw_in_wid, in_wid, cont->Nn, norm, trans, false);
-        auto start = now();
-        // HCONV_IMAGE_BATCH = n > 1 with the bootstrapping chain: the n encryptions are ONE call on the device path
-        std::vector<Ciphertext> enc = EncryptCoeffsBatch(cont, std::vector<const std::vector<double> *>((size_t)(boot ? imageBatch() : 1), &input), cont->ECD_LV, cont->scale);
-        Ciphertext ctxt_input = enc[0];
-        printf("Encryption done in %s \n", dur(start).c_str());
+        const TestCase tc = read_case(case_stem("conv", ker_wid, in_batch), test_iter, raw_in_wid * raw_in_wid * raw_in_batch, raw_in_batch * raw_out_batch * ker_wid * ker_wid, raw_out_batch);
+        const std::vector<double> input = prep_Input(tc.raw_input, raw_in_wid, in_wid, cont->Nn, norm, trans, false);
+        std::vector<Ciphertext> enc = encrypt_inputs(cont, std::vector<const std::vector<double> *>((size_t)nimg, &input));
         if (boot) {                                                                                    // test.go:52-53, eval.go:272-607
             const double pow_ = 4.0, alpha = 0.0;                                                      // test.go:22
-            const double out_scale = exp2(round(log2((double)MODQ[0]) - (pow_ + 8)));                  // eval.go:433
-            // HCONV_IMAGE_BATCH = n > 1 (not a reference feature): n independent encryptions of the input go through the layer as ONE set of launches
-            const int nimg = imageBatch();
-            std::vector<Ciphertext> ins = enc;
-            std::vector<Ciphertext> ct_conv = evalConv_BN_batch(cont, ins, ker_in, bn_a, bn_b, in_wid, ker_wid, raw_in_batch, raw_out_batch, norm, out_scale, trans);
-            HC(cont->hc, hc_sync(cont->hc));                                                           // hand-over to the bootstrapper's context (another stream)
-            std::vector<const uint64_t *> conv_d; for (const Ciphertext &ct : ct_conv) conv_d.push_back(ct.d);
+            std::vector<Ciphertext> ct_conv = evalConv_BN_batch(cont, enc, tc.ker_in, tc.bn_a, tc.bn_b, in_wid, ker_wid, raw_in_batch, raw_out_batch, norm, chain_out_scale(pow_), trans);
             auto layer = now();
-            std::vector<BootCiphertext> ct_res = evalConv_BNRelu_tail_batch(cont->btp, "Conv", 0, conv_d, ct_conv[0].Scale, alpha, pow_, in_wid, kp_wid);
+            std::vector<BootCiphertext> ct_res = conv_tail(cont, ct_conv, "Conv", 0, alpha, pow_, in_wid, kp_wid);
             if (nimg > 1) printf("Bootstrapping + ReLU of %d ciphertexts done in %s \n", nimg, dur(layer).c_str());
-            start = now();
-            std::vector<double> cfs = bootDecryptDecodeCoeffs(cont->btp, ct_res[0]);
-            printf("Decryption Done in %s \n", dur(start).c_str());
-            std::vector<double> test_out = post_process(cfs, raw_in_wid, in_wid);
-            std::vector<double> real_out = readTxt(pre + "reluout" + suf, raw_in_wid * raw_in_wid * raw_in_batch);
-            printDebugCfsPlain(test_out, real_out);
-            for (int z = 1; z < nimg; z++) {                                                           // the other encryptions decrypt to the same values up to the scheme's noise
-                std::vector<double> cz = post_process(bootDecryptDecodeCoeffs(cont->btp, ct_res[(size_t)z]), raw_in_wid, in_wid);
-                double mx = 0, mr = 0; for (size_t i = 0; i < cz.size(); i++) { mx = std::max(mx, fabs(cz[i] - test_out[i])); mr = std::max(mr, fabs(cz[i] - real_out[i])); }
-                printf("image %d of the batch: max |difference| to image 0 = %.3g, to the expected output = %.3g\n", z, mx, mr);
-            }
-            long nk, nks; bootStats(cont->btp, &nk, &nks);
-            if (getenv("HCONV_BOOT_STATS")) printf("boot stats: %ld switching keys generated, %ld key switches\n", nk, nks);
-            if (getenv("HCONV_BOOT_STATS")) { long nd, nm; bool dev; bootEncodeStats(cont->btp, &nd, &nm, &dev); printf("boot stats: %ld diagonals and %ld masks encoded on the %s\n", nd, nm, dev ? "device" : "host"); }
-            for (Ciphertext &ct : ins) freeCt(cont, ct);
-            for (Ciphertext &ct : ct_conv) freeCt(cont, ct);
-            for (BootCiphertext &ct : ct_res) freeBootCt(cont->btp, ct);
+            report_case(now(), tc, true, out_size, nimg, [&](int z, double *) { return post_process(bootDecryptDecodeCoeffs(cont->btp, ct_res[(size_t)z]), raw_in_wid, in_wid); });
+            print_boot_stats(cont, false);
+            free_cts(cont, enc); free_cts(cont, ct_conv); free_boot_cts(cont, ct_res);
             continue;
         }
-        Ciphertext ct_result = evalConv_BN(cont, ctxt_input, ker_in, bn_a, bn_b, in_wid, ker_wid, raw_in_batch, raw_out_batch, norm, (double)(1 << 30), trans);
+        Ciphertext ct_result = evalConv_BN(cont, enc[0], tc.ker_in, tc.bn_a, tc.bn_b, in_wid, ker_wid, raw_in_batch, raw_out_batch, norm, (double)(1 << 30), trans);
         if (getenv("HCONV_PRINT_DIGEST")) print_ct_digest(cont, ct_result);      // lets tests compare code paths bit for bit
-        start = now();
-        std::vector<double> cfs_tmp = DecryptDecodeCoeffs(cont, ct_result);
-        printf("Decryption Done in %s \n", dur(start).c_str());
-        std::vector<double> test_out = post_process(cfs_tmp, raw_in_wid, in_wid);
-        std::vector<double> real_out = readTxt(pre + "out" + suf, raw_in_wid * raw_in_wid * raw_in_batch);
-        printDebugCfsPlain(test_out, real_out);
-        freeCt(cont, ctxt_input); freeCt(cont, ct_result);
+        report_case(now(), tc, false, out_size, 1, [&](int, double *) { return post_process(DecryptDecodeCoeffs(cont, ct_result), raw_in_wid, in_wid); });
+        free_cts(cont, enc); freeCt(cont, ct_result);
     }
     freeContext(cont);
 }
@@ -969,62 +932,42 @@ void testConv_in(int in_batch, int in_wid, int ker_wid, int total_test_num, bool
 void testStrConv_in(int in_batch, int in_wid, int ker_wid, int total_test_num, int pos) {
     if (in_wid % 4 != 0) panic("input wid not divisible by 4");
     const int kp_wid = 2 * (in_wid / 2 - ker_wid / 2), raw_in_wid = kp_wid, out_wid = in_wid / 2, raw_out_wid = kp_wid / 2, out_slots = 4 * in_batch, norm = 1;
-    const std::string test_dir = "test_conv_data/";
     Context *cont = newContext(LOGN, ker_wid, {in_wid}, {kp_wid}, true, "StrConv");
-    printf("vec size: log2 =  %d\n", cont->logN);
-    printf("raw input width:  %d\n", raw_in_wid);
-    printf("kernel width:  %d\n", ker_wid);
-    printf("num raw batches in & out:  %d ,  %d\n", in_batch, in_batch);
+    print_shapes(cont, raw_in_wid, ker_wid, in_batch, in_batch);
     printf("stride layer: keep width  %d , pack position  %d , output width  %d , output slots  %d\n", kp_wid, pos, raw_out_wid, out_slots);
+    const int nimg = imageBatch();
+    // the kept cells: (y', x', c + B pos) of the out_wid grid, y', x' < raw_out_wid; everything else is outside
+    auto kept_of = [&](const std::vector<double> &cf, double *outside) {
+        std::vector<double> kept((size_t)raw_out_wid * raw_out_wid * in_batch); double mx = 0;
+        for (int y = 0; y < out_wid; y++) for (int x = 0; x < out_wid; x++) for (int s = 0; s < out_slots; s++) {
+            const double v = cf[(size_t)(y * out_wid + x) * out_slots + s];
+            if (y < raw_out_wid && x < raw_out_wid && s / in_batch == pos) kept[(size_t)(y * raw_out_wid + x) * in_batch + (size_t)(s % in_batch)] = v; else mx = std::max(mx, fabs(v));
+        }
+        *outside = mx; return kept; };
     for (int test_iter = 0; test_iter < total_test_num; test_iter++) {
-        printf("%d -th iter...start\n", test_iter + 1);
-        const std::string pre = test_dir + "test_strconv" + std::to_string(ker_wid) + "_batch_" + std::to_string(in_batch) + "_";
-        const std::string suf = "_" + std::to_string(test_iter) + ".csv";
-        std::vector<double> raw_input = readTxt(pre + "in" + suf, raw_in_wid * raw_in_wid * in_batch);
-        std::vector<double> ker_in = readTxt(pre + "ker" + suf, in_batch * in_batch * ker_wid * ker_wid);
-        std::vector<double> bn_a = readTxt(pre + "bna" + suf, in_batch);
-        std::vector<double> bn_b = readTxt(pre + "bnb" + suf, in_batch);
-        std::vector<double> input = prep_Input(raw_input, raw_in_wid, in_wid, cont->Nn, norm, false, false);
-        auto start = now();
-        const int nimg = imageBatch();
-        std::vector<Ciphertext> enc = EncryptCoeffsBatch(cont, std::vector<const std::vector<double> *>((size_t)nimg, &input), cont->ECD_LV, cont->scale);
-        printf("Encryption done in %s \n", dur(start).c_str());
+        const TestCase tc = read_case(case_stem("strconv", ker_wid, in_batch), test_iter, raw_in_wid * raw_in_wid * in_batch, in_batch * in_batch * ker_wid * ker_wid, in_batch);
+        const std::vector<double> input = prep_Input(tc.raw_input, raw_in_wid, in_wid, cont->Nn, norm, false, false);
+        std::vector<Ciphertext> enc = encrypt_inputs(cont, std::vector<const std::vector<double> *>((size_t)nimg, &input));
         const double pow_ = 4.0, alpha = 0.0;                                                          // test.go:22
-        std::vector<Ciphertext> ct_conv = evalConv_BN_batch(cont, enc, ker_in, bn_a, bn_b, in_wid, ker_wid, in_batch, in_batch, norm, chain_out_scale(pow_), false);
-        HC(cont->hc, hc_sync(cont->hc));                                                               // hand-over to the bootstrapper's context (another stream)
-        std::vector<const uint64_t *> conv_d; for (const Ciphertext &ct : ct_conv) conv_d.push_back(ct.d);
+        std::vector<Ciphertext> ct_conv = evalConv_BN_batch(cont, enc, tc.ker_in, tc.bn_a, tc.bn_b, in_wid, ker_wid, in_batch, in_batch, norm, chain_out_scale(pow_), false);
         auto layer = now();
-        std::vector<BootCiphertext> ct_res = evalConv_BNRelu_tail_batch(cont->btp, "StrConv", 0, conv_d, ct_conv[0].Scale, alpha, pow_, in_wid, kp_wid, nullptr, "", pos);
+        std::vector<BootCiphertext> ct_res = conv_tail(cont, ct_conv, "StrConv", 0, alpha, pow_, in_wid, kp_wid, nullptr, "", pos);
         if (nimg > 1) printf("Bootstrapping + ReLU of %d ciphertexts done in %s \n", nimg, dur(layer).c_str());
-        start = now();
+        auto start = now();
         std::vector<double> cfs = bootDecryptDecodeCoeffs(cont->btp, ct_res[0]);
         printf("Decryption Done in %s \n", dur(start).c_str());
         if (const char *dump = testOnlyEnv("HCONV_STRCONV_DUMP")) {                                     // test mode: the N decoded coefficients of image 0, raw doubles, for a check outside this driver
             FILE *f = fopen(dump, "wb"); if (!f || fwrite(cfs.data(), sizeof(double), cfs.size(), f) != cfs.size()) panic(std::string("HCONV_STRCONV_DUMP: cannot write ") + dump); fclose(f);
         }
-        // the kept cells: (y', x', c + B pos) of the out_wid grid, y', x' < raw_out_wid; everything else is outside
-        auto kept_of = [&](const std::vector<double> &cf, double *outside) {
-            std::vector<double> kept((size_t)raw_out_wid * raw_out_wid * in_batch); double mx = 0;
-            for (int y = 0; y < out_wid; y++) for (int x = 0; x < out_wid; x++) for (int s = 0; s < out_slots; s++) {
-                const double v = cf[(size_t)(y * out_wid + x) * out_slots + s];
-                if (y < raw_out_wid && x < raw_out_wid && s / in_batch == pos) kept[(size_t)(y * raw_out_wid + x) * in_batch + (size_t)(s % in_batch)] = v; else mx = std::max(mx, fabs(v));
-            }
-            *outside = mx; return kept; };
         double outside = 0;
         std::vector<double> test_out = kept_of(cfs, &outside);
-        std::vector<double> real_out = readTxt(pre + "reluout" + suf, raw_out_wid * raw_out_wid * in_batch);
+        std::vector<double> real_out = tc.expected(true, raw_out_wid * raw_out_wid * in_batch);
         printDebugCfsPlain(test_out, real_out);
         double err = 0; for (size_t i = 0; i < real_out.size(); i++) err = std::max(err, fabs(test_out[i] - real_out[i]));
         printf("stride layer: max |error| on the kept cells = %.6g, max |coefficient| outside them = %.6g\n", err, outside);
-        for (int z = 1; z < nimg; z++) {
-            double oz = 0; std::vector<double> cz = kept_of(bootDecryptDecodeCoeffs(cont->btp, ct_res[(size_t)z]), &oz);
-            double mx = 0, mr = 0; for (size_t i = 0; i < cz.size(); i++) { mx = std::max(mx, fabs(cz[i] - test_out[i])); mr = std::max(mr, fabs(cz[i] - real_out[i])); }
-            printf("image %d of the batch: max |difference| to image 0 = %.3g, to the expected output = %.3g, outside the kept cells = %.3g\n", z, mx, mr, oz);
-        }
+        print_batch_agreement(test_out, real_out, nimg, [&](int z, double *oz) { return kept_of(bootDecryptDecodeCoeffs(cont->btp, ct_res[(size_t)z]), oz); }, true);
         print_boot_stats(cont);
-        for (Ciphertext &ct : enc) freeCt(cont, ct);
-        for (Ciphertext &ct : ct_conv) freeCt(cont, ct);
-        for (BootCiphertext &ct : ct_res) freeBootCt(cont->btp, ct);
+        free_cts(cont, enc); free_cts(cont, ct_conv); free_boot_cts(cont, ct_res);
     }
     freeContext(cont);
 }
@@ -1032,20 +975,16 @@ void testStrConv_in(int in_batch, int in_wid, int ker_wid, int total_test_num, i
 // ---------------------------------------------------------------- testTransConv_in (not a reference routine: testConv_in's shape for kind "TransConv")
 // The reference builds the transposed convolution's operators (set_Variables "TransConv", prep_Input / reshape_ker / prep_Ker with trans) but no
 // command runs them. Here: raw_in_wid = in_wid/2 - ker_wid/2, real_ib = in_batch, real_ob = in_batch/4, norm = 1; the result is TF's
-// conv2d_transpose(strides = 2, padding = 'SAME') on the 2*raw_in_wid grid in the first real_ob channels. Ours only, without bootstrapping.
+// conv2d_transpose(strides = 2, padding = 'SAME') on the 2*raw_in_wid grid in the first real_ob channels. Ours only.
 void testTransConv_in(int in_batch, int in_wid, int ker_wid, int total_test_num, bool boot, bool sparse) {
     const std::string kind = "TransConv";
     const int raw_in_batch = in_batch, raw_in_wid = in_wid / 2 - ker_wid / 2, norm = 1;
-    const std::string test_dir = "test_conv_data/";
     int kp_wid, out_batch, logN; bool trans;
     set_Variables(in_batch, raw_in_wid, in_wid, ker_wid, kind, &kp_wid, &out_batch, &logN, &trans);
-    const int raw_out_batch = out_batch / norm, out_wid = kp_wid;
+    const int raw_out_batch = out_batch / norm, out_wid = kp_wid, out_size = out_wid * out_wid * raw_out_batch;
     if (sparse && !boot) panic("testTransConv_in: the sparse form is a form of the bootstrapping chain");
     Context *cont = newContext(logN, ker_wid, {in_wid}, {kp_wid}, boot, sparse ? "TransConv_sparse" : kind);
-    printf("vec size: log2 =  %d\n", cont->logN);
-    printf("raw input width:  %d\n", raw_in_wid);
-    printf("kernel width:  %d\n", ker_wid);
-    printf("num raw batches in & out:  %d ,  %d\n", raw_in_batch, raw_out_batch);
+    print_shapes(cont, raw_in_wid, ker_wid, raw_in_batch, raw_out_batch);
     if (sparse) printf("layer kind:  TransConv_sparse  log_sparse 2  (output channel o at slot 4*o)\n");
     const int nimg = imageBatch();
     const int ch_step = sparse ? 4 : 1;                                  // the slots between two output channels
@@ -1060,56 +999,28 @@ void testTransConv_in(int in_batch, int in_wid, int ker_wid, int total_test_num,
         return out;
     };
     for (int test_iter = 0; test_iter < total_test_num; test_iter++) {
-        printf("%d -th iter...start\n", test_iter + 1);
-        const std::string pre = test_dir + "test_transconv" + std::to_string(ker_wid) + "_batch_" + std::to_string(in_batch) + "_";
-        const std::string suf = "_" + std::to_string(test_iter) + ".csv";
-        std::vector<double> raw_input = readTxt(pre + "in" + suf, raw_in_wid * raw_in_wid * raw_in_batch);
-        std::vector<double> ker_in = readTxt(pre + "ker" + suf, raw_in_batch * raw_out_batch * ker_wid * ker_wid);
-        std::vector<double> bn_a = readTxt(pre + "bna" + suf, raw_out_batch);
-        std::vector<double> bn_b = readTxt(pre + "bnb" + suf, raw_out_batch);
-        std::vector<double> input = prep_Input(raw_input, raw_in_wid, in_wid, cont->Nn, norm, trans, false);
-        auto start = now();
-        // HCONV_IMAGE_BATCH = n > 1: n independent encryptions of the input (ONE call on the device path) through ONE set of launches (evalConv_BN_batch)
-        std::vector<Ciphertext> ins = EncryptCoeffsBatch(cont, std::vector<const std::vector<double> *>((size_t)nimg, &input), cont->ECD_LV, cont->scale);
-        printf("Encryption done in %s \n", dur(start).c_str());
+        const TestCase tc = read_case(case_stem("transconv", ker_wid, in_batch), test_iter, raw_in_wid * raw_in_wid * raw_in_batch, raw_in_batch * raw_out_batch * ker_wid * ker_wid, raw_out_batch);
+        const std::vector<double> input = prep_Input(tc.raw_input, raw_in_wid, in_wid, cont->Nn, norm, trans, false);
+        // HCONV_IMAGE_BATCH = n > 1: n independent encryptions of the input through ONE set of launches (evalConv_BN_batch)
+        std::vector<Ciphertext> ins = encrypt_inputs(cont, std::vector<const std::vector<double> *>((size_t)nimg, &input));
         if (boot) {                                                                                    // `transconvReLU`: testConv_in's boot branch for the transposed layer
             const double pow_ = 4.0, alpha = 0.0;                                                      // test.go:22
             auto layer = now();
             std::vector<Ciphertext> ct_conv;
-            std::vector<BootCiphertext> ct_res = evalTransConv_BNRelu_batch(cont, ins, ker_in, bn_a, bn_b, alpha, pow_, in_wid, kp_wid, ker_wid, raw_in_batch, raw_out_batch, sparse, &ct_conv);
+            std::vector<BootCiphertext> ct_res = evalTransConv_BNRelu_batch(cont, ins, tc.ker_in, tc.bn_a, tc.bn_b, alpha, pow_, in_wid, kp_wid, ker_wid, raw_in_batch, raw_out_batch, sparse, &ct_conv);
             if (nimg > 1) printf("Convolution + Bootstrapping + ReLU of %d ciphertexts done in %s \n", nimg, dur(layer).c_str());
             if (getenv("HCONV_PRINT_DIGEST")) { printf("convolution out_scale: 2^%d\n", (int)lround(log2(ct_conv[0].Scale))); print_ct_digest(cont, ct_conv[0]); }
-            start = now();
-            std::vector<double> test_out = out_channels(bootDecryptDecodeCoeffs(cont->btp, ct_res[0]));
-            printf("Decryption Done in %s \n", dur(start).c_str());
-            std::vector<double> real_out = readTxt(pre + "reluout" + suf, out_wid * out_wid * raw_out_batch);
-            printDebugCfsPlain(test_out, real_out);
-            for (int z = 1; z < nimg; z++) {
-                std::vector<double> cz = out_channels(bootDecryptDecodeCoeffs(cont->btp, ct_res[(size_t)z]));
-                double mx = 0, mr = 0; for (size_t i = 0; i < cz.size(); i++) { mx = std::max(mx, fabs(cz[i] - test_out[i])); mr = std::max(mr, fabs(cz[i] - real_out[i])); }
-                printf("image %d of the batch: max |difference| to image 0 = %.3g, to the expected output = %.3g\n", z, mx, mr);
-            }
+            report_case(now(), tc, true, out_size, nimg, [&](int z, double *) { return out_channels(bootDecryptDecodeCoeffs(cont->btp, ct_res[(size_t)z])); });
             print_boot_stats(cont);
-            for (Ciphertext &ct : ins) freeCt(cont, ct);
-            for (Ciphertext &ct : ct_conv) freeCt(cont, ct);
-            for (BootCiphertext &ct : ct_res) freeBootCt(cont->btp, ct);
+            free_cts(cont, ins); free_cts(cont, ct_conv); free_boot_cts(cont, ct_res);
             continue;
         }
-        std::vector<Ciphertext> ct_result = evalConv_BN_batch(cont, ins, ker_in, bn_a, bn_b, in_wid, ker_wid, raw_in_batch, raw_out_batch, norm, conv_out_scale, trans);
+        std::vector<Ciphertext> ct_result = evalConv_BN_batch(cont, ins, tc.ker_in, tc.bn_a, tc.bn_b, in_wid, ker_wid, raw_in_batch, raw_out_batch, norm, conv_out_scale, trans);
         if (getenv("HCONV_PRINT_DIGEST")) print_ct_digest(cont, ct_result[0]);      // lets tests compare code paths bit for bit
-        start = now();
-        std::vector<std::vector<double>> dec = DecryptDecodeCoeffsBatch(cont, ct_result);
-        std::vector<double> test_out = out_channels(dec[0]);
-        printf("Decryption Done in %s \n", dur(start).c_str());
-        std::vector<double> real_out = readTxt(pre + "out" + suf, out_wid * out_wid * raw_out_batch);
-        printDebugCfsPlain(test_out, real_out);
-        for (int z = 1; z < nimg; z++) {                                                               // the other encryptions decrypt to the same values up to the scheme's noise
-            std::vector<double> cz = out_channels(dec[(size_t)z]);
-            double mx = 0, mr = 0; for (size_t i = 0; i < cz.size(); i++) { mx = std::max(mx, fabs(cz[i] - test_out[i])); mr = std::max(mr, fabs(cz[i] - real_out[i])); }
-            printf("image %d of the batch: max |difference| to image 0 = %.3g, to the expected output = %.3g\n", z, mx, mr);
-        }
-        for (Ciphertext &ct : ins) freeCt(cont, ct);
-        for (Ciphertext &ct : ct_result) freeCt(cont, ct);
+        auto start = now();
+        const std::vector<std::vector<double>> dec = DecryptDecodeCoeffsBatch(cont, ct_result);
+        report_case(start, tc, false, out_size, nimg, [&](int z, double *) { return out_channels(dec[(size_t)z]); });
+        free_cts(cont, ins); free_cts(cont, ct_result);
     }
     freeContext(cont);
 }

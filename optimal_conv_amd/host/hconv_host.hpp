@@ -21,8 +21,11 @@
 // Keys/encryption/decryption are harness-only (the reference draws them from crypto-random; nothing to match):
 // implemented here on the host with every NTT done on the GPU through the ABI.
 #pragma once
+#include <math.h>
 #include <stdint.h>
+#include <stdio.h>
 
+#include <chrono>
 #include <map>
 #include <string>
 #include <vector>
@@ -44,6 +47,26 @@ extern const std::vector<uint64_t> PARAMS6_P;      // bootstrapping key-switch p
 static const uint64_t PACK_P = 0x1fffffffffe00001ull;   // main.go:449
 
 [[noreturn]] void panic(const std::string &msg);        // Go's panic(): message to stderr, exit status 2
+// a failing library call is a panic with the call's text and the context's last error
+#define HC(c, call) do { int rc_ = (call); if (rc_) panic(std::string(#call) + ": " + hc_last_error(c)); } while (0)
+inline uint64_t mulmod(uint64_t a, uint64_t b, uint64_t q) { return (uint64_t)(((u128)a * b) % q); }
+inline uint64_t addmod(uint64_t a, uint64_t b, uint64_t q) { uint64_t r = a + b; return r >= q ? r - q : r; }
+inline uint64_t submod(uint64_t a, uint64_t b, uint64_t q) { return a >= b ? a - b : a + q - b; }
+inline uint64_t to_mont(uint64_t a, uint64_t q) { return (uint64_t)((((u128)a) << 64) % q); }
+// the timers of the console lines: Go's time.Duration.String() shape ("57.154502ms", "3.40439908s"), and seconds as a number
+inline std::chrono::steady_clock::time_point now() { return std::chrono::steady_clock::now(); }
+inline std::string dur_ns(double ns) {
+    char b[64];
+    if (ns < 1e3) snprintf(b, sizeof b, "%.0fns", ns);
+    else if (ns < 1e6) snprintf(b, sizeof b, "%.6gµs", ns / 1e3);
+    else if (ns < 1e9) snprintf(b, sizeof b, "%.9gms", ns / 1e6);
+    else snprintf(b, sizeof b, "%.9gs", ns / 1e9);
+    return b;
+}
+inline std::string dur(std::chrono::steady_clock::time_point t0) { return dur_ns((double)std::chrono::duration_cast<std::chrono::nanoseconds>(now() - t0).count()); }
+inline double secs(std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double>(now() - t0).count(); }
+// eval.go:433: the out_scale of a convolution that a bootstrapping chain follows
+inline double chain_out_scale(double pow) { return exp2(round(log2((double)PARAMS6_Q[0]) - (pow + 8))); }
 // The library reads no configuration from the environment (include/hconv.h); this CLI does, and hands it over as options right after every hc_ctx_create:
 // HCONV_ASYNC_ALLOC (0 / 1 / 2), HCONV_SMALL32, HCONV_ROT_FUSE, HCONV_PACK32 (A/B switches; same residues in every setting). pack32_default: the value a context takes
 // when HCONV_PACK32 is unset (-1: the library's own default)
@@ -258,6 +281,11 @@ Ciphertext evalConv_BN(Context *cont, const Ciphertext &ct_input, const std::vec
                        const std::vector<double> &bn_b, int in_wid, int ker_wid, int real_ib, int real_ob, int norm, double out_scale, bool trans,
                        int dilation = 1, int ib_stride = 1, int ob_stride = 1);
 void testConv_in(int in_batch, int in_wid, int ker_wid, int total_test_num, bool boot);
+// The marshalling of ONE hc_conv_then_pack_batch call. groups: the images of a launch set, each with one input ciphertext per entry of kers (ciphertext j of every group goes
+// with kers[j]); all inputs share level and scale (checked). bias (or nullptr): added once per group. Returns one fresh level-0 ciphertext per group at the scale the library
+// reports. The call is queued, not waited for, and nothing is printed: the callers sync and print their own timing lines.
+std::vector<Ciphertext> conv_then_pack_batch(Context *cont, const std::vector<std::vector<Ciphertext>> &groups, const std::vector<const hc_ker *> &kers, double ker_scale, const Plaintext *bias,
+                                             int max_batch, int out_norm, double out_scale);
 // `transconv` (not a reference command): kind "TransConv" through prep_Input / prep_Ker with trans = true and the same conv_then_pack, Ours only.
 // boot (`transconvReLU`): the layer evalTransConv_BNRelu_batch; sparse: its log_sparse = 2 form
 void testTransConv_in(int in_batch, int in_wid, int ker_wid, int total_test_num, bool boot = false, bool sparse = false);
@@ -271,8 +299,11 @@ std::vector<Ciphertext> evalConv_BN_multi_batch(Context *cont, const std::vector
 // `multiconv` (not a reference command): `conv`'s layer with n_in * in_batch input channels in n_in input ciphertexts, Ours only
 // boot (`multiconvReLU`): the layer evalConv_BNRelu_multi_batch
 void testMultiConv_in(int in_batch, int in_wid, int ker_wid, int total_test_num, int n_in, bool boot = false);
-// Layers of the new convolution forms (not reference routines): the convolution at out_scale 2^(round(log2 Q0) - (pow + 8)) (eval.go:433), the hand-over to the
-// bootstrapper's context as testConv_in does it, then evalConv_BNRelu_tail_batch. The results stay with the bootstrapper (bootDecryptDecodeCoeffs / freeBootCt).
+// The hand-over of a layer: hc_sync of the convolution context (the bootstrapper's context runs on another stream), then evalConv_BNRelu_tail_batch on the convolution results'
+// device blocks (keep_idx, mask_key, pack_pos: that function's). ct_conv stays the caller's; the results stay with the bootstrapper (bootDecryptDecodeCoeffs / freeBootCt).
+std::vector<BootCiphertext> conv_tail(Context *cont, const std::vector<Ciphertext> &ct_conv, const std::string &kind, int log_sparse, double alpha, double pow, int in_wid, int kp_wid,
+                                      const std::vector<std::vector<int>> *keep_idx = nullptr, const std::string &mask_key = "", int pack_pos = 0);
+// Layers of the new convolution forms (not reference routines): the convolution at chain_out_scale(pow), then conv_tail.
 // ct_conv_out != nullptr: the convolution results are handed to the caller (who frees them) instead of being freed here.
 // Transposed (a context of kind "TransConv" / "TransConv_sparse" with boot): kp_wid = 2 * raw_in_wid. sparse = false: kind "TransConv", the "Conv" tail on full slots, the
 // real_ob = real_ib / 4 output channels at slots o. sparse = true: kind "TransConv_sparse" at log_sparse = 2: the kernel plaintexts with ob_stride = 4 and the pack tree's

@@ -41,19 +41,10 @@
 
 namespace hconv {
 
-#define HCR(call) do { int rc_ = (call); if (rc_) panic(std::string(#call) + ": " + hc_last_error(hc)); } while (0)
 static const int LV_CTS_TOP = 27, LV_SINE_TOP = 23, LV_RELU_TOP = 15;     // the same in parameter sets [6] and [7]: CtS 27..24, sine 23..16
 static const int SIN_K = 25, SIN_DOUBLE = 2;
 typedef std::map<int, std::vector<cplx>> DiagMat;        // rotation k -> diagonal (n complex values)
 
-static inline uint64_t mulmod(uint64_t a, uint64_t b, uint64_t q) { return (uint64_t)(((u128)a * b) % q); }
-static std::string dur_ns(double ns) {                    // a duration as Go prints it
-    char b[64];
-    if (ns < 1e6) snprintf(b, sizeof b, "%.6gµs", ns / 1e3); else if (ns < 1e9) snprintf(b, sizeof b, "%.9gms", ns / 1e6); else snprintf(b, sizeof b, "%.9gs", ns / 1e9);
-    return b;
-}
-static std::string dur(std::chrono::steady_clock::time_point t0) { return dur_ns((double)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count()); }
-static std::chrono::steady_clock::time_point now() { return std::chrono::steady_clock::now(); }
 static int bit_length(int x) { int b = 0; while (x) { b++; x >>= 1; } return b; }
 
 // device-resident ciphertext: two polynomials, each a pooled block of NQ rows of which rows 0..level are live
@@ -107,7 +98,7 @@ struct Boot {
     int nb_max = 1, nb = 1;
     size_t poly_stride() const { return (size_t)NQ * N; }
     size_t qp_stride() const { return (size_t)2 * (NQ + P.size()) * N; }
-    void set_nb(int n) { if (n < 1 || n > nb_max) panic("image batch out of range"); nb = n; HCR(hc_set_batch(hc, n, poly_stride(), qp_stride())); }
+    void set_nb(int n) { if (n < 1 || n > nb_max) panic("image batch out of range"); nb = n; HC(hc, hc_set_batch(hc, n, poly_stride(), qp_stride())); }
     // 4-byte rows (include/hconv.h, option pack32 = 2: the bootstrapping contexts run with it unless HCONV_PACK32 says otherwise): the rows of the ~30-bit limbs of every leveled
     // operand on the device are N 4-byte words at the row's address. The host converts only where IT reads or writes such rows: rows[0 .. nl) <-> limbs 0 .. nl - 1 (rows beyond
     // are special primes: large). Ciphertexts enter and leave the chain at levels 0 / 1 (large limbs), so the layers themselves convert nothing.
@@ -133,7 +124,7 @@ struct Boot {
     std::shared_ptr<uint64_t> pooled(std::vector<uint64_t *> &from, size_t bytes) {
         uint64_t *d;
         if (!from.empty()) { d = from.back(); from.pop_back(); }
-        else { void *v = nullptr; HCR(hc_malloc(hc, bytes, &v)); d = (uint64_t *)v; }
+        else { void *v = nullptr; HC(hc, hc_malloc(hc, bytes, &v)); d = (uint64_t *)v; }
         return std::shared_ptr<uint64_t>(d, [&from](uint64_t *x) { from.push_back(x); });
     }
     std::vector<uint64_t *> pool1, pool_qp;
@@ -149,8 +140,8 @@ struct Boot {
         if (a.level != b.level || 2 * nb > nb_max) panic("merge2: halves differ or the blocks are too small");
         DCt r = new_ct(a.level, a.scale); const int n0 = nb;
         for (int d = 0; d < 2; d++) for (int z = 0; z < n0; z++) {
-            HCR(hc_copy(hc, r.p[d].get() + (size_t)z * poly_stride(), a.p[d].get() + (size_t)z * poly_stride(), (size_t)(a.level + 1) * N * 8));
-            HCR(hc_copy(hc, r.p[d].get() + (size_t)(n0 + z) * poly_stride(), b.p[d].get() + (size_t)z * poly_stride(), (size_t)(a.level + 1) * N * 8));
+            HC(hc, hc_copy(hc, r.p[d].get() + (size_t)z * poly_stride(), a.p[d].get() + (size_t)z * poly_stride(), (size_t)(a.level + 1) * N * 8));
+            HC(hc, hc_copy(hc, r.p[d].get() + (size_t)(n0 + z) * poly_stride(), b.p[d].get() + (size_t)z * poly_stride(), (size_t)(a.level + 1) * N * 8));
         }
         set_nb(2 * n0); alg_ct_at_merge = alg_ct;
         return r;
@@ -161,12 +152,12 @@ struct Boot {
         for (int h = 0; h < 2; h++) {
             out[h] = new_ct(m.level, m.scale);
             for (int d = 0; d < 2; d++) for (int z = 0; z < n0; z++)
-                HCR(hc_copy(hc, out[h].p[d].get() + (size_t)z * poly_stride(), m.p[d].get() + (size_t)(h * n0 + z) * poly_stride(), (size_t)(m.level + 1) * N * 8));
+                HC(hc, hc_copy(hc, out[h].p[d].get() + (size_t)z * poly_stride(), m.p[d].get() + (size_t)(h * n0 + z) * poly_stride(), (size_t)(m.level + 1) * N * 8));
         }
     }
     // rows [0, rows) of every image's polynomial: device-to-device copies between batched blocks
     void copy_rows(uint64_t *dst, const uint64_t *src, size_t rows, size_t dst_off_rows = 0, size_t src_off_rows = 0) {
-        for (int z = 0; z < nb; z++) HCR(hc_copy(hc, dst + (size_t)z * poly_stride() + dst_off_rows * N, src + (size_t)z * poly_stride() + src_off_rows * N, rows * N * 8));
+        for (int z = 0; z < nb; z++) HC(hc, hc_copy(hc, dst + (size_t)z * poly_stride() + dst_off_rows * N, src + (size_t)z * poly_stride() + src_off_rows * N, rows * N * 8));
     }
     DCt new_ct(int level, double scale) { DCt c; c.level = level; c.scale = scale; for (int i = 0; i < 2; i++) c.p[i] = block(); return c; }
     static DCt drop_to(const DCt &a, int level) { if (level > a.level) panic("drop_to: level above the ciphertext's"); DCt c = a; c.level = level; return c; }
@@ -202,7 +193,7 @@ struct Boot {
                 replay_rows_id = pid; replay_rows_level = level;
             }
             const uint64_t id = 1 + key_ids.size();
-            HCR(hc_swk_load(hc, id, level, replay_rows.data()));
+            HC(hc, hc_swk_load(hc, id, level, replay_rows.data()));
             key_ids[{ident, level}] = id; n_keys++;
             return id;
         }
@@ -211,7 +202,7 @@ struct Boot {
             std::vector<int64_t> es((size_t)beta * N), e;
             for (int dgt = 0; dgt < beta; dgt++) { replay::gauss(seed ^ (0xE44E44ull + (uint64_t)dgt * 7919), e); std::copy(e.begin(), e.end(), es.begin() + (long)dgt * N); }
             const uint64_t id = 1 + key_ids.size();
-            HCR(hc_swk_generate_splitmix(hc, id, level, gal, d_sk, seed, es.data()));
+            HC(hc, hc_swk_generate_splitmix(hc, id, level, gal, d_sk, seed, es.data()));
             key_ids[{ident, level}] = id; n_keys++;
             return id;
         }
@@ -220,7 +211,7 @@ struct Boot {
         // host and pushed it through one-row launches: 17-28 s per context, now a fraction of a second.
         if (!have_kg_seed) { for (int i = 0; i < 4; i++) { const uint64_t r = next(); kg_seed[2 * i] = (uint32_t)r; kg_seed[2 * i + 1] = (uint32_t)(r >> 32); } have_kg_seed = true; }
         const uint64_t id = 1 + key_ids.size();
-        HCR(hc_swk_generate(hc, id, level, gal, d_sk, kg_seed));
+        HC(hc, hc_swk_generate(hc, id, level, gal, d_sk, kg_seed));
         key_ids[{ident, level}] = id; n_keys++;
         return id;
     }
@@ -233,7 +224,7 @@ struct Boot {
         const int L = std::min(a0.level, b0.level); same_scale(a0.scale, b0.scale);
         DCt r = new_ct(L, a0.scale);
         alg_ct += 6.0 * (L + 1);
-        HCR(hc_lv_op2(hc, HC_LV_ADD, L, a0.p[0].get(), a0.p[1].get(), b0.p[0].get(), b0.p[1].get(), r.p[0].get(), r.p[1].get(), nullptr));   // both polynomials per launch
+        HC(hc, hc_lv_op2(hc, HC_LV_ADD, L, a0.p[0].get(), a0.p[1].get(), b0.p[0].get(), b0.p[1].get(), r.p[0].get(), r.p[1].get(), nullptr));   // both polynomials per launch
         return r;
     }
     std::vector<uint64_t> consts(const u128 mag, bool neg, int level) const {
@@ -251,7 +242,7 @@ struct Boot {
         u128 mag; bool neg; split_int(k_rounded_value, &mag, &neg);
         std::vector<uint64_t> c = consts(mag, neg, a.level);
         DCt r = new_ct(a.level, a.scale); alg_ct += 4.0 * (a.level + 1);
-        HCR(hc_lv_op2(hc, HC_LV_MUL_CONST, a.level, a.p[0].get(), a.p[1].get(), nullptr, nullptr, r.p[0].get(), r.p[1].get(), c.data()));
+        HC(hc, hc_lv_op2(hc, HC_LV_MUL_CONST, a.level, a.p[0].get(), a.p[1].get(), nullptr, nullptr, r.p[0].get(), r.p[1].get(), c.data()));
         return r;
     }
     // sum_t k_t * a_t (+ c0) at `level` as ONE launch (hc_lv_lincomb2): what a leaf of the polynomial evaluators computes with a MultByConst per power and an Add chain.
@@ -268,14 +259,14 @@ struct Boot {
         }
         if (with_c0) { u128 mag; bool neg; split_int(c0, &mag, &neg); cadd = consts(mag, neg, level); }
         DCt r = new_ct(level, scale); alg_ct += (2.0 * (double)nt_ + 2.0) * (level + 1);
-        HCR(hc_lv_lincomb2(hc, level, (int)nt_, p0.data(), p1.data(), cs.data(), with_c0 ? cadd.data() : nullptr, r.p[0].get(), r.p[1].get()));
+        HC(hc, hc_lv_lincomb2(hc, level, (int)nt_, p0.data(), p1.data(), cs.data(), with_c0 ? cadd.data() : nullptr, r.p[0].get(), r.p[1].get()));
         return r;
     }
     DCt add_const_int(const DCt &a, double k_rounded_value) {
         u128 mag; bool neg; split_int(k_rounded_value, &mag, &neg);
         std::vector<uint64_t> c = consts(mag, neg, a.level);
         DCt r = a; r.p[0] = block(); alg_ct += 2.0 * (a.level + 1);
-        HCR(hc_lv_add_const(hc, a.level, a.p[0].get(), c.data(), r.p[0].get()));
+        HC(hc, hc_lv_add_const(hc, a.level, a.p[0].get(), c.data(), r.p[0].get()));
         return r;
     }
     // evaluator.AddConst with a real constant: scaleUpExact(c, scale, q) = floor(|c * scale| + 0.5), sign restored modulo q (the AddConst digests of
@@ -290,14 +281,14 @@ struct Boot {
     DCt mul_plain(const DCt &a, const DPt &pt) {
         if (pt.level < a.level) panic("mul_plain: plaintext below the ciphertext's level");
         DCt r = new_ct(a.level, a.scale * pt.scale); alg_ct += 4.0 * (a.level + 1); alg_shared += a.level + 1;
-        HCR(hc_lv_op2(hc, HC_LV_MUL_PLAIN, a.level, a.p[0].get(), a.p[1].get(), pt.p.get(), nullptr, r.p[0].get(), r.p[1].get(), nullptr));
+        HC(hc, hc_lv_op2(hc, HC_LV_MUL_PLAIN, a.level, a.p[0].get(), a.p[1].get(), pt.p.get(), nullptr, r.p[0].get(), r.p[1].get(), nullptr));
         return r;
     }
     // MultByi = the product by X^(N/2): one HC_LV_MONOMIAL launch, the factor formed in the kernel (no plaintext)
     DCt mul_by_i(const DCt &a) {
         DCt r = new_ct(a.level, a.scale); alg_ct += 4.0 * (a.level + 1); alg_shared += a.level + 1;
         const uint64_t e[2] = {0, (uint64_t)N / 2};
-        HCR(hc_lv_op2(hc, HC_LV_MONOMIAL, a.level, a.p[0].get(), a.p[1].get(), nullptr, nullptr, r.p[0].get(), r.p[1].get(), e));
+        HC(hc, hc_lv_op2(hc, HC_LV_MONOMIAL, a.level, a.p[0].get(), a.p[1].get(), nullptr, nullptr, r.p[0].get(), r.p[1].get(), e));
         return r;
     }
     // X^e1 (a + X^e0 b) in one pass over the operands (HC_LV_MONOMIAL; exponents below 2N, X^N = -1): re + i im is (N/2, 0), i (a - b) is (N, N/2). Counted as the evaluator
@@ -309,15 +300,15 @@ struct Boot {
         alg_ct += 6.0 * (L + 1);
         if (e1 != 0) { alg_ct += 4.0 * (L + 1); alg_shared += L + 1; }
         const uint64_t e[2] = {(uint64_t)e0, (uint64_t)e1};
-        HCR(hc_lv_op2(hc, HC_LV_MONOMIAL, L, a.p[0].get(), a.p[1].get(), b.p[0].get(), b.p[1].get(), r.p[0].get(), r.p[1].get(), e));
+        HC(hc, hc_lv_op2(hc, HC_LV_MONOMIAL, L, a.p[0].get(), a.p[1].get(), b.p[0].get(), b.p[1].get(), r.p[0].get(), r.p[1].get(), e));
         return r;
     }
     DCt mul_relin(const DCt &a, const DCt &b) {                   // evaluator.MulRelin: tensor, key switch of c2 with the rlk
         const int L = std::min(a.level, b.level);
         DCt r = new_ct(L, a.scale * b.scale); alg_ct += 6.0 * (L + 1); alg_shared += ks_rows(L);
         auto d1 = block(), d2 = block();
-        HCR(hc_lv_mul_tensor(hc, L, a.p[0].get(), a.p[1].get(), b.p[0].get(), b.p[1].get(), r.p[0].get(), d1.get(), d2.get()));
-        HCR(hc_keyswitch_add(hc, key(0, L), L, d2.get(), r.p[0].get(), d1.get(), r.p[0].get(), r.p[1].get())); n_keyswitch++;      // (d0 + ks0, d1 + ks1) inside ModDown's last pass
+        HC(hc, hc_lv_mul_tensor(hc, L, a.p[0].get(), a.p[1].get(), b.p[0].get(), b.p[1].get(), r.p[0].get(), d1.get(), d2.get()));
+        HC(hc, hc_keyswitch_add(hc, key(0, L), L, d2.get(), r.p[0].get(), d1.get(), r.p[0].get(), r.p[1].get())); n_keyswitch++;      // (d0 + ks0, d1 + ks1) inside ModDown's last pass
         return r;
     }
     // MulRelin followed by one Rescale: the key switch's ModDown and the rescale share one forward transform per limb (hc_keyswitch_add_rescale); the residues of the two steps
@@ -326,20 +317,20 @@ struct Boot {
         if (L < 2 || no_fused_rescale()) return rescale(mul_relin(a, b));
         DCt r = new_ct(L - 1, a.scale * b.scale / (double)Q[(size_t)L]); alg_ct += 6.0 * (L + 1) + 2.0 * (2 * L + 1); alg_shared += ks_rows(L);
         auto d0 = block(), d1 = block(), d2 = block();
-        HCR(hc_lv_mul_tensor(hc, L, a.p[0].get(), a.p[1].get(), b.p[0].get(), b.p[1].get(), d0.get(), d1.get(), d2.get()));
-        HCR(hc_keyswitch_add_rescale(hc, key(0, L), L, d2.get(), d0.get(), d1.get(), r.p[0].get(), r.p[1].get())); n_keyswitch++;
+        HC(hc, hc_lv_mul_tensor(hc, L, a.p[0].get(), a.p[1].get(), b.p[0].get(), b.p[1].get(), d0.get(), d1.get(), d2.get()));
+        HC(hc, hc_keyswitch_add_rescale(hc, key(0, L), L, d2.get(), d0.get(), d1.get(), r.p[0].get(), r.p[1].get())); n_keyswitch++;
         return r;
     }
     DCt rescale(const DCt &a) {                                     // one DivRoundByLastModulusNTT
         if (a.level < 1) panic("rescale at level 0");
         DCt r = new_ct(a.level - 1, a.scale / (double)Q[(size_t)a.level]); alg_ct += 2.0 * (2 * a.level + 1);
-        HCR(hc_div_round_last2(hc, a.level, a.p[0].get(), a.p[1].get(), r.p[0].get(), r.p[1].get()));     // both polynomials per launch
+        HC(hc, hc_div_round_last2(hc, a.level, a.p[0].get(), a.p[1].get(), r.p[0].get(), r.p[1].get()));     // both polynomials per launch
         return r;
     }
     DCt galois(const DCt &a, uint64_t gal) {                       // evaluator.permuteNTT: key switch c1, + c0, permute both
         const int L = a.level;
         DCt r = new_ct(L, a.scale); alg_ct += 4.0 * (L + 1); alg_shared += ks_rows(L);
-        HCR(hc_keyswitch_rotate(hc, key(gal, L), gal, L, a.p[0].get(), a.p[1].get(), r.p[0].get(), r.p[1].get(), 0)); n_keyswitch++;   // + c0 and the permutation inside ModDown's last pass
+        HC(hc, hc_keyswitch_rotate(hc, key(gal, L), gal, L, a.p[0].get(), a.p[1].get(), r.p[0].get(), r.p[1].get(), 0)); n_keyswitch++;   // + c0 and the permutation inside ModDown's last pass
         return r;
     }
     DCt rotate(const DCt &a, int k) { k = ((k % n) + n) % n; return k == 0 ? a : galois(a, gal_rot(k)); }
@@ -347,7 +338,7 @@ struct Boot {
     DCt mod_raise(const DCt &a, int level) {                        // ckks.(*Bootstrapper).modUp
         if (a.level != 0) panic("mod_raise expects a level-0 ciphertext");
         DCt r = new_ct(level, a.scale); alg_ct += 2.0 + 2.0 * (level + 1);
-        for (int d = 0; d < 2; d++) HCR(hc_lv_mod_raise(hc, level, a.p[d].get(), r.p[d].get()));
+        for (int d = 0; d < 2; d++) HC(hc, hc_lv_mod_raise(hc, level, a.p[d].get(), r.p[d].get()));
         return r;
     }
     // evaluator.SetScale: MultByConst(scale / ct.Scale) unless that is 1, then Rescale(scale) (drop while scale/q_L >= scale/2), then the scale is forced
@@ -362,8 +353,8 @@ struct Boot {
     std::vector<double> debug_coeffs(const DCt &a, int z = 0) {       // image z of a batch: the coefficient doubles
         Single one(this);
         const int L = std::min(a.level, 1); auto t = block();
-        HCR(hc_lv_mul_plain(hc, L, a.p[1].get() + (size_t)z * poly_stride(), d_sk, t.get())); HCR(hc_lv_add(hc, L, a.p[0].get() + (size_t)z * poly_stride(), t.get(), t.get())); HCR(hc_lv_intt(hc, L, t.get(), t.get()));
-        std::vector<uint64_t> m((size_t)(L + 1) * N); HCR(hc_download(hc, m.data(), t.get(), m.size() * 8));
+        HC(hc, hc_lv_mul_plain(hc, L, a.p[1].get() + (size_t)z * poly_stride(), d_sk, t.get())); HC(hc, hc_lv_add(hc, L, a.p[0].get() + (size_t)z * poly_stride(), t.get(), t.get())); HC(hc, hc_lv_intt(hc, L, t.get(), t.get()));
+        std::vector<uint64_t> m((size_t)(L + 1) * N); HC(hc, hc_download(hc, m.data(), t.get(), m.size() * 8));
         std::vector<double> cf((size_t)N);
         if (L == 0) { const uint64_t q0 = Q[0]; for (int j = 0; j < N; j++) cf[(size_t)j] = (m[(size_t)j] > q0 / 2 ? -(double)(q0 - m[(size_t)j]) : (double)m[(size_t)j]) / a.scale; }
         else {
@@ -403,10 +394,10 @@ struct Boot {
         if (((size_t)1 << lg) != n || lg > LOGN - 1) panic("encode_device: a slot vector of 2^k <= N/2 values expected");
         std::vector<cplx> flat(vals.size() * n);
         for (size_t z = 0; z < vals.size(); z++) { if (vals[z]->size() != n) panic("encode_device: vectors of one length expected"); std::copy(vals[z]->begin(), vals[z]->end(), flat.begin() + z * n); }
-        void *dv = nullptr; HCR(hc_malloc(hc, flat.size() * sizeof(cplx), &dv));
-        HCR(hc_upload(hc, dv, flat.data(), flat.size() * sizeof(cplx)));
-        HCR(hc_encode_slots_ex(hc, (double *)dv, (int)vals.size(), lg, level, with_p ? 1 : 0, scale, 1, out));
-        HCR(hc_free(hc, dv));
+        void *dv = nullptr; HC(hc, hc_malloc(hc, flat.size() * sizeof(cplx), &dv));
+        HC(hc, hc_upload(hc, dv, flat.data(), flat.size() * sizeof(cplx)));
+        HC(hc, hc_encode_slots_ex(hc, (double *)dv, (int)vals.size(), lg, level, with_p ? 1 : 0, scale, 1, out));
+        HC(hc, hc_free(hc, dv));
     }
     DPt encode(const std::vector<cplx> &slots, int level, double scale) {
         n_enc_mask++;
@@ -415,8 +406,8 @@ struct Boot {
         Single one(this);
         DPt pt; pt.level = level; pt.scale = scale; pt.p = block1();
         pack_rows(rows, level + 1);
-        HCR(hc_upload(hc, pt.p.get(), rows.data(), rows.size() * 8));
-        HCR(hc_lv_ntt(hc, level, pt.p.get(), pt.p.get()));
+        HC(hc, hc_upload(hc, pt.p.get(), rows.data(), rows.size() * 8));
+        HC(hc, hc_lv_ntt(hc, level, pt.p.get(), pt.p.get()));
         return pt;
     }
 
@@ -433,11 +424,11 @@ struct Boot {
         }
         Single one(this);
         DPt pt; pt.level = level; pt.scale = scale;
-        { void *v = nullptr; HCR(hc_malloc(hc, rows.size() * 8, &v)); uint64_t *d = (uint64_t *)v; hc_ctx *h = hc; pt.p = std::shared_ptr<uint64_t>(d, [h](uint64_t *x) { hc_free(h, x); }); }
+        { void *v = nullptr; HC(hc, hc_malloc(hc, rows.size() * 8, &v)); uint64_t *d = (uint64_t *)v; hc_ctx *h = hc; pt.p = std::shared_ptr<uint64_t>(d, [h](uint64_t *x) { hc_free(h, x); }); }
         pack_rows(rows, nl);
-        HCR(hc_upload(hc, pt.p.get(), rows.data(), rows.size() * 8));
-        HCR(hc_lv_ntt(hc, level, pt.p.get(), pt.p.get()));
-        for (int j = 0; j < np; j++) { uint64_t *r = pt.p.get() + (size_t)(nl + j) * N; HCR(hc_ntt(hc, NQ + j, r, r, 1)); }
+        HC(hc, hc_upload(hc, pt.p.get(), rows.data(), rows.size() * 8));
+        HC(hc, hc_lv_ntt(hc, level, pt.p.get(), pt.p.get()));
+        for (int j = 0; j < np; j++) { uint64_t *r = pt.p.get() + (size_t)(nl + j) * N; HC(hc, hc_ntt(hc, NQ + j, r, r, 1)); }
         return pt;
     }
 
@@ -545,7 +536,7 @@ struct Boot {
             if (diags.size() < per_call && left) continue;
             if (!dev_encode) lt.giant[diags[0].g][diags[0].b] = encode_qp(diags[0].rolled, level, pt_scale);
             else {
-                void *v = nullptr; HCR(hc_malloc(hc, diags.size() * nt * N * 8, &v)); hc_ctx *h = hc;
+                void *v = nullptr; HC(hc, hc_malloc(hc, diags.size() * nt * N * 8, &v)); hc_ctx *h = hc;
                 std::shared_ptr<uint64_t> base((uint64_t *)v, [h](uint64_t *x) { hc_free(h, x); });
                 std::vector<const std::vector<cplx> *> vals; for (auto &x : diags) vals.push_back(&x.rolled);
                 encode_device(vals, level, true, pt_scale, base.get());
@@ -561,12 +552,12 @@ struct Boot {
         if (!dft_digests) return;
         Sha256 hv; hv.update(rolled.data(), rolled.size() * sizeof(cplx));
         std::vector<uint64_t> rows((size_t)(level + 1) * N), zero((size_t)N, 0);
-        HCR(hc_download(hc, rows.data(), lt.giant.at(g).at(b).p.get(), rows.size() * 8));
+        HC(hc, hc_download(hc, rows.data(), lt.giant.at(g).at(b).p.get(), rows.size() * 8));
         unpack_rows(rows, level + 1);
         for (int l = 0; l <= level; l++) { const uint64_t q = Q[(size_t)l], r = (uint64_t)((((u128)1) << 64) % q); for (int j = 0; j < N; j++) rows[(size_t)l * N + j] = mulmod(rows[(size_t)l * N + j], r, q); }
         Sha256 hq; hq.update(rows.data(), rows.size() * 8); hq.update(zero.data(), zero.size() * 8);
         const int np = (int)P.size(); std::vector<uint64_t> prow((size_t)np * N);
-        HCR(hc_download(hc, prow.data(), lt.giant.at(g).at(b).p.get() + (size_t)(level + 1) * N, prow.size() * 8));
+        HC(hc, hc_download(hc, prow.data(), lt.giant.at(g).at(b).p.get() + (size_t)(level + 1) * N, prow.size() * 8));
         for (int j = 0; j < np; j++) { const uint64_t q = P[(size_t)j], r = (uint64_t)((((u128)1) << 64) % q); for (int i = 0; i < N; i++) prow[(size_t)j * N + i] = mulmod(prow[(size_t)j * N + i], r, q); }
         Sha256 hp; hp.update(prow.data(), prow.size() * 8);
         fprintf(dft_digests, "{\"matrix\": \"%s\", \"chain\": %d, \"level\": %d, \"scale\": %.17g, \"N1\": %d, \"k\": %d, \"values\": \"%s\", \"mQ\": \"%s\", \"mP\": \"%s\"}\n", tag, chain, level, pt_scale, lt.n1, k, hv.hex().c_str(), hq.hex().c_str(), hp.hex().c_str());
@@ -599,39 +590,39 @@ struct Boot {
         for (auto &g : lt.giant) if (g.first) key(gal_rot(g.first), L, 2);
         std::vector<uint64_t> pmod((size_t)nl), zeros((size_t)nl, 0);
         for (int l = 0; l < nl; l++) { uint64_t r = 1; for (uint64_t pj : P) r = mulmod(r, pj % Q[(size_t)l], Q[(size_t)l]); pmod[(size_t)l] = r; }
-        auto pc0 = block(); HCR(hc_lv_mul_const(hc, L, ct.p[0].get(), pmod.data(), pc0.get()));                       // P * c0
+        auto pc0 = block(); HC(hc, hc_lv_mul_const(hc, L, ct.p[0].get(), pmod.data(), pc0.get()));                       // P * c0
         std::map<int, std::shared_ptr<uint64_t>> rot;
         if (!babies.empty()) {
             const uint64_t *cx = hoist_c1 ? hoist_c1 : ct.p[1].get();
-            HCR(hc_keyswitch_decompose(hc, Lb, cx));
+            HC(hc, hc_keyswitch_decompose(hc, Lb, cx));
             auto wide = hoist_c1 ? block_qp2() : std::shared_ptr<uint64_t>();
             if (hoist_c1 && nb != 1) panic("linear_transform_qp: the stale-digit hoisting of the stock Bootstrapp runs one image at a time");
             if (!hoist_c1) {                                                                                            // all baby steps: inner products sharing the digit reads, + P c0, permutation
                 std::vector<uint64_t> ids, gals; std::vector<uint64_t *> outs;
                 for (int b : babies) { const uint64_t gal = gal_rot(b); auto r = block_qp2(); ids.push_back(key(gal, L, 1)); gals.push_back(gal); outs.push_back(r.get()); rot[b] = r; n_keyswitch++; }
                 static const bool one_by_one = getenv("HCONV_ROTATE_ONE_BY_ONE") != nullptr;
-                if (!one_by_one) HCR(hc_keyswitch_qp_rotate_many(hc, (int)ids.size(), ids.data(), gals.data(), L, pc0.get(), cx, outs.data()));
-                else for (size_t i = 0; i < ids.size(); i++) HCR(hc_keyswitch_qp_rotate(hc, ids[i], gals[i], L, pc0.get(), cx, outs[i], 1, 0));
+                if (!one_by_one) HC(hc, hc_keyswitch_qp_rotate_many(hc, (int)ids.size(), ids.data(), gals.data(), L, pc0.get(), cx, outs.data()));
+                else for (size_t i = 0; i < ids.size(); i++) HC(hc, hc_keyswitch_qp_rotate(hc, ids[i], gals[i], L, pc0.get(), cx, outs[i], 1, 0));
             } else for (int b : babies) {
                 const uint64_t gal = gal_rot(b);
                 auto r = block_qp2();
                 {                                                                                                  // [2][Lb+1+np][N] -> rows 0..L and the P rows of each component
                     auto acc = block_qp2();
-                    HCR(hc_keyswitch_qp(hc, key(gal, Lb, 1), Lb, cx, wide.get(), 1));
+                    HC(hc, hc_keyswitch_qp(hc, key(gal, Lb, 1), Lb, cx, wide.get(), 1));
                     const size_t zw = (size_t)(Lb + 1 + np) * N;
                     for (int k = 0; k < 2; k++) {
-                        HCR(hc_copy(hc, acc.get() + (size_t)k * zs, wide.get() + (size_t)k * zw, (size_t)nl * N * 8));
-                        HCR(hc_copy(hc, acc.get() + (size_t)k * zs + (size_t)nl * N, wide.get() + (size_t)k * zw + (size_t)(Lb + 1) * N, (size_t)np * N * 8));
+                        HC(hc, hc_copy(hc, acc.get() + (size_t)k * zs, wide.get() + (size_t)k * zw, (size_t)nl * N * 8));
+                        HC(hc, hc_copy(hc, acc.get() + (size_t)k * zs + (size_t)nl * N, wide.get() + (size_t)k * zw + (size_t)(Lb + 1) * N, (size_t)np * N * 8));
                     }
-                    HCR(hc_lv_add(hc, L, acc.get(), pc0.get(), acc.get()));                                              // the Q rows of the first component
-                    HCR(hc_qp_permute2(hc, gal, L, acc.get(), r.get()));
+                    HC(hc, hc_lv_add(hc, L, acc.get(), pc0.get(), acc.get()));                                              // the Q rows of the first component
+                    HC(hc, hc_qp_permute2(hc, gal, L, acc.get(), r.get()));
                 }
                 n_keyswitch++;
                 rot[b] = r;
             }
         }
         DCt res = new_ct(L, ct.scale * lt.pt_scale); bool have_res[2] = {false, false};
-        auto add_to_res = [&](int k, const std::shared_ptr<uint64_t> &x) { if (have_res[k]) HCR(hc_lv_add(hc, L, res.p[k].get(), x.get(), res.p[k].get())); else { res.p[k] = x; have_res[k] = true; } };
+        auto add_to_res = [&](int k, const std::shared_ptr<uint64_t> &x) { if (have_res[k]) HC(hc, hc_lv_add(hc, L, res.p[k].get(), x.get(), res.p[k].get())); else { res.p[k] = x; have_res[k] = true; } };
         auto B = block_qp2(); bool haveB = false;
         // the diagonal sums of all giant steps first, THREE per pass over the rotations (hc_qp_mul_sum_many, up to four: the rotated ciphertexts - the largest operands of a linear transform - are
         // read once per group instead of once per giant step); giant step 0's sum lands in the accumulators B, which the other giant steps' key switches then add to
@@ -652,7 +643,7 @@ struct Boot {
             std::vector<const uint64_t *> as, pts(ng * un.size(), nullptr); std::vector<uint64_t *> outs; std::vector<int> accs(ng, 0);
             size_t t = 0; for (int i : un) { as.push_back(rot[i].get()); for (size_t v = 0; v < ng; v++) if (sums[u + v].pt.count(i)) pts[v * un.size() + t] = sums[u + v].pt[i]; t++; }
             for (size_t v = 0; v < ng; v++) outs.push_back(sums[u + v].out);
-            HCR(hc_qp_mul_sum_many(hc, L, (int)as.size(), (int)ng, as.data(), pts.data(), outs.data(), accs.data()));
+            HC(hc, hc_qp_mul_sum_many(hc, L, (int)as.size(), (int)ng, as.data(), pts.data(), outs.data(), accs.data()));
         }
         for (auto &ix : index) {
             const int j = ix.first; if (j == 0) continue;
@@ -660,28 +651,28 @@ struct Boot {
             const auto &row = lt.giant.at(g);
             const bool haveA = Aof.count(j) != 0;
             auto a0 = block(), a1 = block();
-            if (haveA) HCR(hc_mod_down2(hc, L, Aof[j].get(), a0.get(), a1.get()));
-            else { HCR(hc_lv_mul_const(hc, L, ct.p[0].get(), zeros.data(), a0.get())); HCR(hc_lv_mul_const(hc, L, ct.p[0].get(), zeros.data(), a1.get())); }
-            if (row.count(0)) { const uint64_t *pt = row.at(0).p.get(); HCR(hc_lv_op2(hc, HC_LV_MUL_ACC_PLAIN, L, ct.p[0].get(), ct.p[1].get(), pt, nullptr, a0.get(), a1.get(), nullptr)); }
-            { auto t = block(); HCR(hc_lv_permute(hc, gal, L, a0.get(), t.get())); add_to_res(0, t); }
-            HCR(hc_keyswitch_qp_rotate(hc, key(gal, L, 2), gal, L, nullptr, a1.get(), B.get(), 0, haveB ? 1 : 0)); n_keyswitch++; haveB = true;     // SwitchKeysInPlaceNoModDown, permuted into the accumulators
+            if (haveA) HC(hc, hc_mod_down2(hc, L, Aof[j].get(), a0.get(), a1.get()));
+            else { HC(hc, hc_lv_mul_const(hc, L, ct.p[0].get(), zeros.data(), a0.get())); HC(hc, hc_lv_mul_const(hc, L, ct.p[0].get(), zeros.data(), a1.get())); }
+            if (row.count(0)) { const uint64_t *pt = row.at(0).p.get(); HC(hc, hc_lv_op2(hc, HC_LV_MUL_ACC_PLAIN, L, ct.p[0].get(), ct.p[1].get(), pt, nullptr, a0.get(), a1.get(), nullptr)); }
+            { auto t = block(); HC(hc, hc_lv_permute(hc, gal, L, a0.get(), t.get())); add_to_res(0, t); }
+            HC(hc, hc_keyswitch_qp_rotate(hc, key(gal, L, 2), gal, L, nullptr, a1.get(), B.get(), 0, haveB ? 1 : 0)); n_keyswitch++; haveB = true;     // SwitchKeysInPlaceNoModDown, permuted into the accumulators
             Aof.erase(j);
         }
         const bool fuse = fuse_min_scale > 0 && haveB && L >= 2 && !no_fused_rescale() && res.scale / (double)Q[(size_t)L] >= fuse_min_scale / 2;
         auto diag0 = [&]() {
             if (!(lt.giant.count(0) && lt.giant.at(0).count(0))) return;
             const uint64_t *pt = lt.giant.at(0).at(0).p.get();
-            if (have_res[0] && have_res[1]) HCR(hc_lv_op2(hc, HC_LV_MUL_ACC_PLAIN, L, ct.p[0].get(), ct.p[1].get(), pt, nullptr, res.p[0].get(), res.p[1].get(), nullptr));
-            else for (int k = 0; k < 2; k++) { auto t = block(); HCR(hc_lv_mul_plain(hc, L, ct.p[k].get(), pt, t.get())); add_to_res(k, t); }
+            if (have_res[0] && have_res[1]) HC(hc, hc_lv_op2(hc, HC_LV_MUL_ACC_PLAIN, L, ct.p[0].get(), ct.p[1].get(), pt, nullptr, res.p[0].get(), res.p[1].get(), nullptr));
+            else for (int k = 0; k < 2; k++) { auto t = block(); HC(hc, hc_lv_mul_plain(hc, L, ct.p[k].get(), pt, t.get())); add_to_res(k, t); }
         };
         if (fuse) {            // every other term first (modular sums commute), then ModDown(B) + them + the first drop of the caller's Rescale in one pass
             diag0();
-            if (have_res[0] != have_res[1]) for (int k = 0; k < 2; k++) if (!have_res[k]) { auto z = block(); HCR(hc_lv_mul_const(hc, L, ct.p[k].get(), zeros.data(), z.get())); add_to_res(k, z); }
+            if (have_res[0] != have_res[1]) for (int k = 0; k < 2; k++) if (!have_res[k]) { auto z = block(); HC(hc, hc_lv_mul_const(hc, L, ct.p[k].get(), zeros.data(), z.get())); add_to_res(k, z); }
             DCt out = new_ct(L - 1, res.scale / (double)Q[(size_t)L]); alg_ct += 2.0 * (2 * L + 1);
-            HCR(hc_mod_down2_add_rescale(hc, L, B.get(), have_res[0] ? res.p[0].get() : nullptr, have_res[0] ? res.p[1].get() : nullptr, out.p[0].get(), out.p[1].get()));
+            HC(hc, hc_mod_down2_add_rescale(hc, L, B.get(), have_res[0] ? res.p[0].get() : nullptr, have_res[0] ? res.p[1].get() : nullptr, out.p[0].get(), out.p[1].get()));
             return out;
         }
-        if (haveB) { auto d0 = block(), d1 = block(); HCR(hc_mod_down2(hc, L, B.get(), d0.get(), d1.get())); add_to_res(0, d0); add_to_res(1, d1); }
+        if (haveB) { auto d0 = block(), d1 = block(); HC(hc, hc_mod_down2(hc, L, B.get(), d0.get(), d1.get())); add_to_res(0, d0); add_to_res(1, d1); }
         diag0();
         if (!have_res[0] || !have_res[1]) panic("linear_transform_qp: empty matrix");
         return res;
@@ -720,9 +711,9 @@ struct Boot {
         const DCt bb = k > 1 ? mul_const_int(tmp, k) : tmp;
         DCt r = new_ct(L - 1, ps / (double)Q[(size_t)L]); alg_ct += 6.0 * (L + 1) + 6.0 * (L + 1) + 2.0 * (2 * L + 1); alg_shared += ks_rows(L);
         auto d0 = block(), d1 = block(), d2 = block();
-        HCR(hc_lv_mul_tensor(hc, L, a.p[0].get(), a.p[1].get(), b.p[0].get(), b.p[1].get(), d0.get(), d1.get(), d2.get()));
-        HCR(hc_lv_op2(hc, HC_LV_ADD, L, d0.get(), d1.get(), bb.p[0].get(), bb.p[1].get(), d0.get(), d1.get(), nullptr));
-        HCR(hc_keyswitch_add_rescale(hc, key(0, L), L, d2.get(), d0.get(), d1.get(), r.p[0].get(), r.p[1].get())); n_keyswitch++;
+        HC(hc, hc_lv_mul_tensor(hc, L, a.p[0].get(), a.p[1].get(), b.p[0].get(), b.p[1].get(), d0.get(), d1.get(), d2.get()));
+        HC(hc, hc_lv_op2(hc, HC_LV_ADD, L, d0.get(), d1.get(), bb.p[0].get(), bb.p[1].get(), d0.get(), d1.get(), nullptr));
+        HC(hc, hc_keyswitch_add_rescale(hc, key(0, L), L, d2.get(), d0.get(), d1.get(), r.p[0].get(), r.p[1].get())); n_keyswitch++;
         return lt_rescale(r, sc);
     }
     // C[n] = C[a] C[b], a = ceil(n/2), b = n/2; Chebyshev: C[n] = 2 C[a] C[b] - C[a-b] (a - b is 0 or 1, and C[1] is the input)
@@ -803,12 +794,12 @@ struct Boot {
         applyEnvOptions(hc, 2);                                                        // pack32 = 2 unless HCONV_PACK32 says otherwise: 4-byte rows for the ~30-bit limbs of every leveled operand (HCONV_PACK32=0 / 1: A/B against the 8-byte forms)
         row32.assign((size_t)NQ, 0); for (int l = 0; l < NQ; l++) row32[(size_t)l] = (char)hc_row_is32(hc, l);
         const int nm = NQ + (int)P.size();
-        { void *v = nullptr; HCR(hc_malloc(hc, (size_t)nm * N * 8, &v)); d_sk = (uint64_t *)v; }
+        { void *v = nullptr; HC(hc, hc_malloc(hc, (size_t)nm * N * 8, &v)); d_sk = (uint64_t *)v; }
         std::vector<uint64_t> h((size_t)N);
         for (int m = 0; m < nm; m++) {
             const uint64_t q = m < NQ ? Q[(size_t)m] : P[(size_t)(m - NQ)];
             for (int j = 0; j < N; j++) h[(size_t)j] = sk[(size_t)j] >= 0 ? (uint64_t)sk[(size_t)j] : q - (uint64_t)(-sk[(size_t)j]);
-            HCR(hc_upload(hc, d_sk + (size_t)m * N, h.data(), (size_t)N * 8)); HCR(hc_ntt(hc, m, d_sk + (size_t)m * N, d_sk + (size_t)m * N, 1));
+            HC(hc, hc_upload(hc, d_sk + (size_t)m * N, h.data(), (size_t)N * 8)); HC(hc, hc_ntt(hc, m, d_sk + (size_t)m * N, d_sk + (size_t)m * N, 1));
         }
         key(2ull * N - 1, LV_SINE_TOP);                                      // conjugation
         for (int l = LV_SINE_TOP; l >= lv_relin_lo; l--) if (chain == 6 || l > LV_RELU_TOP || l <= 12) key(0, l);     // kgen.GenRelinearizationKey (main.go:411), at the levels that multiply
@@ -1069,7 +1060,7 @@ void freeBoot(Boot *b) {
 // HCONV_PROFILE=1: per-kernel HIP-event totals of one layer's tail (hc_set_option("profile")) on stderr; event records between
 // launches perturb the stream, so the printed wall times of such a run are not the ones to quote
 static void profile_dump(Boot *B, const char *label) {
-    hc_ctx *hc = B->hc; char names[8192]; HCR(hc_sync(hc));
+    hc_ctx *hc = B->hc; char names[8192]; HC(hc, hc_sync(hc));
     if (hc_profile_names(hc, names, sizeof names)) return;
     std::vector<std::pair<double, std::string>> rows; double tot = 0; long nl = 0;
     for (char *tok = strtok(names, ","); tok; tok = strtok(nullptr, ",")) { double ms = 0; long n = 0; hc_profile_get(hc, tok, &ms, &n); char b[160]; snprintf(b, sizeof b, "%-28s %6ld launches %8.3f ms %7.1f us/launch", tok, n, ms, n ? 1e3 * ms / (double)n : 0.0); rows.push_back({ms, b}); tot += ms; nl += n; }
@@ -1087,7 +1078,7 @@ static void replay_digest_line(Boot *B, const char *what, const DCt &c, int firs
         const int img = first_image + z;
         std::string line = std::string("replay digest") + (img ? "[" + std::to_string(img) + "] " : " ") + what + " level " + std::to_string(c.level);
         char sc[40]; snprintf(sc, sizeof sc, " scale %.17g", c.scale); line += sc;
-        for (int d = 0; d < 2; d++) { std::vector<uint64_t> rows((size_t)(c.level + 1) * N); HCR(hc_download(hc, rows.data(), c.p[d].get() + (size_t)z * B->poly_stride(), rows.size() * 8)); B->unpack_rows(rows, c.level + 1); Sha256 h; h.update(rows.data(), rows.size() * 8); line += " " + h.hex(); }
+        for (int d = 0; d < 2; d++) { std::vector<uint64_t> rows((size_t)(c.level + 1) * N); HC(hc, hc_download(hc, rows.data(), c.p[d].get() + (size_t)z * B->poly_stride(), rows.size() * 8)); B->unpack_rows(rows, c.level + 1); Sha256 h; h.update(rows.data(), rows.size() * 8); line += " " + h.hex(); }
         printf("%s\n", line.c_str());
     }
 }
@@ -1131,9 +1122,9 @@ struct LayerDebug {
             for (int z = 0; z < B->nb; z++) { c0.push_back(c->p[0].get() + (size_t)z * B->poly_stride()); c1.push_back(c->p[1].get() + (size_t)z * B->poly_stride()); }
         }
         const int count = (int)c0.size(); const size_t per = ls < 0 ? (size_t)N : (size_t)2 << ls;
-        void *v = nullptr; HCR(hc_malloc(hc, (size_t)count * per * 8, &v));
-        HCR(hc_decrypt_decode_lv(hc, count, f.level, c0.data(), c1.data(), B->d_sk, f.scale, ls, (double *)v));
-        std::vector<double> out((size_t)count * per); HCR(hc_download(hc, out.data(), v, out.size() * 8)); HCR(hc_free(hc, v));
+        void *v = nullptr; HC(hc, hc_malloc(hc, (size_t)count * per * 8, &v));
+        HC(hc, hc_decrypt_decode_lv(hc, count, f.level, c0.data(), c1.data(), B->d_sk, f.scale, ls, (double *)v));
+        std::vector<double> out((size_t)count * per); HC(hc, hc_download(hc, out.data(), v, out.size() * 8)); HC(hc, hc_free(hc, v));
         if (check) {
             const int nb = B->nb; size_t k = 0;
             for (const DCt *c : cts) for (int z = 0; z < nb; z++, k++) {
@@ -1255,11 +1246,11 @@ std::vector<BootCiphertext> evalConv_BNRelu_tail_batch(Boot *B, const std::strin
     if (nimg < 1 || nimg > (B->merge_parts ? B->nb_max / 2 : B->nb_max)) panic("evalConv_BNRelu_tail: more images than the bootstrapper's image batch (HCONV_IMAGE_BATCH)");
     Boot::Batch batch_scope(B, nimg); B->alg_ct = B->alg_shared = 0;                                  // hc_set_batch(nimg) here, hc_set_batch(1) wherever this function is left
     DCt ct = B->new_ct(0, ct_scale * pow(2.0, pow_));                                           // eval.go:437
-    for (int z = 0; z < nimg; z++) for (int d = 0; d < 2; d++) HCR(hc_copy(hc, ct.p[d].get() + (size_t)z * B->poly_stride(), ct_conv_dev[(size_t)z] + (size_t)d * N, (size_t)N * 8));
+    for (int z = 0; z < nimg; z++) for (int d = 0; d < 2; d++) HC(hc, hc_copy(hc, ct.p[d].get() + (size_t)z * B->poly_stride(), ct_conv_dev[(size_t)z] + (size_t)d * N, (size_t)N * 8));
     // ct_conv_dev belongs to ANOTHER context (the convolution's): the copies above are queued on this context's stream, and the caller frees
     // the sources as soon as this function returns. Wait for them (the stream holds nothing else at this point) so that the hand-over
     // does not depend on how the two contexts' streams happen to be scheduled (cached allocations recycle a freed block at once).
-    HCR(hc_sync(hc));
+    HC(hc, hc_sync(hc));
     // test mode: image z of the batch is image first_image + z of the replay; image 0 carries the input gotrace -chain plants at the entry of
     // BootstrappConv_CtoS - SEED_OPIN(4000, 0, poly, limb 0) -, image i > 0 the same generator keyed seed + 0x1000003 i (keys are common)
     const int first_image = B->replay_seed && testOnlyEnv("HCONV_REPLAY_IMAGE0") ? atoi(testOnlyEnv("HCONV_REPLAY_IMAGE0")) : 0;
@@ -1270,7 +1261,7 @@ std::vector<BootCiphertext> evalConv_BNRelu_tail_batch(Boot *B, const std::strin
         for (int z = 0; z < nimg; z++) for (int k = 0; k < 2; k++) {
             const uint64_t sd = B->replay_seed + 0x1000003ull * (uint64_t)(first_image + z) + ((6ull << 32) | (uint64_t)((((4000 * 2 + 0) * 4 + k) * 64) + 0));
             for (int j = 0; j < N; j++) row[(size_t)j] = Boot::splitmix_at(sd, (uint64_t)j) % B->Q[0];
-            HCR(hc_upload(hc, ct.p[k].get() + (size_t)z * B->poly_stride(), row.data(), (size_t)N * 8));
+            HC(hc, hc_upload(hc, ct.p[k].get() + (size_t)z * B->poly_stride(), row.data(), (size_t)N * 8));
         }
     }
     const bool prof = profiling();
@@ -1280,7 +1271,7 @@ std::vector<BootCiphertext> evalConv_BNRelu_tail_batch(Boot *B, const std::strin
         dbg.reset(new LayerDebug{B, kind, log_sparse, nimg, in_wid, kp_wid, alpha, pow_, inside ? keep_idx : nullptr, ck && atoi(ck) != 0, {}, {}, pack_pos});
         dbg->after_conv(ct);
     }
-    if (prof) { HCR(hc_set_option(hc, "profile", 1)); hc_profile_get(hc, nullptr, nullptr, nullptr); }
+    if (prof) { HC(hc, hc_set_option(hc, "profile", 1)); hc_profile_get(hc, nullptr, nullptr, nullptr); }
     printf("Bootstrapping... Ours (until CtoS):\n");
     auto start = now();
     // test mode, with HCONV_CHAIN_REPLAY: HCONV_REPLAY_LOG_SPARSE=ls runs BootstrappConv_CtoS of the SPARSE-slot bootstrapper on the planted input, as
@@ -1289,7 +1280,7 @@ std::vector<BootCiphertext> evalConv_BNRelu_tail_batch(Boot *B, const std::strin
     const char *rls = B->replay_seed ? testOnlyEnv("HCONV_REPLAY_LOG_SPARSE") : nullptr;
     const int ls_run = rls ? atoi(rls) : log_sparse;
     DCt boots[2]; const int iter = B->ctos(ct, ls_run, boots);                                         // eval.go:450-461
-    HCR(hc_sync(hc));
+    HC(hc, hc_sync(hc));
     printf("Done in %s \n", dur(start).c_str());
     if (prof) profile_dump(B, "sine");
     if (B->replay_seed) {
@@ -1305,7 +1296,7 @@ std::vector<BootCiphertext> evalConv_BNRelu_tail_batch(Boot *B, const std::strin
         boots[ul] = B->mul_const_int(r, pow(2.0, pow_));                                              // MulByPow2 (eval.go:474)
     }
     if (B->parts_merged) { DCt both = boots[0]; B->split2(both, boots); B->parts_merged = false; }    // the halves part again: their masks differ
-    HCR(hc_sync(hc));
+    HC(hc, hc_sync(hc));
     printf("ReLU Done in %s \n", dur(start).c_str());
     if (prof) profile_dump(B, "ReLU");
     if (dbg) dbg->after_relu(boots, iter);
@@ -1320,20 +1311,20 @@ std::vector<BootCiphertext> evalConv_BNRelu_tail_batch(Boot *B, const std::strin
     // "Conv_sparse" on full packing (wide_case 3, block 1) keeps with gen_keep_vec per half, like "Conv" (main.go:155-156)
     else for (int ul = 0; ul < 2; ul++) keep[ul] = keep_ctxt(B, boots[ul], gen_keep_vec(N / 2, in_wid, kp_wid, ul), "keep/" + mk + "/" + std::to_string(ul));
     DCt res = B->stoc(keep[0], iter == 2 ? &keep[1] : nullptr, log_sparse);                              // eval.go:550-561 ; Rescale (564) is a no-op here
-    HCR(hc_sync(hc));
+    HC(hc, hc_sync(hc));
     printf("Boot (StoC) Done in %s \n", dur(start).c_str());
     if (B->replay_seed) replay_digest("final", res);
     if (dbg) dbg->after_stoc(res, iter);
-    if (prof) { profile_dump(B, ("mask + SlotsToCoeffs; the layer was " + kind + " log_sparse " + std::to_string(log_sparse)).c_str()); HCR(hc_set_option(hc, "profile", 0)); }
+    if (prof) { profile_dump(B, ("mask + SlotsToCoeffs; the layer was " + kind + " log_sparse " + std::to_string(log_sparse)).c_str()); HC(hc, hc_set_option(hc, "profile", 0)); }
     if (getenv("HCONV_ALG_BYTES")) printf("algorithmic traffic of the layer's tail: %.6g GB per ciphertext + %.6g GB shared by the %d image%s of the launch set\n", B->alg_ct * N * 8 / 1e9, B->alg_shared * N * 8 / 1e9, nimg, nimg > 1 ? "s" : "");
     B->alg_ct = B->alg_shared = 0;
     std::vector<BootCiphertext> outs((size_t)nimg);
     for (int z = 0; z < nimg; z++) {
         BootCiphertext &out = outs[(size_t)z]; out.level = res.level; out.Scale = res.scale;
-        { void *v = nullptr; HCR(hc_malloc(hc, (size_t)2 * (res.level + 1) * N * 8, &v)); out.d = (uint64_t *)v; }
-        for (int d = 0; d < 2; d++) HCR(hc_copy(hc, out.d + (size_t)d * (res.level + 1) * N, res.p[d].get() + (size_t)z * B->poly_stride(), (size_t)(res.level + 1) * N * 8));
+        { void *v = nullptr; HC(hc, hc_malloc(hc, (size_t)2 * (res.level + 1) * N * 8, &v)); out.d = (uint64_t *)v; }
+        for (int d = 0; d < 2; d++) HC(hc, hc_copy(hc, out.d + (size_t)d * (res.level + 1) * N, res.p[d].get() + (size_t)z * B->poly_stride(), (size_t)(res.level + 1) * N * 8));
     }
-    HCR(hc_sync(hc));
+    HC(hc, hc_sync(hc));
     return outs;
 }
 BootCiphertext evalConv_BNRelu_tail(Boot *B, const std::string &kind, int log_sparse, const uint64_t *ct_conv_dev, double ct_scale, double alpha, double pow_, int in_wid, int kp_wid) {
@@ -1351,12 +1342,12 @@ void blBootReLU(Boot *B, const uint64_t *ct_res0, const uint64_t *ct_res1, doubl
     DCt c[2];
     for (int pos = 0; pos < 2; pos++) {
         DCt t = B->new_ct(1, scale); const uint64_t *src = pos ? ct_res1 : ct_res0;
-        for (int d = 0; d < 2; d++) HCR(hc_copy(hc, t.p[d].get(), src + (size_t)d * 2 * N, (size_t)2 * N * 8));
+        for (int d = 0; d < 2; d++) HC(hc, hc_copy(hc, t.p[d].get(), src + (size_t)d * 2 * N, (size_t)2 * N * 8));
         c[pos] = B->add(B->conjugate(t), t);                                                             // test_BL.go:116
         if (pos == 1) c[pos] = B->mul_by_i(c[pos]);                                                      // MultByiNew (118)
     }
     DCt ct = B->add(c[0], c[1]);                                                                         // test_BL.go:122
-    HCR(hc_sync(hc));
+    HC(hc, hc_sync(hc));
     const double img_part = std::chrono::duration<double>(now() - img_eval).count();
     ct.scale = ct.scale * exp2(pow_ + 2);                                                                // test_BL.go:128
     printf("\n ========= Bootstrapping... (original) ========= \n");
@@ -1370,7 +1361,7 @@ void blBootReLU(Boot *B, const uint64_t *ct_res0, const uint64_t *ct_res1, doubl
         for (int k = 0; k < 2; k++) {
             for (int l = 0; l < 2; l++) { const uint64_t sd = B->replay_seed + ((6ull << 32) | (uint64_t)((((4001 * 2 + 0) * 4 + k) * 64) + l));
                 for (int j = 0; j < N; j++) rows[(size_t)l * N + (size_t)j] = Boot::splitmix_at(sd, (uint64_t)j) % B->Q[(size_t)l]; }
-            HCR(hc_upload(hc, ct.p[k].get(), rows.data(), rows.size() * 8));
+            HC(hc, hc_upload(hc, ct.p[k].get(), rows.data(), rows.size() * 8));
         }
     }
     DCt halves[2]; if (B->ctos(ct, 0, halves) != 2) panic("Bootstrapp: full-slot CoeffsToSlots returns two ciphertexts");
@@ -1378,7 +1369,7 @@ void blBootReLU(Boot *B, const uint64_t *ct_res0, const uint64_t *ct_res1, doubl
     DCt ct_boot = B->stoc(halves[0], &halves[1], 0);
     if (B->replay_seed) { replay_digest_line(B, "bootstrapp", ct_boot); printf("replay of the baseline's Bootstrapp done\n"); fflush(stdout); exit(0); }
     if (dbg) Boot::debug_compare("Bootstrapp", z_in, B->debug_slots(ct_boot));
-    HCR(hc_sync(hc));
+    HC(hc, hc_sync(hc));
     printf("Boot Done in %s \n", dur(start_boot).c_str());
     img_eval = now();
     // test_BL.go:146-153: an all-ones plaintext at scale 2^30 q14 q13 / ct_boot.Scale, Mul, Rescale(params.Scale): level 14, scale ~2^120 -> level 12, scale 2^30
@@ -1389,7 +1380,7 @@ void blBootReLU(Boot *B, const uint64_t *ct_res0, const uint64_t *ct_res1, doubl
     if (dbg) Boot::debug_compare("Bootstrapp + scale plaintext", z_in, B->debug_slots(ct_boot));
     DCt ct_iboot = B->conjugate(ct_boot);                                                                // test_BL.go:155
     DCt res[2] = {B->add(ct_boot, ct_iboot), B->monomial_fma(ct_iboot, ct_boot, N, N / 2)};                    // DivByi(a - b) = i (b - a)
-    HCR(hc_sync(hc));
+    HC(hc, hc_sync(hc));
     printf("Imaginary packing and unpacking done in %s \n", dur_ns((img_part + std::chrono::duration<double>(now() - img_eval).count()) * 1e9).c_str());
     auto start = now();
     for (int pos = 0; pos < 2; pos++) {                                                                  // test_BL.go:160-167
@@ -1398,10 +1389,10 @@ void blBootReLU(Boot *B, const uint64_t *ct_res0, const uint64_t *ct_res1, doubl
         r = B->set_scale(r, 1073741824.0);
         if (r.level != 1) panic("baseline ReLU ended at an unexpected level");
         uint64_t *dst = pos ? out1 : out0;
-        for (int d = 0; d < 2; d++) HCR(hc_copy(hc, dst + (size_t)d * 2 * N, r.p[d].get(), (size_t)2 * N * 8));
+        for (int d = 0; d < 2; d++) HC(hc, hc_copy(hc, dst + (size_t)d * 2 * N, r.p[d].get(), (size_t)2 * N * 8));
         *out_scale = r.scale;
     }
-    HCR(hc_sync(hc));
+    HC(hc, hc_sync(hc));
     printf("Relu Done in %s \n", dur(start).c_str());
 }
 
@@ -1410,15 +1401,15 @@ std::vector<double> bootDecryptDecodeCoeffs(Boot *B, const BootCiphertext &ct) {
     hc_ctx *hc = B->hc;
     if (ct.level != 1) panic("bootDecryptDecodeCoeffs expects the level-1 result of the chain");
     if (deviceEncrypt()) {            // HCONV_DEVICE_ENCRYPT=1 and no replay: the device's decoder (level 1: the same kernel and bits as the host loop below)
-        void *o = nullptr; HCR(hc_malloc(hc, (size_t)N * 8, &o));
+        void *o = nullptr; HC(hc, hc_malloc(hc, (size_t)N * 8, &o));
         const uint64_t *c0 = ct.d, *c1 = ct.d + (size_t)2 * N;
-        HCR(hc_decrypt_decode_lv(hc, 1, 1, &c0, &c1, B->d_sk, ct.Scale, -1, (double *)o));
-        std::vector<double> cf((size_t)N); HCR(hc_download(hc, cf.data(), o, cf.size() * 8)); HCR(hc_free(hc, o));
+        HC(hc, hc_decrypt_decode_lv(hc, 1, 1, &c0, &c1, B->d_sk, ct.Scale, -1, (double *)o));
+        std::vector<double> cf((size_t)N); HC(hc, hc_download(hc, cf.data(), o, cf.size() * 8)); HC(hc, hc_free(hc, o));
         return cf;
     }
-    void *v = nullptr; HCR(hc_malloc(hc, (size_t)2 * N * 8, &v)); uint64_t *t = (uint64_t *)v;
-    HCR(hc_lv_mul_plain(hc, 1, ct.d + (size_t)2 * N, B->d_sk, t)); HCR(hc_lv_add(hc, 1, ct.d, t, t)); HCR(hc_lv_intt(hc, 1, t, t));
-    std::vector<uint64_t> m((size_t)2 * N); HCR(hc_download(hc, m.data(), t, m.size() * 8)); HCR(hc_free(hc, t));
+    void *v = nullptr; HC(hc, hc_malloc(hc, (size_t)2 * N * 8, &v)); uint64_t *t = (uint64_t *)v;
+    HC(hc, hc_lv_mul_plain(hc, 1, ct.d + (size_t)2 * N, B->d_sk, t)); HC(hc, hc_lv_add(hc, 1, ct.d, t, t)); HC(hc, hc_lv_intt(hc, 1, t, t));
+    std::vector<uint64_t> m((size_t)2 * N); HC(hc, hc_download(hc, m.data(), t, m.size() * 8)); HC(hc, hc_free(hc, t));
     const uint64_t q0 = B->Q[0], q1 = B->Q[1]; uint64_t inv = 1; { uint64_t b = q0 % q1, e = q1 - 2; while (e) { if (e & 1) inv = mulmod(inv, b, q1); b = mulmod(b, b, q1); e >>= 1; } }
     const u128 QQ = (u128)q0 * q1; std::vector<double> cf((size_t)N);
     for (int j = 0; j < N; j++) {
@@ -1428,7 +1419,7 @@ std::vector<double> bootDecryptDecodeCoeffs(Boot *B, const BootCiphertext &ct) {
     }
     return cf;
 }
-void freeBootCt(Boot *B, BootCiphertext &ct) { hc_ctx *hc = B->hc; if (ct.d) HCR(hc_free(hc, ct.d)); ct.d = nullptr; }
+void freeBootCt(Boot *B, BootCiphertext &ct) { hc_ctx *hc = B->hc; if (ct.d) HC(hc, hc_free(hc, ct.d)); ct.d = nullptr; }
 void bootStats(Boot *B, long *keys, long *keyswitches) { *keys = B->n_keys; *keyswitches = B->n_keyswitch; }
 std::vector<int> bootSets(Boot *B) { std::vector<int> r; for (auto &e : B->sets) r.push_back(e.first); return r; }
 void bootEncodeStats(Boot *B, long *diagonals, long *masks, bool *device) { *diagonals = B->n_enc_diag; *masks = B->n_enc_mask; *device = B->dev_encode; }

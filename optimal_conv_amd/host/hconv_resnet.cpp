@@ -33,17 +33,26 @@
 
 namespace hconv {
 
-#define HCX(c, call) do { int rc_ = (call); if (rc_) panic(std::string(#call) + ": " + hc_last_error(c)); } while (0)
-static std::string dur(std::chrono::steady_clock::time_point t0) {
-    double ns = (double)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count();
-    char b[64];
-    if (ns < 1e6) snprintf(b, sizeof b, "%.6gµs", ns / 1e3); else if (ns < 1e9) snprintf(b, sizeof b, "%.9gms", ns / 1e6); else snprintf(b, sizeof b, "%.9gs", ns / 1e9);
-    return b;
-}
-static std::chrono::steady_clock::time_point now() { return std::chrono::steady_clock::now(); }
-static double secs(std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); }
+// conv_tail for the convolution results of one launch set (freed here), and its outputs as blocks of the convolution context
 static std::vector<Ciphertext> tail_of_conv(Context *cont, const std::string &kind, int log_sparse, std::vector<Ciphertext> &ct_conv, double alpha, double pow_, int in_wid, int kp_wid,
-                                            const std::vector<std::vector<int>> *keep_idx, const std::string &mask_key, int pack_pos = 0);
+                                            const std::vector<std::vector<int>> *keep_idx, const std::string &mask_key, int pack_pos = 0) {
+    const int nimg = (int)ct_conv.size();
+    std::vector<BootCiphertext> r = conv_tail(cont, ct_conv, kind, log_sparse, alpha, pow_, in_wid, kp_wid, keep_idx, mask_key, pack_pos);
+    for (Ciphertext &c : ct_conv) freeCt(cont, c);
+    // [2][2][N] over (Q0, Q1): what the next convolution reads. The result blocks belong to the bootstrapper's context and go back to it; the layer's outputs are
+    // blocks of the convolution context (a block released into a context that did not allocate it would leave the owner's block table pointing at memory it no longer
+    // owns - the lifetime bug hc_free's stream synchronisation used to hide). The tail has synchronised its stream, so the copies see the finished results.
+    std::vector<Ciphertext> outs((size_t)nimg);
+    for (int z = 0; z < nimg; z++) {
+        Ciphertext &out = outs[(size_t)z]; out.level = r[(size_t)z].level; out.Scale = r[(size_t)z].Scale;
+        const size_t bytes = (size_t)2 * (out.level + 1) * N * 8;
+        { void *v = nullptr; HC(cont->hc, hc_malloc(cont->hc, bytes, &v)); out.d = (uint64_t *)v; }
+        HC(cont->hc, hc_copy(cont->hc, out.d, r[(size_t)z].d, bytes));
+    }
+    HC(cont->hc, hc_sync(cont->hc));
+    for (BootCiphertext &b : r) freeBootCt(cont->btp, b);
+    return outs;
+}
 
 // eval.go:272-607 for the kinds the conv / convReLU / resnet command lines reach, for the images of a batch (ct_inputs.size() <= HCONV_IMAGE_BATCH): every image
 // sees the operations of the reference's per-image flow, but a launch covers all of them (hc_conv_then_pack_batch; hc_set_batch inside the tail)
@@ -54,7 +63,7 @@ std::vector<Ciphertext> evalConv_BNRelu_new_batch(Context *cont, const std::vect
     const bool inside = kind == "Conv_inside" || kind == "StrConv_inside";
     if (ib_stride != 1 && !inside) panic("evalConv_BNRelu_new: ib_stride is for the inside kinds only");
     const int nimg = (int)ct_inputs.size();
-    const double out_scale = exp2(round(log2((double)PARAMS6_Q[0]) - (pow_ + 8)));                       // eval.go:433
+    const double out_scale = chain_out_scale(pow_);
     std::vector<Ciphertext> ct_conv;
     if (kind == "StrConv_sparse") {                                                                       // eval.go:335-392 (modify_ker, !full)
         std::vector<double> a0((size_t)real_ob / 2), a1((size_t)real_ob / 2), b0((size_t)real_ob / 2), b1((size_t)real_ob / 2);
@@ -72,7 +81,7 @@ std::vector<Ciphertext> evalConv_BNRelu_new_batch(Context *cont, const std::vect
         const uint64_t e[2] = {(uint64_t)(norm / 4), (in_wid - ker_wid / 2) % 2 == 0 ? (uint64_t)(2 * N - max_batch * (in_wid + 1)) : 0};
         for (int z = 0; z < nimg; z++) {
             uint64_t *a = r1[(size_t)z].d, *b = r2[(size_t)z].d;
-            HCX(cont->hc, hc_lv_op2(cont->hc, HC_LV_MONOMIAL, 0, a, a + N, b, b + N, a, a + N, e));
+            HC(cont->hc, hc_lv_op2(cont->hc, HC_LV_MONOMIAL, 0, a, a + N, b, b + N, a, a + N, e));
             freeCt(cont, r2[(size_t)z]);
         }
         ct_conv = r1;
@@ -90,30 +99,6 @@ std::vector<Ciphertext> evalConv_BNRelu_new_batch(Context *cont, const std::vect
         keep_idx = &it->second;
     }
     return tail_of_conv(cont, kind, log_sparse, ct_conv, alpha, pow_, in_wid, kp_wid, keep_idx, "step" + std::to_string(step), pack_pos);
-}
-// the tail of a layer for the convolution results of one launch set (freed here), and its outputs as blocks of the convolution context
-static std::vector<Ciphertext> tail_of_conv(Context *cont, const std::string &kind, int log_sparse, std::vector<Ciphertext> &ct_conv, double alpha, double pow_, int in_wid, int kp_wid,
-                                            const std::vector<std::vector<int>> *keep_idx, const std::string &mask_key, int pack_pos) {
-    const int nimg = (int)ct_conv.size();
-    // hand-over to the bootstrapper's context (its own stream): everything queued on the convolution context - the stride layers end on a product and an addition that
-    // nothing has waited for - must be complete before the other stream reads ct_conv
-    HCX(cont->hc, hc_sync(cont->hc));
-    std::vector<const uint64_t *> conv_d; for (const Ciphertext &c : ct_conv) conv_d.push_back(c.d);
-    std::vector<BootCiphertext> r = evalConv_BNRelu_tail_batch(cont->btp, kind, log_sparse, conv_d, ct_conv[0].Scale, alpha, pow_, in_wid, kp_wid, keep_idx, mask_key, pack_pos);
-    for (Ciphertext &c : ct_conv) freeCt(cont, c);
-    // [2][2][N] over (Q0, Q1): what the next convolution reads. The result blocks belong to the bootstrapper's context and go back to it; the layer's outputs are
-    // blocks of the convolution context (a block released into a context that did not allocate it would leave the owner's block table pointing at memory it no longer
-    // owns - the lifetime bug hc_free's stream synchronisation used to hide). The tail has synchronised its stream, so the copies see the finished results.
-    std::vector<Ciphertext> outs((size_t)nimg);
-    for (int z = 0; z < nimg; z++) {
-        Ciphertext &out = outs[(size_t)z]; out.level = r[(size_t)z].level; out.Scale = r[(size_t)z].Scale;
-        const size_t bytes = (size_t)2 * (out.level + 1) * N * 8;
-        { void *v = nullptr; HCX(cont->hc, hc_malloc(cont->hc, bytes, &v)); out.d = (uint64_t *)v; }
-        HCX(cont->hc, hc_copy(cont->hc, out.d, r[(size_t)z].d, bytes));
-    }
-    HCX(cont->hc, hc_sync(cont->hc));
-    for (BootCiphertext &b : r) freeBootCt(cont->btp, b);
-    return outs;
 }
 Ciphertext evalConv_BNRelu_new(Context *cont, const Ciphertext &ct_input, const std::vector<double> &ker_in, const std::vector<double> &bn_a,
                                const std::vector<double> &bn_b, double alpha, double pow_, int in_wid, int kp_wid, int ker_wid, int real_ib, int real_ob,
@@ -145,32 +130,98 @@ static void writeTxt(const std::string &name, const std::vector<double> &v) {
     for (double d : v) { snprintf(buf, sizeof buf, "%.17g\n", d); f << buf; }
 }
 
+// ---------------------------------------------------------------- what `resnet`, `resnet_fast` and `resnet_packed` share: the CIFAR-10 network's files, schedule and head
+static const int PK_W = 32, PK_SLOTS = 64;                  // the first block's grid and its channel slots (`resnet_fast` and `resnet_packed` stay on it throughout)
+static const int RESNET_BATCH[3] = {16, 32, 64};            // the channels of block 1, 2, 3 (test.go:107)
+struct ResnetFiles {                                        // test.go:84-105: the directories of (ker_wid, depth), and the layers per block of that depth
+    std::string ker_name, weight_dir, out_dir, img_dir;
+    int num_blcs[3];
+    ResnetFiles(int ker_wid, int depth) : ker_name("ker" + std::to_string(ker_wid)) {
+        const std::string tag = "crop_" + ker_name + "_d" + std::to_string(depth) + "_wid1/";
+        weight_dir = "Resnet_weights/weights_" + tag; out_dir = "Resnet_enc_results/results_" + tag; img_dir = "Resnet_plain_data/" + tag;
+        if (depth == 20) { num_blcs[0] = 7; num_blcs[1] = 5; num_blcs[2] = 5; } else if (depth == 14) { num_blcs[0] = 5; num_blcs[1] = 3; num_blcs[2] = 3; }
+        else if (depth == 8) { num_blcs[0] = 3; num_blcs[1] = 1; num_blcs[2] = 1; } else panic("wrong depth (not in 8, 14, 20)!");
+    }
+    void make_out_dir() const { mkdir("Resnet_enc_results", 0755); mkdir(out_dir.c_str(), 0755); }
+    std::vector<double> W(int i, const char *what, int size) const { return readTxt(weight_dir + "w" + std::to_string(i) + "-" + what + ".csv", size); }
+    void write_scores(int image, const std::vector<double> &scores) const { writeTxt(out_dir + "class_result_" + ker_name + "_" + std::to_string(image) + ".csv", scores); }
+};
+// test.go:141-150: test image `iter`, sparse packed - its raw x raw corner on the 32-wide grid, channel b at slot 4b of the 64
+static std::vector<double> resnet_input(const ResnetFiles &files, int iter, int ker_wid, int raw) {
+    printf("Running  %d -th iter... ker size:  %d\n", iter, ker_wid);
+    const std::vector<double> image = readTxt(files.img_dir + "test_image_" + std::to_string(iter) + ".csv", PK_W * PK_W * 3);
+    std::vector<double> input((size_t)N, 0.0); int k = 0;
+    for (int i = 0; i < PK_W; i++) for (int j = 0; j < PK_W; j++) for (int b = 0; b < 3; b++) {
+        if (i < raw && j < raw) input[(size_t)(i * PK_W * PK_SLOTS + j * PK_SLOTS + b * 4)] = image[(size_t)k];
+        k++;
+    }
+    return input;
+}
+// test.go:160-277: the layers in the reference's order - block 1, the stride layer into block 2, block 2, the stride layer into block 3, block 3 - with its console lines and
+// the five stage times. inside(w, cin, blk, pow) runs the layer of the weight files w<w>-*.csv, cin input channels, inside block blk; strided(w, blk, pow) the layer that
+// enters blk. pow is init_pow for the first layer, final_pow for the last and mid_pow between (test.go:160, 173, 262).
+template <class Inside, class Strided>
+static void resnet_schedule(const int num_blcs[3], double init_pow, double mid_pow, double final_pow, const Inside &inside, const Strided &strided, double timings[6]) {
+    auto start = now();
+    double pow_ = init_pow;                                                                              // ResNet Block 1
+    for (int i = 1; i <= num_blcs[0]; i++) {
+        inside(i - 1, i == 1 ? 3 : RESNET_BATCH[0], 0, pow_);
+        pow_ = mid_pow;
+        printf("Block1, Layer  %d done!\n", i);
+    }
+    printf("Block1 done.\n"); timings[0] = secs(start); start = now();
+    strided(num_blcs[0], 1, pow_);                                                                       // test.go:200 / 480-495
+    printf("Block1 to 2 done!\n"); timings[1] = secs(start); start = now();
+    for (int i = 1; i <= num_blcs[1]; i++) {                                                             // ResNet Block 2
+        inside(num_blcs[0] + i, RESNET_BATCH[1], 1, pow_);
+        printf("Block2, Layer  %d done!\n", i);
+    }
+    printf("Block2 done.\n"); timings[2] = secs(start); start = now();
+    strided(num_blcs[0] + num_blcs[1] + 1, 2, pow_);                                                     // test.go:225 / 513-529
+    printf("Block2 to 3 done!\n"); timings[3] = secs(start); start = now();
+    for (int i = 1; i <= num_blcs[2]; i++) {                                                             // ResNet Block 3
+        if (i == num_blcs[2]) pow_ = final_pow;
+        inside(num_blcs[0] + num_blcs[1] + i + 1, RESNET_BATCH[2], 2, pow_);
+        printf("Block3, Layer  %d done!\n", i);
+    }
+    printf("Block3 done.\n"); timings[4] = secs(start);
+}
+// test.go:279-334: reduce-mean + FC as ONE convolution - final-fckernel.csv (64 x fc_out) on every one of the kernel's taps, bn_a = 1 / raw^2 (the mean over the last block's
+// raw x raw cells), bn_b = final-fcbias.csv
+struct FcHead { std::vector<double> ker, bn_a, bn_b; };
+static FcHead resnet_fc_head(const ResnetFiles &files, int taps, int fc_out, int raw) {
+    const std::vector<double> fc = readTxt(files.weight_dir + "final-fckernel.csv", RESNET_BATCH[2] * fc_out);
+    FcHead h; h.bn_b = readTxt(files.weight_dir + "final-fcbias.csv", fc_out);
+    h.ker.resize((size_t)taps * fc.size());
+    for (size_t i = 0; i < fc.size(); i++) for (int b = 0; b < taps; b++) h.ker[i + (size_t)b * fc.size()] = fc[i];
+    h.bn_a.assign((size_t)fc_out, 1.0 / (double)(raw * raw));
+    return h;
+}
+static void print_stage_times(const double t[6]) {
+    printf("Blc1:  %g  sec\nBlc1->2:  %g  sec\nBlc2:  %g  sec\nBlc2->3:  %g  sec\nBlc3:  %g  sec\nFinal (reduce_mean & FC):  %g  sec\n", t[0], t[1], t[2], t[3], t[4], t[5]);
+}
+
 // test.go:76-370: `resnet ker depth 1 n false` (BASELINE config 5). The wide drivers (wide_case 2 / 3: testResNet_crop_sparse_wide, test.go:638-912) and the CIFAR-100 head
 // (cf100: two final convolutions, test.go:287-315) are SURVEY section 2 row 14 - out of scope - and were removed from this host in round 6 (they lived here in rounds 1-5).
 // fast = true: test.go:372-636 testResNet_crop_fast_in, the same network, files and console lines; every layer runs on the 32-wide grid at full slots (log_sparse 0),
 // norm 4 / 2 / 1, outputs at stride step 1 / 2 / 4 kept in place (ext_idx[step]), the stride layers' weights read with their input channels at ib_stride 2.
 static void testResNet_crop(int st, int end, int ker_wid, int depth, bool fast) {
     if (const char *fi = testOnlyEnv("HCONV_RESNET_FIRST_IMAGE")) st = atoi(fi);      // test mode: images st .. end - 1 (one image of a batch run alone, for the batch == single digest test)
-    const std::string ker_name = "ker" + std::to_string(ker_wid), tag = "crop_" + ker_name + "_d" + std::to_string(depth) + "_wid1/";
-    const std::string weight_dir = "Resnet_weights/weights_" + tag, out_dir = "Resnet_enc_results/results_" + tag, img_dir = "Resnet_plain_data/" + tag;
+    const ResnetFiles files(ker_wid, depth);
     const int fc_out = 10; const double init_pow = 6.0, mid_pow = 6.0, final_pow = 6.0;                  // test.go:84-89 (cifar10)
-    int num_blcs[3];
-    if (depth == 20) { num_blcs[0] = 7; num_blcs[1] = 5; num_blcs[2] = 5; } else if (depth == 14) { num_blcs[0] = 5; num_blcs[1] = 3; num_blcs[2] = 3; }
-    else if (depth == 8) { num_blcs[0] = 3; num_blcs[1] = 1; num_blcs[2] = 1; } else panic("wrong depth (not in 8, 14, 20)!");
-    const int real_batch[3] = {16, 32, 64}, norm_sparse[3] = {4, 8, 16}, log_sparse_sparse[3] = {2, 3, 4};   // test.go:107-112
+    const int *real_batch = RESNET_BATCH, norm_sparse[3] = {4, 8, 16}, log_sparse_sparse[3] = {2, 3, 4};      // test.go:107-112
     const int norm_fast[3] = {4, 2, 1}, log_sparse_fast[3] = {0, 0, 0}, steps[3] = {1, 2, 4};                 // test.go:409-411
     const int *norm = fast ? norm_fast : norm_sparse, *log_sparse = fast ? log_sparse_fast : log_sparse_sparse;
     const int logN = 16; const double alpha = 0.0;
     const std::vector<int> in_wids = {32, 16, 8}, raw_in_wids = {32 - ker_wid / 2, 16 - ker_wid / 2, 8 - ker_wid / 2};
     const int ker_size = ker_wid * ker_wid;
     int max_batch[3]; for (int i = 0; i < 3; i++) max_batch[i] = (1 << logN) / (in_wids[(size_t)i] * in_wids[(size_t)i]);
-    mkdir("Resnet_enc_results", 0755); mkdir(out_dir.c_str(), 0755);
-    auto W = [&](int i, const char *what, int size) { return readTxt(weight_dir + "w" + std::to_string(i) + "-" + what + ".csv", size); };
+    files.make_out_dir();
     const char *kind_name = fast ? "Resnet_crop_fast" : "Resnet_crop_sparse";
     // one conv-BN-ReLU layer whose output belongs to block blk (strided: the layer that enters it). Sparse: on block blk's grid (a stride layer on the previous one's, its
     // sparse bootstrapper one slot set below: test.go:200, 225). Fast: on the 32-wide grid, the output at stride steps[blk], dilated kernels, a stride layer's input channels at 2c.
     auto layer = [&](Context *cont, const std::vector<Ciphertext> &in, int w, int ib, int ob, int blk, bool strided, double pow_) {
-        const std::vector<double> ker = W(w, "conv", ib * ob * ker_size), a = W(w, "a", ob), b = W(w, "b", ob);
+        const std::vector<double> ker = files.W(w, "conv", ib * ob * ker_size), a = files.W(w, "a", ob), b = files.W(w, "b", ob);
         if (fast) return evalConv_BNRelu_new_batch(cont, in, ker, a, b, alpha, pow_, in_wids[0], raw_in_wids[(size_t)blk], ker_wid, ib, ob, norm[blk], 0,
                                                    strided ? "StrConv_inside" : "Conv_inside", steps[blk], strided ? 2 : 1);
         const int gb = strided ? blk - 1 : blk;
@@ -197,66 +248,34 @@ static void testResNet_crop(int st, int end, int ker_wid, int depth, bool fast) 
         std::vector<Ciphertext> ct_layer;
         auto enc_start = now();
         for (int iter = g0; iter < g0 + nimg; iter++) {
-            printf("Running  %d -th iter... ker size:  %d\n", iter, ker_wid);
-            std::vector<double> image = readTxt(img_dir + "test_image_" + std::to_string(iter) + ".csv", in_wids[0] * in_wids[0] * 3);
-            std::vector<double> input((size_t)N, 0.0); int k = 0;
-            for (int i = 0; i < in_wids[0]; i++) for (int j = 0; j < in_wids[0]; j++) for (int b = 0; b < 3; b++) {
-                if (i < raw_in_wids[0] && j < raw_in_wids[0]) input[(size_t)(i * in_wids[0] * max_batch[0] + j * max_batch[0] + b * norm[0])] = image[(size_t)k];   // sparse pack the input
-                k++;
-            }
+            const std::vector<double> input = resnet_input(files, iter, ker_wid, raw_in_wids[0]);
             if (resnetReplaySeed()) cont->replay_encryptions = iter;     // test mode: the encryption randomness of an image depends on its index only, not on which images ran before it in this process
             ct_layer.push_back(EncryptNew(cont, EncodeCoeffs(input, cont->ECD_LV, cont->scale), cont->ECD_LV, cont->scale));
         }
         printf("vec size:  %d\n", N); printf("input width:  [%d %d %d]\n", raw_in_wids[0], raw_in_wids[1], raw_in_wids[2]);
         printf("kernel width:  %d\n", ker_wid); printf("num batches:  [%d %d %d]\n", real_batch[0], real_batch[1], real_batch[2]);
         printf("Encryption done in %s \n", dur(enc_start).c_str());
-        double timings[6]; auto begin_start = now(), start = now();
+        double timings[6]; auto begin_start = now();
         int layer_no = 0;
         auto step = [&](std::vector<Ciphertext> next) {
             for (Ciphertext &c : ct_layer) freeCt(cont, c);
             ct_layer = std::move(next);
             if (resnetReplaySeed()) for (size_t z = 0; z < ct_layer.size(); z++) {      // test mode: SHA-256 of the ciphertext the layer hands on ([2][level+1][N], as tests/parity_cases.py sha_ct)
-                std::vector<uint64_t> rows((size_t)2 * (ct_layer[z].level + 1) * N); HCX(cont->hc, hc_download(cont->hc, rows.data(), ct_layer[z].d, rows.size() * 8));
+                std::vector<uint64_t> rows((size_t)2 * (ct_layer[z].level + 1) * N); HC(cont->hc, hc_download(cont->hc, rows.data(), ct_layer[z].d, rows.size() * 8));
                 Sha256 h; h.update(rows.data(), rows.size() * 8);
                 printf("replay digest layer %d image %d level %d scale %.17g %s\n", layer_no, g0 + (int)z, ct_layer[z].level, ct_layer[z].Scale, h.hex().c_str());
             }
             layer_no++;
         };
-
-        double pow_ = init_pow;                                                                          // ResNet Block 1
-        for (int i = 1; i <= num_blcs[0]; i++) {
-            step(layer(cont, ct_layer, i - 1, i == 1 ? 3 : real_batch[0], real_batch[0], 0, false, pow_));
-            pow_ = mid_pow;
-            printf("Block1, Layer  %d done!\n", i);
-        }
-        printf("Block1 done.\n"); timings[0] = secs(start); start = now();
-        step(layer(cont, ct_layer, num_blcs[0], real_batch[0], real_batch[1], 1, true, pow_));                                           // test.go:200 / 480-495
-        printf("Block1 to 2 done!\n"); timings[1] = secs(start); start = now();
-        for (int i = 1; i <= num_blcs[1]; i++) {                                                         // ResNet Block 2
-            step(layer(cont, ct_layer, num_blcs[0] + i, real_batch[1], real_batch[1], 1, false, pow_));
-            printf("Block2, Layer  %d done!\n", i);
-        }
-        printf("Block2 done.\n"); timings[2] = secs(start); start = now();
-        step(layer(cont, ct_layer, num_blcs[0] + num_blcs[1] + 1, real_batch[1], real_batch[2], 2, true, pow_));                        // test.go:225 / 513-529
-        printf("Block2 to 3 done!\n"); timings[3] = secs(start); start = now();
-        for (int i = 1; i <= num_blcs[2]; i++) {                                                         // ResNet Block 3
-            if (i == num_blcs[2]) pow_ = final_pow;
-            step(layer(cont, ct_layer, num_blcs[0] + num_blcs[1] + i + 1, real_batch[2], real_batch[2], 2, false, pow_));
-            printf("Block3, Layer  %d done!\n", i);
-        }
-        printf("Block3 done.\n"); timings[4] = secs(start); start = now();
+        resnet_schedule(files.num_blcs, init_pow, mid_pow, final_pow,
+                        [&](int w, int cin, int blk, double pow_) { step(layer(cont, ct_layer, w, cin, real_batch[blk], blk, false, pow_)); },
+                        [&](int w, int blk, double pow_) { step(layer(cont, ct_layer, w, real_batch[blk - 1], real_batch[blk], blk, true, pow_)); }, timings);
+        auto start = now();
 
         const int fb = fast ? 0 : 2;                                                                     // the grid the FC convolution runs on (fast: test.go:555-600)
         int ker_inf_wid = raw_in_wids[(size_t)fb]; if (ker_inf_wid % 2 == 0) ker_inf_wid++;             // test.go:279-334: reduce_mean + FC
-        std::vector<double> ker_inf = readTxt(weight_dir + "final-fckernel.csv", real_batch[2] * fc_out);
-        std::vector<double> bn_bf = readTxt(weight_dir + "final-fcbias.csv", fc_out);
-        std::vector<Ciphertext> ct_result;
-        {                                                                                                // test.go:316-334
-            std::vector<double> ker_inf_((size_t)(ker_inf_wid * ker_inf_wid * real_batch[2] * fc_out));
-            for (size_t i = 0; i < ker_inf.size(); i++) for (int b = 0; b < ker_inf_wid * ker_inf_wid; b++) ker_inf_[i + (size_t)b * real_batch[2] * fc_out] = ker_inf[i];
-            std::vector<double> bn_af((size_t)fc_out, 1.0 / (double)(raw_in_wids[2] * raw_in_wids[2]));
-            ct_result = evalConv_BN_batch(cont, ct_layer, ker_inf_, bn_af, bn_bf, in_wids[(size_t)fb], ker_inf_wid, real_batch[2], fc_out, norm[2], (double)(1 << 30), false);
-        }
+        const FcHead head = resnet_fc_head(files, ker_inf_wid * ker_inf_wid, fc_out, raw_in_wids[2]);
+        std::vector<Ciphertext> ct_result = evalConv_BN_batch(cont, ct_layer, head.ker, head.bn_a, head.bn_b, in_wids[(size_t)fb], ker_inf_wid, real_batch[2], fc_out, norm[2], (double)(1 << 30), false);
         printf("Final FC done.\n"); timings[5] = secs(start); start = now();
         printf("\n===============  DECRYPTION  ===============\n\n");
         for (int z = 0; z < nimg; z++) {
@@ -266,10 +285,10 @@ static void testResNet_crop(int st, int end, int ker_wid, int depth, bool fast) 
             res_out.resize((size_t)fc_out);
             printf("\n result:  ["); for (double v : res_out) printf("%.10f ", v);
             printf("]\n");
-            writeTxt(out_dir + "class_result_" + ker_name + "_" + std::to_string(g0 + z) + ".csv", res_out);
+            files.write_scores(g0 + z, res_out);
             freeCt(cont, ct_layer[(size_t)z]); freeCt(cont, ct_result[(size_t)z]);
         }
-        printf("Blc1:  %g  sec\nBlc1->2:  %g  sec\nBlc2:  %g  sec\nBlc2->3:  %g  sec\nBlc3:  %g  sec\nFinal (reduce_mean & FC):  %g  sec\n", timings[0], timings[1], timings[2], timings[3], timings[4], timings[5]);
+        print_stage_times(timings);
         printf("Total done in %s %s\n", dur(begin_start).c_str(), nimg > 1 ? ("(" + std::to_string(nimg) + " images)").c_str() : "");
     }
     { std::lock_guard<std::mutex> g(mu); freeContext(cont); }
@@ -346,7 +365,7 @@ void testImagenet_final_fast_in(int st, int end, int ker_wid, int c1) {
                 Ciphertext &x = half[0][(size_t)z], &y = half[1][(size_t)z];
                 if (x.level != y.level || x.Scale != y.Scale) panic("imagenet: the halves of the stride layer differ in level or scale");
                 const size_t poly = (size_t)(x.level + 1) * N;
-                HCX(cont->hc, hc_lv_op2(cont->hc, HC_LV_ADD, x.level, x.d, x.d + poly, y.d, y.d + poly, x.d, x.d + poly, nullptr));
+                HC(cont->hc, hc_lv_op2(cont->hc, HC_LV_ADD, x.level, x.d, x.d + poly, y.d, y.d + poly, x.d, x.d + poly, nullptr));
                 freeCt(cont, y);
             }
             step(half[0]);
@@ -373,17 +392,15 @@ void testImagenet_final_fast_in(int st, int end, int ker_wid, int c1) {
             const double out_scale = (double)(1 << 30);
             auto t0 = now();
             KerPlain pl_ker; pl_ker.max_bat = max_batch[1]; pl_ker.Scale = cont->scale;
-            HCX(cont->hc, hc_prep_ker_fc(cont->hc, fcf.data(), bn_af.data(), in_wids[1], 7, full_b2, fin_out_batch, norm, cont->scale, 1, &pl_ker.h));
-            HCX(cont->hc, hc_sync(cont->hc));
+            HC(cont->hc, hc_prep_ker_fc(cont->hc, fcf.data(), bn_af.data(), in_wids[1], 7, full_b2, fin_out_batch, norm, cont->scale, 1, &pl_ker.h));
+            HC(cont->hc, hc_sync(cont->hc));
             printf("Plaintext (kernel) preparation, Done in %s \n", dur(t0).c_str());
             t0 = now();
             if (nimg == 1) ct_result[0] = conv_then_pack(cont, ct_layer[0], pl_ker, max_batch[1], norm, cont->ECD_LV, out_scale, nullptr);
             else {
-                std::vector<const uint64_t *> ins; std::vector<const hc_ker *> kers((size_t)nimg, pl_ker.h); std::vector<uint64_t *> outs; double sc = 0;
-                for (int z = 0; z < nimg; z++) { void *v = nullptr; HCX(cont->hc, hc_malloc(cont->hc, (size_t)2 * N * 8, &v)); ct_result[(size_t)z].d = (uint64_t *)v; ct_result[(size_t)z].level = 0; ins.push_back(ct_layer[(size_t)z].d); outs.push_back(ct_result[(size_t)z].d); }
-                HCX(cont->hc, hc_conv_then_pack_batch(cont->hc, nimg, ins.data(), ct_layer[0].Scale, kers.data(), pl_ker.Scale, max_batch[1], norm, out_scale, nullptr, outs.data(), &sc));
-                HCX(cont->hc, hc_sync(cont->hc));
-                for (Ciphertext &c : ct_result) c.Scale = sc;
+                std::vector<std::vector<Ciphertext>> groups; for (const Ciphertext &c : ct_layer) groups.push_back({c});
+                ct_result = conv_then_pack_batch(cont, groups, {pl_ker.h}, pl_ker.Scale, nullptr, max_batch[1], norm, out_scale);
+                HC(cont->hc, hc_sync(cont->hc));
             }
             if (nimg > 1) printf("Conv (with BN) Done in %s  (%d images)\n", dur(t0).c_str(), nimg); else printf("Conv (with BN) Done in %s \n", dur(t0).c_str());
             hc_ker_free(cont->hc, pl_ker.h);
@@ -408,7 +425,6 @@ void testImagenet_final_fast_in(int st, int end, int ker_wid, int c1) {
 // ---------------------------------------------------------------- `resnet_packed` (not a reference command): the network of `resnet_fast` with every coefficient in use
 // The layout, the slot assignment (packed_slot) and the expanded kernels are stated in hconv_host.hpp; DESIGN.md "The packed layout" says why the stride layers merge after the mask.
 // Every convolution is 64 slots to 64 slots at norm 1: the block-diagonal expansion of the layer's weights through hc_prep_ker_ex2, dilated by the input lattice's step.
-static const int PK_W = 32, PK_SLOTS = 64;
 // the tails of convolution results (freed here) in launch sets of HCONV_IMAGE_BATCH, kept with the context's ext_idx[mask_id]
 static std::vector<Ciphertext> packed_tails(Context *cont, std::vector<Ciphertext> &ct_conv, const char *kind, double alpha, double pow_, int kp_wid, int mask_id, const std::string &mask_key) {
     auto it = cont->ext_idx.find(mask_id);
@@ -421,12 +437,11 @@ static std::vector<Ciphertext> packed_tails(Context *cont, std::vector<Ciphertex
     ct_conv.clear();
     return outs;
 }
-static double packed_out_scale(double pow_) { return exp2(round(log2((double)PARAMS6_Q[0]) - (pow_ + 8))); }      // eval.go:433
 // a layer inside block blk (norm, step s, keep width raw): ONE kernel preparation and one convolution call for the group's ciphertexts, then their tails with the all-phases mask
 static std::vector<Ciphertext> packed_layer(Context *cont, const std::vector<Ciphertext> &in, const std::vector<double> &ker, const std::vector<double> &a, const std::vector<double> &b,
                                             double alpha, double pow_, int ker_wid, int cin, int cout, int norm, int s, int raw) {
     std::vector<Ciphertext> ct_conv = evalConv_BN_batch(cont, in, packed_expand_ker(ker, ker_wid * ker_wid, cin, cout, norm, norm, 0, norm, PK_SLOTS), packed_expand_bn(a, norm), packed_expand_bn(b, norm),
-                                                        PK_W, ker_wid, PK_SLOTS, PK_SLOTS, 1, packed_out_scale(pow_), false, s, 1);
+                                                        PK_W, ker_wid, PK_SLOTS, PK_SLOTS, 1, chain_out_scale(pow_), false, s, 1);
     return packed_tails(cont, ct_conv, "Conv_inside", alpha, pow_, raw, packedMaskKey(s), "packed" + std::to_string(s));
 }
 // the stride layer that enters the block of (norm, step s, keep width raw) from the block of (2 norm, s / 2). Result r = 2q + h is input ciphertext q convolved with the kernel of
@@ -439,7 +454,7 @@ static std::vector<Ciphertext> packed_stride_layer(Context *cont, const std::vec
     std::vector<Ciphertext> ct_conv(2 * nin);
     for (int h = 0; h < 2; h++) {
         std::vector<Ciphertext> r = evalConv_BN_batch(cont, in, packed_expand_ker(ker, ker_wid * ker_wid, cin, cout, 2 * norm, norm, h * norm, norm, PK_SLOTS), packed_expand_bn(a, norm), packed_expand_bn(b, norm),
-                                                      PK_W, ker_wid, PK_SLOTS, PK_SLOTS, 1, packed_out_scale(pow_), false, s / 2, 1);
+                                                      PK_W, ker_wid, PK_SLOTS, PK_SLOTS, 1, chain_out_scale(pow_), false, s / 2, 1);
         for (size_t q = 0; q < nin; q++) ct_conv[2 * q + (size_t)h] = r[q];
     }
     std::vector<Ciphertext> res = packed_tails(cont, ct_conv, "StrConv_inside", alpha, pow_, raw, packedStrideMaskKey(s), "packedstride" + std::to_string(s));
@@ -451,10 +466,10 @@ static std::vector<Ciphertext> packed_stride_layer(Context *cont, const std::vec
         if (res[r].level != acc.level || res[r].Scale != acc.Scale) panic("resnet_packed: the results of a stride layer share level and scale");
         // whole cells: (dy, dx) is the exponent (32 dy + dx) * 64; the live cells end at row and column (s/2 - 1) + s (raw - 1) + s/2 < 32, so none wraps past the ring's end
         const uint64_t e[2] = {(uint64_t)((PK_W * (s / 2) * (t / 2) + (s / 2) * (t % 2)) * PK_SLOTS), 0};
-        HCX(cont->hc, hc_lv_op2(cont->hc, HC_LV_MONOMIAL, acc.level, acc.d, acc.d + poly, res[r].d, res[r].d + poly, acc.d, acc.d + poly, e));
+        HC(cont->hc, hc_lv_op2(cont->hc, HC_LV_MONOMIAL, acc.level, acc.d, acc.d + poly, res[r].d, res[r].d + poly, acc.d, acc.d + poly, e));
         freeCt(cont, res[r]);
     }
-    HCX(cont->hc, hc_sync(cont->hc));
+    HC(cont->hc, hc_sync(cont->hc));
     return outs;
 }
 // HCONV_PACKED_DUMP_LAYERS (test mode): every image slot of a ciphertext the layer hands on, unpacked to its raw x raw x C activation (an observer: the ciphertext is only read)
@@ -474,13 +489,9 @@ static void packed_dump(Context *cont, const std::vector<Ciphertext> &cts, int b
 }
 void testResNet_crop_packed(int st, int end, int ker_wid, int depth) {
     if (ker_wid != 3 && ker_wid != 7) panic("resnet_packed: kernel width 3 or 7 (the even keep widths of 5 put init at step - 1)");
-    const std::string ker_name = "ker" + std::to_string(ker_wid), tag = "crop_" + ker_name + "_d" + std::to_string(depth) + "_wid1/";
-    const std::string weight_dir = "Resnet_weights/weights_" + tag, out_dir = "Resnet_enc_results/results_" + tag, img_dir = "Resnet_plain_data/" + tag;
-    const int fc_out = 10; const double pow_ = 6.0, alpha = 0.0;
-    int num_blcs[3];
-    if (depth == 20) { num_blcs[0] = 7; num_blcs[1] = 5; num_blcs[2] = 5; } else if (depth == 14) { num_blcs[0] = 5; num_blcs[1] = 3; num_blcs[2] = 3; }
-    else if (depth == 8) { num_blcs[0] = 3; num_blcs[1] = 1; num_blcs[2] = 1; } else panic("wrong depth (not in 8, 14, 20)!");
-    const int real_batch[3] = {16, 32, 64}, norm[3] = {4, 2, 1}, steps[3] = {1, 2, 4};
+    const ResnetFiles files(ker_wid, depth);
+    const int fc_out = 10; const double init_pow = 6.0, mid_pow = 6.0, final_pow = 6.0, alpha = 0.0;     // resnet_fast's (test.go:84-89)
+    const int *real_batch = RESNET_BATCH, norm[3] = {4, 2, 1}, steps[3] = {1, 2, 4};
     const std::vector<int> in_wids = {32, 16, 8}, raw = {32 - ker_wid / 2, 16 - ker_wid / 2, 8 - ker_wid / 2};
     const int ker_size = ker_wid * ker_wid;
     std::vector<int> dump_layers;
@@ -489,8 +500,7 @@ void testResNet_crop_packed(int st, int end, int ker_wid, int depth) {
         if (e == p || (*e && *e != ',')) panic("HCONV_PACKED_DUMP_LAYERS: a comma list of layer numbers");
         dump_layers.push_back((int)v); p = *e ? e + 1 : e;
     }
-    mkdir("Resnet_enc_results", 0755); mkdir(out_dir.c_str(), 0755);
-    auto W = [&](int i, const char *what, int size) { return readTxt(weight_dir + "w" + std::to_string(i) + "-" + what + ".csv", size); };
+    files.make_out_dir();
     Context *cont = newContext(LOGN, ker_wid, in_wids, raw, true, "Resnet_crop_packed");
     auto run_start = now();
     for (int g0 = st; g0 < end; g0 += PACKED_GROUP) {
@@ -500,54 +510,35 @@ void testResNet_crop_packed(int st, int end, int ker_wid, int depth) {
         for (int q0 = 0; q0 < nimg; q0 += 4) {                                                          // block 0: images 4q .. 4q + 3 of the group into ciphertext q
             std::vector<Ciphertext> four;
             for (int m = q0; m < std::min(nimg, q0 + 4); m++) {
-                printf("Running  %d -th iter... ker size:  %d\n", g0 + m, ker_wid);
-                std::vector<double> image = readTxt(img_dir + "test_image_" + std::to_string(g0 + m) + ".csv", PK_W * PK_W * 3);
-                std::vector<double> input((size_t)N, 0.0); int k = 0;
-                for (int i = 0; i < PK_W; i++) for (int j = 0; j < PK_W; j++) for (int b = 0; b < 3; b++) {
-                    if (i < raw[0] && j < raw[0]) input[(size_t)(i * PK_W * PK_SLOTS + j * PK_SLOTS + b * norm[0])] = image[(size_t)k];   // as resnet_fast encodes it: channel b at slot 4b
-                    k++;
-                }
+                const std::vector<double> input = resnet_input(files, g0 + m, ker_wid, raw[0]);                   // as resnet_fast encodes it
                 four.push_back(EncryptNew(cont, EncodeCoeffs(input, cont->ECD_LV, cont->scale), cont->ECD_LV, cont->scale));
             }
             ct_layer.push_back(mergePackedInputs(cont, four));
         }
-        HCX(cont->hc, hc_sync(cont->hc));
+        HC(cont->hc, hc_sync(cont->hc));
         printf("Encryption done in %s  (%d images in %zu ciphertexts)\n", dur(enc_start).c_str(), nimg, ct_layer.size());
-        double timings[6]; auto begin_start = now(), start = now();
+        double timings[6]; auto begin_start = now();
         int layer_no = 0;
         auto step = [&](std::vector<Ciphertext> next, int blk) {
             for (Ciphertext &c : ct_layer) freeCt(cont, c);
             ct_layer = std::move(next);
-            if (std::find(dump_layers.begin(), dump_layers.end(), layer_no) != dump_layers.end()) packed_dump(cont, ct_layer, blk, layer_no, g0, nimg, raw[(size_t)blk], real_batch[blk], out_dir);
+            if (std::find(dump_layers.begin(), dump_layers.end(), layer_no) != dump_layers.end()) packed_dump(cont, ct_layer, blk, layer_no, g0, nimg, raw[(size_t)blk], real_batch[blk], files.out_dir);
             layer_no++;
         };
-        auto inside = [&](int w, int cin, int blk) {
-            step(packed_layer(cont, ct_layer, W(w, "conv", cin * real_batch[blk] * ker_size), W(w, "a", real_batch[blk]), W(w, "b", real_batch[blk]), alpha, pow_, ker_wid, cin, real_batch[blk],
-                              norm[blk], steps[blk], raw[(size_t)blk]), blk);
-        };
-        auto strided = [&](int w, int blk) {
-            step(packed_stride_layer(cont, ct_layer, W(w, "conv", real_batch[blk - 1] * real_batch[blk] * ker_size), W(w, "a", real_batch[blk]), W(w, "b", real_batch[blk]), alpha, pow_, ker_wid,
-                                     real_batch[blk - 1], real_batch[blk], norm[blk], steps[blk], raw[(size_t)blk]), blk);
-        };
-        for (int i = 1; i <= num_blcs[0]; i++) { inside(i - 1, i == 1 ? 3 : real_batch[0], 0); printf("Block1, Layer  %d done!\n", i); }
-        printf("Block1 done.\n"); timings[0] = secs(start); start = now();
-        strided(num_blcs[0], 1);
-        printf("Block1 to 2 done!\n"); timings[1] = secs(start); start = now();
-        for (int i = 1; i <= num_blcs[1]; i++) { inside(num_blcs[0] + i, real_batch[1], 1); printf("Block2, Layer  %d done!\n", i); }
-        printf("Block2 done.\n"); timings[2] = secs(start); start = now();
-        strided(num_blcs[0] + num_blcs[1] + 1, 2);
-        printf("Block2 to 3 done!\n"); timings[3] = secs(start); start = now();
-        for (int i = 1; i <= num_blcs[2]; i++) { inside(num_blcs[0] + num_blcs[1] + i + 1, real_batch[2], 2); printf("Block3, Layer  %d done!\n", i); }
-        printf("Block3 done.\n"); timings[4] = secs(start); start = now();
+        resnet_schedule(files.num_blcs, init_pow, mid_pow, final_pow,
+                        [&](int w, int cin, int blk, double pow_) {
+                            step(packed_layer(cont, ct_layer, files.W(w, "conv", cin * real_batch[blk] * ker_size), files.W(w, "a", real_batch[blk]), files.W(w, "b", real_batch[blk]), alpha, pow_, ker_wid,
+                                              cin, real_batch[blk], norm[blk], steps[blk], raw[(size_t)blk]), blk); },
+                        [&](int w, int blk, double pow_) {
+                            step(packed_stride_layer(cont, ct_layer, files.W(w, "conv", real_batch[blk - 1] * real_batch[blk] * ker_size), files.W(w, "a", real_batch[blk]), files.W(w, "b", real_batch[blk]), alpha, pow_,
+                                                     ker_wid, real_batch[blk - 1], real_batch[blk], norm[blk], steps[blk], raw[(size_t)blk]), blk); }, timings);
+        auto start = now();
 
         // reduce-mean and FC as ONE convolution at norm 1: raw[2] x raw[2] taps of the FC weights over raw[2]^2, dilated by 4, so that a tap set reads the cells of ONE phase
         // (resnet_fast's undilated 31-wide kernel would sum across the phases). The image at phase (py, px) has its scores at cell (kd/2 + py, kd/2 + px).
         const int kd = steps[2] * (raw[2] - 1) + 1;
-        std::vector<double> ker_inf = readTxt(weight_dir + "final-fckernel.csv", real_batch[2] * fc_out), bn_bf = readTxt(weight_dir + "final-fcbias.csv", fc_out);
-        std::vector<double> ker_inf_((size_t)(raw[2] * raw[2] * real_batch[2] * fc_out));
-        for (size_t i = 0; i < ker_inf.size(); i++) for (int b = 0; b < raw[2] * raw[2]; b++) ker_inf_[i + (size_t)b * ker_inf.size()] = ker_inf[i];
-        std::vector<double> bn_af((size_t)fc_out, 1.0 / (double)(raw[2] * raw[2]));
-        std::vector<Ciphertext> ct_result = evalConv_BN_batch(cont, ct_layer, ker_inf_, bn_af, bn_bf, PK_W, raw[2], real_batch[2], fc_out, 1, (double)(1 << 30), false, steps[2], 1);
+        const FcHead head = resnet_fc_head(files, raw[2] * raw[2], fc_out, raw[2]);
+        std::vector<Ciphertext> ct_result = evalConv_BN_batch(cont, ct_layer, head.ker, head.bn_a, head.bn_b, PK_W, raw[2], real_batch[2], fc_out, 1, (double)(1 << 30), false, steps[2], 1);
         printf("Final FC done.\n"); timings[5] = secs(start); start = now();
         printf("\n===============  DECRYPTION  ===============\n\n");
         const std::vector<double> res_tmp = DecryptDecodeCoeffs(cont, ct_result[0]);
@@ -558,11 +549,11 @@ void testResNet_crop_packed(int st, int end, int ker_wid, int depth) {
             for (int o = 0; o < fc_out; o++) res_out[(size_t)o] = res_tmp[((size_t)(kd / 2 + p.py) * PK_W + (size_t)(kd / 2 + p.px)) * PK_SLOTS + (size_t)o];
             printf("\n result %d:  [", g0 + m); for (double v : res_out) printf("%.10f ", v);
             printf("]\n");
-            writeTxt(out_dir + "class_result_" + ker_name + "_" + std::to_string(g0 + m) + ".csv", res_out);
+            files.write_scores(g0 + m, res_out);
         }
         for (Ciphertext &c : ct_layer) freeCt(cont, c);
         for (Ciphertext &c : ct_result) freeCt(cont, c);
-        printf("Blc1:  %g  sec\nBlc1->2:  %g  sec\nBlc2:  %g  sec\nBlc2->3:  %g  sec\nBlc3:  %g  sec\nFinal (reduce_mean & FC):  %g  sec\n", timings[0], timings[1], timings[2], timings[3], timings[4], timings[5]);
+        print_stage_times(timings);
         printf("Total done in %s (%d images)\n", dur(begin_start).c_str(), nimg);
     }
     printf("All %d images done in %s  (first encryption to last result)\n", end - st, dur(run_start).c_str());
