@@ -52,6 +52,20 @@ HC_HD double hc_f64_mulmod(double x, double w, double wq, double q) {
     const double r = __builtin_fma(-k, q, h);
     return r + l;
 }
+// x*w mod q from the ONE word w (no companion w/q): the product of two VARIABLE operands, both exact integers below q < 2^49 in magnitude (hc_k_a1p<1> / hc_k_a1g<1>: kernel
+// plaintext times c'). h = fl(x*w) < 2^98 and l = x*w - h exactly (|l| <= ulp(h)/2 <= 2^44). The quotient estimate comes from h itself: fl(h * qinv) with qinv = fl(1/q) carries
+// three roundings, so it is x*w/q (1 + e), |e| < 3.01 * 2^-53, off by less than q * 2^-51 < 1/4; k = rint(.) is then within 1/2 + q * 2^-51 of x*w/q. h - k*q = (x*w - k*q) - l
+// is an integer below 3q/4 + 2^44 < 2^50 in magnitude, so the fused multiply-add gives it exactly, and adding l is exact too. Result: congruent to x*w, an exact integer,
+//   |result| <= (1/2 + q * 2^-51) * q < 3q/4.
+// Six instructions, as hc_f64_mulmod. No contraction.
+HC_HD double hc_f64_mulmod_q(double x, double w, double q, double qinv) {
+#pragma clang fp contract(off)
+    const double h = x * w;
+    const double l = __builtin_fma(x, w, -h);
+    const double k = __builtin_rint(h * qinv);
+    const double r = __builtin_fma(-k, q, h);
+    return r + l;
+}
 HC_HD double hc_f64_reduce(double u, double q, double qinv) {
 #pragma clang fp contract(off)
     return __builtin_fma(-__builtin_rint(u * qinv), q, u);

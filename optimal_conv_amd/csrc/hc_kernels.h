@@ -853,12 +853,19 @@ __global__ __launch_bounds__(HC_TPB) void hc_k_make_pairs(const u64 *w, HcTw *ou
 
 // ct_in times MultByConst's per-limb integer constants, as Shoup pairs (c', floor(c' * 2^64 / q)): the fixed operand of loop A.
 // grid = (64, 4 rows = [poly][limb], ciphertexts of a batch)
+// out1 != nullptr (Q1 < 2^49, the fp64 form of hc_k_a1p / hc_k_a1g): limb 1 goes to out1 instead, a DENSE array [z][2 polys][N] of doubles holding c' (canonical, < Q1 < 2^49: exact),
+// one 8-byte word per coefficient and no companion (hc_f64_mulmod_q needs none): its slots of `out` stay unwritten and unread.
 #define HC_MAXB 16                    // ciphertexts per batched conv launch set
 struct HcPtrs { const u64 *p[HC_MAXB]; };      // one device pointer per ciphertext of a batch (kernel argument, indexed by blockIdx)
 struct HcCtc { HcMod m0, m1; HcTw c0, c1; };
-__global__ __launch_bounds__(HC_TPB) void hc_k_ctc_pairs(HcPtrs ct_in, HcTw *out, HcCtc K) {
+__global__ __launch_bounds__(HC_TPB) void hc_k_ctc_pairs(HcPtrs ct_in, HcTw *out, double *out1, HcCtc K) {
     const int r = blockIdx.y, l = r & 1; const HcMod m = l ? K.m1 : K.m0; const HcTw cst = l ? K.c1 : K.c0;
     const u64 *in = ct_in.p[blockIdx.z] + (size_t)r * 65536;
+    if (l && out1) {
+        double *d = out1 + ((size_t)blockIdx.z * 2 + (r >> 1)) * 65536;
+        for (size_t i = (size_t)blockIdx.x * HC_TPB + threadIdx.x; i < 65536; i += (size_t)gridDim.x * HC_TPB) d[i] = hc_f64_from_u(hc_mul_shoup(in[i], cst.w, cst.ws, m.q));
+        return;
+    }
     HcTw *o = out + ((size_t)blockIdx.z * 4 + r) * 65536;
     for (size_t i = (size_t)blockIdx.x * HC_TPB + threadIdx.x; i < 65536; i += (size_t)gridDim.x * HC_TPB) {
         HcTw p; p.w = hc_mul_shoup(in[i], cst.w, cst.ws, m.q); p.ws = hc_shoup_companion(p.w, m.q);
@@ -1035,46 +1042,59 @@ struct HcLoopA {
 // runs in fp64 (T1inv = the fp64 table) and tmp carries doubles (bit patterns) to KA2. The kernel-plaintext tile
 // k_i[1] is loaded once and every T1inv twiddle once for the two transforms (hc_rows_inv_twl on two tiles / hc_rows_inv2_f64); one LDS tile, used by the two polynomials in turn.
 // The row's 16 rowsA twiddles come through LDS (HcTwL): one load per thread at kernel entry, the image in the tile behind the last read-back.
+// F64 = 1 forms the product in fp64 as well (hc_f64_mulmod_q): c' comes as ONE double per coefficient from ctc1 = [z][2 polys][N] (hc_k_ctc_pairs' dense limb-1 array), 16 bytes per
+// coefficient pair of polynomials where the Shoup pairs of A.ctc were 32, and k_1 < Q1 < 2^49 converts exactly. The products (|.| < 3*Q1/4, exact integers) go through the
+// linear -> lo-local exchange as bit patterns and straight into hc_rows_inv2_f64, whose rounds take any |input| < Q1 (hc_gs_round_f64's bounds: the sums of two such values are folded
+// after stages 1 and 3, the differences are below 4*Q1 < 2^51 where hc_f64_mulmod takes them): no hc_f64_reduce in between. F64 = 0 does not read ctc1.
 template <int F64>
-__global__ __launch_bounds__(HC_TPB, HC_W_A1) void hc_k_a1p(HcLoopA A, HcTwTab T1inv) {
+__global__ __launch_bounds__(HC_TPB, HC_W_A1) void hc_k_a1p(HcLoopA A, HcTwTab T1inv, const double *ctc1) {
     __shared__ __attribute__((aligned(16))) u64 lds[HC_ROWS_LDS];
     const int t = threadIdx.x, tid = t & 15, rloc = t >> 4, row = HC_TILE * 16 + rloc;
     const int ch = HC_JOB, i = A.i0 + ch * A.norm, z = blockIdx.z;
-    const HcTw *__restrict__ c0 = A.ctc + ((size_t)z * 4 + 1) * 65536 + (size_t)HC_TILE * 4096 + t;          // c'_0[1] ; c'_1[1] is 2 * 65536 pairs on
+    const HcTw *__restrict__ c0 = A.ctc + ((size_t)z * 4 + 1) * 65536 + (size_t)HC_TILE * 4096 + t;          // F64 = 0: c'_0[1] ; c'_1[1] is 2 * 65536 pairs on
     const u64 *__restrict__ k = A.ker.p[z] + ((size_t)i * 2 + 1) * 65536 + (size_t)HC_TILE * 4096 + t;
-    const HcQ Q = hc_q(A.m1.q);
-    const HcTw wA = hc_twl_load(T1inv, HC_TILE, t);
-    u64 e0[16], e1[16];
-#pragma unroll
-    for (int kk = 0; kk < 16; kk++) {
-        const u64 kv = k[kk * 256];
-        const HcTw w0 = c0[kk * 256], w1 = c0[2 * 65536 + kk * 256];
-        e0[kk] = hc_shoup4(kv, w0.w, w0.ws, Q);                                 // [0, 4*Q1)
-        e1[kk] = hc_shoup4(kv, w1.w, w1.ws, Q);
-    }
-    u64 *o = A.tmp + ((size_t)z * A.njobs + 2 * ch) * 65536 + (size_t)row * 256;     // polynomial 1 is 65536 words on
-    hc_xchg(lds, [&](int kk) { return hc_rows_lds(kk, t); }, [&](int lo) { return hc_rows_lds(rloc, tid * 16 + lo); }, [] { __syncthreads(); }, e0, e1);
-    HC_ROW_SYNC();        // row-local: the reads before and the writes after stay inside the 16 lanes of a row
-    if (F64) {
+    if constexpr (F64) {
+        const double *__restrict__ d0 = ctc1 + (size_t)z * 2 * 65536 + (size_t)HC_TILE * 4096 + t;            // c'_0[1] ; c'_1[1] is 65536 doubles on
+        const HcTw wA = hc_twl_load(T1inv, HC_TILE, t);
         const HcF64Mod m{(double)A.m1.q, 1.0 / (double)A.m1.q};
         double f0[16], f1[16];
 #pragma unroll
-        for (int kk = 0; kk < 16; kk++) { f0[kk] = hc_f64_reduce(hc_f64_from_u(e0[kk]), m.q, m.qinv); f1[kk] = hc_f64_reduce(hc_f64_from_u(e1[kk]), m.q, m.qinv); }   // 4*Q1 < 2^51: exact; |f| <= Q1/2
+        for (int kk = 0; kk < 16; kk++) {
+            const double kv = hc_f64_from_u(k[kk * 256]);                                                     // k_1 < Q1 < 2^49: exact
+            f0[kk] = hc_f64_mulmod_q(kv, d0[kk * 256], m.q, m.qinv);
+            f1[kk] = hc_f64_mulmod_q(kv, d0[65536 + kk * 256], m.q, m.qinv);
+        }
+        u64 *o = A.tmp + ((size_t)z * A.njobs + 2 * ch) * 65536 + (size_t)row * 256;     // polynomial 1 is 65536 words on
+        hc_xchg(lds, [&](int kk) { return hc_rows_lds(kk, t); }, [&](int lo) { return hc_rows_lds(rloc, tid * 16 + lo); }, [] { __syncthreads(); }, f0, f1);
+        HC_ROW_SYNC();        // row-local: the reads before and the writes after stay inside the 16 lanes of a row
         hc_rows_inv2_f64(f0, f1, lds, T1inv, wA, row, rloc, tid, m);
 #pragma unroll
         for (int hi = 0; hi < 16; hi++) { o[hi * 16 + tid] = hc_d2u(f0[hi]); o[65536 + hi * 16 + tid] = hc_d2u(f1[hi]); }
     } else {
+        const HcQ Q = hc_q(A.m1.q);
+        const HcTw wA = hc_twl_load(T1inv, HC_TILE, t);
+        u64 e0[16], e1[16];
+#pragma unroll
+        for (int kk = 0; kk < 16; kk++) {
+            const u64 kv = k[kk * 256];
+            const HcTw w0 = c0[kk * 256], w1 = c0[2 * 65536 + kk * 256];
+            e0[kk] = hc_shoup4(kv, w0.w, w0.ws, Q);                                 // [0, 4*Q1)
+            e1[kk] = hc_shoup4(kv, w1.w, w1.ws, Q);
+        }
+        u64 *o = A.tmp + ((size_t)z * A.njobs + 2 * ch) * 65536 + (size_t)row * 256;     // polynomial 1 is 65536 words on
+        hc_xchg(lds, [&](int kk) { return hc_rows_lds(kk, t); }, [&](int lo) { return hc_rows_lds(rloc, tid * 16 + lo); }, [] { __syncthreads(); }, e0, e1);
+        HC_ROW_SYNC();        // row-local: the reads before and the writes after stay inside the 16 lanes of a row
         hc_rows_inv_twl(HcLazy<>{Q}, lds, T1inv, wA, row, rloc, tid, e0, e1);
 #pragma unroll
         for (int hi = 0; hi < 16; hi++) { o[hi * 16 + tid] = e0[hi]; o[65536 + hi * 16 + tid] = e1[hi]; }
     }
 }
 // KA1 for a group of m input ciphertexts of ONE convolution (hc_conv_then_pack_batch's members with one ct_out): a_1 = sum_j c'_j,p[1] (*) k_j,i[1] mod Q1, summed before the one
-// rows-inverse pass. grid = (jobs / 2, 16, groups): blockIdx.z = group g, member j is ciphertext g*m + j of ctc and ker; tmp is per group. Every term is a hc_shoup4 product in [0, 4*Q1).
-//   F64 = 1 (Q1 < 2^49, every Q0 class): a term is below 2^51, so TWO terms sum below 2^52, which is what hc_f64_from_u converts exactly (its bit trick ends at 2^52, not 2^53): the
-//     members go in pairs, each pair sum is folded by hc_f64_reduce to |.| <= Q1/2 + 1 and added in fp64. At most 8 pair sums (m <= HC_MAXB = 16): |sum| <= 8 (Q1/2 + 1) < 2^51 + 8,
-//     an exact integer; one more hc_f64_reduce gives the |f| <= Q1/2 + 1 that hc_rows_inv2_f64 takes from hc_k_a1p. An odd m leaves its last member alone in its pair.
-//   F64 = 0 (2^49 <= Q1, 4*Q1 < 2^64): 4*Q1 may reach 2^63 and beyond, so two lazy terms can already pass 2^64. Each term is made canonical (hc_canon4: [0, 4*Q1) -> [0, Q1)) and
+// rows-inverse pass. grid = (jobs / 2, 16, groups): blockIdx.z = group g, member j is ciphertext g*m + j of ctc (ctc1) and ker; tmp is per group.
+//   F64 = 1 (Q1 < 2^49, every Q0 class): every term is a hc_f64_mulmod_q product formed as in hc_k_a1p<1> (k_j,1 as a double times the one double of c'_j from ctc1), an exact integer
+//     below 3*Q1/4 in magnitude, added in fp64. The sum is folded by hc_f64_reduce (to |.| <= Q1/2 + 1) after every FOURTH term and after the last: between folds it stays below
+//     Q1/2 + 1 + 4 * 3*Q1/4 = 3.5*Q1 + 1 < 2^51, an exact integer inside what hc_f64_reduce takes (< 2^53), whatever m is. What leaves is |f| <= Q1/2 + 1 < Q1, which hc_rows_inv2_f64 takes.
+//   F64 = 0 (2^49 <= Q1, 4*Q1 < 2^64): every term is a hc_shoup4 product in [0, 4*Q1). 4*Q1 may reach 2^63 and beyond, so two lazy terms can already pass 2^64. Each term is made canonical (hc_canon4: [0, 4*Q1) -> [0, Q1)) and
 //     added to a canonical sum with one conditional subtraction (hc_fold at Q1: acc + term < 2*Q1 <= 2^63): the sum stays in [0, Q1), inside the [0, 4*Q1) the transform takes.
 // The sums are congruent to the one-input kernel's product summed over the members, and everything after the transform is canonical, so the words are those of the Lattigo sequence.
 // hc_rows_inv2_f64 and hc_k_a3p's front end (hc_rows_fwd_twl on two tiles, then lo-local -> linear) under names of their own: as second callers of those helpers the grouped kernels
@@ -1100,7 +1120,7 @@ __device__ __forceinline__ void hc_rows_fwd2_lin_g(u64 (&e0)[16], u64 (&e1)[16],
     hc_xchg(lds, [&](int lo) { return hc_rows_lds(rloc, tid * 16 + lo); }, [&](int kk) { return hc_rows_lds(kk, t); }, [] { __syncthreads(); }, e0, e1);
 }
 template <int F64>
-__global__ __launch_bounds__(HC_TPB, HC_W_A1) void hc_k_a1g(HcLoopA A, HcTwTab T1inv) {
+__global__ __launch_bounds__(HC_TPB, HC_W_A1) void hc_k_a1g(HcLoopA A, HcTwTab T1inv, const double *ctc1) {
     __shared__ __attribute__((aligned(16))) u64 lds[HC_ROWS_LDS];
     const int t = threadIdx.x, tid = t & 15, rloc = t >> 4, row = HC_TILE * 16 + rloc;
     const int ch = HC_JOB, i = A.i0 + ch * A.norm, g = blockIdx.z, m = A.gm;
@@ -1113,26 +1133,20 @@ __global__ __launch_bounds__(HC_TPB, HC_W_A1) void hc_k_a1g(HcLoopA A, HcTwTab T
         double f0[16], f1[16];
 #pragma unroll
         for (int kk = 0; kk < 16; kk++) f0[kk] = f1[kk] = 0.0;
-        for (int j = 0; j < m; j += 2) {
-            const bool two = j + 1 < m;
-            const int za = g * m + j, zb = two ? za + 1 : za;
-            const HcTw *__restrict__ ca = A.ctc + ((size_t)za * 4 + 1) * 65536 + tile, *__restrict__ cb = A.ctc + ((size_t)zb * 4 + 1) * 65536 + tile;
-            const u64 *__restrict__ ka = A.ker.p[za] + ((size_t)i * 2 + 1) * 65536 + tile, *__restrict__ kb = A.ker.p[zb] + ((size_t)i * 2 + 1) * 65536 + tile;
+        for (int j = 0; j < m; j++) {
+            const int z = g * m + j;
+            const double *__restrict__ d0 = ctc1 + (size_t)z * 2 * 65536 + tile;                          // c'_j,0[1] ; c'_j,1[1] is 65536 doubles on
+            const u64 *__restrict__ k = A.ker.p[z] + ((size_t)i * 2 + 1) * 65536 + tile;
+            const bool fold = (j & 3) == 3 || j == m - 1;
 #pragma unroll
             for (int kk = 0; kk < 16; kk++) {
-                const u64 kv = ka[kk * 256];
-                const HcTw w0 = ca[kk * 256], w1 = ca[2 * 65536 + kk * 256];
-                u64 s0 = hc_shoup4(kv, w0.w, w0.ws, Q), s1 = hc_shoup4(kv, w1.w, w1.ws, Q);            // [0, 4*Q1) < 2^51
-                if (two) {
-                    const u64 kv2 = kb[kk * 256];
-                    const HcTw x0 = cb[kk * 256], x1 = cb[2 * 65536 + kk * 256];
-                    s0 += hc_shoup4(kv2, x0.w, x0.ws, Q); s1 += hc_shoup4(kv2, x1.w, x1.ws, Q);         // < 2^52
-                }
-                f0[kk] += hc_f64_reduce(hc_f64_from_u(s0), fm.q, fm.qinv); f1[kk] += hc_f64_reduce(hc_f64_from_u(s1), fm.q, fm.qinv);
+                const double kv = hc_f64_from_u(k[kk * 256]);                                            // k_j,1 < Q1 < 2^49: exact
+                f0[kk] += hc_f64_mulmod_q(kv, d0[kk * 256], fm.q, fm.qinv); f1[kk] += hc_f64_mulmod_q(kv, d0[65536 + kk * 256], fm.q, fm.qinv);
+                if (fold) { f0[kk] = hc_f64_reduce(f0[kk], fm.q, fm.qinv); f1[kk] = hc_f64_reduce(f1[kk], fm.q, fm.qinv); }
             }
         }
 #pragma unroll
-        for (int kk = 0; kk < 16; kk++) { e0[kk] = hc_d2u(hc_f64_reduce(f0[kk], fm.q, fm.qinv)); e1[kk] = hc_d2u(hc_f64_reduce(f1[kk], fm.q, fm.qinv)); }
+        for (int kk = 0; kk < 16; kk++) { e0[kk] = hc_d2u(f0[kk]); e1[kk] = hc_d2u(f1[kk]); }
     } else {
 #pragma unroll
         for (int kk = 0; kk < 16; kk++) e0[kk] = e1[kk] = 0;

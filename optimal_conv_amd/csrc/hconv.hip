@@ -119,6 +119,7 @@ struct hc_ctx {
     u64 *ws_cts = nullptr; size_t ws_cts_rows = 0;     // loop A output / tree ping
     u64 *ws_cts2 = nullptr; size_t ws_cts2_rows = 0;   // tree pong
     HcTw *ws_ctc = nullptr; size_t ws_ctc_cts = 0;     // [batch][2 polys][2 limbs][N] ct_in times the MultByConst constants, Shoup pairs
+    double *ws_ctc1 = nullptr; size_t ws_ctc1_cts = 0; // [batch][2 polys][N] limb 1 of the same as doubles, dense (Q1 < 2^49: hc_k_a1p<1> / hc_k_a1g<1>); limb 1 of ws_ctc is then unused
     u64 *ws_tmp = nullptr; size_t ws_tmp_rows = 0;
     HcMod *d_mods = nullptr; HcTw *d_csts = nullptr;      // device copies: all moduli (Q then P); per-call constants of the leveled ops
     u64 *d_mono = nullptr;                                // per modulus (Q then P): HC_MONO_WORDS powers of psi in Montgomery form (hc_k_lv_monomial)
@@ -431,7 +432,7 @@ extern "C" void hc_ctx_destroy(hc_ctx *c) {
     if (c->ev_fork) D(hipEventDestroy(c->ev_fork), "hipEventDestroy");
     if (c->ev_shard) D(hipEventDestroy(c->ev_shard), "hipEventDestroy");
     F(c->enc_roots); F(c->enc_rot_group); F(c->d_flag); F(c->crt_tab);
-    F(c->ws_ctc); F(c->ws_tmp); F(c->d_mods); F(c->d_mono); F(c->d_rowmods); F(c->ws_mm); F(c->ws_accm);
+    F(c->ws_ctc); F(c->ws_ctc1); F(c->ws_tmp); F(c->d_mods); F(c->d_mono); F(c->d_rowmods); F(c->ws_mm); F(c->ws_accm);
     for (auto &kv : c->ks_plan) { F(kv.second.bx); F(kv.second.bxdown); F(kv.second.pinv); F(kv.second.pmod); F(kv.second.pinv_qlinv); }
     for (auto &kv : c->rescale_plan) F(kv.second);
     F(c->d_csts);
@@ -517,7 +518,10 @@ static int hc_ensure(hc_ctx *c, T *&ws, size_t &cap, size_t units, size_t unit_b
 }
 static int hc_ensure_tmp(hc_ctx *c, size_t rows) { return hc_ensure(c, c->ws_tmp, c->ws_tmp_rows, rows, HC_N * sizeof(u64)); }
 static int hc_ensure_cts(hc_ctx *c, size_t rows) { return hc_ensure(c, c->ws_cts, c->ws_cts_rows, rows, HC_N * sizeof(u64)); }
-static int hc_ensure_ctc(hc_ctx *c, size_t nct) { return hc_ensure(c, c->ws_ctc, c->ws_ctc_cts, nct, 4 * HC_N * sizeof(HcTw)); }
+static int hc_ensure_ctc(hc_ctx *c, size_t nct) {
+    if (hc_f64_ok(c->mods[1].m.q)) HC_TRY(hc_ensure(c, c->ws_ctc1, c->ws_ctc1_cts, nct, 2 * HC_N * sizeof(double)));
+    return hc_ensure(c, c->ws_ctc, c->ws_ctc_cts, nct, 4 * HC_N * sizeof(HcTw));
+}
 // ws_mm is handed out by two claims and by nothing else: this one (Rescale at level 2 and above, hc_lv_mod_raise) and the key switch's (hc_ks_claim). Its first words are where a
 // held decomposition's digits lie, so the hold ends before the caller has the pointer.
 static int hc_mm_claim(hc_ctx *c, size_t rows, u64 **t) {
@@ -863,12 +867,12 @@ static int hc_fill_loopA(hc_ctx *c, HcLoopA *A, const HcPtrs &kers, u64 *cts, si
 }
 
 // ct_in (2x2 rows) of n ciphertexts times per-limb constants -> ws_ctc as Shoup pairs: c' is the fixed operand of the 2B products
-// of loop A, so its companion floor(c' * 2^64 / q) is computed once per conv (4 rows per ciphertext)
+// of loop A, so its companion floor(c' * 2^64 / q) is computed once per conv (4 rows per ciphertext; Q1 < 2^49: 2 rows, limb 1 goes to ws_ctc1 as one double per word)
 static int hc_prepare_ctc(hc_ctx *c, const HcPtrs &ct_in, int n, const u64 cst[2]) {
     HC_TRY(hc_ensure_ctc(c, (size_t)n));
     HcCtc K; K.m0 = c->mods[0].m; K.m1 = c->mods[1].m;
     K.c0 = h_pair(cst[0] % K.m0.q, K.m0.q); K.c1 = h_pair(cst[1] % K.m1.q, K.m1.q);
-    return hc_launch(c, "ctc", hc_k_ctc_pairs, dim3(64, 4, (unsigned)n), ct_in, c->ws_ctc, K);
+    return hc_launch(c, "ctc", hc_k_ctc_pairs, dim3(64, 4, (unsigned)n), ct_in, c->ws_ctc, c->ws_ctc1, K);
 }
 
 // loop A over the channels i = i_first + j*i_stride, j < nch, of each of the n ciphertexts of a batch (blockIdx.z); result j goes to
@@ -890,18 +894,18 @@ static int hc_loopA_run_set(hc_ctx *c, const HcPtrs &kers, int n, int i_first, i
         if (gm > 1) {
             const bool f64 = hc_f64_ok(m1.m.q);
             const HcTwTab &t1 = f64 ? m1.inv_f64 : m1.inv;
-            HC_TRY(f64 ? hc_launch(c, "a1g_mulsum_rowsinv", hc_k_a1g<1>, pair, A, t1) : hc_launch(c, "a1g_mulsum_rowsinv", hc_k_a1g<0>, pair, A, t1));
+            HC_TRY(f64 ? hc_launch(c, "a1g_mulsum_rowsinv", hc_k_a1g<1>, pair, A, t1, (const double *)c->ws_ctc1) : hc_launch(c, "a1g_mulsum_rowsinv", hc_k_a1g<0>, pair, A, t1, (const double *)c->ws_ctc1));
             if (f64) HC_TRY(hc_fm_free(m0.m.q) ? hc_launch(c, "a2_colsinv_lift_colsfwd", hc_k_a2<HC_FM_FREE, 1>, flat, A, t1, m0.fwd) : hc_launch(c, "a2_colsinv_lift_colsfwd", hc_k_a2<HC_FM_ALT, 1>, flat, A, t1, m0.fwd));
             else HC_TRY(hc_fm_free(m0.m.q) ? hc_launch(c, "a2_colsinv_lift_colsfwd", hc_k_a2<HC_FM_FREE, 0>, flat, A, t1, m0.fwd) : hc_launch(c, "a2_colsinv_lift_colsfwd", hc_k_a2<HC_FM_ALT, 0>, flat, A, t1, m0.fwd));
             HC_TRY(HC_LAUNCH_FM(m0.m.q, c, "a3g_rowsfwd_sum_rescale", hc_k_a3g, pair, A, m0.fwd));
             continue;
         }
         if (hc_f64_ok(m1.m.q)) {
-            HC_TRY(hc_launch(c, "a1_mul_rowsinv", hc_k_a1p<1>, pair, A, m1.inv_f64));
+            HC_TRY(hc_launch(c, "a1_mul_rowsinv", hc_k_a1p<1>, pair, A, m1.inv_f64, (const double *)c->ws_ctc1));
             HC_TRY(hc_fm_free(m0.m.q) ? hc_launch(c, "a2_colsinv_lift_colsfwd", hc_k_a2<HC_FM_FREE, 1>, flat, A, m1.inv_f64, m0.fwd)
                                       : hc_launch(c, "a2_colsinv_lift_colsfwd", hc_k_a2<HC_FM_ALT, 1>, flat, A, m1.inv_f64, m0.fwd));
         } else {
-            HC_TRY(hc_launch(c, "a1_mul_rowsinv", hc_k_a1p<0>, pair, A, m1.inv));
+            HC_TRY(hc_launch(c, "a1_mul_rowsinv", hc_k_a1p<0>, pair, A, m1.inv, (const double *)c->ws_ctc1));
             HC_TRY(hc_fm_free(m0.m.q) ? hc_launch(c, "a2_colsinv_lift_colsfwd", hc_k_a2<HC_FM_FREE, 0>, flat, A, m1.inv, m0.fwd)
                                       : hc_launch(c, "a2_colsinv_lift_colsfwd", hc_k_a2<HC_FM_ALT, 0>, flat, A, m1.inv, m0.fwd));
         }
@@ -2287,7 +2291,7 @@ extern "C" int hc_set_option(hc_ctx *c, const char *name, long value) {
         if (value < 0 || value > 2) return hc_fail(c, HC_ERR_ARG, "async_alloc must be 0, 1 or 2");
         if ((int)value == c->async_alloc) return HC_OK;
         // the stream and the ownership of every block follow the mode: it can only change while the context owns nothing but its tables (right after hc_ctx_create)
-        if (c->allocs_live || !c->evk.empty() || !c->swk.empty() || c->idx_pairs || c->ws_cts || c->ws_tmp || c->ws_mm || c->ws_ctc || !c->cache_blk.empty())
+        if (c->allocs_live || !c->evk.empty() || !c->swk.empty() || c->idx_pairs || c->ws_cts || c->ws_tmp || c->ws_mm || c->ws_ctc || c->ws_ctc1 || !c->cache_blk.empty())
             return hc_fail(c, HC_ERR_STATE, "async_alloc: set it right after hc_ctx_create, before the context allocates");
         HC_ENTER(c); HC_HIP(c, hipStreamSynchronize(c->stream));
         hipStream_t ns = nullptr;
